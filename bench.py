@@ -1,7 +1,12 @@
 """bench.py -- cas_id files/s (+ checksum GB/s) on 1..8 MI355X, one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps that give `value`, writes the last timed
+step's outputs with --dump-outputs, and prints the line.  Everything else below (the serial
+steps' kernel breakdown, the oracle checks, every further leg, the CPU baseline, the full
+record in a file) runs with --full.
 
 Workload (BASELINE.json configs[4], weak-scaled): a 10 M-file synthetic library with the
 configs[0] mixture (60 % of files <= 100 KiB hashed whole, 40 % sampled), sharded by file
@@ -13,7 +18,7 @@ sort + group, Object owners).  Inputs are resident in HBM before timing (generat
 device from the counter-based generator); PCIe-inclusive rates are reported beside
 `value` ("with_h2d"), never as it.
 
-After the timed steps: configs[3] (full-file checksums of 16 x 4 GiB files, then its mixed 2..8 GiB variant) on every
+With --full, after the timed steps: configs[3] (full-file checksums of 16 x 4 GiB files, then its mixed 2..8 GiB variant) on every
 rank as `checksum`; on rank 0 at N = 1 the configs[1]/[2] kernel legs, the with-H2D legs
 (cas_ids and checksums from pinned host memory), the file-backed legs (cas_ids and
 checksums from tmpfs beside the reference's read schedule on the CPU), single-call
@@ -113,6 +118,15 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps that give the value, run everything else: the serial steps and "
+                        "their kernel breakdown, the oracle checks of the timed output, the checksum, split, "
+                        "with-H2D, file-backed, latency and configs[1]/[2] legs, the measured VALU peak and the "
+                        "CPU baseline, and write the full record (--full-out); a plain run does none of it")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step returned as DIR/<name>.npy (float32 / float64; a fixed "
+                        "seeded sample of the rows where the whole would pass 64 MB: see dump_outputs; at N > 1 "
+                        "every rank writes DIR/<name>.rank<r>.npy)")
     p.add_argument("--files-per-gpu", type=int, default=1_250_000)
     p.add_argument("--checksum-gib", type=int, default=64, help="configs[3] size per GPU; 0 = skip")
     p.add_argument("--checksum-steps", type=int, default=5)
@@ -1535,8 +1549,8 @@ def _g(d, *path):
 
 
 def _par(p):
-    """a parity record as [files, mismatches]"""
-    return [p.get("files"), p.get("mismatches")] if isinstance(p, dict) else None
+    """a parity record as [files, mismatches]; None for a check that did not run"""
+    return [p.get("files"), p.get("mismatches")] if isinstance(p, dict) and p else None
 
 
 def _prune(d):
@@ -1682,6 +1696,62 @@ def emit(out: dict, stream, full_path: str = None) -> str:
     return line
 
 
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_ROWS = 1 << 18  # rows per sampled array: 32 MiB of hashes + 10 MiB of records at most
+DUMP_SEED = 20240607
+
+
+def dump_rows(n: int, k: int = None) -> np.ndarray:
+    """The rows of an n-row output that --dump-outputs keeps: all of them when n <= k
+    (DUMP_ROWS), else k drawn without replacement from a fixed seed, ascending -- the same
+    rows at every run."""
+    k = DUMP_ROWS if k is None else k
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False)).astype(np.int64)
+
+
+def u64_halves(x: np.ndarray) -> np.ndarray:
+    """[m] int64 holding u64 bit patterns (the cas_id keys) as [m, 2] float64: the high and
+    the low 32 bits, each exact in a float64 (the whole 64 bits would not be)"""
+    u = np.ascontiguousarray(x).view(np.uint64)
+    return np.stack([(u >> np.uint64(32)).astype(np.float64), (u & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1)
+
+
+def dump_outputs(d: str, d_hash: torch.Tensor, n: int, res, suffix: str = "") -> dict:
+    """Writes what the last timed step handed its caller as d/<name><suffix>.npy:
+      hashes        float32 [k, 32]  the 32 hash bytes of files hash_rows (cas_id = the first 8)
+      hash_rows     float64 [k]      their indices in the shard
+      records       float64 [j, 3]   the dedup step's grouped records record_rows: cas_id key
+                                     high 32 bits, low 32 bits, global file index
+      representative float64 [j]     each record's group representative
+      owners        float64 [j]      each record's Object owner
+      record_rows   float64 [j]      their row numbers in the step's output
+      counts        float64 [2]      records, groups of the whole output
+    k, j = min(rows, DUMP_ROWS): a fixed seeded sample (dump_rows) where the output is larger,
+    so the files stay under 64 MB.  Every integer written is exact in its float type."""
+    recs, rep, n_groups, owners = res
+    os.makedirs(d, exist_ok=True)
+    dev = d_hash.device
+    hi = dump_rows(n)
+    ri = dump_rows(int(recs.shape[0]))
+    t_ri = torch.from_numpy(ri).to(recs.device)
+    r = recs[t_ri].cpu().numpy()
+    arrays = {
+        "hashes": d_hash.view(-1, 32)[torch.from_numpy(hi).to(dev)].cpu().numpy().astype(np.float32),
+        "hash_rows": hi.astype(np.float64),
+        "records": np.concatenate([u64_halves(r[:, 0]), r[:, 1:2].astype(np.float64)], axis=1),
+        "representative": rep[t_ri].cpu().numpy().astype(np.float64),
+        "owners": owners[t_ri].cpu().numpy().astype(np.float64),
+        "record_rows": ri.astype(np.float64),
+        "counts": np.array([recs.shape[0], n_groups], np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + suffix + ".npy"), a)
+    return {"dir": d, "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "arrays": {name: list(a.shape) for name, a in arrays.items()}}
+
+
 # ------------------------------------------------------------------ main
 def main():
     args = parse()
@@ -1780,55 +1850,42 @@ def main():
         return r
 
     tm.lap("setup")
-    for _ in range(args.warmup):
-        step()
-    torch.cuda.synchronize()
-    if DIST:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for k in range(args.steps):
-        res = step(k)
-    torch.cuda.synchronize()
-    if DIST:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
-    if DIST:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-
-    def avg(a, b):
-        return sum(ev[k][a].elapsed_time(ev[k][b]) for k in range(args.steps)) / args.steps
-
-    hash_ms, sampled_ms, dedup_ms = avg(0, 2), avg(0, 1), avg(2, 3)
-    recs, rep, n_groups, owners = res
-    # every valid file lands on exactly one rank; groups never straddle ranks
-    tot = torch.tensor([recs.shape[0], n_groups, int((sizes != 0).sum())], dtype=torch.int64, device=cdev)
-    if DIST:
-        dist.all_reduce(tot)
-    # the exchange's balance: records each rank groups after the prefix all-to-all
-    per_rank = [torch.zeros(1, dtype=torch.int64, device=cdev) for _ in range(world)]
-    mine = torch.tensor([recs.shape[0]], dtype=torch.int64, device=cdev)
-    if DIST:
-        dist.all_gather(per_rank, mine)
-    else:
-        per_rank = [mine]
-    dedup_totals = {"records": int(tot[0]), "groups": int(tot[1]), "valid_files": int(tot[2]),
-                    "records_per_rank": [int(x.item()) for x in per_rank],
-                    "records_on_rank0": int(recs.shape[0]),
-                    "objects_created_on_rank0": int((owners == recs[:, 1]).sum()), "transport": transport}
-    if transport_note:
-        dedup_totals["transport_note"] = transport_note
-    assert dedup_totals["records"] == dedup_totals["valid_files"], dedup_totals
     files_total = n_total * args.steps
-    s_hash_ms, s_sampled_ms = hash_ms, sampled_ms
-    serial = {"value": files_total / elapsed, "ms_per_step": elapsed / args.steps * 1e3,
-              "note": "each step's hashing, then its dedup, on one stream (the kernel breakdown below)"}
-    value = serial["value"]
+    # the pipelined steps give the value wherever they can run; the serial steps then run
+    # beside them only with --full (their kernel breakdown, and a second result to compare)
+    overlap = rccl is not None and not args.no_overlap
+    serial = res = None
+    if args.full or not overlap:
+        for _ in range(args.warmup):
+            step()
+        torch.cuda.synchronize()
+        if DIST:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for k in range(args.steps):
+            res = step(k)
+        torch.cuda.synchronize()
+        if DIST:
+            dist.barrier()
+        elapsed = time.perf_counter() - t0
+        if DIST:
+            t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t.item())
+
+        def avg(a, b):
+            return sum(ev[k][a].elapsed_time(ev[k][b]) for k in range(args.steps)) / args.steps
+
+        hash_ms, sampled_ms, dedup_ms = avg(0, 2), avg(0, 1), avg(2, 3)
+        s_hash_ms, s_sampled_ms = hash_ms, sampled_ms
+        serial = {"value": files_total / elapsed, "ms_per_step": elapsed / args.steps * 1e3,
+                  "note": "each step's hashing, then its dedup, on one stream (the kernel breakdown below)"}
+        value = serial["value"]
+        d_last = d_hash  # the hashes of the last timed step
     pipelined = None
     clock_res = None
-    if rccl is not None and not args.no_overlap:
+    if overlap:
         # The same K steps as an indexer runs consecutive batches: batch k's exchange and
         # grouping (sd_cas_dedup_mgpu, its host syncs, the RCCL collectives) on one stream
         # while batch k+1 hashes on another; two hash buffers alternate.
@@ -1839,7 +1896,8 @@ def main():
         hs = torch.cuda.Stream(device=dev, priority=-1)
         ds = torch.cuda.Stream(device=dev, priority=0)
         d_hash2 = [d_hash, torch.empty_like(d_hash)]
-        ser = (recs.clone(), owners.clone())  # the runner's output buffers are reused by every call
+        # the serial result (--full), kept: the runner's output buffers are reused by every call
+        ser = (res[0].clone(), res[3].clone(), res[2]) if serial else None
         e_hash = [torch.cuda.Event() for _ in range(2)]
         e_ded = [torch.cuda.Event() for _ in range(2)]
         ded_seen = [False, False]
@@ -1872,7 +1930,7 @@ def main():
                 ded_seen[b] = True
             return r
 
-        tm.lap("steps_serial")
+        tm.lap("steps_serial" if serial else "setup")
         pipelined_steps(args.warmup)
         torch.cuda.synchronize()
         if DIST:
@@ -1890,26 +1948,64 @@ def main():
             t = torch.tensor([p_elapsed], dtype=torch.float64, device=cdev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             p_elapsed = float(t.item())
-        # the last batch's exchange gives the serial pass's result exactly
-        same = (pres[2] == n_groups and pres[0].shape == ser[0].shape and torch.equal(pres[0], ser[0])
-                and torch.equal(pres[3], ser[1]))
+        # the last batch's exchange gives the serial pass's result exactly (--full: both ran)
+        same = None
+        if ser is not None:
+            same = (pres[2] == ser[2] and pres[0].shape == ser[0].shape and torch.equal(pres[0], ser[0])
+                    and torch.equal(pres[3], ser[1]))
+        d_last = d_hash2[(args.steps - 1) & 1]
         del d_hash2, ser
         p_sampled = sum(pev[k][0].elapsed_time(pev[k][1]) for k in range(args.steps)) / args.steps
         p_hash = sum(pev[k][0].elapsed_time(pev[k][2]) for k in range(args.steps)) / args.steps
         pipelined = {"value": files_total / p_elapsed, "ms_per_step": p_elapsed / args.steps * 1e3,
-                     "equal_to_serial": bool(same), "sampled_ms": p_sampled, "hash_ms": p_hash,
+                     "equal_to_serial": None if same is None else bool(same), "sampled_ms": p_sampled,
+                     "hash_ms": p_hash,
                      "note": "batch k's dedup (sd_cas_dedup_mgpu) on one stream while batch k+1 hashes on "
                              "another; the value"}
-        assert same, "the pipelined steps' dedup differs from the serial steps'"
+        assert same is not False, "the pipelined steps' dedup differs from the serial steps'"
+        res = pres
         value, elapsed = pipelined["value"], p_elapsed
         # the roofline comes from the timed region that gives `value`: these steps' own events
         sampled_ms, hash_ms = p_sampled, p_hash
+
+    recs, rep, n_groups, owners = res
+    # every valid file lands on exactly one rank; groups never straddle ranks
+    tot = torch.tensor([recs.shape[0], n_groups, int((sizes != 0).sum())], dtype=torch.int64, device=cdev)
+    if DIST:
+        dist.all_reduce(tot)
+    # the exchange's balance: records each rank groups after the prefix all-to-all
+    per_rank = [torch.zeros(1, dtype=torch.int64, device=cdev) for _ in range(world)]
+    mine = torch.tensor([recs.shape[0]], dtype=torch.int64, device=cdev)
+    if DIST:
+        dist.all_gather(per_rank, mine)
+    else:
+        per_rank = [mine]
+    dedup_totals = {"records": int(tot[0]), "groups": int(tot[1]), "valid_files": int(tot[2]),
+                    "records_per_rank": [int(x.item()) for x in per_rank],
+                    "records_on_rank0": int(recs.shape[0]),
+                    "objects_created_on_rank0": int((owners == recs[:, 1]).sum()), "transport": transport}
+    if transport_note:
+        dedup_totals["transport_note"] = transport_note
+    assert dedup_totals["records"] == dedup_totals["valid_files"], dedup_totals
+    dumped = None
+    if args.dump_outputs:  # the last timed step's outputs, before anything else runs
+        dumped = dump_outputs(args.dump_outputs, d_last, n, res, f".rank{rank}" if world > 1 else "")
+    if serial:
+        kernels = {"hash_ms": s_hash_ms, "sampled_ms": s_sampled_ms, "whole_ms": s_hash_ms - s_sampled_ms,
+                   "dedup_and_exchange_ms": dedup_ms,
+                   "host_overhead_ms": serial["ms_per_step"] - s_hash_ms - dedup_ms,
+                   "sampled_files": batch.n_sampled, "whole_files": batch.n_whole,
+                   "note": "the serial steps' event breakdown (steps_serial)"}
+    else:
+        kernels = {"hash_ms": hash_ms, "sampled_ms": sampled_ms, "whole_ms": hash_ms - sampled_ms,
+                   "sampled_files": batch.n_sampled, "whole_files": batch.n_whole,
+                   "note": "the pipelined steps' hash kernels (the serial steps' breakdown needs --full)"}
 
     # roofline of the dominant kernels, the sampled pair k_cas_sampled_lanes + _merge (81 % of
     # the shard's compressions, one unit: the merge finishes what the lanes kernel starts),
     # timed on its own with HIP events on its launch stream: 953 compressions x 672 VALU
     # lane-ops per sampled file; bytes = 57 352 B message read + 32 B hash written per file
-    valu_peak = ctx.valu_peak()
+    valu_peak = ctx.valu_peak() if args.full else None  # a measurement of its own
     dom_comp = 953 * batch.n_sampled
     dom_bytes = batch.n_sampled * (SAMPLED_MSG + 32)
     dom = valu_roof(dom_comp, sampled_ms)
@@ -1941,7 +2037,7 @@ def main():
                      "frac_of_issue_ceiling_at_clock": (
                          dom["achieved"] * 1e12 / (G_MIX_LANE_OPS_PER_CLK * N_CUS * clock_res["sclk_mhz_median"] * 1e6)
                          if clock_res else None),
-                     "measured_valu_peak": valu_peak / 1e12,
+                     "measured_valu_peak": valu_peak / 1e12 if valu_peak else None,
                      "frac_of_measured_peak": dom["achieved"] * 1e12 / valu_peak if valu_peak else None,
                      "issue_rate_pmc": pmc_issue_rate(SAMPLED_KERNELS[0], s_grid[0]),
                      "hbm": {"achieved": dom_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -1962,14 +2058,46 @@ def main():
                              note="the library's host thread budget (sd_host_cpu_budget): min(affinity, cgroup quota) "
                                   "/ LOCAL_WORLD_SIZE; every call's readers, CPU-path workers and co-hashing threads "
                                   "are capped by it"),
-        "kernels": {"hash_ms": s_hash_ms, "sampled_ms": s_sampled_ms, "whole_ms": s_hash_ms - s_sampled_ms,
-                    "dedup_and_exchange_ms": dedup_ms,
-                    "host_overhead_ms": serial["ms_per_step"] - s_hash_ms - dedup_ms,
-                    "sampled_files": batch.n_sampled, "whole_files": batch.n_whole,
-                    "note": "the serial steps' event breakdown (steps_serial)"},
+        "kernels": kernels,
         "dedup": dedup_totals,
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     tm.lap("steps_pipelined" if pipelined else "steps_serial")
+
+    def finish():
+        """The run's timing and launch records, the process group's end, and the line."""
+        if comm is not None:
+            comm.close()
+        total_s = time.perf_counter() - t_main
+        tot = torch.tensor([total_s], dtype=torch.float64, device=cdev)
+        if DIST:
+            dist.all_reduce(tot, op=dist.ReduceOp.MAX)
+        try:  # the process's whole life so far: interpreter start, imports, launch included
+            import psutil
+            proc_s = round(time.time() - psutil.Process().create_time(), 3)
+        except Exception:  # noqa: BLE001 -- a diagnostic
+            proc_s = None
+        out["timing"] = {"rank0_s": dict(tm), "rank0_total_s": round(total_s, 3), "rank0_process_s": proc_s,
+                         "total_s_max_over_ranks": round(float(tot.item()), 3),
+                         "host_threads_budget": _native.host_cpu_budget()["budget"],
+                         "note": "wall seconds per leg on rank 0, from main() to the line (the process's import and "
+                                 "launch before main() excluded); *_oracle_check legs compare with the committed "
+                                 "oracle goldens unless --oracle-live"}
+        out["launch"] = {"requested_gpus": args.gpus, "mode": mode, "full": bool(args.full),
+                         "spawned_by_bench": os.environ.get("SD_BENCH_SPAWNED") == "1",
+                         "share_gpu": bool(args.share_gpu),
+                         "devices_used": len({(r % torch.cuda.device_count()) if args.share_gpu else r
+                                              for r in range(world)}) if world > 1 else 1}
+        if DIST:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:  # the full record is --full's
+            emit(out, json_out, (args.full_out or None) if args.full else None)
+
+    if not args.full:  # a plain run ends here: the timed steps, their outputs, the line
+        finish()
+        return
     # ---- the timed steps' output, checked (outside the timed regions) --------------------
     # (1) hashes: a fixed sample of every rank's shard against the C oracle
     ps = parity_sample(sizes, cids, twins, d_hash, start)
@@ -2129,33 +2257,7 @@ def main():
                                                       note="reference read schedule from files (page cache)")
         tm.lap("cpu_baseline")
         out["cpu_baseline"]["end_to_end_vs_library_cpu_path"] = end_to_end_summary(out)
-    if comm is not None:
-        comm.close()
-    total_s = time.perf_counter() - t_main
-    tot = torch.tensor([total_s], dtype=torch.float64, device=cdev)
-    if DIST:
-        dist.all_reduce(tot, op=dist.ReduceOp.MAX)
-    try:  # the process's whole life so far: interpreter start, imports, launch included
-        import psutil
-        proc_s = round(time.time() - psutil.Process().create_time(), 3)
-    except Exception:  # noqa: BLE001 -- a diagnostic
-        proc_s = None
-    out["timing"] = {"rank0_s": dict(tm), "rank0_total_s": round(total_s, 3), "rank0_process_s": proc_s,
-                     "total_s_max_over_ranks": round(float(tot.item()), 3),
-                     "host_threads_budget": _native.host_cpu_budget()["budget"],
-                     "note": "wall seconds per leg on rank 0, from main() to the line (the process's import and "
-                             "launch before main() excluded); *_oracle_check legs compare with the committed "
-                             "oracle goldens unless --oracle-live"}
-    out["launch"] = {"requested_gpus": args.gpus, "mode": mode,
-                     "spawned_by_bench": os.environ.get("SD_BENCH_SPAWNED") == "1",
-                     "share_gpu": bool(args.share_gpu),
-                     "devices_used": len({(r % torch.cuda.device_count()) if args.share_gpu else r
-                                          for r in range(world)}) if world > 1 else 1}
-    if DIST:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        emit(out, json_out, args.full_out or None)
+    finish()
 
 
 if __name__ == "__main__":

@@ -8,7 +8,7 @@ set -u
 A=${AB_A:-$PWD/ab/libsdcas_old.so}
 B=${AB_B:-$PWD/spacedrive_amd/libsdcas.so}
 TAG=${AB_TAG:-ab}
-ARGS=${AB_ARGS:---no-extras --no-cpu-baseline --config-files 0 --checksum-gib 0 --split-gib 0 --steps 30}
+ARGS=${AB_ARGS:---full --no-extras --no-cpu-baseline --config-files 0 --checksum-gib 0 --split-gib 0 --steps 30}
 mkdir -p gpurun_out/$TAG
 for r in 1 2 3; do
   for v in A B; do

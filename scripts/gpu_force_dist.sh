@@ -10,7 +10,7 @@ set -u
 mkdir -p gpurun_out
 export PYTHONUNBUFFERED=1
 timeout -k 10 ${FORCE_DIST_TIMEOUT:-600} python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-    --master-addr 127.0.0.1 --master-port ${MASTER_PORT:-29541} bench.py --gpus 1 --dist-backend nccl --force-dist \
+    --master-addr 127.0.0.1 --master-port ${MASTER_PORT:-29541} bench.py --full --gpus 1 --dist-backend nccl --force-dist \
     ${FORCE_DIST_ARGS:-} > gpurun_out/force_dist.json 2> gpurun_out/force_dist.err
 rc=$?; echo "force-dist rc=$rc"; tail -5 gpurun_out/force_dist.err; head -c 600 gpurun_out/force_dist.json; echo
 exit $rc

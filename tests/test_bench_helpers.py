@@ -231,3 +231,58 @@ def test_pmc_lookups_cover_the_default_launch_shapes():
     ck = bench.pmc_issue_rate("k_ck_leaf", bench.ck_leaf_grid(16 * 4096))
     assert ck is not None and 0.95 < ck["frac"] <= 1.02, ck
     assert bench.pmc_issue_rate("k_cas_sampled_lanes", 12345) is None
+
+
+# ------------------------------------------------------------------ --dump-outputs
+def test_dump_rows_are_fixed_and_bounded():
+    assert np.array_equal(bench.dump_rows(0), np.zeros(0, np.int64))
+    assert np.array_equal(bench.dump_rows(bench.DUMP_ROWS), np.arange(bench.DUMP_ROWS))
+    r = bench.dump_rows(1_250_000)
+    assert r.dtype == np.int64 and len(r) == bench.DUMP_ROWS and (np.diff(r) > 0).all() and r[-1] < 1_250_000
+    assert np.array_equal(r, bench.dump_rows(1_250_000))
+    # the default shard's dump: hashes float32 [k, 32] + 6 float64 columns of k rows + their row numbers
+    assert bench.DUMP_ROWS * (32 * 4 + 8 + 5 * 8 + 8) + 16 <= 64e6
+
+
+def test_u64_halves_are_exact():
+    x = np.array([0, 1, -1, (1 << 63) - 1, -(1 << 63), 0x0123456789ABCDEF, (1 << 53) + 1], np.int64)
+    h = bench.u64_halves(x)
+    assert h.dtype == np.float64 and h.shape == (len(x), 2)
+    back = (h[:, 0].astype(np.uint64) << np.uint64(32)) | h[:, 1].astype(np.uint64)
+    assert np.array_equal(back, x.view(np.uint64))
+
+
+def test_dump_outputs_writes_the_sampled_rows(tmp_path, monkeypatch):
+    """dump_outputs on host tensors: every array float32 / float64, the sampled rows the rows
+    dump_rows names, every integer exact, the same files at every call."""
+    import torch
+    monkeypatch.setattr(bench, "DUMP_ROWS", 100)
+    rng = np.random.default_rng(5)
+    n, m = 257, 180
+    h = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    recs = rng.integers(-(1 << 63), (1 << 63) - 1, (m, 2), dtype=np.int64)
+    recs[:, 1] = rng.integers(0, 10_000_000, m)
+    rep, own = rng.integers(0, 10_000_000, m), rng.integers(0, 10_000_000, m)
+    res = (torch.from_numpy(recs), torch.from_numpy(rep), 77, torch.from_numpy(own))
+    info = bench.dump_outputs(str(tmp_path / "a"), torch.from_numpy(h.reshape(-1).copy()), n, res)
+    bench.dump_outputs(str(tmp_path / "b"), torch.from_numpy(h.reshape(-1).copy()), n, res, suffix=".rank3")
+    a = {p.name[:-4]: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert info["bytes"] == sum(v.nbytes for v in a.values()) and set(info["arrays"]) == set(a)
+    hi, ri = bench.dump_rows(n), bench.dump_rows(m)
+    assert len(hi) == len(ri) == 100
+    assert a["hashes"].dtype == np.float32 and np.array_equal(a["hashes"], h[hi])
+    assert np.array_equal(a["hash_rows"], hi) and np.array_equal(a["record_rows"], ri)
+    assert np.array_equal(a["records"][:, :2], bench.u64_halves(recs[ri, 0]))
+    assert np.array_equal(a["records"][:, 2], recs[ri, 1])
+    assert np.array_equal(a["representative"], rep[ri]) and np.array_equal(a["owners"], own[ri])
+    assert a["counts"].tolist() == [m, 77]
+    assert all(v.dtype == np.float64 for k, v in a.items() if k != "hashes")
+    for name, v in a.items():
+        assert np.array_equal(np.load(tmp_path / "b" / (name + ".rank3.npy")), v)
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
