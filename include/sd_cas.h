@@ -281,6 +281,71 @@ int sd_file_checksums_learned(sd_cas_ctx* ctx, double out[4]);
 int sd_file_checksums(sd_cas_ctx* ctx, const char* const* paths, size_t n, char* out_hex65,
                       int32_t* status);
 
+/* ---------------------------------------------------------------- fingerprints */
+/* cas_id AND checksum of files whose bytes are already resident, from one copy of them: what
+ * the watcher's inner_update_file computes per file (core/src/location/manager/watcher/
+ * utils.rs:393 FileMetadata::new -> generate_cas_id, :438-446 file_checksum on the same path)
+ * and what a location that is identified and then validated computes per job.  A gather
+ * kernel builds each file's cas message -- le64(size) || file, or le64(size) || head || 4
+ * samples || tail (cas.rs:25-58) -- from the file's bytes in device memory into a staged
+ * extent; the cas and checksum kernels then run as they are.
+ * Semantics: results equal generate_cas_id(path, size) and file_checksum(path) for a file that
+ * holds exactly size = lens[i] bytes.  A caller whose metadata size may disagree with the
+ * file keeps using the path entries.  Empty ranges are hashed; the caller
+ * applies FileMetadata::new's skip of empty files, as with sd_cas_ids. */
+typedef struct sd_fingerprint_batch sd_fingerprint_batch;
+/* utils.rs:393,438-446 for device-resident files: files = byte ranges of one device buffer
+ * (host arrays; starts 16-B aligned, the buffer itself too, readable up to the next 64-byte
+ * boundary after each range, as for sd_checksum_batch_create); size hashed = lens[i].  The
+ * batch's device scratch (the staged messages) is allocated here, once. */
+int sd_fingerprint_batch_create(sd_cas_ctx* ctx, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                                sd_fingerprint_batch** out);
+void sd_fingerprint_batch_destroy(sd_fingerprint_batch* batch);
+/* [0] files [1] sampled [2] whole [3] file bytes [4] staged bytes (the scratch size, what
+ * the gather writes into) [5] cas compressions [6] checksum compressions [7] bytes the
+ * gather reads */
+int sd_fingerprint_batch_stats(const sd_fingerprint_batch* batch, uint64_t out[8]);
+/* the extents of the gathered messages: sd_cas_stage_plan's layout for sizes = lens */
+int sd_fingerprint_batch_extents(const sd_fingerprint_batch* batch, sd_extent* extents_out /* n */);
+/* utils.rs:393's message alone: the gather into the caller's buffer of >= stats[4] bytes
+ * (every message and its zero padding up to SD_STAGE_ALIGN; nothing else is written);
+ * afterwards sd_cas_batch_run over these extents gives the cas hashes.  Asynchronous. */
+int sd_fingerprint_batch_gather(sd_cas_ctx* ctx, const sd_fingerprint_batch* batch, const uint8_t* d_data,
+                                uint8_t* d_staged, void* stream);
+/* utils.rs:393,438-446: gather into the batch's own scratch + cas kernels + checksum kernels;
+ * d_cas_hash32 and d_checksum32 (device) n x 32 B each; asynchronous on stream.  Runs of one
+ * batch are ordered (one stream, or an event between streams), as for sd_cas_batch. */
+int sd_fingerprint_batch_run(sd_cas_ctx* ctx, const sd_fingerprint_batch* batch, const uint8_t* d_data,
+                             uint8_t* d_cas_hash32, uint8_t* d_checksum32, void* stream);
+/* Drop-in over host memory (pinned or pageable; utils.rs:393,438-446 on data already read):
+ * n ranges of `data` (starts 16-B aligned) -> a 17-byte cas_id hex and a 65-byte checksum hex
+ * each, every file byte sent to the device once.  Consecutive ranges that fit a window
+ * ("fingerprint_window_mb", default 256) go up together, and one fingerprint batch runs per
+ * window; two windows alternate so the copies
+ * overlap the kernels.  A range longer than the window streams through the checksum kernels
+ * window by window, and the host copies its 57 352-byte cas message (six pieces, ~0.02 % of
+ * such a range) into a pinned side list hashed as one ordinary cas batch at the end.  The GPU
+ * route only: no host thread co-hashes and no route is learned here -- from files both routes
+ * are bound by the reads, and the right policy needs measurements nobody
+ * has; sd_cpu_fingerprints is the explicit host sibling.
+ * Copies: ranges that ascend in `data` with no whole page between them that holds no range
+ * byte keep their relative offsets and go up as ONE H2D per window, starting on a 128-B device
+ * line (the bytes between two such neighbours ride along; as in sd_checksums, no page that
+ * holds no range byte is read); a range after a hole, or one of 1 MiB or more that would start
+ * mid-line, starts a copy of its own on the next 128-B line. */
+int sd_fingerprints(sd_cas_ctx* ctx, const uint8_t* data, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                    char* out_hex17, char* out_hex65);
+/* sd_fingerprints on this context so far: [0] bytes sent H2D -- payload: each range's bytes,
+ * counted when the range is put into its copy, and each side-list message's 57 352 (not the
+ * alignment bytes that ride along between neighbours, nor the plans' tables), so a call adds
+ * exactly sum(lens) + 57352 x its large ranges when every byte went up once; [1] files gathered
+ * on the device; [2] large ranges (message staged by the host) */
+int sd_fingerprints_stats(sd_cas_ctx* ctx, uint64_t out[3]);
+/* utils.rs:393,438-446 on host cores, no device: each message built from its range, both
+ * hashed by the library's CPU BLAKE3 on nthreads threads */
+int sd_cpu_fingerprints(const uint8_t* data, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                        char* out_hex17, char* out_hex65, int nthreads);
+
 /* ---------------------------------------------------------------- latency path */
 /* Single-file generate_cas_id (cas.rs:23) / file_checksum (hash.rs:10) for the
  * reference's per-file callers -- the location watcher (core/src/location/manager/
@@ -505,7 +570,8 @@ int sd_checksum_batch_time(sd_cas_ctx* ctx, const sd_checksum_batch* batch, cons
  * of 16 measured best there); "host_cpu_budget" (0 = resolved, see sd_host_cpu_budget): the cap
  * on every call's host threads -- thread counts callers pass (nthreads) and the knobs above
  * are clamped to it; "comm_timeout_ms" (300000): the longest sd_cas_dedup_mgpu waits for its
- * RCCL peers (0 = no bound).  Unknown keys fail with SD_ERR_INVALID. */
+ * RCCL peers (0 = no bound); "fingerprint_window_mb" (256): the device window of ranges
+ * sd_fingerprints uploads at once (a longer range streams).  Unknown keys fail with SD_ERR_INVALID. */
 int sd_cas_set_tuning(const char* key, int value);
 int sd_cas_get_tuning(const char* key, int* value);
 /* Read-only probe over d_buf[0, bytes) (bytes a multiple of 4096) for calibrating the

@@ -39,6 +39,11 @@ pub struct sd_split_checksum {
 }
 
 #[repr(C)]
+pub struct sd_fingerprint_batch {
+    _p: [u8; 0],
+}
+
+#[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct sd_extent {
     pub size: u64,
@@ -87,6 +92,22 @@ extern "C" {
     pub fn sd_file_checksums_learned(ctx: *mut sd_cas_ctx, out: *mut f64) -> c_int;
     // what the context learned for sd_checksums' co-hashed calls vs the CPU path alone
     pub fn sd_checksums_learned(ctx: *mut sd_cas_ctx, out: *mut f64) -> c_int;
+    // fingerprints: cas_id and checksum of resident files from one copy of their bytes
+    // (watcher/utils.rs:393,438-446); device-resident batches, the host drop-in, the CPU sibling
+    pub fn sd_fingerprint_batch_create(ctx: *mut sd_cas_ctx, offsets: *const u64, lens: *const u64, n: usize,
+                                       out: *mut *mut sd_fingerprint_batch) -> c_int;
+    pub fn sd_fingerprint_batch_destroy(batch: *mut sd_fingerprint_batch);
+    pub fn sd_fingerprint_batch_stats(batch: *const sd_fingerprint_batch, out: *mut u64) -> c_int;
+    pub fn sd_fingerprint_batch_extents(batch: *const sd_fingerprint_batch, extents_out: *mut sd_extent) -> c_int;
+    pub fn sd_fingerprint_batch_gather(ctx: *mut sd_cas_ctx, batch: *const sd_fingerprint_batch, d_data: *const u8,
+                                       d_staged: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn sd_fingerprint_batch_run(ctx: *mut sd_cas_ctx, batch: *const sd_fingerprint_batch, d_data: *const u8,
+                                    d_cas_hash32: *mut u8, d_checksum32: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn sd_fingerprints(ctx: *mut sd_cas_ctx, data: *const u8, offsets: *const u64, lens: *const u64, n: usize,
+                           out_hex17: *mut c_char, out_hex65: *mut c_char) -> c_int;
+    pub fn sd_fingerprints_stats(ctx: *mut sd_cas_ctx, out: *mut u64) -> c_int;
+    pub fn sd_cpu_fingerprints(data: *const u8, offsets: *const u64, lens: *const u64, n: usize,
+                               out_hex17: *mut c_char, out_hex65: *mut c_char, nthreads: c_int) -> c_int;
     // the CPU path (no device)
     pub fn sd_cpu_simd_lanes() -> c_int;
     pub fn sd_cpu_cas_ids_files(paths: *const *const c_char, sizes: *const u64, n: usize, out_hex17: *mut c_char,
@@ -251,6 +272,32 @@ pub fn checksum_blocking(path: &Path) -> Result<String, io::Error> {
         }
     };
     per_file(rc, &[st], &hex, 65, 64).pop().expect("one result")
+}
+
+/// cas_id and checksum of files already read into one buffer (`ranges`: (offset, len), offsets
+/// 16-byte aligned), every byte sent to the device once: what `inner_update_file` computes per
+/// file (watcher/utils.rs:393 and :438-446).  Equal to generate_cas_id(path, len) and
+/// file_checksum(path) for files holding exactly `len` bytes; empty ranges are hashed, the
+/// caller applies FileMetadata::new's skip.  Without a device: the CPU path on 16 threads.
+pub fn fingerprints_blocking(data: &[u8], ranges: &[(u64, u64)]) -> Result<Vec<(String, String)>, io::Error> {
+    let n = ranges.len();
+    if ranges.iter().any(|r| r.0 % 16 != 0 || r.0.checked_add(r.1).map_or(true, |e| e > data.len() as u64)) {
+        return Err(io::Error::new(io::ErrorKind::InvalidInput, "range misaligned or beyond the buffer"));
+    }
+    let offs: Vec<u64> = ranges.iter().map(|r| r.0).collect();
+    let lens: Vec<u64> = ranges.iter().map(|r| r.1).collect();
+    let mut h17 = vec![0 as c_char; 17 * n];
+    let mut h65 = vec![0 as c_char; 65 * n];
+    let rc = unsafe {
+        match ctx() {
+            Ok(g) => sd_fingerprints(g.0, data.as_ptr(), offs.as_ptr(), lens.as_ptr(), n, h17.as_mut_ptr(), h65.as_mut_ptr()),
+            Err(_) => sd_cpu_fingerprints(data.as_ptr(), offs.as_ptr(), lens.as_ptr(), n, h17.as_mut_ptr(), h65.as_mut_ptr(), 16),
+        }
+    };
+    if rc != SD_OK {
+        return Err(io::Error::new(io::ErrorKind::Other, last_error()));
+    }
+    Ok((0..n).map(|i| (hex_at(&h17, i, 17, 16), hex_at(&h65, i, 65, 64))).collect())
 }
 
 /// libsdcas's RCCL communicator for a multi-GPU library scan (one process per GPU).

@@ -131,6 +131,15 @@ SIGNATURES = [
     ("sd_host_cpu_budget", I32, [P]),
     ("sd_host_numa", I32, [P]),
     ("sd_comm_rccl_info", I32, [ctypes.POINTER(I32), ctypes.c_char_p, SZ]),
+    ("sd_fingerprint_batch_create", I32, [P, P, P, SZ, ctypes.POINTER(P)]),
+    ("sd_fingerprint_batch_destroy", None, [P]),
+    ("sd_fingerprint_batch_stats", I32, [P, P]),
+    ("sd_fingerprint_batch_extents", I32, [P, P]),
+    ("sd_fingerprint_batch_gather", I32, [P, P, P, P, P]),
+    ("sd_fingerprint_batch_run", I32, [P, P, P, P, P, P]),
+    ("sd_fingerprints", I32, [P, P, P, P, SZ, P, P]),
+    ("sd_fingerprints_stats", I32, [P, P]),
+    ("sd_cpu_fingerprints", I32, [P, P, P, SZ, P, P, I32]),
 ]
 
 

@@ -117,6 +117,55 @@ def file_checksum(path: Union[str, os.PathLike], device: Optional[int] = None) -
     return out.raw[:64].decode()
 
 
+def _host_ranges(data, offsets, lens):
+    """(keepalive, address, offsets u64, lens u64) of n byte ranges of a host buffer: a numpy
+    array, a CPU torch tensor (pinned or not) or any object with the buffer protocol."""
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    ls = np.ascontiguousarray(lens, dtype=np.uint64)
+    if len(offs) != len(ls):
+        raise ValueError("offsets and lens differ in length")
+    if hasattr(data, "data_ptr"):  # torch tensor
+        if data.is_cuda or not data.is_contiguous():
+            raise ValueError("data must be a contiguous host tensor")
+        addr, size = data.data_ptr(), data.numel() * data.element_size()
+    else:
+        data = data if isinstance(data, np.ndarray) else np.frombuffer(data, np.uint8)
+        if not data.flags.c_contiguous:
+            raise ValueError("data must be contiguous")
+        addr, size = data.ctypes.data, data.nbytes
+    if len(ls) and int((offs + ls).max()) > size:
+        raise ValueError("a range ends beyond the buffer")
+    return data, addr, offs, ls
+
+
+def _split_hex(buf, width: int, n: int) -> List[str]:
+    raw = buf.raw  # one copy: each .raw access copies the whole buffer
+    return [raw[(width + 1) * i:(width + 1) * i + width].decode() for i in range(n)]
+
+
+def fingerprints(data, offsets, lens, device: Optional[int] = None):
+    """cas_id and checksum of n files that are byte ranges of one host buffer, every byte sent
+    to the device once (sd_fingerprints; watcher/utils.rs:393,438-446 on data already read)
+    -> (cas_ids, checksums).  Range starts are 16-byte aligned; the size hashed is ``lens[i]``.
+    Empty ranges are hashed: the caller applies FileMetadata.new's skip."""
+    keep, addr, offs, ls = _host_ranges(data, offsets, lens)
+    n = len(ls)
+    if n == 0:
+        return [], []
+    ctx = default_context(device)
+    o17, o65 = ctypes.create_string_buffer(17 * n), ctypes.create_string_buffer(65 * n)
+    check(lib().sd_fingerprints(ctx.handle, addr, _ptr(offs), _ptr(ls), n, o17, o65))
+    return _split_hex(o17, 16, n), _split_hex(o65, 64, n)
+
+
+def fingerprints_stats(device: Optional[int] = None) -> dict:
+    """sd_fingerprints_stats: bytes sent to the device, files whose message the device gathered,
+    large ranges (message staged by the host), since the context was created."""
+    v = np.zeros(3, np.uint64)
+    check(lib().sd_fingerprints_stats(default_context(device).handle, _ptr(v)))
+    return {"h2d_bytes": int(v[0]), "gathered": int(v[1]), "large": int(v[2])}
+
+
 def cas_ids_files_stats(device: Optional[int] = None) -> dict:
     """Routes taken by generate_cas_ids (sd_cas_ids_files) on the device's default context:
     calls hashed on the CPU path by the batch-size policy ("batch_cpu_max") and calls that

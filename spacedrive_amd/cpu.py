@@ -83,6 +83,17 @@ def cas_ids_staged(staged: np.ndarray, extents: np.ndarray, status: Optional[np.
     return [raw[17 * i:17 * i + 16].decode() for i in range(n)]
 
 
+def fingerprints(data, offsets, lens, nthreads: int = THREADS):
+    """sd_cpu_fingerprints: (cas_ids, checksums) of n byte ranges of a host buffer (starts
+    16-byte aligned, size hashed = lens[i]) on host threads; no device."""
+    from .cas import _host_ranges, _split_hex
+    keep, addr, offs, ls = _host_ranges(data, offsets, lens)
+    n = len(ls)
+    o17, o65 = ctypes.create_string_buffer(17 * max(n, 1)), ctypes.create_string_buffer(65 * max(n, 1))
+    check(lib().sd_cpu_fingerprints(addr, offs.ctypes.data, ls.ctypes.data, n, o17, o65, nthreads))
+    return _split_hex(o17, 16, n), _split_hex(o65, 64, n)
+
+
 def blake3(data: bytes) -> bytes:
     """Full 32-byte BLAKE3 of a host buffer (sd_cpu_checksums of one range)."""
     buf = np.frombuffer(bytes(data) + bytes(64), np.uint8)

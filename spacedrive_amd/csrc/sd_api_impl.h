@@ -184,6 +184,20 @@ struct sd_cas_batch {
     const uint4* d_wrows() const { return tab.at<uint4>(o_wrows); }
 };
 
+// cas_id and checksum of files that are byte ranges of one device buffer (sd_fingerprint.cpp):
+// the gather's tables, the two batches it feeds, and the staged messages between them
+struct sd_fingerprint_batch {
+    size_t n = 0;
+    GatherPlan gp;
+    sdi::Tables tab;  // rows, tile_first
+    size_t o_rows = 0, o_tiles = 0;
+    sd_cas_batch cas;
+    sd_checksum_batch ck;
+    sdi::DevBuf scratch;  // gp.staged_bytes: what the gather writes and the cas kernels read
+    const gather_row* d_rows() const { return tab.at<gather_row>(o_rows); }
+    const uint32_t* d_tiles() const { return tab.at<uint32_t>(o_tiles); }
+};
+
 namespace sdi {
 
 // per-call working set of the host drop-in entry points; its batches persist with the slot
@@ -195,6 +209,7 @@ struct Slot {
     Tables aux;  // a call's own tables (the split checksum's block map), grown with the slot
     sd_cas_batch cas;
     sd_checksum_batch ck;
+    sd_fingerprint_batch fp;  // sd_fingerprints' window
     hipEvent_t drained = nullptr;  // sync()'s blocking-sync event
     Slot() = default;
     Slot(const Slot&) = delete;
@@ -229,6 +244,8 @@ struct sd_cas_ctx {
     std::atomic<uint64_t> checksum_bytes_gpu{0}, checksum_bytes_cpu_split{0};
     std::atomic<uint64_t> cas_ids_gpu_files{0}, cas_ids_host_files{0};  // sd_cas_ids: who hashed
     std::atomic<uint64_t> checksums_gpu_bytes{0}, checksums_host_bytes{0};  // sd_checksums: who hashed
+    // sd_fingerprints: bytes sent H2D, files gathered on the device, large ranges
+    std::atomic<uint64_t> fp_h2d_bytes{0}, fp_gathered{0}, fp_large{0};
     std::mutex split_mu;
     SplitRoutes split_routes;  // sd_file_checksums: the split or the CPU path, learned (sd_host.h)
     uint64_t split_routes_gen = 0;  // split_route_tuning_gen() the rates were learned under
@@ -326,4 +343,10 @@ void run_checksum_batch(const sd_checksum_batch* b, const uint8_t* d_data, uint8
 void plan_cas_batch(sd_cas_batch* b, const sd_extent* ext, size_t n, hipStream_t stream);
 void run_cas_batch(const sd_cas_batch* b, const uint8_t* d_staged, uint8_t* d_hash32, hipStream_t s,
                    int parts = SD_PART_SAMPLED | SD_PART_WHOLE);
+// fingerprint batches (device, sd_fingerprint.cpp): gather -> d_staged; gather + cas + checksum
+void plan_fingerprint_batch(sd_fingerprint_batch* b, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                            hipStream_t stream);
+void run_fingerprint_gather(const sd_fingerprint_batch* b, const uint8_t* d_data, uint8_t* d_staged, hipStream_t s);
+void run_fingerprint_batch(const sd_fingerprint_batch* b, const uint8_t* d_data, uint8_t* d_cas_hash32,
+                           uint8_t* d_checksum32, hipStream_t s);
 }  // namespace sdi

@@ -78,7 +78,8 @@ enum sd_tune_key {
     SD_TUNE_CHECKSUM_SPLIT_BLOCKS = 18,    // sd_file_checksums' split: 1 = claims by blocks, 0 = by files
     SD_TUNE_CHECKSUM_SPLIT_ADAPT = 19,     // split-eligible calls: 0 = always split, k = learn the faster route
     SD_TUNE_COMM_TIMEOUT_MS = 20,          // sd_cas_dedup_mgpu over RCCL: longest wait for the peers (0 = none)
-    SD_TUNE_NKEYS = 21
+    SD_TUNE_FINGERPRINT_WINDOW_MB = 21,    // sd_fingerprints: device window of ranges per upload (MiB)
+    SD_TUNE_NKEYS = 22
 };
 int tuning_get(int key);
 
@@ -218,6 +219,32 @@ struct CkPlan {
     uint64_t total_bytes = 0, compressions = 0, blocks = 0;
 };
 void plan_checksum(CkPlan& p, const uint64_t* offsets, const uint64_t* lens, size_t n);
+
+// ------------------------------------------------------------------ fingerprints
+// k_cas_gather (gather.hip) builds each file's cas message from its resident bytes.  Its
+// output is cut into 16-byte units; the units of all files, in file order, form one flat
+// space cut into tiles of SD_GATHER_TILE_UNITS units, one workgroup each, so a million
+// small files cost as many workgroups as their bytes need and a sampled file 3.5.
+struct gather_row {
+    uint64_t data_off;  // first file byte in the data buffer (16-B aligned)
+    uint64_t msg_off;   // the message's offset in the staged buffer
+    uint64_t len;       // file length = the size hashed; the kind follows from it (cas.rs:27)
+    uint64_t unit0;     // first 16-byte output unit of this file in the flat space
+};
+constexpr uint32_t SD_GATHER_TILE_UNITS = 1024;
+struct GatherPlan {
+    std::vector<sd_extent> extents;    // as sd_cas_stage_plan lays them out for sizes = lens
+    std::vector<gather_row> rows;      // n files + one sentinel row (unit0 = units)
+    std::vector<uint32_t> tile_first;  // tile t's units belong to files [tile_first[t], tile_first[t + 1]]
+    uint64_t units = 0, staged_bytes = 0, file_bytes = 0, read_bytes = 0;
+    uint32_t n_sampled = 0, n_whole = 0;
+};
+// throws SD_ERR_INVALID on a start that is not 16-byte aligned
+void plan_gather(GatherPlan& p, const uint64_t* offsets, const uint64_t* lens, size_t n);
+// The cas message of a file that holds exactly `len` bytes (cas.rs:25-58 on memory): le64(len)
+// || file, or le64(len) || head || 4 samples || tail.  out holds 8 + min(len, 102400) or
+// SD_SAMPLED_MSG_LEN bytes; returns the message length.
+uint32_t cas_message_from_bytes(const uint8_t* file, uint64_t len, uint8_t* out);
 
 // One file over R ranks (sd_split_range, include/sd_cas.h): nb = max(1, ceil(total / 1 MiB))
 // blocks, rank r holds blocks [b0, b1) = [r*q, min((r+1)*q, nb)), q = ceil(nb / R), i.e.

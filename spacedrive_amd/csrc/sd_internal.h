@@ -39,6 +39,10 @@ hipError_t launch_synth_stage_cas(const uint64_t* sizes, const uint64_t* cids, c
                                   const sd_extent* ext, uint32_t n, uint8_t* staged, hipStream_t s);
 hipError_t launch_synth_fill(uint64_t cid, uint32_t twin, uint64_t offset, uint64_t len, uint8_t* out,
                              hipStream_t s);
+// cas messages of the files of a fingerprint batch, from their resident bytes (gather.hip;
+// rows / tile_first: sd_host.h GatherPlan)
+hipError_t launch_cas_gather(const uint8_t* data, const gather_row* rows, const uint32_t* tile_first,
+                             uint64_t total_units, uint8_t* staged, hipStream_t s);
 hipError_t launch_read_probe(const uint8_t* buf, uint64_t bytes, int pattern, hipStream_t s);
 constexpr uint32_t VALU_PEAK_OPS_PER_ITER = 384;  // k_valu_peak: VALU instructions per wave per iteration
 hipError_t launch_valu_peak(uint32_t* sink, uint32_t iters, uint32_t grid, hipStream_t s);

@@ -81,6 +81,9 @@ class Context:
     def checksum_batch(self, offsets, lens) -> "ChecksumBatch":
         return ChecksumBatch(self, offsets, lens)
 
+    def fingerprint_batch(self, offsets, lens) -> "FingerprintBatch":
+        return FingerprintBatch(self, offsets, lens)
+
     # -------------------------------------------------------------- files -> device hashes
     def hashes_files(self, paths, sizes, d_hash32, d_valid=None, nthreads: int = 16) -> np.ndarray:
         """sd_cas_hashes_files: generate_cas_id's messages of these files hashed into
@@ -284,6 +287,51 @@ class ChecksumBatch:
     def close(self) -> None:
         if self.handle:
             lib().sd_checksum_batch_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FingerprintBatch:
+    """Prepared fingerprint batch (sd_fingerprint_batch): cas hash and checksum of files that
+    are byte ranges of one device buffer, the cas messages gathered on the device."""
+
+    def __init__(self, ctx: Context, offsets, lens):
+        self.ctx = ctx
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self.lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        if len(self.offsets) != len(self.lens):
+            raise ValueError("offsets and lens differ in length")
+        h = ctypes.c_void_p()
+        check(lib().sd_fingerprint_batch_create(ctx.handle, _ptr(self.offsets), _ptr(self.lens), len(self.lens),
+                                                ctypes.byref(h)))
+        self.handle = h
+        st = np.zeros(8, np.uint64)
+        check(lib().sd_fingerprint_batch_stats(h, _ptr(st)))
+        (self.n, self.n_sampled, self.n_whole, self.file_bytes, self.staged_bytes, self.cas_compressions,
+         self.checksum_compressions, self.gather_read_bytes) = (int(v) for v in st)
+        self.extents = np.zeros(self.n, dtype=EXTENT_DTYPE)
+        check(lib().sd_fingerprint_batch_extents(h, _ptr(self.extents)))
+
+    def gather(self, d_data: torch.Tensor, d_staged: torch.Tensor, stream=None) -> None:
+        """The cas messages alone, into d_staged (>= staged_bytes) at ``extents``."""
+        assert d_staged.numel() >= self.staged_bytes and d_data.is_cuda and d_staged.is_cuda
+        check(lib().sd_fingerprint_batch_gather(self.ctx.handle, self.handle, _ptr(d_data), _ptr(d_staged),
+                                                _stream(stream)))
+
+    def run(self, d_data: torch.Tensor, d_cas_hash32: torch.Tensor, d_checksum32: torch.Tensor, stream=None) -> None:
+        """gather + cas kernels + checksum kernels; n x 32 B each (the cas_id is a row's first 8)."""
+        assert d_cas_hash32.numel() >= 32 * self.n and d_checksum32.numel() >= 32 * self.n and d_data.is_cuda
+        check(lib().sd_fingerprint_batch_run(self.ctx.handle, self.handle, _ptr(d_data), _ptr(d_cas_hash32),
+                                             _ptr(d_checksum32), _stream(stream)))
+
+    def close(self) -> None:
+        if self.handle:
+            lib().sd_fingerprint_batch_destroy(self.handle)
             self.handle = None
 
     def __del__(self):  # pragma: no cover
