@@ -415,6 +415,78 @@ int sd_dedup_group(sd_cas_ctx* ctx, uint64_t* d_records, uint64_t m, int flags, 
 int sd_dedup_owners(sd_cas_ctx* ctx, const uint64_t* d_records, uint64_t m, const uint64_t* d_rep,
                     uint64_t chunk_size, uint64_t* d_owner, void* stream);
 
+/* ---------------------------------------------------------------- Object index */
+/* Which Object of the library already owns a cas_id: the join identifier_job_step does per
+ * 100-row step through the DB (file_identifier/mod.rs:168-175, `find_many ... cas_id in_vec`)
+ * before it links each file to the FIRST such Object (mod.rs:189-225).  The index keeps, on
+ * the device, one entry per cas_id key (the big-endian u64 of its first 8 hash bytes = the
+ * 16 hex digits read as a number, as in d_records) -> Object id, so a re-scan, a second
+ * location, the watcher's single file or a resumed job link to Objects of earlier scans
+ * without a DB round trip per step.  Object ids are the host's (the DB's); any u64 is legal.
+ * The cycle: scan (sd_dedup_owners_indexed gives owners and the new group heads) -> the host
+ * creates those Objects and gives them ids -> insert (key, id) of the new heads.
+ * Semantics of insert are KEEP FIRST: an entry the index has wins over any new pair, and
+ * among new pairs with equal keys the earliest in the caller's order (DB order) wins -- the
+ * first Object, in the order the caller lists them, that owns the cas_id (mod.rs:189-225).
+ * An index created for (nparts, part) keeps only the keys sd_dedup_partition sends to rank
+ * `part` of `nparts` and skips the others, so every rank can be handed the same DB dump;
+ * nparts 1, part 0 = unsharded.  Entries are never deleted (rebuild the index instead).
+ * Thread safety: concurrent sd_object_index_lookup / _count / _export calls on one index are
+ * safe; sd_object_index_insert* is exclusive (no other call on the index, and no kernel of
+ * an earlier call still reading it, while it runs), and sd_dedup_owners_indexed uses
+ * scratch owned by the index: one such call in flight per index. */
+typedef struct sd_object_index sd_object_index;
+int sd_object_index_create(sd_cas_ctx* ctx, int nparts, int part, sd_object_index** out);
+void sd_object_index_destroy(sd_object_index* index);
+/* m pairs (key, Object id) on the device, in the caller's (DB) order; *taken (host, may be
+ * NULL) = the entries added: first of their key, of this shard, and not already present
+ * (mod.rs:168-225: the first Object wins).  Runs on `stream` and syncs it; buffers grow
+ * (hipMalloc) when the count exceeds their capacity.  m == 0 is a no-op. */
+int sd_object_index_insert(sd_cas_ctx* ctx, sd_object_index* index, const uint64_t* d_keys,
+                           const uint64_t* d_object_ids, uint64_t m, uint64_t* taken, void* stream);
+/* The same from host memory: hex17 = m x 17 bytes, each a 16-digit lower-case hex cas_id
+ * and a NUL (what sd_cas_ids writes; mod.rs:168-175 reads the same strings from the DB). */
+int sd_object_index_insert_hex(sd_cas_ctx* ctx, sd_object_index* index, const char* hex17,
+                               const uint64_t* object_ids, uint64_t m, uint64_t* taken);
+int sd_object_index_count(const sd_object_index* index, uint64_t* n);
+/* d_found[i] (u8) = 1 and d_object_ids[i] = the Object id if d_keys[i] is in the index, else
+ * 0 and 0 (mod.rs:168-175 for m keys in any order).  Asynchronous on `stream`. */
+int sd_object_index_lookup(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_keys, uint64_t m,
+                           uint64_t* d_object_ids, uint8_t* d_found, void* stream);
+/* The index's entries in ascending key order into device arrays of `capacity` entries
+ * (SD_ERR_CAPACITY if smaller than the count).  Asynchronous on `stream`. */
+int sd_object_index_export(sd_cas_ctx* ctx, const sd_object_index* index, uint64_t* d_keys_out,
+                           uint64_t* d_object_ids_out, uint64_t capacity, void* stream);
+/* sd_dedup_owners against the Objects the library already has (mod.rs:168-225, then
+ * :229-333 for the rest), per grouped record i:
+ *   d_owner[i] = index[cas_id], d_existing[i] = 1     if the index has the record's cas_id;
+ *   d_owner[i] = what sd_dedup_owners writes (a file index), d_existing[i] = 0   otherwise.
+ * d_new_out (2 x u64 per entry, capacity m) receives (key, smallest file index) of every
+ * group the index does not have, in ascending key order, and *d_n_new (device u64) their
+ * count: the Objects the host creates, names and inserts.  Only the first *d_n_new entries
+ * of d_new_out are defined.  index == NULL is sd_dedup_owners itself (d_existing,
+ * d_new_out and d_n_new are not touched and may be NULL).  Asynchronous on `stream`; no
+ * host sync. */
+int sd_dedup_owners_indexed(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_records, uint64_t m,
+                            const uint64_t* d_rep, uint64_t chunk_size, uint64_t* d_owner, uint8_t* d_existing,
+                            uint64_t* d_new_out, uint64_t* d_n_new, void* stream);
+/* The host-only siblings, over host arrays, for a host without a gfx950 device: the same
+ * semantics, layout and directory (mod.rs:168-225).  sd_cpu_dedup_owners_indexed takes
+ * *n_new on the host. */
+typedef struct sd_cpu_object_index sd_cpu_object_index;
+int sd_cpu_object_index_create(int nparts, int part, sd_cpu_object_index** out);
+void sd_cpu_object_index_destroy(sd_cpu_object_index* index);
+int sd_cpu_object_index_insert(sd_cpu_object_index* index, const uint64_t* keys, const uint64_t* object_ids,
+                               uint64_t m, uint64_t* taken);
+int sd_cpu_object_index_lookup(const sd_cpu_object_index* index, const uint64_t* keys, uint64_t m,
+                               uint64_t* object_ids, uint8_t* found);
+int sd_cpu_object_index_count(const sd_cpu_object_index* index, uint64_t* n);
+int sd_cpu_object_index_export(const sd_cpu_object_index* index, uint64_t* keys_out, uint64_t* object_ids_out,
+                               uint64_t capacity);
+int sd_cpu_dedup_owners_indexed(const sd_cpu_object_index* index, const uint64_t* records, uint64_t m,
+                                const uint64_t* rep, uint64_t chunk_size, uint64_t* owner, uint8_t* existing,
+                                uint64_t* new_out, uint64_t* n_new);
+
 /* ---------------------------------------------------------------- multi-GPU dedup (RCCL) */
 /* One process (or thread) per GPU, files sharded by global index.  The
  * communicator is RCCL's: rank 0 calls sd_comm_id (ncclGetUniqueId) and hands the 128
@@ -460,6 +532,18 @@ int sd_cas_dedup_mgpu(sd_cas_ctx* ctx, sd_comm* comm, const uint8_t* d_hash32, c
                       uint64_t global_index_base, uint64_t chunk_size, uint64_t* d_records_out, uint64_t* d_rep_out,
                       uint64_t* d_owner_out, uint64_t capacity, uint64_t* m_out, uint64_t* n_groups_out,
                       void* stream);
+/* sd_cas_dedup_mgpu with its last step's owners taken through this rank's Object index
+ * (sd_dedup_owners_indexed; file_identifier/mod.rs:168-225): d_existing_out (u8) and d_new_out
+ * (2 x u64) hold `capacity` entries, *n_new_out (host) = the new heads.  The index must have
+ * been created on `ctx` for (nparts, part) = the communicator's (nranks, rank); if any rank's
+ * is not, EVERY rank returns SD_ERR_INVALID before any record moves (the gathered rows carry
+ * it, as they carry the capacities).  index == NULL: sd_cas_dedup_mgpu itself (the three
+ * extra outputs are not touched and may be NULL). */
+int sd_cas_dedup_mgpu_indexed(sd_cas_ctx* ctx, sd_comm* comm, const uint8_t* d_hash32, const uint8_t* d_valid,
+                              uint64_t n, uint64_t global_index_base, uint64_t chunk_size, uint64_t* d_records_out,
+                              uint64_t* d_rep_out, uint64_t* d_owner_out, uint64_t capacity, uint64_t* m_out,
+                              uint64_t* n_groups_out, void* stream, const sd_object_index* index,
+                              uint8_t* d_existing_out, uint64_t* d_new_out, uint64_t* n_new_out);
 /* Phase timing of sd_cas_dedup_mgpu (diagnostics): with timing on, each call records HIP
  * events on its stream at the phase boundaries; sd_comm_last_phases waits for the last
  * call's events and returns the SD_DEDUP_PHASES durations in ms, in order:
@@ -571,7 +655,9 @@ int sd_checksum_batch_time(sd_cas_ctx* ctx, const sd_checksum_batch* batch, cons
  * on every call's host threads -- thread counts callers pass (nthreads) and the knobs above
  * are clamped to it; "comm_timeout_ms" (300000): the longest sd_cas_dedup_mgpu waits for its
  * RCCL peers (0 = no bound); "fingerprint_window_mb" (256): the device window of ranges
- * sd_fingerprints uploads at once (a longer range streams).  Unknown keys fail with SD_ERR_INVALID. */
+ * sd_fingerprints uploads at once (a longer range streams); "index_dir_max_bits" (24): the
+ * most prefix-directory bits an Object-index insert chooses (0 = no directory: every lookup is
+ * a binary search over the whole key array).  Unknown keys fail with SD_ERR_INVALID. */
 int sd_cas_set_tuning(const char* key, int value);
 int sd_cas_get_tuning(const char* key, int* value);
 /* Read-only probe over d_buf[0, bytes) (bytes a multiple of 4096) for calibrating the

@@ -210,3 +210,28 @@ impl LookAhead {
 //
 // with the rest of the function (mod.rs:136-333) as it is.  shallow (shallow.rs:94-114)
 // keeps one LookAhead for its loop over chunks and fills it the same way.
+//
+// Existing Objects from the Object index instead of find_many (mod.rs:168-225).  A batched
+// scan (sd_cas_hashes_files -> sd_dedup_partition / sd_cas_dedup_mgpu_indexed) does not run
+// the per-step `object().find_many(vec![object::file_paths::some(vec![file_path::cas_id::
+// in_vec(unique_cas_ids)])])` of mod.rs:168-175 at all: the library's Objects sit in a
+// device-resident index (sd_object_index, include/sd_cas.h), loaded once per scan from the
+// DB in Object order --
+//
+//     let rows = db.file_path().find_many(vec![file_path::cas_id::not(None), file_path::object_id::not(None)])
+//         .order_by(file_path::object_id::order(SortOrder::Asc))
+//         .select(file_path::select!({ cas_id object_id })).exec().await?;
+//     sd_object_index_insert_hex(ctx, index, hex17(&rows), object_ids(&rows), rows.len() as u64, &mut taken);
+//
+// (keep first: the first Object in that order that owns a cas_id is the one mod.rs:189-225
+// links to), and sd_dedup_owners_indexed answers for every file of the scan at once:
+//
+//     d_existing[i] == 1  ->  link file_path i to Object d_owner[i]            (mod.rs:189-225)
+//     d_existing[i] == 0  ->  d_owner[i] is the file whose new Object it takes (mod.rs:229-333)
+//
+// The DB owns the Object ids: the host creates one Object per (key, file) pair of d_new_out
+// with create_many (mod.rs:300-333), reads their ids back, and inserts (key, id) into the
+// index (sd_object_index_insert) before the next scan, so a re-scan, a second location or a
+// resumed job links to them.  The watcher's single new file asks sd_object_index_lookup with
+// m = 1.  On a host without the device the same calls exist as sd_cpu_object_index_* /
+// sd_cpu_dedup_owners_indexed.

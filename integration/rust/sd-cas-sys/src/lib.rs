@@ -42,6 +42,14 @@ pub struct sd_split_checksum {
 pub struct sd_fingerprint_batch {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct sd_object_index {
+    _p: [u8; 0],
+}
+#[repr(C)]
+pub struct sd_cpu_object_index {
+    _p: [u8; 0],
+}
 
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -131,6 +139,41 @@ extern "C" {
                              n: u64, global_index_base: u64, chunk_size: u64, d_records_out: *mut u64,
                              d_rep_out: *mut u64, d_owner_out: *mut u64, capacity: u64, m_out: *mut u64,
                              n_groups_out: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_cas_dedup_mgpu_indexed(ctx: *mut sd_cas_ctx, comm: *mut sd_comm, d_hash32: *const u8,
+                                     d_valid: *const u8, n: u64, global_index_base: u64, chunk_size: u64,
+                                     d_records_out: *mut u64, d_rep_out: *mut u64, d_owner_out: *mut u64,
+                                     capacity: u64, m_out: *mut u64, n_groups_out: *mut u64, stream: *mut c_void,
+                                     index: *const sd_object_index, d_existing_out: *mut u8, d_new_out: *mut u64,
+                                     n_new_out: *mut u64) -> c_int;
+    // the Object index: which Object already owns a cas_id (file_identifier/mod.rs:168-225)
+    pub fn sd_object_index_create(ctx: *mut sd_cas_ctx, nparts: c_int, part: c_int,
+                                  out: *mut *mut sd_object_index) -> c_int;
+    pub fn sd_object_index_destroy(index: *mut sd_object_index);
+    pub fn sd_object_index_insert(ctx: *mut sd_cas_ctx, index: *mut sd_object_index, d_keys: *const u64,
+                                  d_object_ids: *const u64, m: u64, taken: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_object_index_insert_hex(ctx: *mut sd_cas_ctx, index: *mut sd_object_index, hex17: *const c_char,
+                                      object_ids: *const u64, m: u64, taken: *mut u64) -> c_int;
+    pub fn sd_object_index_count(index: *const sd_object_index, n: *mut u64) -> c_int;
+    pub fn sd_object_index_lookup(ctx: *mut sd_cas_ctx, index: *const sd_object_index, d_keys: *const u64, m: u64,
+                                  d_object_ids: *mut u64, d_found: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn sd_object_index_export(ctx: *mut sd_cas_ctx, index: *const sd_object_index, d_keys_out: *mut u64,
+                                  d_object_ids_out: *mut u64, capacity: u64, stream: *mut c_void) -> c_int;
+    pub fn sd_dedup_owners_indexed(ctx: *mut sd_cas_ctx, index: *const sd_object_index, d_records: *const u64,
+                                   m: u64, d_rep: *const u64, chunk_size: u64, d_owner: *mut u64,
+                                   d_existing: *mut u8, d_new_out: *mut u64, d_n_new: *mut u64,
+                                   stream: *mut c_void) -> c_int;
+    pub fn sd_cpu_object_index_create(nparts: c_int, part: c_int, out: *mut *mut sd_cpu_object_index) -> c_int;
+    pub fn sd_cpu_object_index_destroy(index: *mut sd_cpu_object_index);
+    pub fn sd_cpu_object_index_insert(index: *mut sd_cpu_object_index, keys: *const u64, object_ids: *const u64,
+                                      m: u64, taken: *mut u64) -> c_int;
+    pub fn sd_cpu_object_index_lookup(index: *const sd_cpu_object_index, keys: *const u64, m: u64,
+                                      object_ids: *mut u64, found: *mut u8) -> c_int;
+    pub fn sd_cpu_object_index_count(index: *const sd_cpu_object_index, n: *mut u64) -> c_int;
+    pub fn sd_cpu_object_index_export(index: *const sd_cpu_object_index, keys_out: *mut u64,
+                                      object_ids_out: *mut u64, capacity: u64) -> c_int;
+    pub fn sd_cpu_dedup_owners_indexed(index: *const sd_cpu_object_index, records: *const u64, m: u64,
+                                       rep: *const u64, chunk_size: u64, owner: *mut u64, existing: *mut u8,
+                                       new_out: *mut u64, n_new: *mut u64) -> c_int;
     pub fn sd_shard_plan(sizes: *const u64, n: usize, nranks: c_int, bounds_out: *mut u64) -> c_int;
     // one file's checksum over many GPUs (its 1 MiB blocks sharded by rank)
     pub fn sd_split_range(total_len: u64, nranks: c_int, rank: c_int, offset: *mut u64, len: *mut u64,

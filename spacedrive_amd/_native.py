@@ -140,6 +140,22 @@ SIGNATURES = [
     ("sd_fingerprints", I32, [P, P, P, P, SZ, P, P]),
     ("sd_fingerprints_stats", I32, [P, P]),
     ("sd_cpu_fingerprints", I32, [P, P, P, SZ, P, P, I32]),
+    ("sd_object_index_create", I32, [P, I32, I32, ctypes.POINTER(P)]),
+    ("sd_object_index_destroy", None, [P]),
+    ("sd_object_index_insert", I32, [P, P, P, P, U64, PU64, P]),
+    ("sd_object_index_insert_hex", I32, [P, P, P, P, U64, PU64]),
+    ("sd_object_index_count", I32, [P, PU64]),
+    ("sd_object_index_lookup", I32, [P, P, P, U64, P, P, P]),
+    ("sd_object_index_export", I32, [P, P, P, P, U64, P]),
+    ("sd_dedup_owners_indexed", I32, [P, P, P, U64, P, U64, P, P, P, P, P]),
+    ("sd_cas_dedup_mgpu_indexed", I32, [P, P, P, P, U64, U64, U64, P, P, P, U64, PU64, PU64, P, P, P, P, PU64]),
+    ("sd_cpu_object_index_create", I32, [I32, I32, ctypes.POINTER(P)]),
+    ("sd_cpu_object_index_destroy", None, [P]),
+    ("sd_cpu_object_index_insert", I32, [P, P, P, U64, PU64]),
+    ("sd_cpu_object_index_lookup", I32, [P, P, U64, P, P]),
+    ("sd_cpu_object_index_count", I32, [P, PU64]),
+    ("sd_cpu_object_index_export", I32, [P, P, P, U64]),
+    ("sd_cpu_dedup_owners_indexed", I32, [P, P, U64, P, U64, P, P, P, PU64]),
 ]
 
 

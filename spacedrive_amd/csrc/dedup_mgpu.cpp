@@ -41,6 +41,7 @@
 #include <thread>
 #include <vector>
 
+#include "sd_api_impl.h"
 #include "sd_internal.h"
 
 struct sd_comm {
@@ -261,9 +262,25 @@ int sd_cas_dedup_mgpu(sd_cas_ctx* ctx, sd_comm* comm, const uint8_t* d_hash32, c
                       uint64_t global_index_base, uint64_t chunk_size, uint64_t* d_records_out, uint64_t* d_rep_out,
                       uint64_t* d_owner_out, uint64_t capacity, uint64_t* m_out, uint64_t* n_groups_out,
                       void* stream) {
+    return sd_cas_dedup_mgpu_indexed(ctx, comm, d_hash32, d_valid, n, global_index_base, chunk_size, d_records_out,
+                                     d_rep_out, d_owner_out, capacity, m_out, n_groups_out, stream, nullptr, nullptr,
+                                     nullptr, nullptr);
+}
+
+// sd_cas_dedup_mgpu with step 4's owners taken through an Object index (index == NULL: the
+// plain rule, nothing else differs).  An index sharded for another (nparts, part) than this
+// rank's goes into the gathered row's `valid` field as ~0, so every rank sees it in the same
+// matrix and all return SD_ERR_INVALID together before any record moves.
+int sd_cas_dedup_mgpu_indexed(sd_cas_ctx* ctx, sd_comm* comm, const uint8_t* d_hash32, const uint8_t* d_valid,
+                              uint64_t n, uint64_t global_index_base, uint64_t chunk_size, uint64_t* d_records_out,
+                              uint64_t* d_rep_out, uint64_t* d_owner_out, uint64_t capacity, uint64_t* m_out,
+                              uint64_t* n_groups_out, void* stream, const sd_object_index* index,
+                              uint8_t* d_existing_out, uint64_t* d_new_out, uint64_t* n_new_out) {
     SD_GUARD_BEGIN
     if (!ctx || !comm || !m_out || !n_groups_out || (n && !d_hash32) ||
         (capacity && (!d_records_out || !d_rep_out || !d_owner_out)))
+        throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (index && (!n_new_out || (capacity && (!d_existing_out || !d_new_out))))
         throw sd_failure(SD_ERR_INVALID, "null argument");
     if (chunk_size == 0) throw sd_failure(SD_ERR_INVALID, "chunk_size must be positive");
     check_usable(comm);
@@ -293,9 +310,13 @@ int sd_cas_dedup_mgpu(sd_cas_ctx* ctx, sd_comm* comm, const uint8_t* d_hash32, c
     h_row[R] = global_index_base;
     h_row[R + 1] = n;
     h_row[R + 2] = capacity;
-    HIP_OK(hipMemcpyAsync(d_row + R, h_row + R, sizeof(uint64_t) * 3, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(d_row + R + 3, pscratch + psb / sizeof(uint64_t) - 1, sizeof(uint64_t),
-                          hipMemcpyDeviceToDevice, s));
+    constexpr uint64_t BAD_INDEX = ~0ull;  // in place of the valid-record count (never that large)
+    const bool bad_index = index && (index->ctx != ctx || index->nparts != R || index->part != me);
+    h_row[R + 3] = BAD_INDEX;
+    HIP_OK(hipMemcpyAsync(d_row + R, h_row + R, sizeof(uint64_t) * (bad_index ? 4 : 3), hipMemcpyHostToDevice, s));
+    if (!bad_index)
+        HIP_OK(hipMemcpyAsync(d_row + R + 3, pscratch + psb / sizeof(uint64_t) - 1, sizeof(uint64_t),
+                              hipMemcpyDeviceToDevice, s));
     uint64_t* all = comm->h_rows + row;
     if (comm->group) {  // in-process: every rank's row straight into this rank's host table
         comm->group->slot_b[me] = comm->d_send;  // read by the peers after the barriers below
@@ -310,6 +331,11 @@ int sd_cas_dedup_mgpu(sd_cas_ctx* ctx, sd_comm* comm, const uint8_t* d_hash32, c
     const ExchangePlan plan = exchange_plan(all, R, me);
     *m_out = plan.recv_total;
     *n_groups_out = 0;
+    if (n_new_out) *n_new_out = 0;
+    for (int p = 0; p < R; p++)
+        if (all[(size_t)p * row + R + 3] == BAD_INDEX)
+            throw sd_failure(SD_ERR_INVALID, "rank " + std::to_string(p) + "'s Object index is not sharded for its "
+                                             "(nranks, rank) on this context; no rank exchanged records");
     // every rank sees the same matrix, so every rank stops here together, before any record
     // moves (a rank that stopped alone would leave its peers waiting in the send/receive)
     if (!plan.fits)
@@ -348,8 +374,16 @@ int sd_cas_dedup_mgpu(sd_cas_ctx* ctx, sd_comm* comm, const uint8_t* d_hash32, c
     if (!comm->group) wait_peers(comm, s, "send/receive of the records");
     // 4. group by cas_id and assign Objects (chunk-of-100 rule) on the received records
     uint64_t ng = 0;
-    dedup_group_owners(ctx, d_records_out, *m_out, plan.ascending ? SD_DEDUP_INDEX_SORTED : 0, d_rep_out, chunk_size,
-                       d_owner_out, &ng, s);
+    dedup_group_owners(ctx, d_records_out, *m_out, plan.ascending ? SD_DEDUP_INDEX_SORTED : 0, d_rep_out,
+                       index ? 0 : chunk_size, d_owner_out, &ng, s);
+    if (index) {  // the owners through the index, and its new heads' count back to the host
+        uint64_t* d_n_new = index->counts.as<uint64_t>() + sdk::OI_COUNT_SLOTS;
+        HIP_OK(sdk::owners_indexed(index->view(), d_records_out, *m_out, d_rep_out, chunk_size, d_owner_out,
+                                   d_existing_out, d_new_out, d_n_new, index->counts.as<uint64_t>(), s));
+        HIP_OK(hipMemcpyAsync(index->host.p, d_n_new, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        *n_new_out = *reinterpret_cast<const uint64_t*>(index->host.p);
+    }
     mark(comm, 5, s);
     comm->timed = comm->timing;
     *n_groups_out = ng;

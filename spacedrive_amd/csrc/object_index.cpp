@@ -1,0 +1,169 @@
+// object_index.cpp -- the device-resident Object index behind the C ABI (include/sd_cas.h):
+// which Object already owns a cas_id, the join identifier_job_step does per 100-row step
+// through the DB (core/src/object/file_identifier/mod.rs:168-175) before it links each file
+// to the first such Object (:189-225).  Kernels: object_index.hip; layout, lookup and the
+// directory / growth policies: object_index.h, object_index_host.cpp (shared with the
+// sd_cpu_object_index_* mirror).
+#include <vector>
+
+#include "object_index.h"
+#include "sd_api_impl.h"
+
+namespace {
+
+void check_index(const sd_cas_ctx* ctx, const sd_object_index* index) {
+    if (index->ctx != ctx) throw sd_failure(SD_ERR_INVALID, "the index belongs to another context");
+}
+
+}  // namespace
+
+extern "C" {
+
+int sd_object_index_create(sd_cas_ctx* ctx, int nparts, int part, sd_object_index** out) {
+    SD_GUARD_BEGIN
+    if (!ctx || !out) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (nparts < 1 || nparts > 64 || part < 0 || part >= nparts)
+        throw sd_failure(SD_ERR_INVALID, "part / nparts out of range (1..64 parts)");
+    *out = nullptr;
+    ctx->bind();
+    auto x = std::make_unique<sd_object_index>();
+    x->ctx = ctx;
+    x->nparts = nparts;
+    x->part = part;
+    for (int k = 0; k < 2; k++) {
+        x->keys[k].alloc(0);
+        x->vals[k].alloc(0);
+    }
+    x->dir.alloc(2 * sizeof(uint64_t));
+    HIP_CHECK(hipMemset(x->dir.p, 0, 2 * sizeof(uint64_t)));
+    x->counts.alloc((sdk::OI_COUNT_SLOTS + 1) * sizeof(uint64_t));  // + sd_cas_dedup_mgpu_indexed's count
+    x->host.ensure(sizeof(uint64_t));
+    *out = x.release();
+    return SD_OK;
+    SD_GUARD_END
+}
+
+void sd_object_index_destroy(sd_object_index* index) {
+    try {
+        if (index) (void)hipSetDevice(index->ctx->device);
+        delete index;
+    } catch (...) {
+    }
+}
+
+int sd_object_index_count(const sd_object_index* index, uint64_t* n) {
+    SD_GUARD_BEGIN
+    if (!index || !n) throw sd_failure(SD_ERR_INVALID, "null argument");
+    *n = index->n;
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_object_index_insert(sd_cas_ctx* ctx, sd_object_index* index, const uint64_t* d_keys,
+                           const uint64_t* d_object_ids, uint64_t m, uint64_t* taken, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index || (m && (!d_keys || !d_object_ids))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (taken) *taken = 0;
+    if (m == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    sd_object_index* x = index;
+    x->scratch.ensure(sdk::index_insert_scratch(m));
+    const uint64_t *nk = nullptr, *nv = nullptr, *d_total = nullptr;
+    HIP_CHECK(sdk::index_insert_select(x->view(), x->nparts, x->part, d_keys, d_object_ids, m, x->scratch.p,
+                                       x->counts.as<uint64_t>(), &nk, &nv, &d_total, s));
+    HIP_CHECK(hipMemcpyAsync(x->host.p, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const uint64_t r = *reinterpret_cast<const uint64_t*>(x->host.p);
+    if (r > m) throw sd_failure(SD_ERR_INTERNAL, "insert: more survivors than pairs");
+    if (taken) *taken = r;
+    if (r == 0) return SD_OK;
+    // merge into the other buffer pair (grown first if short; grow-only), then swap
+    const uint64_t cap = oi_grow_capacity(x->n + r, x->cap);
+    const int to = 1 - x->cur;
+    x->keys[to].ensure(cap * sizeof(uint64_t));
+    x->vals[to].ensure(cap * sizeof(uint64_t));
+    HIP_CHECK(sdk::index_merge(x->view(), nk, nv, r, x->keys[to].as<uint64_t>(), x->vals[to].as<uint64_t>(), s));
+    HIP_CHECK(hipStreamSynchronize(s));  // the merge read the old buffers and the old directory
+    x->keys[x->cur].ensure(cap * sizeof(uint64_t));
+    x->vals[x->cur].ensure(cap * sizeof(uint64_t));
+    x->cap = cap;
+    x->cur = to;
+    x->n += r;
+    x->bits = oi_dir_bits(x->n);  // re-chosen when n crosses a power of two
+    x->dir.ensure(((1ull << x->bits) + 1) * sizeof(uint64_t));
+    HIP_CHECK(sdk::index_build_dir(x->keys[to].as<uint64_t>(), x->n, x->bits, x->dir.as<uint64_t>(), s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_object_index_insert_hex(sd_cas_ctx* ctx, sd_object_index* index, const char* hex17, const uint64_t* object_ids,
+                               uint64_t m, uint64_t* taken) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index || (m && (!hex17 || !object_ids))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (taken) *taken = 0;
+    if (m == 0) return SD_OK;
+    std::vector<uint64_t> keys(m);
+    for (uint64_t i = 0; i < m; i++)
+        if (!oi_key_from_hex(hex17 + 17 * i, &keys[i]))
+            throw sd_failure(SD_ERR_INVALID, "cas_id " + std::to_string(i) + " is not 16 lower-case hex digits");
+    ctx->bind();
+    sdi::DevBuf dk, dv;
+    dk.alloc(m * sizeof(uint64_t));
+    dv.alloc(m * sizeof(uint64_t));
+    HIP_CHECK(hipMemcpy(dk.p, keys.data(), m * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dv.p, object_ids, m * sizeof(uint64_t), hipMemcpyHostToDevice));
+    return sd_object_index_insert(ctx, index, dk.as<uint64_t>(), dv.as<uint64_t>(), m, taken, nullptr);
+    SD_GUARD_END
+}
+
+int sd_object_index_lookup(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_keys, uint64_t m,
+                           uint64_t* d_object_ids, uint8_t* d_found, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index || (m && (!d_keys || !d_object_ids || !d_found)))
+        throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (m == 0) return SD_OK;
+    ctx->bind();
+    HIP_CHECK(sdk::index_lookup(index->view(), d_keys, m, d_object_ids, d_found, ctx->pick(stream)));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_object_index_export(sd_cas_ctx* ctx, const sd_object_index* index, uint64_t* d_keys_out,
+                           uint64_t* d_object_ids_out, uint64_t capacity, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index || (index->n && (!d_keys_out || !d_object_ids_out)))
+        throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (capacity < index->n) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the index's count");
+    if (index->n == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    const sdk::oi_view v = index->view();
+    HIP_CHECK(hipMemcpyAsync(d_keys_out, v.keys, v.n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_object_ids_out, v.vals, v.n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_dedup_owners_indexed(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_records, uint64_t m,
+                            const uint64_t* d_rep, uint64_t chunk_size, uint64_t* d_owner, uint8_t* d_existing,
+                            uint64_t* d_new_out, uint64_t* d_n_new, void* stream) {
+    SD_GUARD_BEGIN
+    if (!index) return sd_dedup_owners(ctx, d_records, m, d_rep, chunk_size, d_owner, stream);
+    if (!ctx || !d_n_new || (m && (!d_records || !d_rep || !d_owner || !d_existing || !d_new_out)))
+        throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (chunk_size == 0) throw sd_failure(SD_ERR_INVALID, "chunk_size must be positive");
+    check_index(ctx, index);
+    ctx->bind();
+    HIP_CHECK(sdk::owners_indexed(index->view(), d_records, m, d_rep, chunk_size, d_owner, d_existing, d_new_out,
+                                  d_n_new, index->counts.as<uint64_t>(), ctx->pick(stream)));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+}  // extern "C"

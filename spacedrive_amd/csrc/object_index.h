@@ -1,0 +1,59 @@
+// object_index.h -- the Object index's layout and lookup, stated once for the host code
+// (object_index_host.cpp, g++) and the kernels (object_index.hip, hipcc).
+//
+// Reference semantics: identifier_job_step first finds the Objects the library already has
+// for a step's cas_ids (core/src/object/file_identifier/mod.rs:168-175) and links each file
+// to the first of them (:189-225).  The index is that join's table: keys[n] strictly
+// ascending (the big-endian u64 of the cas_id, dedup.hip cas_key), vals[n] the Object ids,
+// and a prefix directory dir[2^bits + 1]: dir[p] = the first position whose key's top
+// `bits` bits are >= p (dir[2^bits] = n).  cas_ids are uniform hash bits, so a bucket
+// [dir[p], dir[p + 1]) holds ~8-16 keys; the search inside it is a binary search bounded by
+// the bucket, so keys that all share a prefix cost O(log n), never a scan.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define SD_OI_HD __host__ __device__ __forceinline__
+#else
+#define SD_OI_HD inline
+#endif
+
+SD_OI_HD uint64_t oi_prefix(uint64_t key, uint32_t bits) { return bits ? key >> (64 - bits) : 0; }
+
+// the rank that owns a key among nparts: its top 16 bits scaled (dedup.hip dest_of, k_part_*)
+SD_OI_HD uint32_t oi_dest_of(uint64_t key, int nparts) { return (uint32_t)(((key >> 48) * (uint64_t)nparts) >> 16); }
+
+// first position in [lo, hi) whose key is >= key (hi if none); unsigned comparisons
+SD_OI_HD uint64_t oi_lower_bound(const uint64_t* keys, uint64_t lo, uint64_t hi, uint64_t key) {
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// lower bound of `key` over the whole index through the directory: every key before the
+// bucket is smaller and every key after it larger, so the bucket's bound is the global one
+SD_OI_HD uint64_t oi_rank(const uint64_t* keys, const uint64_t* dir, uint32_t bits, uint64_t key) {
+    const uint64_t p = oi_prefix(key, bits);
+    return oi_lower_bound(keys, dir[p], dir[p + 1], key);
+}
+
+// position of `key` in the index, or false
+SD_OI_HD bool oi_find(const uint64_t* keys, const uint64_t* dir, uint32_t bits, uint64_t key, uint64_t* pos) {
+    const uint64_t p = oi_prefix(key, bits);
+    const uint64_t hi = dir[p + 1];
+    const uint64_t at = oi_lower_bound(keys, dir[p], hi, key);
+    *pos = at;
+    return at < hi && keys[at] == key;
+}
+
+// ---- policies (object_index_host.cpp; the device path calls the same functions)
+// directory bits for n entries: ~log2(n / 8), 0 for tiny indexes, at most 24
+uint32_t oi_dir_bits(uint64_t n);
+// grow-only capacity: `cap` while `need` fits, else at least need and 1.5 x cap
+uint64_t oi_grow_capacity(uint64_t need, uint64_t cap);
+// 16 lower-case hex digits -> the key (false on any other character)
+bool oi_key_from_hex(const char* hex16, uint64_t* key);

@@ -1,0 +1,304 @@
+// object_index.hip -- the device-resident Object index: lookup, the indexed owner rule with
+// its compacted list of new group heads, and insertion (merge by rank + directory rebuild).
+//
+// Reference semantics: identifier_job_step joins a step's cas_ids against the Objects the
+// library already has (core/src/object/file_identifier/mod.rs:168-175), links each file to
+// the first of them (:189-225) and creates Objects for the rest (:229-333).  Layout and
+// lookup: object_index.h (shared with the host mirror, object_index_host.cpp).
+//
+// Ordered compaction (new heads; an insert's surviving pairs) without atomics on the data
+// path: a fixed grid in which workgroup b owns the contiguous slice b of the input; the
+// flagging pass leaves one count per workgroup, and the compaction pass gives each
+// workgroup the sum of the counts before it, then ranks its flags in order (ballot /
+// popcount inside a wave, LDS counts across the four waves).
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "object_index.h"
+#include "sd_internal.h"
+
+namespace {
+
+constexpr uint32_t OI_BLOCKS = 1024;  // most workgroups of a sliced pass (= the count slots)
+
+struct oi_slice { uint64_t lo, hi; };
+__device__ __forceinline__ oi_slice oi_slice_of(uint64_t n) {
+    const uint64_t per = ((n + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;  // whole tiles
+    uint64_t lo = (uint64_t)blockIdx.x * per, hi = lo + per;
+    if (lo > n) lo = n;
+    if (hi > n) hi = n;
+    return {lo, hi};
+}
+
+uint32_t grid_for(uint64_t n) {
+    uint64_t g = (n + 255) / 256;
+    if (g < 1) g = 1;
+    if (g > 4096) g = 4096;
+    return (uint32_t)g;
+}
+
+uint32_t sliced_grid(uint64_t n) { return std::min<uint32_t>(grid_for(n), OI_BLOCKS); }
+
+// workgroup total of `mine` (256 lanes) -> counts[blockIdx.x], by lane 0
+__device__ __forceinline__ void block_count(uint32_t mine, uint64_t* __restrict__ counts) {
+    __shared__ uint32_t ws[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = (uint64_t)ws[0] + ws[1] + ws[2] + ws[3];
+}
+
+// sum of counts[0 .. blockIdx.x) for every lane; the last workgroup also writes the total
+__device__ __forceinline__ uint64_t block_base(const uint64_t* __restrict__ counts, uint64_t* __restrict__ total) {
+    __shared__ uint64_t ws[4];
+    __shared__ uint64_t base;
+    uint64_t v = 0;
+    for (uint32_t k = threadIdx.x; k < blockIdx.x; k += blockDim.x) v += counts[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        base = ws[0] + ws[1] + ws[2] + ws[3];
+        if (blockIdx.x + 1 == gridDim.x && total) *total = base + counts[blockIdx.x];
+    }
+    __syncthreads();
+    return base;
+}
+
+// this lane's output slot among the flagged lanes of the tile, in lane order; `run` (the
+// slot of the tile's first flagged lane) advances by the tile's count
+__device__ __forceinline__ uint64_t tile_slot(bool flag, uint64_t& run) {
+    __shared__ uint32_t wcnt[4];
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint64_t bal = __ballot(flag);
+    if (lane == 0) wcnt[w] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint64_t slot = run + __popcll(bal & ((1ull << lane) - 1));
+    for (uint32_t k = 0; k < w; k++) slot += wcnt[k];
+    const uint32_t all = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    __syncthreads();
+    run += all;
+    return slot;
+}
+
+__global__ __launch_bounds__(256) void k_index_lookup(const uint64_t* __restrict__ keys,
+                                                      const uint64_t* __restrict__ vals,
+                                                      const uint64_t* __restrict__ dir, uint32_t bits,
+                                                      const uint64_t* __restrict__ q, uint64_t m,
+                                                      uint64_t* __restrict__ out, uint8_t* __restrict__ found) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t at;
+        const bool f = oi_find(keys, dir, bits, q[i], &at);
+        found[i] = f ? 1 : 0;
+        out[i] = f ? vals[at] : 0;
+    }
+}
+
+// The indexed owner rule per grouped record (sorted by (key, index): neighbouring lanes read
+// neighbouring index lines).  existing[i] = 1 if owner[i] is an Object id of the index, else
+// owner[i] is what k_owners writes; bit 1 of existing[i] carries the new-head flag (a group's
+// first record whose key the index does not have) to k_heads_compact, which clears it.
+__global__ __launch_bounds__(256) void k_owners_indexed(const uint64_t* __restrict__ keys,
+                                                        const uint64_t* __restrict__ vals,
+                                                        const uint64_t* __restrict__ dir, uint32_t bits,
+                                                        const uint64_t* __restrict__ rec, uint64_t m,
+                                                        const uint64_t* __restrict__ rep, uint64_t chunk,
+                                                        uint64_t* __restrict__ owner, uint8_t* __restrict__ existing,
+                                                        uint64_t* __restrict__ counts) {
+    const oi_slice sl = oi_slice_of(m);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+        const uint64_t key = rec[2 * i], idx = rec[2 * i + 1], r = rep[i];
+        uint64_t at;
+        const bool f = oi_find(keys, dir, bits, key, &at);
+        const bool head = !f && (i == 0 || rec[2 * (i - 1)] != key);
+        owner[i] = f ? vals[at] : (idx / chunk == r / chunk ? idx : r);
+        existing[i] = (uint8_t)((f ? 1 : 0) | (head ? 2 : 0));
+        mine += head;
+    }
+    block_count(mine, counts);
+}
+
+// (key, index) of the flagged heads, in record order = ascending key order
+__global__ __launch_bounds__(256) void k_heads_compact(const uint64_t* __restrict__ rec, uint64_t m,
+                                                       uint8_t* __restrict__ existing,
+                                                       const uint64_t* __restrict__ counts,
+                                                       uint64_t* __restrict__ new_out, uint64_t* __restrict__ n_new) {
+    uint64_t run = block_base(counts, n_new);
+    const oi_slice sl = oi_slice_of(m);
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool act = i < sl.hi;
+        const uint8_t e = act ? existing[i] : 0;
+        const bool flag = (e & 2) != 0;
+        const uint64_t slot = tile_slot(flag, run);
+        if (flag) {
+            new_out[2 * slot] = rec[2 * i];
+            new_out[2 * slot + 1] = rec[2 * i + 1];
+            existing[i] = e & 1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_iota(uint64_t* __restrict__ p, uint64_t m) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x)
+        p[i] = i;
+}
+
+// an insert's pairs sorted by (key, position): a pair survives if it is its key's first, its
+// key belongs to this shard and the index does not have it
+__global__ __launch_bounds__(256) void k_insert_flag(const uint64_t* __restrict__ keys,
+                                                     const uint64_t* __restrict__ dir, uint32_t bits, int nparts,
+                                                     int part, const uint64_t* __restrict__ sk, uint64_t m,
+                                                     uint8_t* __restrict__ flags, uint64_t* __restrict__ counts) {
+    const oi_slice sl = oi_slice_of(m);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+        const uint64_t k = sk[i];
+        bool keep = (i == 0 || sk[i - 1] != k) && oi_dest_of(k, nparts) == (uint32_t)part;
+        if (keep) {
+            uint64_t at;
+            keep = !oi_find(keys, dir, bits, k, &at);
+        }
+        flags[i] = keep ? 1 : 0;
+        mine += keep;
+    }
+    block_count(mine, counts);
+}
+
+__global__ __launch_bounds__(256) void k_insert_compact(const uint64_t* __restrict__ sk,
+                                                        const uint64_t* __restrict__ spos,
+                                                        const uint64_t* __restrict__ in_vals, uint64_t m,
+                                                        const uint8_t* __restrict__ flags,
+                                                        const uint64_t* __restrict__ counts,
+                                                        uint64_t* __restrict__ nk, uint64_t* __restrict__ nv,
+                                                        uint64_t* __restrict__ total) {
+    uint64_t run = block_base(counts, total);
+    const oi_slice sl = oi_slice_of(m);
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool flag = i < sl.hi && flags[i];
+        const uint64_t slot = tile_slot(flag, run);
+        if (flag) {
+            nk[slot] = sk[i];
+            nv[slot] = in_vals[spos[i]];
+        }
+    }
+}
+
+// Merge by rank of two sorted runs without common keys: lanes [0, r) place the new entries
+// (rank + the old keys below, through the old directory), lanes [r, r + n) the old ones
+// (position + the new keys below).
+__global__ __launch_bounds__(256) void k_index_merge(const uint64_t* __restrict__ keys,
+                                                     const uint64_t* __restrict__ vals,
+                                                     const uint64_t* __restrict__ dir, uint32_t bits, uint64_t n,
+                                                     const uint64_t* __restrict__ nk, const uint64_t* __restrict__ nv,
+                                                     uint64_t r, uint64_t* __restrict__ out_keys,
+                                                     uint64_t* __restrict__ out_vals) {
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n + r; t += (uint64_t)gridDim.x * blockDim.x) {
+        if (t < r) {
+            const uint64_t k = nk[t], at = t + oi_rank(keys, dir, bits, k);
+            out_keys[at] = k;
+            out_vals[at] = nv[t];
+        } else {
+            const uint64_t i = t - r, k = keys[i], at = i + oi_lower_bound(nk, 0, r, k);
+            out_keys[at] = k;
+            out_vals[at] = vals[i];
+        }
+    }
+}
+
+// dir[q] = i for q in (prefix(key[i-1]), prefix(key[i])]; the last position fills the tail with n
+__global__ __launch_bounds__(256) void k_index_dir(const uint64_t* __restrict__ keys, uint64_t n, uint32_t bits,
+                                                   uint64_t* __restrict__ dir) {
+    const uint64_t nb = 1ull << bits;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t first = i == 0 ? 0 : oi_prefix(keys[i - 1], bits) + 1;
+        const uint64_t cur = oi_prefix(keys[i], bits);
+        for (uint64_t q = first; q <= cur; q++) dir[q] = i;
+        if (i + 1 == n)
+            for (uint64_t q = cur + 1; q <= nb; q++) dir[q] = n;
+    }
+}
+
+size_t insert_sort_bytes(uint64_t m, hipStream_t s) {
+    size_t b = 0;
+    uint64_t* nul = nullptr;
+    if (rocprim::radix_sort_pairs(nullptr, b, nul, nul, nul, nul, (size_t)m, 0, 64, s) != hipSuccess) return 0;
+    return (b + 255) & ~size_t(255);
+}
+
+}  // namespace
+
+namespace sdk {
+
+hipError_t index_lookup(const oi_view& x, const uint64_t* q, uint64_t m, uint64_t* out, uint8_t* found,
+                        hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_index_lookup, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, q, m, out,
+                       found);
+    return hipGetLastError();
+}
+
+hipError_t owners_indexed(const oi_view& x, const uint64_t* records, uint64_t m, const uint64_t* rep, uint64_t chunk,
+                          uint64_t* owner, uint8_t* existing, uint64_t* new_out, uint64_t* n_new, uint64_t* counts,
+                          hipStream_t s) {
+    if (m == 0) return hipMemsetAsync(n_new, 0, sizeof(uint64_t), s);
+    const uint32_t g = sliced_grid(m);
+    hipLaunchKernelGGL(k_owners_indexed, dim3(g), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, records, m, rep,
+                       chunk, owner, existing, counts);
+    hipLaunchKernelGGL(k_heads_compact, dim3(g), dim3(256), 0, s, records, m, existing, counts, new_out, n_new);
+    return hipGetLastError();
+}
+
+// scratch: sk[m], spos[m], pos[m], nk[m], nv[m] (u64), flags[m] (u8), total (u64), then the
+// radix sort's temporary storage
+size_t index_insert_scratch(uint64_t m) {
+    return ((5 * m * sizeof(uint64_t) + m + 255) & ~size_t(255)) + 256 + insert_sort_bytes(m, nullptr) + 256;
+}
+
+hipError_t index_insert_select(const oi_view& x, int nparts, int part, const uint64_t* in_keys,
+                               const uint64_t* in_vals, uint64_t m, void* scratch, uint64_t* counts,
+                               const uint64_t** nk_out, const uint64_t** nv_out, const uint64_t** total_out,
+                               hipStream_t s) {
+    uint64_t* sk = reinterpret_cast<uint64_t*>(scratch);
+    uint64_t* spos = sk + m;
+    uint64_t* pos = spos + m;
+    uint64_t* nk = pos + m;
+    uint64_t* nv = nk + m;
+    uint8_t* flags = reinterpret_cast<uint8_t*>(nv + m);
+    uint64_t* total = reinterpret_cast<uint64_t*>(((uintptr_t)(flags + m) + 255) & ~uintptr_t(255));
+    void* tmp = reinterpret_cast<uint8_t*>(total) + 256;
+    size_t tb = insert_sort_bytes(m, s);
+    hipLaunchKernelGGL(k_iota, dim3(grid_for(m)), dim3(256), 0, s, pos, m);
+    // a stable sort by key leaves equal keys in ascending position: (key, position) order
+    hipError_t e = rocprim::radix_sort_pairs(tmp, tb, in_keys, sk, pos, spos, (size_t)m, 0, 64, s);
+    if (e != hipSuccess) return e;
+    const uint32_t g = sliced_grid(m);
+    hipLaunchKernelGGL(k_insert_flag, dim3(g), dim3(256), 0, s, x.keys, x.dir, x.bits, nparts, part, sk, m, flags,
+                       counts);
+    hipLaunchKernelGGL(k_insert_compact, dim3(g), dim3(256), 0, s, sk, spos, in_vals, m, flags, counts, nk, nv, total);
+    *nk_out = nk;
+    *nv_out = nv;
+    *total_out = total;
+    return hipGetLastError();
+}
+
+hipError_t index_merge(const oi_view& x, const uint64_t* nk, const uint64_t* nv, uint64_t r, uint64_t* out_keys,
+                       uint64_t* out_vals, hipStream_t s) {
+    if (x.n + r == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_index_merge, dim3(grid_for(x.n + r)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, x.n, nk,
+                       nv, r, out_keys, out_vals);
+    return hipGetLastError();
+}
+
+hipError_t index_build_dir(const uint64_t* keys, uint64_t n, uint32_t bits, uint64_t* dir, hipStream_t s) {
+    if (n == 0) return hipMemsetAsync(dir, 0, 2 * sizeof(uint64_t), s);
+    hipLaunchKernelGGL(k_index_dir, dim3(grid_for(n)), dim3(256), 0, s, keys, n, bits, dir);
+    return hipGetLastError();
+}
+
+}  // namespace sdk

@@ -1,0 +1,202 @@
+// object_index_host.cpp -- the GPU-free half of the Object index (include/sd_cas.h): the
+// directory-size and growth policies the device path shares, and the sd_cpu_object_index_*
+// / sd_cpu_dedup_owners_indexed entry points over host arrays, with the device path's layout
+// (object_index.h) and semantics.
+//
+// Reference: the join of a step's cas_ids against the Objects the library already has
+// (core/src/object/file_identifier/mod.rs:168-175) and the link to the first of them
+// (:189-225).  No HIP: built with g++ under the sanitizers too (object_index_selftest.cpp,
+// `make sanitize-object-index`).
+#include <string.h>
+
+#include <algorithm>
+#include <numeric>
+#include <vector>
+
+#include "object_index.h"
+#include "sd_host.h"
+
+uint32_t oi_dir_bits(uint64_t n) {
+    const int cap = tuning_get(SD_TUNE_INDEX_DIR_MAX_BITS);  // "index_dir_max_bits" (24)
+    const uint32_t most = cap < 0 ? 0u : cap > 24 ? 24u : (uint32_t)cap;
+    uint32_t b = 0;
+    while (b < most && ((uint64_t)16 << b) <= n) b++;  // 2^b <= n / 8 < 2^(b+1): 8-16 keys per bucket
+    return b;
+}
+
+uint64_t oi_grow_capacity(uint64_t need, uint64_t cap) {
+    if (need <= cap) return cap;
+    return std::max<uint64_t>({need, cap + cap / 2, 16});
+}
+
+bool oi_key_from_hex(const char* hex16, uint64_t* key) {
+    uint64_t k = 0;
+    for (int i = 0; i < 16; i++) {
+        const char c = hex16[i];
+        uint64_t d;
+        if (c >= '0' && c <= '9') d = (uint64_t)(c - '0');
+        else if (c >= 'a' && c <= 'f') d = (uint64_t)(c - 'a' + 10);
+        else return false;
+        k = (k << 4) | d;
+    }
+    *key = k;
+    return true;
+}
+
+struct sd_cpu_object_index {
+    int nparts = 1, part = 0;
+    uint64_t n = 0, cap = 0;
+    uint32_t bits = 0;
+    std::vector<uint64_t> keys, vals, keys2, vals2;  // two buffers of `cap`, swapped by an insert
+    std::vector<uint64_t> dir{0, 0};
+};
+
+namespace {
+
+// dir[q] = i for q in (prefix(key[i-1]), prefix(key[i])], the tail filled with n (k_index_dir)
+void build_dir(sd_cpu_object_index* x) {
+    x->bits = oi_dir_bits(x->n);
+    const uint64_t nb = 1ull << x->bits;
+    x->dir.assign(nb + 1, x->n);
+    if (x->n == 0) x->dir[0] = 0;
+    for (uint64_t i = 0; i < x->n; i++) {
+        const uint64_t first = i == 0 ? 0 : oi_prefix(x->keys[i - 1], x->bits) + 1;
+        const uint64_t cur = oi_prefix(x->keys[i], x->bits);
+        for (uint64_t q = first; q <= cur; q++) x->dir[q] = i;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sd_cpu_object_index_create(int nparts, int part, sd_cpu_object_index** out) {
+    SD_GUARD_BEGIN
+    if (!out) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (nparts < 1 || nparts > 64 || part < 0 || part >= nparts)
+        throw sd_failure(SD_ERR_INVALID, "part / nparts out of range (1..64 parts)");
+    auto* x = new sd_cpu_object_index();
+    x->nparts = nparts;
+    x->part = part;
+    *out = x;
+    return SD_OK;
+    SD_GUARD_END
+}
+
+void sd_cpu_object_index_destroy(sd_cpu_object_index* index) { delete index; }
+
+int sd_cpu_object_index_count(const sd_cpu_object_index* index, uint64_t* n) {
+    SD_GUARD_BEGIN
+    if (!index || !n) throw sd_failure(SD_ERR_INVALID, "null argument");
+    *n = index->n;
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_object_index_insert(sd_cpu_object_index* index, const uint64_t* keys, const uint64_t* object_ids, uint64_t m,
+                               uint64_t* taken) {
+    SD_GUARD_BEGIN
+    if (!index || (m && (!keys || !object_ids))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (taken) *taken = 0;
+    if (m == 0) return SD_OK;
+    sd_cpu_object_index* x = index;
+    // keep first: order the pairs by (key, position), keep each key's first pair, drop the
+    // other shards' keys and those the index already has
+    std::vector<uint64_t> pos(m);
+    std::iota(pos.begin(), pos.end(), 0);
+    std::stable_sort(pos.begin(), pos.end(), [&](uint64_t a, uint64_t b) { return keys[a] < keys[b]; });
+    std::vector<uint64_t> nk, nv;
+    for (uint64_t j = 0; j < m; j++) {
+        const uint64_t k = keys[pos[j]];
+        if (j && keys[pos[j - 1]] == k) continue;
+        if (oi_dest_of(k, x->nparts) != (uint32_t)x->part) continue;
+        uint64_t at;
+        if (oi_find(x->keys.data(), x->dir.data(), x->bits, k, &at)) continue;
+        nk.push_back(k);
+        nv.push_back(object_ids[pos[j]]);
+    }
+    const uint64_t r = nk.size();
+    if (taken) *taken = r;
+    if (r == 0) return SD_OK;
+    const uint64_t cap = oi_grow_capacity(x->n + r, x->cap);
+    if (cap != x->cap) {
+        x->keys.resize(cap);
+        x->vals.resize(cap);
+        x->keys2.resize(cap);
+        x->vals2.resize(cap);
+        x->cap = cap;
+    }
+    // merge by rank: a new entry goes to its rank + the old keys below it, an old entry to its
+    // position + the new keys below it
+    for (uint64_t j = 0; j < r; j++) {
+        const uint64_t at = j + oi_rank(x->keys.data(), x->dir.data(), x->bits, nk[j]);
+        x->keys2[at] = nk[j];
+        x->vals2[at] = nv[j];
+    }
+    for (uint64_t i = 0; i < x->n; i++) {
+        const uint64_t at = i + oi_lower_bound(nk.data(), 0, r, x->keys[i]);
+        x->keys2[at] = x->keys[i];
+        x->vals2[at] = x->vals[i];
+    }
+    x->keys.swap(x->keys2);
+    x->vals.swap(x->vals2);
+    x->n += r;
+    build_dir(x);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_object_index_lookup(const sd_cpu_object_index* index, const uint64_t* keys, uint64_t m, uint64_t* object_ids,
+                               uint8_t* found) {
+    SD_GUARD_BEGIN
+    if (!index || (m && (!keys || !object_ids || !found))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    for (uint64_t i = 0; i < m; i++) {
+        uint64_t at;
+        const bool f = oi_find(index->keys.data(), index->dir.data(), index->bits, keys[i], &at);
+        found[i] = f ? 1 : 0;
+        object_ids[i] = f ? index->vals[at] : 0;
+    }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_object_index_export(const sd_cpu_object_index* index, uint64_t* keys_out, uint64_t* object_ids_out,
+                               uint64_t capacity) {
+    SD_GUARD_BEGIN
+    if (!index || (index->n && (!keys_out || !object_ids_out))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (capacity < index->n) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the index's count");
+    if (index->n) {
+        memcpy(keys_out, index->keys.data(), index->n * sizeof(uint64_t));
+        memcpy(object_ids_out, index->vals.data(), index->n * sizeof(uint64_t));
+    }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_dedup_owners_indexed(const sd_cpu_object_index* index, const uint64_t* records, uint64_t m,
+                                const uint64_t* rep, uint64_t chunk_size, uint64_t* owner, uint8_t* existing,
+                                uint64_t* new_out, uint64_t* n_new) {
+    SD_GUARD_BEGIN
+    if (m && (!records || !rep || !owner)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (index && (!n_new || (m && (!existing || !new_out)))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (chunk_size == 0) throw sd_failure(SD_ERR_INVALID, "chunk_size must be positive");
+    uint64_t heads = 0;
+    for (uint64_t i = 0; i < m; i++) {
+        const uint64_t key = records[2 * i], idx = records[2 * i + 1], r = rep[i];
+        uint64_t at = 0;
+        const bool f = index && oi_find(index->keys.data(), index->dir.data(), index->bits, key, &at);
+        owner[i] = f ? index->vals[at] : (idx / chunk_size == r / chunk_size ? idx : r);
+        if (!index) continue;
+        existing[i] = f ? 1 : 0;
+        if (!f && (i == 0 || records[2 * (i - 1)] != key)) {
+            new_out[2 * heads] = key;
+            new_out[2 * heads + 1] = idx;
+            heads++;
+        }
+    }
+    if (index) *n_new = heads;
+    return SD_OK;
+    SD_GUARD_END
+}
+
+}  // extern "C"

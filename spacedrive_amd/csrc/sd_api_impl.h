@@ -198,6 +198,25 @@ struct sd_fingerprint_batch {
     const uint32_t* d_tiles() const { return tab.at<uint32_t>(o_tiles); }
 };
 
+// The device-resident Object index (object_index.cpp; layout in object_index.h): two
+// buffers of `cap` keys and values swapped by an insert, the prefix directory, and scratch
+// of its own (an insert's sort and compaction; the per-workgroup counts of an ordered
+// compaction), so no call borrows a context slot it could not hold until its kernels ran.
+struct sd_object_index {
+    sd_cas_ctx* ctx = nullptr;
+    int nparts = 1, part = 0;
+    uint64_t n = 0, cap = 0;
+    uint32_t bits = 0;
+    int cur = 0;                        // which buffer pair holds the index
+    sdi::DevBuf keys[2], vals[2], dir;  // dir: 2^bits + 1 offsets
+    sdi::DevBuf counts;                 // OI_COUNT_SLOTS u64, then one device count
+    sdi::DevBuf scratch;                // sdk::index_insert_scratch
+    sdi::PinnedBuf host;                // an insert's survivor count
+    sdk::oi_view view() const {
+        return {keys[cur].as<uint64_t>(), vals[cur].as<uint64_t>(), dir.as<uint64_t>(), n, bits};
+    }
+};
+
 namespace sdi {
 
 // per-call working set of the host drop-in entry points; its batches persist with the slot

@@ -79,7 +79,8 @@ enum sd_tune_key {
     SD_TUNE_CHECKSUM_SPLIT_ADAPT = 19,     // split-eligible calls: 0 = always split, k = learn the faster route
     SD_TUNE_COMM_TIMEOUT_MS = 20,          // sd_cas_dedup_mgpu over RCCL: longest wait for the peers (0 = none)
     SD_TUNE_FINGERPRINT_WINDOW_MB = 21,    // sd_fingerprints: device window of ranges per upload (MiB)
-    SD_TUNE_NKEYS = 22
+    SD_TUNE_INDEX_DIR_MAX_BITS = 22,       // Object index: most directory bits an insert chooses (0 = no directory)
+    SD_TUNE_NKEYS = 23
 };
 int tuning_get(int key);
 

@@ -62,4 +62,29 @@ hipError_t dedup_group_buckets(uint64_t* records, uint64_t m, uint64_t* rep, uin
                                size_t scratch_bytes, hipStream_t s);
 hipError_t dedup_owners(const uint64_t* records, uint64_t m, const uint64_t* rep, uint64_t chunk, uint64_t* owner,
                         hipStream_t s);
+// Object index (object_index.hip; layout in object_index.h): the current device arrays
+struct oi_view {
+    const uint64_t *keys, *vals, *dir;
+    uint64_t n;
+    uint32_t bits;
+};
+constexpr uint32_t OI_COUNT_SLOTS = 1024;  // u64 per-workgroup counts of an ordered compaction
+hipError_t index_lookup(const oi_view& x, const uint64_t* q, uint64_t m, uint64_t* out, uint8_t* found,
+                        hipStream_t s);
+// the indexed owner rule + the compacted new heads (2 x u64 each, ascending key) and their
+// count (device u64); counts: OI_COUNT_SLOTS device u64 of scratch
+hipError_t owners_indexed(const oi_view& x, const uint64_t* records, uint64_t m, const uint64_t* rep, uint64_t chunk,
+                          uint64_t* owner, uint8_t* existing, uint64_t* new_out, uint64_t* n_new, uint64_t* counts,
+                          hipStream_t s);
+// insert, first half: the pairs that survive (first of their key, this shard's, not in the
+// index), sorted by key, left in `scratch` with their count (device u64); m > 0
+size_t index_insert_scratch(uint64_t m);
+hipError_t index_insert_select(const oi_view& x, int nparts, int part, const uint64_t* in_keys,
+                               const uint64_t* in_vals, uint64_t m, void* scratch, uint64_t* counts,
+                               const uint64_t** nk_out, const uint64_t** nv_out, const uint64_t** total_out,
+                               hipStream_t s);
+// second half: merge the r survivors with the index into out_keys / out_vals (n + r entries)
+hipError_t index_merge(const oi_view& x, const uint64_t* nk, const uint64_t* nv, uint64_t r, uint64_t* out_keys,
+                       uint64_t* out_vals, hipStream_t s);
+hipError_t index_build_dir(const uint64_t* keys, uint64_t n, uint32_t bits, uint64_t* dir, hipStream_t s);
 }  // namespace sdk

@@ -101,7 +101,7 @@ def shards_ascend(n_local: int, global_base: int, group: Optional[dist.ProcessGr
 
 
 def dedup_shard(ctx, d_hash32: torch.Tensor, d_valid: Optional[torch.Tensor], n_local: int, global_base: int,
-                group: Optional[dist.ProcessGroup] = None, index_sorted: Optional[bool] = None):
+                group: Optional[dist.ProcessGroup] = None, index_sorted: Optional[bool] = None, index=None):
     """Full distributed step on one rank: partition -> exchange -> group -> Object owners.
 
     Returns (records int64 [m, 2] sorted by (key, index), rep int64 [m], n_groups,
@@ -109,6 +109,11 @@ def dedup_shard(ctx, d_hash32: torch.Tensor, d_valid: Optional[torch.Tensor], n_
     Object each record links to under the reference's chunk-of-100 rule
     (spacedrive_amd/identifier.py).  ``index_sorted``: whether the shards' index ranges
     ascend with the rank (checked with one small all-gather when None).
+
+    With ``index`` (a device.ObjectIndex sharded as this rank's prefix range) the owners come
+    from sd_dedup_owners_indexed -- a file whose cas_id the library already has links to that
+    Object (file_identifier/mod.rs:168-225) -- and the tuple gains (existing uint8 [m], new
+    heads int64 [n_new, 2] = (key, creating file index) in ascending key order).
     """
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     dev = d_hash32.device
@@ -123,9 +128,16 @@ def dedup_shard(ctx, d_hash32: torch.Tensor, d_valid: Optional[torch.Tensor], n_
     # order, and one stable cas_id sort suffices
     records, rep, ng = group_device(ctx, recv, index_sorted=index_sorted)
     # identifier.object_owners is the torch statement of the same rule (tests compare them)
-    owners = torch.empty(max(records.shape[0], 1), dtype=torch.int64, device=dev)
-    ctx.dedup_owners(records, records.shape[0], rep, owners)
-    return records, rep, ng, owners[:records.shape[0]]
+    m = records.shape[0]
+    owners = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+    if index is None:
+        ctx.dedup_owners(records, m, rep, owners)
+        return records, rep, ng, owners[:m]
+    existing = torch.empty(max(m, 1), dtype=torch.uint8, device=dev)
+    new = torch.empty((max(m, 1), 2), dtype=torch.int64, device=dev)
+    n_new = torch.zeros(1, dtype=torch.int64, device=dev)
+    index.owners(records, m, rep, owners, existing, new, n_new)
+    return records, rep, ng, owners[:m], existing[:m], new[:int(n_new.item())]
 
 
 def make_comm(ctx, group: Optional[dist.ProcessGroup] = None):
@@ -154,12 +166,24 @@ class RcclDedup:
             self.records = torch.empty((cap, 2), dtype=torch.int64, device=self.device)
             self.rep = torch.empty(cap, dtype=torch.int64, device=self.device)
             self.owner = torch.empty(cap, dtype=torch.int64, device=self.device)
+            self.existing = self.new = None  # allocated by the first call that brings an index
             self.capacity = cap
 
-    def __call__(self, d_hash32, d_valid, n_local: int, global_base: int, chunk_size: int = 100, stream=None):
+    def __call__(self, d_hash32, d_valid, n_local: int, global_base: int, chunk_size: int = 100, stream=None,
+                 index=None):
+        """With ``index`` (this rank's shard of the Object index) the tuple gains (existing
+        uint8 [m], new heads int64 [n_new, 2]), as dedup_shard's does."""
         from ._native import SD_ERR_CAPACITY, SdCasError
         for _ in range(2):
             try:
+                if index is not None:
+                    if self.existing is None:
+                        self.existing = torch.empty(self.capacity, dtype=torch.uint8, device=self.device)
+                        self.new = torch.empty((self.capacity, 2), dtype=torch.int64, device=self.device)
+                    m, ng, nn = self.ctx.dedup_mgpu_indexed(self.comm, d_hash32, d_valid, n_local, global_base,
+                                                            self.records, self.rep, self.owner, self.capacity, index,
+                                                            self.existing, self.new, chunk_size, stream)
+                    return self.records[:m], self.rep[:m], ng, self.owner[:m], self.existing[:m], self.new[:nn]
                 m, ng = self.ctx.dedup_mgpu(self.comm, d_hash32, d_valid, n_local, global_base, self.records,
                                             self.rep, self.owner, self.capacity, chunk_size, stream)
                 return self.records[:m], self.rep[:m], ng, self.owner[:m]
@@ -201,3 +225,50 @@ def group_host(records: np.ndarray):
     head[1:] = ks[1:] != ks[:-1]
     head_pos = np.maximum.accumulate(np.where(head, np.arange(len(r)), 0))
     return r, r[head_pos, 1], int(head.sum())
+
+
+def index_insert_host(keys: np.ndarray, vals: np.ndarray, new_keys, new_vals, nparts: int = 1, part: int = 0):
+    """Host mirror of sd_object_index_insert on an index given as (keys uint64 ascending,
+    vals uint64): keep first -- an entry the index has wins, then the earliest pair of a key
+    in input (DB) order -- and only keys of shard `part` of `nparts`.  Returns (keys, vals,
+    taken)."""
+    nk = np.ascontiguousarray(new_keys, dtype=np.uint64).reshape(-1)
+    nv = np.ascontiguousarray(new_vals, dtype=np.uint64).reshape(-1)
+    order = np.argsort(nk, kind="stable")
+    nk, nv = nk[order], nv[order]
+    first = np.ones(len(nk), bool)
+    first[1:] = nk[1:] != nk[:-1]
+    keep = first & (dest_of(nk, nparts) == part) & ~np.isin(nk, keys)
+    nk, nv = nk[keep], nv[keep]
+    allk = np.concatenate([np.asarray(keys, np.uint64), nk])
+    allv = np.concatenate([np.asarray(vals, np.uint64), nv])
+    o = np.argsort(allk, kind="stable")
+    return allk[o], allv[o], int(keep.sum())
+
+
+def owners_indexed_host(records: np.ndarray, rep: np.ndarray, keys: np.ndarray, vals: np.ndarray,
+                        chunk_size: int = 100):
+    """Host mirror of sd_dedup_owners_indexed on grouped records (int64 [m, 2] sorted by (key,
+    index), rep int64 [m]) against an index (keys uint64 ascending, vals uint64):
+        owner(i) = index[cas(i)]                       if the index has cas(i)   (existing = 1)
+                 = i if chunk(i) == chunk(rep(i)) else rep(i)                    (existing = 0)
+    Returns (owner uint64 [m], existing uint8 [m], new heads uint64 [n_new, 2]: (key, file
+    index) of each group the index lacks, ascending)."""
+    m = len(records)
+    if m == 0:
+        return np.zeros(0, np.uint64), np.zeros(0, np.uint8), np.zeros((0, 2), np.uint64)
+    k = np.ascontiguousarray(records[:, 0]).view(np.uint64)
+    idx = np.ascontiguousarray(records[:, 1]).view(np.uint64)
+    r = np.ascontiguousarray(rep).view(np.uint64)
+    keys = np.asarray(keys, np.uint64)
+    at = np.searchsorted(keys, k)
+    found = np.zeros(m, bool)
+    inside = at < len(keys)
+    found[inside] = keys[at[inside]] == k[inside]
+    c = np.uint64(chunk_size)
+    owner = np.where(idx // c == r // c, idx, r)
+    owner[found] = np.asarray(vals, np.uint64)[at[found]]
+    head = np.ones(m, bool)
+    head[1:] = k[1:] != k[:-1]
+    head &= ~found
+    return owner, found.astype(np.uint8), np.stack([k[head], idx[head]], axis=1)

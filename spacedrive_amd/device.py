@@ -151,6 +151,174 @@ class Context:
             raise
         return int(m.value), int(ng.value)
 
+    def dedup_mgpu_indexed(self, comm: "Comm", d_hash32, d_valid, n: int, base: int, d_records, d_rep, d_owner,
+                           capacity: int, index: "ObjectIndex", d_existing, d_new, chunk_size: int = 100, stream=None):
+        """sd_cas_dedup_mgpu_indexed: dedup_mgpu with the owners taken through this rank's shard
+        of the Object index.  Returns (m, n_groups, n_new); a wrongly sharded index on any rank
+        raises SdCasError (SD_ERR_INVALID) on every rank."""
+        m = ctypes.c_uint64(0)
+        ng = ctypes.c_uint64(0)
+        nn = ctypes.c_uint64(0)
+        rc = lib().sd_cas_dedup_mgpu_indexed(self.handle, comm.handle, _ptr(d_hash32), _ptr(d_valid), n, base,
+                                             chunk_size, _ptr(d_records), _ptr(d_rep), _ptr(d_owner), capacity,
+                                             ctypes.byref(m), ctypes.byref(ng), _stream(stream),
+                                             None if index is None else index.handle, _ptr(d_existing), _ptr(d_new),
+                                             ctypes.byref(nn))
+        try:
+            check(rc)
+        except SdCasError as e:
+            e.needed = int(m.value)
+            raise
+        return int(m.value), int(ng.value), int(nn.value)
+
+
+class ObjectIndex:
+    """The device-resident Object index (sd_object_index): cas_id key -> the Object of the
+    library that already owns it (file_identifier/mod.rs:168-225).  Keys are carried in int64
+    tensors (the bit pattern of the u64); Object ids likewise.  Insert is keep-first and
+    exclusive; lookups may run concurrently (include/sd_cas.h)."""
+
+    def __init__(self, ctx: Context, nparts: int = 1, part: int = 0):
+        self.ctx, self.nparts, self.part = ctx, nparts, part
+        h = ctypes.c_void_p()
+        check(lib().sd_object_index_create(ctx.handle, nparts, part, ctypes.byref(h)))
+        self.handle = h
+
+    def __len__(self) -> int:
+        n = ctypes.c_uint64(0)
+        check(lib().sd_object_index_count(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
+    def insert(self, d_keys: torch.Tensor, d_object_ids: torch.Tensor, stream=None) -> int:
+        """(key, Object id) pairs in DB order; returns how many entries were added."""
+        m = int(d_keys.numel())
+        assert d_object_ids.numel() == m and d_keys.dtype == d_object_ids.dtype == torch.int64
+        assert m == 0 or (d_keys.is_cuda and d_object_ids.is_cuda and d_keys.is_contiguous()
+                          and d_object_ids.is_contiguous())
+        taken = ctypes.c_uint64(0)
+        check(lib().sd_object_index_insert(self.ctx.handle, self.handle, _ptr(d_keys) if m else None,
+                                           _ptr(d_object_ids) if m else None, m, ctypes.byref(taken), _stream(stream)))
+        return int(taken.value)
+
+    def insert_hex(self, cas_ids, object_ids) -> int:
+        """The same from the DB's strings: 16-hex-digit cas_ids and their Object ids."""
+        m = len(cas_ids)
+        buf = b"".join(c.encode("ascii") + b"\0" for c in cas_ids)
+        if len(buf) != 17 * m:
+            raise ValueError("a cas_id is not 16 characters")
+        ids = np.ascontiguousarray(object_ids, dtype=np.uint64)
+        assert ids.size == m
+        taken = ctypes.c_uint64(0)
+        torch.cuda.current_stream().synchronize()
+        check(lib().sd_object_index_insert_hex(self.ctx.handle, self.handle, buf if m else None,
+                                               _ptr(ids) if m else None, m, ctypes.byref(taken)))
+        return int(taken.value)
+
+    def lookup(self, d_keys: torch.Tensor, d_object_ids: torch.Tensor = None, d_found: torch.Tensor = None,
+               m: Optional[int] = None, stream=None):
+        """-> (object ids int64 [m], found uint8 [m]) for m keys in any order."""
+        m = int(d_keys.numel()) if m is None else m
+        if d_object_ids is None:
+            d_object_ids = torch.empty(max(m, 1), dtype=torch.int64, device=d_keys.device)
+        if d_found is None:
+            d_found = torch.empty(max(m, 1), dtype=torch.uint8, device=d_keys.device)
+        check(lib().sd_object_index_lookup(self.ctx.handle, self.handle, _ptr(d_keys) if m else None, m,
+                                           _ptr(d_object_ids), _ptr(d_found), _stream(stream)))
+        return d_object_ids[:m], d_found[:m]
+
+    def export(self, stream=None):
+        """-> (keys int64 [n] ascending as u64, object ids int64 [n]) on the context's device."""
+        n = len(self)
+        dev = torch.device("cuda", self.ctx.device)
+        k = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        v = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        check(lib().sd_object_index_export(self.ctx.handle, self.handle, _ptr(k), _ptr(v), max(n, 1), _stream(stream)))
+        return k[:n], v[:n]
+
+    def owners(self, d_records, m: int, d_rep, d_owner, d_existing, d_new, d_n_new, chunk_size: int = 100,
+               stream=None) -> None:
+        """sd_dedup_owners_indexed on grouped records; d_n_new is a device int64 [1]."""
+        check(lib().sd_dedup_owners_indexed(self.ctx.handle, self.handle, _ptr(d_records), m, _ptr(d_rep), chunk_size,
+                                            _ptr(d_owner), _ptr(d_existing), _ptr(d_new), _ptr(d_n_new),
+                                            _stream(stream)))
+
+    def close(self) -> None:
+        if self.handle:
+            lib().sd_object_index_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HostObjectIndex:
+    """The host twin (sd_cpu_object_index): the same index over numpy arrays, for a host
+    without a gfx950 device.  Keys and Object ids are uint64 arrays."""
+
+    def __init__(self, nparts: int = 1, part: int = 0):
+        self.nparts, self.part = nparts, part
+        h = ctypes.c_void_p()
+        check(lib().sd_cpu_object_index_create(nparts, part, ctypes.byref(h)))
+        self.handle = h
+
+    def __len__(self) -> int:
+        n = ctypes.c_uint64(0)
+        check(lib().sd_cpu_object_index_count(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
+    def insert(self, keys, object_ids) -> int:
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        v = np.ascontiguousarray(object_ids, dtype=np.uint64)
+        assert k.size == v.size
+        taken = ctypes.c_uint64(0)
+        check(lib().sd_cpu_object_index_insert(self.handle, _ptr(k) if k.size else None, _ptr(v) if k.size else None,
+                                               k.size, ctypes.byref(taken)))
+        return int(taken.value)
+
+    def lookup(self, keys):
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        ids = np.zeros(max(k.size, 1), np.uint64)
+        found = np.zeros(max(k.size, 1), np.uint8)
+        check(lib().sd_cpu_object_index_lookup(self.handle, _ptr(k) if k.size else None, k.size, _ptr(ids),
+                                               _ptr(found)))
+        return ids[:k.size], found[:k.size]
+
+    def export(self):
+        n = len(self)
+        k = np.zeros(max(n, 1), np.uint64)
+        v = np.zeros(max(n, 1), np.uint64)
+        check(lib().sd_cpu_object_index_export(self.handle, _ptr(k), _ptr(v), max(n, 1)))
+        return k[:n], v[:n]
+
+    def owners(self, records: np.ndarray, rep: np.ndarray, chunk_size: int = 100):
+        """sd_cpu_dedup_owners_indexed on grouped records (int64 [m, 2], rep int64 [m]) ->
+        (owner uint64 [m], existing uint8 [m], new heads uint64 [n_new, 2])."""
+        m = len(records)
+        r = np.ascontiguousarray(records).view(np.uint64).reshape(-1)
+        p = np.ascontiguousarray(rep).view(np.uint64)
+        owner = np.zeros(max(m, 1), np.uint64)
+        existing = np.zeros(max(m, 1), np.uint8)
+        new = np.zeros((max(m, 1), 2), np.uint64)
+        n_new = ctypes.c_uint64(0)
+        check(lib().sd_cpu_dedup_owners_indexed(self.handle, _ptr(r) if m else None, m, _ptr(p) if m else None,
+                                                chunk_size, _ptr(owner), _ptr(existing), _ptr(new),
+                                                ctypes.byref(n_new)))
+        return owner[:m], existing[:m], new[:int(n_new.value)]
+
+    def close(self) -> None:
+        if self.handle:
+            lib().sd_cpu_object_index_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class CommGroup:
     """sd_comm_group: the in-process rendezvous of ``nranks`` ranks that are threads of one

@@ -33,6 +33,21 @@ def object_owners(index: torch.Tensor, rep: torch.Tensor, chunk_size: int = CHUN
     return torch.where(same_step, index, rep)
 
 
+def object_owners_indexed(key: torch.Tensor, index: torch.Tensor, rep: torch.Tensor, idx_keys: torch.Tensor,
+                          idx_vals: torch.Tensor, chunk_size: int = CHUNK_SIZE):
+    """object_owners against the Objects the library already has (mod.rs:168-225): a record
+    whose cas_id key is in the index (idx_keys ascending AS UNSIGNED, carried in int64;
+    idx_vals the Object ids) is owned by that Object; the rest follow object_owners.  Returns
+    (owner, existing bool) -- the torch statement of sd_dedup_owners_indexed."""
+    owner = object_owners(index, rep, chunk_size)
+    if idx_keys.numel() == 0:
+        return owner, torch.zeros_like(owner, dtype=torch.bool)
+    flip = torch.tensor(-2 ** 63, dtype=torch.int64, device=key.device)  # unsigned order in int64
+    at = torch.searchsorted(idx_keys ^ flip, key ^ flip).clamp(max=idx_keys.numel() - 1)
+    existing = idx_keys[at] == key
+    return torch.where(existing, idx_vals[at], owner), existing
+
+
 def step_counts(index: torch.Tensor, owner: torch.Tensor, n_files: int, empty_index: torch.Tensor = None,
                 chunk_size: int = CHUNK_SIZE):
     """(created, linked) per identifier step, as identifier_job_step returns them (mod.rs:335)."""

@@ -23,13 +23,16 @@ from ._native import SD_FILE_OK
 
 
 def scan_library(ctx, paths: Sequence[str], sizes, comm=None, group: Optional[dist.ProcessGroup] = None,
-                 chunk_size: int = 100, nthreads: int = 16) -> dict:
+                 chunk_size: int = 100, nthreads: int = 16, index=None) -> dict:
     """This rank's share of the scan of the whole library (`paths`, `sizes` as the walker's
     metadata reported them; the same lists on every rank).  With `comm` (libsdcas's RCCL
     communicator, dedup.make_comm) the exchange runs inside the library; without it, over
     torch.distributed.  Returns {"shard": (lo, hi), "cas_ids": [str | OSError] for files
     lo..hi-1, "records": int64 [m, 2] (cas_id key, global index) sorted, "rep": [m],
-    "owner": [m], "n_groups": int}."""
+    "owner": [m], "n_groups": int}.  With `index` (a device.ObjectIndex of the Objects the
+    library already has, sharded as this rank's prefix range) owners of known cas_ids are those Objects' ids, and the result gains "existing"
+    (uint8 [m]) and "new_heads" (int64 [n_new, 2]: key, creating file) to insert once the
+    host has given the new Objects their ids."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
@@ -40,7 +43,15 @@ def scan_library(ctx, paths: Sequence[str], sizes, comm=None, group: Optional[di
     d_hash = torch.zeros((max(n, 1), 32), dtype=torch.uint8, device=dev)
     d_valid = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
     status = ctx.hashes_files(list(paths[lo:hi]), sizes[lo:hi], d_hash, d_valid, nthreads=nthreads)
-    if comm is not None:
+    extra = {}
+    if index is not None:
+        if comm is not None:
+            runner = dedup.RcclDedup(ctx, comm, dev, capacity=n * 5 // 4 + 4096)
+            recs, rep, ng, owner, existing, new = runner(d_hash, d_valid, n, lo, chunk_size=chunk_size, index=index)
+        else:
+            recs, rep, ng, owner, existing, new = dedup.dedup_shard(ctx, d_hash, d_valid, n, lo, group, index=index)
+        extra = {"existing": existing, "new_heads": new}
+    elif comm is not None:
         runner = dedup.RcclDedup(ctx, comm, dev, capacity=n * 5 // 4 + 4096)
         recs, rep, ng, owner = runner(d_hash, d_valid, n, lo, chunk_size=chunk_size)
     else:
@@ -48,4 +59,4 @@ def scan_library(ctx, paths: Sequence[str], sizes, comm=None, group: Optional[di
     h = d_hash[:n].cpu().numpy()
     ids = [h[i, :8].tobytes().hex() if status[i] == SD_FILE_OK else _status_error(int(status[i]), str(paths[lo + i]))
            for i in range(n)]
-    return {"shard": (lo, hi), "cas_ids": ids, "records": recs, "rep": rep, "owner": owner, "n_groups": ng}
+    return {"shard": (lo, hi), "cas_ids": ids, "records": recs, "rep": rep, "owner": owner, "n_groups": ng, **extra}
