@@ -430,11 +430,13 @@ int sd_dedup_owners(sd_cas_ctx* ctx, const uint64_t* d_records, uint64_t m, cons
  * first Object, in the order the caller lists them, that owns the cas_id (mod.rs:189-225).
  * An index created for (nparts, part) keeps only the keys sd_dedup_partition sends to rank
  * `part` of `nparts` and skips the others, so every rank can be handed the same DB dump;
- * nparts 1, part 0 = unsharded.  Entries are never deleted (rebuild the index instead).
+ * nparts 1, part 0 = unsharded.  Entries leave through sd_object_index_remove* as the DB's
+ * Objects and file_paths do (below), so a live library never rebuilds the index.
  * Thread safety: concurrent sd_object_index_lookup / _count / _export calls on one index are
- * safe; sd_object_index_insert* is exclusive (no other call on the index, and no kernel of
- * an earlier call still reading it, while it runs), and sd_dedup_owners_indexed uses
- * scratch owned by the index: one such call in flight per index. */
+ * safe; sd_object_index_insert* and sd_object_index_remove* are exclusive (no other call on
+ * the index, and no kernel of an earlier call still reading it, while one runs), and
+ * sd_dedup_owners_indexed uses scratch owned by the index: one such call in flight per
+ * index. */
 typedef struct sd_object_index sd_object_index;
 int sd_object_index_create(sd_cas_ctx* ctx, int nparts, int part, sd_object_index** out);
 void sd_object_index_destroy(sd_object_index* index);
@@ -448,6 +450,41 @@ int sd_object_index_insert(sd_cas_ctx* ctx, sd_object_index* index, const uint64
  * and a NUL (what sd_cas_ids writes; mod.rs:168-175 reads the same strings from the DB). */
 int sd_object_index_insert_hex(sd_cas_ctx* ctx, sd_object_index* index, const char* hex17,
                                const uint64_t* object_ids, uint64_t m, uint64_t* taken);
+/* Removal.  The reference takes Objects and their cas_ids away all the time: the orphan
+ * remover deletes every Object without a file_path, 512 per query
+ * (core/src/object/orphan_remover.rs:57-95); deleting a file takes a file_path from its
+ * Object; a content change moves a file_path from cas_id A to B on the same Object
+ * (core/src/location/manager/watcher/utils.rs:410-494).  After a removal the index is
+ * bit-identical to a fresh one built from the surviving entries with the same (nparts,
+ * part): the same keys and ids in ascending key order, the same count, the directory bits
+ * re-chosen for the new count and the directory rebuilt.  Buffers never shrink.
+ * Both calls: *removed (host, may be NULL) = the entries dropped; d_removed_out (device, may
+ * be NULL; `capacity` entries of 2 x u64) receives (key, Object id) of each dropped entry in
+ * ascending key order, so the host can ask the DB who else owns those cas_ids; nothing past
+ * the first *removed entries is written.  If d_removed_out is given and `capacity` is
+ * smaller than the count, the call returns SD_ERR_CAPACITY with *removed = the requirement
+ * and the index (and d_removed_out) unchanged.  They run on `stream` and sync it, are
+ * exclusive on the index as insert is, and are not collective: a sharded index drops what
+ * it holds, so every rank can be handed the same list.  m == 0 is a no-op; after a removal
+ * that empties the index, lookups miss everything and insert works.
+ * By key (watcher/utils.rs:410-494; a deleted file_path): entry (k, v) goes iff some pair i
+ * has d_keys[i] == k and either d_object_ids == NULL or d_object_ids[i] == v -- "drop A -> O
+ * only if the index still says O", without a lookup round trip.  Repeated keys, absent keys,
+ * keys of other shards and pairs whose id does not match are no-ops. */
+int sd_object_index_remove(sd_cas_ctx* ctx, sd_object_index* index, const uint64_t* d_keys,
+                           const uint64_t* d_object_ids, uint64_t m, uint64_t* d_removed_out, uint64_t capacity,
+                           uint64_t* removed, void* stream);
+/* By Object (orphan_remover.rs:57-95; its batch is 512 ids, :62): every entry whose Object
+ * id is among the m ids goes.  One Object may own several keys after watcher updates; any
+ * u64 is a legal id; repeated and absent ids are no-ops. */
+int sd_object_index_remove_objects(sd_cas_ctx* ctx, sd_object_index* index, const uint64_t* d_object_ids,
+                                   uint64_t m, uint64_t* d_removed_out, uint64_t capacity, uint64_t* removed,
+                                   void* stream);
+/* sd_object_index_remove from the DB's strings (hex17 as sd_object_index_insert_hex takes
+ * it; watcher/utils.rs:410-494 holds the old cas_id as such a string); object_ids on the
+ * host, may be NULL. */
+int sd_object_index_remove_hex(sd_cas_ctx* ctx, sd_object_index* index, const char* hex17,
+                               const uint64_t* object_ids, uint64_t m, uint64_t* removed);
 int sd_object_index_count(const sd_object_index* index, uint64_t* n);
 /* d_found[i] (u8) = 1 and d_object_ids[i] = the Object id if d_keys[i] is in the index, else
  * 0 and 0 (mod.rs:168-175 for m keys in any order).  Asynchronous on `stream`. */
@@ -472,12 +509,17 @@ int sd_dedup_owners_indexed(sd_cas_ctx* ctx, const sd_object_index* index, const
                             uint64_t* d_new_out, uint64_t* d_n_new, void* stream);
 /* The host-only siblings, over host arrays, for a host without a gfx950 device: the same
  * semantics, layout and directory (mod.rs:168-225).  sd_cpu_dedup_owners_indexed takes
- * *n_new on the host. */
+ * *n_new on the host; the removals (orphan_remover.rs:57-95, watcher/utils.rs:410-494) take
+ * removed_out / capacity / removed on the host. */
 typedef struct sd_cpu_object_index sd_cpu_object_index;
 int sd_cpu_object_index_create(int nparts, int part, sd_cpu_object_index** out);
 void sd_cpu_object_index_destroy(sd_cpu_object_index* index);
 int sd_cpu_object_index_insert(sd_cpu_object_index* index, const uint64_t* keys, const uint64_t* object_ids,
                                uint64_t m, uint64_t* taken);
+int sd_cpu_object_index_remove(sd_cpu_object_index* index, const uint64_t* keys, const uint64_t* object_ids,
+                               uint64_t m, uint64_t* removed_out, uint64_t capacity, uint64_t* removed);
+int sd_cpu_object_index_remove_objects(sd_cpu_object_index* index, const uint64_t* object_ids, uint64_t m,
+                                       uint64_t* removed_out, uint64_t capacity, uint64_t* removed);
 int sd_cpu_object_index_lookup(const sd_cpu_object_index* index, const uint64_t* keys, uint64_t m,
                                uint64_t* object_ids, uint8_t* found);
 int sd_cpu_object_index_count(const sd_cpu_object_index* index, uint64_t* n);

@@ -153,6 +153,16 @@ extern "C" {
                                   d_object_ids: *const u64, m: u64, taken: *mut u64, stream: *mut c_void) -> c_int;
     pub fn sd_object_index_insert_hex(ctx: *mut sd_cas_ctx, index: *mut sd_object_index, hex17: *const c_char,
                                       object_ids: *const u64, m: u64, taken: *mut u64) -> c_int;
+    // removal: Objects deleted (orphan_remover.rs:57-95), file_paths deleted or moved to another
+    // cas_id (watcher/utils.rs:410-494)
+    pub fn sd_object_index_remove(ctx: *mut sd_cas_ctx, index: *mut sd_object_index, d_keys: *const u64,
+                                  d_object_ids: *const u64, m: u64, d_removed_out: *mut u64, capacity: u64,
+                                  removed: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_object_index_remove_objects(ctx: *mut sd_cas_ctx, index: *mut sd_object_index,
+                                          d_object_ids: *const u64, m: u64, d_removed_out: *mut u64, capacity: u64,
+                                          removed: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_object_index_remove_hex(ctx: *mut sd_cas_ctx, index: *mut sd_object_index, hex17: *const c_char,
+                                      object_ids: *const u64, m: u64, removed: *mut u64) -> c_int;
     pub fn sd_object_index_count(index: *const sd_object_index, n: *mut u64) -> c_int;
     pub fn sd_object_index_lookup(ctx: *mut sd_cas_ctx, index: *const sd_object_index, d_keys: *const u64, m: u64,
                                   d_object_ids: *mut u64, d_found: *mut u8, stream: *mut c_void) -> c_int;
@@ -166,6 +176,10 @@ extern "C" {
     pub fn sd_cpu_object_index_destroy(index: *mut sd_cpu_object_index);
     pub fn sd_cpu_object_index_insert(index: *mut sd_cpu_object_index, keys: *const u64, object_ids: *const u64,
                                       m: u64, taken: *mut u64) -> c_int;
+    pub fn sd_cpu_object_index_remove(index: *mut sd_cpu_object_index, keys: *const u64, object_ids: *const u64,
+                                      m: u64, removed_out: *mut u64, capacity: u64, removed: *mut u64) -> c_int;
+    pub fn sd_cpu_object_index_remove_objects(index: *mut sd_cpu_object_index, object_ids: *const u64, m: u64,
+                                              removed_out: *mut u64, capacity: u64, removed: *mut u64) -> c_int;
     pub fn sd_cpu_object_index_lookup(index: *const sd_cpu_object_index, keys: *const u64, m: u64,
                                       object_ids: *mut u64, found: *mut u8) -> c_int;
     pub fn sd_cpu_object_index_count(index: *const sd_cpu_object_index, n: *mut u64) -> c_int;
@@ -342,6 +356,30 @@ pub fn fingerprints_blocking(data: &[u8], ranges: &[(u64, u64)]) -> Result<Vec<(
     }
     Ok((0..n).map(|i| (hex_at(&h17, i, 17, 16), hex_at(&h65, i, 65, 64))).collect())
 }
+
+// Keeping the Object index true while the library changes.  The invariant:
+// index[c] = the first live Object, in DB order, that owns a file_path with cas_id c.  Remove
+// and insert are two calls; both are exclusive on the index.
+//
+// The orphan remover's hook (orphan_remover.rs:57-95), after its delete_many of <= 512 ids:
+//
+//     let mut removed = 0u64;
+//     sd_object_index_remove_objects(ctx, index, d_ids, ids.len() as u64, d_removed, capacity, &mut removed, stream);
+//     // d_removed holds (key, Object id) of the entries that went; usually nobody else owns those
+//     // cas_ids, but a same-chunk duplicate's own Object may (mod.rs:233-333):
+//     let rows = db.file_path().find_many(vec![cas_id::in_vec(hex(&d_removed, removed))]).order_by(object_id).exec();
+//     sd_object_index_insert_hex(ctx, index, hex17(&rows), object_ids(&rows), rows.len() as u64, &mut taken);
+//
+// The watcher's update hook (watcher/utils.rs:410-494), file_path of Object O: cas_id A -> B:
+//
+//     sd_object_index_remove_hex(ctx, index, hex17(&[a]), [o].as_ptr(), 1, &mut removed);   // A -> O only if it still says O
+//     if lookup(b).map_or(false, |owner| db_order(owner) > db_order(o)) {
+//         sd_object_index_remove_hex(ctx, index, hex17(&[b]), std::ptr::null(), 1, &mut removed);
+//     }
+//     let rows = db.file_path().find_many(vec![cas_id::in_vec(vec![a, b])]).order_by(object_id).exec();
+//     sd_object_index_insert_hex(ctx, index, hex17(&rows), object_ids(&rows), rows.len() as u64, &mut taken);
+//
+// A deleted file_path (c, O) is the first and the last line of that hook with c for A.
 
 /// libsdcas's RCCL communicator for a multi-GPU library scan (one process per GPU).
 /// A member of an in-process group holds a reference to the group, so the group is

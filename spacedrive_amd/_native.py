@@ -144,6 +144,9 @@ SIGNATURES = [
     ("sd_object_index_destroy", None, [P]),
     ("sd_object_index_insert", I32, [P, P, P, P, U64, PU64, P]),
     ("sd_object_index_insert_hex", I32, [P, P, P, P, U64, PU64]),
+    ("sd_object_index_remove", I32, [P, P, P, P, U64, P, U64, PU64, P]),
+    ("sd_object_index_remove_objects", I32, [P, P, P, U64, P, U64, PU64, P]),
+    ("sd_object_index_remove_hex", I32, [P, P, P, P, U64, PU64]),
     ("sd_object_index_count", I32, [P, PU64]),
     ("sd_object_index_lookup", I32, [P, P, P, U64, P, P, P]),
     ("sd_object_index_export", I32, [P, P, P, P, U64, P]),
@@ -152,6 +155,8 @@ SIGNATURES = [
     ("sd_cpu_object_index_create", I32, [I32, I32, ctypes.POINTER(P)]),
     ("sd_cpu_object_index_destroy", None, [P]),
     ("sd_cpu_object_index_insert", I32, [P, P, P, U64, PU64]),
+    ("sd_cpu_object_index_remove", I32, [P, P, P, U64, P, U64, PU64]),
+    ("sd_cpu_object_index_remove_objects", I32, [P, P, U64, P, U64, PU64]),
     ("sd_cpu_object_index_lookup", I32, [P, P, U64, P, P]),
     ("sd_cpu_object_index_count", I32, [P, PU64]),
     ("sd_cpu_object_index_export", I32, [P, P, P, U64]),

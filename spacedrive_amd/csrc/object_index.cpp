@@ -1,9 +1,11 @@
 // object_index.cpp -- the device-resident Object index behind the C ABI (include/sd_cas.h):
 // which Object already owns a cas_id, the join identifier_job_step does per 100-row step
 // through the DB (core/src/object/file_identifier/mod.rs:168-175) before it links each file
-// to the first such Object (:189-225).  Kernels: object_index.hip; layout, lookup and the
-// directory / growth policies: object_index.h, object_index_host.cpp (shared with the
-// sd_cpu_object_index_* mirror).
+// to the first such Object (:189-225), and the removals that keep it true while Objects are
+// deleted (core/src/object/orphan_remover.rs:57-95) and files change
+// (location/manager/watcher/utils.rs:410-494).  Kernels: object_index.hip; layout, lookup,
+// the removal rules and the directory / growth policies: object_index.h,
+// object_index_host.cpp (shared with the sd_cpu_object_index_* mirror).
 #include <vector>
 
 #include "object_index.h"
@@ -13,6 +15,33 @@ namespace {
 
 void check_index(const sd_cas_ctx* ctx, const sd_object_index* index) {
     if (index->ctx != ctx) throw sd_failure(SD_ERR_INVALID, "the index belongs to another context");
+}
+
+// The second half of both removals, after the flagging pass: the per-slice counts give the
+// number of dropped entries; it is checked against `capacity` BEFORE anything is written, so
+// a short d_removed_out leaves the index (and d_removed_out) as they were.  Then the two-way
+// compaction into the other buffer pair, the swap, and the directory for the new count.
+void finish_remove(sd_object_index* x, uint64_t* d_removed_out, uint64_t capacity, uint64_t* removed, hipStream_t s) {
+    const uint32_t slots = sdk::index_remove_slots(x->n);
+    HIP_CHECK(hipMemcpyAsync(x->host.p, x->counts.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const uint64_t* c = reinterpret_cast<const uint64_t*>(x->host.p);
+    uint64_t r = 0;
+    for (uint32_t k = 0; k < slots; k++) r += c[k];
+    if (r > x->n) throw sd_failure(SD_ERR_INTERNAL, "remove: more dropped entries than entries");
+    if (removed) *removed = r;
+    if (r == 0) return;
+    if (d_removed_out && capacity < r)
+        throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of removed entries");
+    const int to = 1 - x->cur;  // both pairs hold `cap` entries since the insert that grew them
+    HIP_CHECK(sdk::index_remove_compact(x->view(), x->scratch.p, x->counts.as<uint64_t>(), x->keys[to].as<uint64_t>(),
+                                        x->vals[to].as<uint64_t>(), d_removed_out, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // the compaction read the old buffers
+    x->cur = to;
+    x->n -= r;
+    x->bits = oi_dir_bits(x->n);  // re-chosen for the new count; the directory's buffer never shrinks
+    HIP_CHECK(sdk::index_build_dir(x->keys[to].as<uint64_t>(), x->n, x->bits, x->dir.as<uint64_t>(), s));
+    HIP_CHECK(hipStreamSynchronize(s));
 }
 
 }  // namespace
@@ -37,7 +66,7 @@ int sd_object_index_create(sd_cas_ctx* ctx, int nparts, int part, sd_object_inde
     x->dir.alloc(2 * sizeof(uint64_t));
     HIP_CHECK(hipMemset(x->dir.p, 0, 2 * sizeof(uint64_t)));
     x->counts.alloc((sdk::OI_COUNT_SLOTS + 1) * sizeof(uint64_t));  // + sd_cas_dedup_mgpu_indexed's count
-    x->host.ensure(sizeof(uint64_t));
+    x->host.ensure(sdk::OI_COUNT_SLOTS * sizeof(uint64_t));  // an insert's count; a removal's per-slice counts
     *out = x.release();
     return SD_OK;
     SD_GUARD_END
@@ -117,6 +146,66 @@ int sd_object_index_insert_hex(sd_cas_ctx* ctx, sd_object_index* index, const ch
     HIP_CHECK(hipMemcpy(dk.p, keys.data(), m * sizeof(uint64_t), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dv.p, object_ids, m * sizeof(uint64_t), hipMemcpyHostToDevice));
     return sd_object_index_insert(ctx, index, dk.as<uint64_t>(), dv.as<uint64_t>(), m, taken, nullptr);
+    SD_GUARD_END
+}
+
+int sd_object_index_remove(sd_cas_ctx* ctx, sd_object_index* index, const uint64_t* d_keys,
+                           const uint64_t* d_object_ids, uint64_t m, uint64_t* d_removed_out, uint64_t capacity,
+                           uint64_t* removed, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index || (m && !d_keys)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (removed) *removed = 0;
+    sd_object_index* x = index;
+    if (m == 0 || x->n == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    x->scratch.ensure(sdk::index_remove_scratch(x->n, 0));
+    HIP_CHECK(sdk::index_remove_flag_keys(x->view(), d_keys, d_object_ids, m, x->scratch.p, x->counts.as<uint64_t>(),
+                                          s));
+    finish_remove(x, d_removed_out, capacity, removed, s);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_object_index_remove_objects(sd_cas_ctx* ctx, sd_object_index* index, const uint64_t* d_object_ids, uint64_t m,
+                                   uint64_t* d_removed_out, uint64_t capacity, uint64_t* removed, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index || (m && !d_object_ids)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (removed) *removed = 0;
+    sd_object_index* x = index;
+    if (m == 0 || x->n == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    x->scratch.ensure(sdk::index_remove_scratch(x->n, m));
+    HIP_CHECK(sdk::index_remove_flag_objects(x->view(), d_object_ids, m, x->scratch.p, x->counts.as<uint64_t>(), s));
+    finish_remove(x, d_removed_out, capacity, removed, s);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_object_index_remove_hex(sd_cas_ctx* ctx, sd_object_index* index, const char* hex17, const uint64_t* object_ids,
+                               uint64_t m, uint64_t* removed) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index || (m && !hex17)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (removed) *removed = 0;
+    if (m == 0) return SD_OK;
+    std::vector<uint64_t> keys(m);
+    for (uint64_t i = 0; i < m; i++)
+        if (!oi_key_from_hex(hex17 + 17 * i, &keys[i]))
+            throw sd_failure(SD_ERR_INVALID, "cas_id " + std::to_string(i) + " is not 16 lower-case hex digits");
+    ctx->bind();
+    sdi::DevBuf dk, dv;
+    dk.alloc(m * sizeof(uint64_t));
+    HIP_CHECK(hipMemcpy(dk.p, keys.data(), m * sizeof(uint64_t), hipMemcpyHostToDevice));
+    if (object_ids) {
+        dv.alloc(m * sizeof(uint64_t));
+        HIP_CHECK(hipMemcpy(dv.p, object_ids, m * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    return sd_object_index_remove(ctx, index, dk.as<uint64_t>(), object_ids ? dv.as<uint64_t>() : nullptr, m, nullptr,
+                                  0, removed, nullptr);
     SD_GUARD_END
 }
 

@@ -50,6 +50,20 @@ SD_OI_HD bool oi_find(const uint64_t* keys, const uint64_t* dir, uint32_t bits, 
     return at < hi && keys[at] == key;
 }
 
+// ---- removal (orphan_remover.rs:57-95; watcher/utils.rs:410-494), stated once for both paths
+// By key: the position of the entry a pair (key, *id) removes, or false: the key is in the
+// index (keys of other shards never are) and, where an id is given, the entry still names it.
+SD_OI_HD bool oi_remove_hit(const uint64_t* keys, const uint64_t* vals, const uint64_t* dir, uint32_t bits,
+                            uint64_t key, const uint64_t* id, uint64_t* pos) {
+    return oi_find(keys, dir, bits, key, pos) && (!id || vals[*pos] == *id);
+}
+
+// By Object: is `id` among the m ids sorted ascending (unsigned)?
+SD_OI_HD bool oi_id_listed(const uint64_t* sorted_ids, uint64_t m, uint64_t id) {
+    const uint64_t at = oi_lower_bound(sorted_ids, 0, m, id);
+    return at < m && sorted_ids[at] == id;
+}
+
 // ---- policies (object_index_host.cpp; the device path calls the same functions)
 // directory bits for n entries: ~log2(n / 8), 0 for tiny indexes, at most 24
 uint32_t oi_dir_bits(uint64_t n);

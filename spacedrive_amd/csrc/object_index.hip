@@ -1,13 +1,15 @@
 // object_index.hip -- the device-resident Object index: lookup, the indexed owner rule with
-// its compacted list of new group heads, and insertion (merge by rank + directory rebuild).
+// its compacted list of new group heads, insertion (merge by rank + directory rebuild) and
+// removal by key or by Object (flag, two-way ordered compaction, directory rebuild).
 //
 // Reference semantics: identifier_job_step joins a step's cas_ids against the Objects the
 // library already has (core/src/object/file_identifier/mod.rs:168-175), links each file to
 // the first of them (:189-225) and creates Objects for the rest (:229-333).  Layout and
 // lookup: object_index.h (shared with the host mirror, object_index_host.cpp).
 //
-// Ordered compaction (new heads; an insert's surviving pairs) without atomics on the data
-// path: a fixed grid in which workgroup b owns the contiguous slice b of the input; the
+// Ordered compaction (new heads; an insert's surviving pairs; a removal's survivors and its
+// dropped entries) without atomics on the data path: a fixed grid in which workgroup b
+// owns the contiguous slice b of the input; the
 // flagging pass leaves one count per workgroup, and the compaction pass gives each
 // workgroup the sum of the counts before it, then ranks its flags in order (ballot /
 // popcount inside a wave, LDS counts across the four waves).
@@ -224,12 +226,90 @@ __global__ __launch_bounds__(256) void k_index_dir(const uint64_t* __restrict__ 
     }
 }
 
+// ---- removal (orphan_remover.rs:57-95 deletes Objects; watcher/utils.rs:410-494 moves a
+// file_path to another cas_id).  flags[n], one byte per entry of the index: 1 = dropped.
+// By key: every input pair marks the entry it removes (oi_remove_hit); pairs that hit the same
+// entry all write the same byte, so the flags do not depend on the order the lanes ran in.
+__global__ __launch_bounds__(256) void k_remove_mark(const uint64_t* __restrict__ keys,
+                                                     const uint64_t* __restrict__ vals,
+                                                     const uint64_t* __restrict__ dir, uint32_t bits,
+                                                     const uint64_t* __restrict__ rk, const uint64_t* __restrict__ rid,
+                                                     uint64_t m, uint8_t* __restrict__ flags) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t id = rid ? rid[i] : 0;
+        uint64_t at;
+        if (oi_remove_hit(keys, vals, dir, bits, rk[i], rid ? &id : nullptr, &at)) flags[at] = 1;
+    }
+}
+
+// the marks of k_remove_mark counted per workgroup slice
+__global__ __launch_bounds__(256) void k_remove_count(const uint8_t* __restrict__ flags, uint64_t n,
+                                                      uint64_t* __restrict__ counts) {
+    const oi_slice sl = oi_slice_of(n);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) mine += flags[i];
+    block_count(mine, counts);
+}
+
+// By Object: an entry goes if its value is among the ids (sorted ascending)
+__global__ __launch_bounds__(256) void k_remove_flag_objects(const uint64_t* __restrict__ vals, uint64_t n,
+                                                             const uint64_t* __restrict__ sorted_ids, uint64_t m,
+                                                             uint8_t* __restrict__ flags,
+                                                             uint64_t* __restrict__ counts) {
+    const oi_slice sl = oi_slice_of(n);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+        const bool drop = oi_id_listed(sorted_ids, m, vals[i]);
+        flags[i] = drop ? 1 : 0;
+        mine += drop;
+    }
+    block_count(mine, counts);
+}
+
+// Two-way ordered compaction: tile_slot gives every lane the number of dropped entries before
+// it, which is a dropped entry's row of rm_out (may be null) and, taken from its position, a
+// survivor's place in the other buffer pair.
+__global__ __launch_bounds__(256) void k_remove_compact(const uint64_t* __restrict__ keys,
+                                                        const uint64_t* __restrict__ vals, uint64_t n,
+                                                        const uint8_t* __restrict__ flags,
+                                                        const uint64_t* __restrict__ counts,
+                                                        uint64_t* __restrict__ out_keys,
+                                                        uint64_t* __restrict__ out_vals,
+                                                        uint64_t* __restrict__ rm_out) {
+    uint64_t run = block_base(counts, nullptr);
+    const oi_slice sl = oi_slice_of(n);
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool act = i < sl.hi;
+        const bool flag = act && flags[i];
+        const uint64_t slot = tile_slot(flag, run);
+        if (!act) continue;
+        const uint64_t k = keys[i], v = vals[i];
+        if (!flag) {
+            out_keys[i - slot] = k;
+            out_vals[i - slot] = v;
+        } else if (rm_out) {
+            rm_out[2 * slot] = k;
+            rm_out[2 * slot + 1] = v;
+        }
+    }
+}
+
 size_t insert_sort_bytes(uint64_t m, hipStream_t s) {
     size_t b = 0;
     uint64_t* nul = nullptr;
     if (rocprim::radix_sort_pairs(nullptr, b, nul, nul, nul, nul, (size_t)m, 0, 64, s) != hipSuccess) return 0;
     return (b + 255) & ~size_t(255);
 }
+
+size_t remove_sort_bytes(uint64_t m, hipStream_t s) {
+    size_t b = 0;
+    uint64_t* nul = nullptr;
+    if (rocprim::radix_sort_keys(nullptr, b, nul, nul, (size_t)m, 0, 64, s) != hipSuccess) return 0;
+    return (b + 255) & ~size_t(255);
+}
+
+size_t remove_flag_bytes(uint64_t n) { return (n + 255) & ~size_t(255); }
 
 }  // namespace
 
@@ -292,6 +372,47 @@ hipError_t index_merge(const oi_view& x, const uint64_t* nk, const uint64_t* nv,
     if (x.n + r == 0) return hipSuccess;
     hipLaunchKernelGGL(k_index_merge, dim3(grid_for(x.n + r)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, x.n, nk,
                        nv, r, out_keys, out_vals);
+    return hipGetLastError();
+}
+
+// scratch: flags[n] (u8), then for a removal by Object the sorted ids[m_ids] (u64) and the
+// radix sort's temporary storage
+size_t index_remove_scratch(uint64_t n, uint64_t m_ids) {
+    size_t b = remove_flag_bytes(n) + 256;
+    if (m_ids) b += ((m_ids * sizeof(uint64_t) + 255) & ~size_t(255)) + remove_sort_bytes(m_ids, nullptr) + 256;
+    return b;
+}
+
+uint32_t index_remove_slots(uint64_t n) { return sliced_grid(n); }
+
+hipError_t index_remove_flag_keys(const oi_view& x, const uint64_t* rm_keys, const uint64_t* rm_ids, uint64_t m,
+                                  void* scratch, uint64_t* counts, hipStream_t s) {
+    uint8_t* flags = reinterpret_cast<uint8_t*>(scratch);
+    hipError_t e = hipMemsetAsync(flags, 0, x.n, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_remove_mark, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, rm_keys,
+                       rm_ids, m, flags);
+    hipLaunchKernelGGL(k_remove_count, dim3(sliced_grid(x.n)), dim3(256), 0, s, flags, x.n, counts);
+    return hipGetLastError();
+}
+
+hipError_t index_remove_flag_objects(const oi_view& x, const uint64_t* ids, uint64_t m, void* scratch,
+                                     uint64_t* counts, hipStream_t s) {
+    uint8_t* flags = reinterpret_cast<uint8_t*>(scratch);
+    uint64_t* sorted = reinterpret_cast<uint64_t*>(flags + remove_flag_bytes(x.n));
+    void* tmp = reinterpret_cast<uint8_t*>(sorted) + ((m * sizeof(uint64_t) + 255) & ~size_t(255));
+    size_t tb = remove_sort_bytes(m, s);
+    hipError_t e = rocprim::radix_sort_keys(tmp, tb, ids, sorted, (size_t)m, 0, 64, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_remove_flag_objects, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.vals, x.n, sorted, m, flags,
+                       counts);
+    return hipGetLastError();
+}
+
+hipError_t index_remove_compact(const oi_view& x, const void* scratch, const uint64_t* counts, uint64_t* out_keys,
+                                uint64_t* out_vals, uint64_t* rm_out, hipStream_t s) {
+    hipLaunchKernelGGL(k_remove_compact, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, x.n,
+                       reinterpret_cast<const uint8_t*>(scratch), counts, out_keys, out_vals, rm_out);
     return hipGetLastError();
 }
 

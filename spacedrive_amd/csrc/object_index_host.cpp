@@ -5,8 +5,10 @@
 //
 // Reference: the join of a step's cas_ids against the Objects the library already has
 // (core/src/object/file_identifier/mod.rs:168-175) and the link to the first of them
-// (:189-225).  No HIP: built with g++ under the sanitizers too (object_index_selftest.cpp,
-// `make sanitize-object-index`).
+// (:189-225); removal as Objects are deleted (core/src/object/orphan_remover.rs:57-95) and
+// files change (location/manager/watcher/utils.rs:410-494).  No HIP: built with g++ under
+// the sanitizers too (object_index_selftest.cpp, object_index_remove_selftest.cpp; `make
+// sanitize-object-index`, `make sanitize-object-index-remove`).
 #include <string.h>
 
 #include <algorithm>
@@ -47,7 +49,7 @@ struct sd_cpu_object_index {
     int nparts = 1, part = 0;
     uint64_t n = 0, cap = 0;
     uint32_t bits = 0;
-    std::vector<uint64_t> keys, vals, keys2, vals2;  // two buffers of `cap`, swapped by an insert
+    std::vector<uint64_t> keys, vals, keys2, vals2;  // two buffers of `cap`, swapped by an insert or a removal
     std::vector<uint64_t> dir{0, 0};
 };
 
@@ -64,6 +66,36 @@ void build_dir(sd_cpu_object_index* x) {
         const uint64_t cur = oi_prefix(x->keys[i], x->bits);
         for (uint64_t q = first; q <= cur; q++) x->dir[q] = i;
     }
+}
+
+// The second half of both removals (object_index.cpp finish_remove): the count against
+// `capacity` before anything is written, the dropped entries in order into removed_out, the
+// survivors in order into the other buffer pair, the swap and the directory.
+void finish_remove(sd_cpu_object_index* x, const std::vector<uint8_t>& flags, uint64_t* removed_out, uint64_t capacity,
+                   uint64_t* removed) {
+    const uint64_t r = (uint64_t)std::count(flags.begin(), flags.end(), (uint8_t)1);
+    if (removed) *removed = r;
+    if (r == 0) return;
+    if (removed_out && capacity < r)
+        throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of removed entries");
+    uint64_t kept = 0, gone = 0;
+    for (uint64_t i = 0; i < x->n; i++) {
+        if (!flags[i]) {
+            x->keys2[kept] = x->keys[i];
+            x->vals2[kept] = x->vals[i];
+            kept++;
+        } else {
+            if (removed_out) {
+                removed_out[2 * gone] = x->keys[i];
+                removed_out[2 * gone + 1] = x->vals[i];
+            }
+            gone++;
+        }
+    }
+    x->keys.swap(x->keys2);
+    x->vals.swap(x->vals2);
+    x->n = kept;
+    build_dir(x);
 }
 
 }  // namespace
@@ -142,6 +174,41 @@ int sd_cpu_object_index_insert(sd_cpu_object_index* index, const uint64_t* keys,
     x->vals.swap(x->vals2);
     x->n += r;
     build_dir(x);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_object_index_remove(sd_cpu_object_index* index, const uint64_t* keys, const uint64_t* object_ids, uint64_t m,
+                               uint64_t* removed_out, uint64_t capacity, uint64_t* removed) {
+    SD_GUARD_BEGIN
+    if (!index || (m && !keys)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (removed) *removed = 0;
+    sd_cpu_object_index* x = index;
+    if (m == 0 || x->n == 0) return SD_OK;
+    std::vector<uint8_t> flags(x->n, 0);
+    for (uint64_t i = 0; i < m; i++) {
+        uint64_t at;
+        if (oi_remove_hit(x->keys.data(), x->vals.data(), x->dir.data(), x->bits, keys[i],
+                          object_ids ? &object_ids[i] : nullptr, &at))
+            flags[at] = 1;
+    }
+    finish_remove(x, flags, removed_out, capacity, removed);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_object_index_remove_objects(sd_cpu_object_index* index, const uint64_t* object_ids, uint64_t m,
+                                       uint64_t* removed_out, uint64_t capacity, uint64_t* removed) {
+    SD_GUARD_BEGIN
+    if (!index || (m && !object_ids)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (removed) *removed = 0;
+    sd_cpu_object_index* x = index;
+    if (m == 0 || x->n == 0) return SD_OK;
+    std::vector<uint64_t> sorted(object_ids, object_ids + m);
+    std::sort(sorted.begin(), sorted.end());
+    std::vector<uint8_t> flags(x->n);
+    for (uint64_t i = 0; i < x->n; i++) flags[i] = oi_id_listed(sorted.data(), m, x->vals[i]) ? 1 : 0;
+    finish_remove(x, flags, removed_out, capacity, removed);
     return SD_OK;
     SD_GUARD_END
 }

@@ -199,9 +199,10 @@ struct sd_fingerprint_batch {
 };
 
 // The device-resident Object index (object_index.cpp; layout in object_index.h): two
-// buffers of `cap` keys and values swapped by an insert, the prefix directory, and scratch
-// of its own (an insert's sort and compaction; the per-workgroup counts of an ordered
-// compaction), so no call borrows a context slot it could not hold until its kernels ran.
+// buffers of `cap` keys and values swapped by an insert or a removal, the prefix directory,
+// and scratch of its own (an insert's sort and compaction; a removal's flags and sorted ids;
+// the per-workgroup counts of an ordered compaction), so no call borrows a context slot it
+// could not hold until its kernels ran.
 struct sd_object_index {
     sd_cas_ctx* ctx = nullptr;
     int nparts = 1, part = 0;
@@ -210,8 +211,8 @@ struct sd_object_index {
     int cur = 0;                        // which buffer pair holds the index
     sdi::DevBuf keys[2], vals[2], dir;  // dir: 2^bits + 1 offsets
     sdi::DevBuf counts;                 // OI_COUNT_SLOTS u64, then one device count
-    sdi::DevBuf scratch;                // sdk::index_insert_scratch
-    sdi::PinnedBuf host;                // an insert's survivor count
+    sdi::DevBuf scratch;                // sdk::index_insert_scratch / index_remove_scratch
+    sdi::PinnedBuf host;                // an insert's survivor count; a removal's per-slice counts
     sdk::oi_view view() const {
         return {keys[cur].as<uint64_t>(), vals[cur].as<uint64_t>(), dir.as<uint64_t>(), n, bits};
     }

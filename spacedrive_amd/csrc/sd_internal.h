@@ -86,5 +86,18 @@ hipError_t index_insert_select(const oi_view& x, int nparts, int part, const uin
 // second half: merge the r survivors with the index into out_keys / out_vals (n + r entries)
 hipError_t index_merge(const oi_view& x, const uint64_t* nk, const uint64_t* nv, uint64_t r, uint64_t* out_keys,
                        uint64_t* out_vals, hipStream_t s);
+// removal, first half: flags[n] in `scratch` (1 = the entry goes) and one count per workgroup
+// slice in counts[0 .. index_remove_slots(n)); n > 0, m > 0.  By key (rm_ids may be null:
+// unconditional) or by Object (m_ids = m sizes the scratch for the sorted ids).
+size_t index_remove_scratch(uint64_t n, uint64_t m_ids);
+uint32_t index_remove_slots(uint64_t n);
+hipError_t index_remove_flag_keys(const oi_view& x, const uint64_t* rm_keys, const uint64_t* rm_ids, uint64_t m,
+                                  void* scratch, uint64_t* counts, hipStream_t s);
+hipError_t index_remove_flag_objects(const oi_view& x, const uint64_t* ids, uint64_t m, void* scratch,
+                                     uint64_t* counts, hipStream_t s);
+// second half: the survivors in order into out_keys / out_vals, the dropped entries (key,
+// Object id) in order into rm_out (may be null)
+hipError_t index_remove_compact(const oi_view& x, const void* scratch, const uint64_t* counts, uint64_t* out_keys,
+                                uint64_t* out_vals, uint64_t* rm_out, hipStream_t s);
 hipError_t index_build_dir(const uint64_t* keys, uint64_t n, uint32_t bits, uint64_t* dir, hipStream_t s);
 }  // namespace sdk

@@ -246,6 +246,34 @@ def index_insert_host(keys: np.ndarray, vals: np.ndarray, new_keys, new_vals, np
     return allk[o], allv[o], int(keep.sum())
 
 
+def _index_drop(keys: np.ndarray, vals: np.ndarray, drop: np.ndarray):
+    keys, vals = np.asarray(keys, np.uint64), np.asarray(vals, np.uint64)
+    return keys[~drop], vals[~drop], np.stack([keys[drop], vals[drop]], axis=1)
+
+
+def index_remove_host(keys: np.ndarray, vals: np.ndarray, rm_keys, rm_ids=None):
+    """Host mirror of sd_object_index_remove on an index given as (keys uint64 ascending, vals
+    uint64): entry (k, v) goes iff some pair i has rm_keys[i] == k and (rm_ids is None or
+    rm_ids[i] == v).  Returns (keys, vals, removed pairs uint64 [r, 2] ascending by key)."""
+    keys, vals = np.asarray(keys, np.uint64), np.asarray(vals, np.uint64)
+    rk = np.ascontiguousarray(rm_keys, dtype=np.uint64).reshape(-1)
+    drop = np.zeros(len(keys), bool)
+    if len(keys) and len(rk):
+        at = np.minimum(np.searchsorted(keys, rk), len(keys) - 1)
+        hit = keys[at] == rk
+        if rm_ids is not None:
+            hit &= vals[at] == np.ascontiguousarray(rm_ids, dtype=np.uint64).reshape(-1)
+        drop[at[hit]] = True
+    return _index_drop(keys, vals, drop)
+
+
+def index_remove_objects_host(keys: np.ndarray, vals: np.ndarray, ids):
+    """Host mirror of sd_object_index_remove_objects: every entry whose Object id is among
+    `ids` goes.  Returns (keys, vals, removed pairs uint64 [r, 2] ascending by key)."""
+    drop = np.isin(np.asarray(vals, np.uint64), np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1))
+    return _index_drop(keys, vals, drop)
+
+
 def owners_indexed_host(records: np.ndarray, rep: np.ndarray, keys: np.ndarray, vals: np.ndarray,
                         chunk_size: int = 100):
     """Host mirror of sd_dedup_owners_indexed on grouped records (int64 [m, 2] sorted by (key,

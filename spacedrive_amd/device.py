@@ -11,7 +11,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._native import Extent, SdCasError, check, lib
+from ._native import SD_ERR_CAPACITY, Extent, SdCasError, check, lib
 
 EXTENT_DTYPE = np.dtype([("size", "<u8"), ("msg_offset", "<u8"), ("msg_len", "<u4"), ("kind", "<u4")])
 assert EXTENT_DTYPE.itemsize == ctypes.sizeof(Extent) == 24
@@ -175,8 +175,8 @@ class Context:
 class ObjectIndex:
     """The device-resident Object index (sd_object_index): cas_id key -> the Object of the
     library that already owns it (file_identifier/mod.rs:168-225).  Keys are carried in int64
-    tensors (the bit pattern of the u64); Object ids likewise.  Insert is keep-first and
-    exclusive; lookups may run concurrently (include/sd_cas.h)."""
+    tensors (the bit pattern of the u64); Object ids likewise.  Insert is keep-first; insert
+    and the removals are exclusive; lookups may run concurrently (include/sd_cas.h)."""
 
     def __init__(self, ctx: Context, nparts: int = 1, part: int = 0):
         self.ctx, self.nparts, self.part = ctx, nparts, part
@@ -213,6 +213,72 @@ class ObjectIndex:
         check(lib().sd_object_index_insert_hex(self.ctx.handle, self.handle, buf if m else None,
                                                _ptr(ids) if m else None, m, ctypes.byref(taken)))
         return int(taken.value)
+
+    # -------------------------------------------------------------- removal
+    def _removal(self, call, bound: int, d_removed_out, capacity):
+        """Run call(out pointer, capacity, removed) -> rc.  Without a caller's buffer the
+        dropped pairs go to one of `bound` rows at most, regrown once to the requirement the
+        library reports (SD_ERR_CAPACITY leaves the index unchanged)."""
+        removed = ctypes.c_uint64(0)
+        own = d_removed_out is None
+        cap = max(int(bound), 1) if own else int(d_removed_out.numel() // 2 if capacity is None else capacity)
+        for _ in range(2):
+            if own:
+                d_removed_out = torch.empty((cap, 2), dtype=torch.int64, device=torch.device("cuda", self.ctx.device))
+            rc = call(_ptr(d_removed_out), cap, ctypes.byref(removed))
+            if rc == SD_ERR_CAPACITY and own:
+                cap = int(removed.value)
+                continue
+            try:
+                check(rc)
+            except SdCasError as e:
+                e.needed = int(removed.value)
+                raise
+            r = int(removed.value)
+            return d_removed_out.view(-1, 2)[:r], r
+        raise RuntimeError("sd_object_index_remove: capacity still short after regrowing")
+
+    def remove(self, d_keys: torch.Tensor, d_object_ids: Optional[torch.Tensor] = None, stream=None,
+               d_removed_out: Optional[torch.Tensor] = None, capacity: Optional[int] = None):
+        """Drop entry (k, v) iff some pair i has d_keys[i] == k and (d_object_ids is None or
+        d_object_ids[i] == v).  -> (removed pairs int64 [r, 2] = (key, Object id) in ascending
+        key order, r).  With d_removed_out (int64, `capacity` rows of 2) too small the call
+        raises SdCasError (SD_ERR_CAPACITY, ``.needed`` rows) and the index is unchanged."""
+        m = int(d_keys.numel())
+        assert d_keys.dtype == torch.int64 and (m == 0 or (d_keys.is_cuda and d_keys.is_contiguous()))
+        if d_object_ids is not None:
+            assert d_object_ids.numel() == m and d_object_ids.dtype == torch.int64
+            assert m == 0 or (d_object_ids.is_cuda and d_object_ids.is_contiguous())
+        st = _stream(stream)
+        return self._removal(lambda out, cap, removed: lib().sd_object_index_remove(
+            self.ctx.handle, self.handle, _ptr(d_keys) if m else None,
+            _ptr(d_object_ids) if m and d_object_ids is not None else None, m, out, cap, removed, st),
+            min(m, len(self)), d_removed_out, capacity)
+
+    def remove_objects(self, d_object_ids: torch.Tensor, stream=None, d_removed_out: Optional[torch.Tensor] = None,
+                       capacity: Optional[int] = None):
+        """Drop every entry whose Object id is among d_object_ids (orphan_remover.rs:57-95).
+        -> (removed pairs int64 [r, 2], r), as remove."""
+        m = int(d_object_ids.numel())
+        assert d_object_ids.dtype == torch.int64 and (m == 0 or (d_object_ids.is_cuda and d_object_ids.is_contiguous()))
+        st = _stream(stream)
+        return self._removal(lambda out, cap, removed: lib().sd_object_index_remove_objects(
+            self.ctx.handle, self.handle, _ptr(d_object_ids) if m else None, m, out, cap, removed, st),
+            min(len(self), max(4 * m, 1024)) if m else 0, d_removed_out, capacity)
+
+    def remove_hex(self, cas_ids, object_ids=None) -> int:
+        """remove from the DB's strings (object_ids None: unconditional); returns the count."""
+        m = len(cas_ids)
+        buf = b"".join(c.encode("ascii") + b"\0" for c in cas_ids)
+        if len(buf) != 17 * m:
+            raise ValueError("a cas_id is not 16 characters")
+        ids = None if object_ids is None else np.ascontiguousarray(object_ids, dtype=np.uint64)
+        assert ids is None or ids.size == m
+        removed = ctypes.c_uint64(0)
+        torch.cuda.current_stream().synchronize()
+        check(lib().sd_object_index_remove_hex(self.ctx.handle, self.handle, buf if m else None,
+                                               _ptr(ids) if m and ids is not None else None, m, ctypes.byref(removed)))
+        return int(removed.value)
 
     def lookup(self, d_keys: torch.Tensor, d_object_ids: torch.Tensor = None, d_found: torch.Tensor = None,
                m: Optional[int] = None, stream=None):
@@ -277,6 +343,39 @@ class HostObjectIndex:
         check(lib().sd_cpu_object_index_insert(self.handle, _ptr(k) if k.size else None, _ptr(v) if k.size else None,
                                                k.size, ctypes.byref(taken)))
         return int(taken.value)
+
+    def _removal(self, call, bound: int, capacity):
+        removed = ctypes.c_uint64(0)
+        cap = max(int(bound), 1) if capacity is None else int(capacity)
+        out = np.zeros((max(cap, 1), 2), np.uint64)
+        try:
+            check(call(_ptr(out), cap, ctypes.byref(removed)))
+        except SdCasError as e:
+            e.needed = int(removed.value)
+            raise
+        r = int(removed.value)
+        return out[:r], r
+
+    def remove(self, keys, object_ids=None, capacity: Optional[int] = None):
+        """sd_cpu_object_index_remove -> (removed pairs uint64 [r, 2] ascending by key, r);
+        `capacity` (rows) below the count raises SdCasError (SD_ERR_CAPACITY, ``.needed``)
+        and leaves the index unchanged."""
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        v = None if object_ids is None else np.ascontiguousarray(object_ids, dtype=np.uint64)
+        assert v is None or v.size == k.size
+        return self._removal(lambda out, cap, removed: lib().sd_cpu_object_index_remove(
+            self.handle, _ptr(k) if k.size else None, _ptr(v) if k.size and v is not None else None, k.size, out, cap,
+            removed), min(k.size, len(self)), capacity)
+
+    def remove_hex(self, cas_ids, object_ids=None) -> int:
+        """remove from the DB's strings; returns the count."""
+        return self.remove(np.array([int(c, 16) for c in cas_ids], dtype=np.uint64), object_ids)[1]
+
+    def remove_objects(self, object_ids, capacity: Optional[int] = None):
+        """sd_cpu_object_index_remove_objects -> (removed pairs uint64 [r, 2], r)."""
+        v = np.ascontiguousarray(object_ids, dtype=np.uint64)
+        return self._removal(lambda out, cap, removed: lib().sd_cpu_object_index_remove_objects(
+            self.handle, _ptr(v) if v.size else None, v.size, out, cap, removed), len(self), capacity)
 
     def lookup(self, keys):
         k = np.ascontiguousarray(keys, dtype=np.uint64)
