@@ -494,6 +494,57 @@ int sd_object_index_lookup(sd_cas_ctx* ctx, const sd_object_index* index, const 
  * (SD_ERR_CAPACITY if smaller than the count).  Asynchronous on `stream`. */
 int sd_object_index_export(sd_cas_ctx* ctx, const sd_object_index* index, uint64_t* d_keys_out,
                            uint64_t* d_object_ids_out, uint64_t capacity, void* stream);
+/* The OWNERS MODE: every owner of a cas_id and its link count.  The one entry per cas_id
+ * above cannot tell whether another Object, or another file_path of the same Object, still
+ * owns a cas_id after a file_path goes, so its host asks the DB for "the remaining owners"
+ * after every deletion, content change and orphan pass.  Duplicates inside one 100-row step
+ * each get an Object of their own (mod.rs:229-333) and every later duplicate links to an
+ * existing Object (mod.rs:189-225), so both cases are the normal ones.  An owners-mode index
+ * holds one entry per (cas_id, Object) pair with the number of file_paths that link them;
+ * deleting a file_path takes one link, the entry leaves at zero, and the next owner becomes
+ * the answer by itself.  The cycle: scan (sd_dedup_owners_indexed / sd_cas_dedup_mgpu_indexed
+ * as above; the host creates the new heads' Objects) -> ONE insert of (key, Object id) for
+ * EVERY record of the scan, linked and created alike; a file_path (c, O) deleted -> remove of
+ * the pair (c, O) with the id given; a file_path changed A -> B on O -> remove (A, O), insert
+ * (B, O); the orphan remover -> sd_object_index_remove_objects(ids).  No DB query for owners.
+ * Opting in: sd_object_index_create_ex(ctx, nparts, part, flags, &index) with
+ *   SD_OBJECT_INDEX_OWNERS (1); flags 0 is sd_object_index_create.  sd_object_index_flags
+ *   (index, &flags) reads the mode back.  An index made without the flag behaves bit for bit
+ *   as described above.
+ * Layout: three arrays plus the directory.  keys[n] ascending, no longer strictly; vals[n]
+ *   Object ids, strictly ascending (unsigned) within equal keys; links[n] u64 >= 1; the same
+ *   prefix directory over keys.  THE FIRST OWNER OF A KEY IS ITS SMALLEST OBJECT ID: the
+ *   reference's existing_objects.iter().find(..) over a find_many in id order (mod.rs:168-210).
+ *   sd_object_index_lookup, sd_dedup_owners_indexed and sd_cas_dedup_mgpu_indexed answer with
+ *   that entry, by the same rule as in the first mode.
+ * insert (m pairs): each pair of this shard adds one link to (k, v); the entry is created at
+ *   1 if absent.  Repeated pairs in one call add up.  *taken = entries created.  The order of
+ *   the pairs does not matter.
+ * remove with ids: each pair takes one link from (k, v).  Pairs naming one entry add up.  An
+ *   entry asked for at least as many links as it has is dropped; asking for more is not an
+ *   error.  Absent pairs, keys of other shards, and a present key with another id are no-ops.
+ * remove with d_object_ids == NULL: every entry of each listed key goes.
+ * remove_objects: every entry whose id is listed goes, whatever its links.
+ * Outputs of all three removals: d_removed_out receives (key, id) of each dropped entry in
+ *   ascending (key, id) order; *removed = dropped entries.  On SD_ERR_CAPACITY nothing
+ *   changes, the link counts of entries that would have survived included; *removed = the
+ *   requirement.  After any removal the index is bit-identical to a fresh owners-mode index
+ *   built from the surviving links.
+ * sd_object_index_export and _count report entries (pairs); _insert_hex / _remove_hex follow
+ * the mode.  Memory: 24 bytes per entry, one entry per pair. */
+#define SD_OBJECT_INDEX_OWNERS 1
+int sd_object_index_create_ex(sd_cas_ctx* ctx, int nparts, int part, int flags, sd_object_index** out);
+int sd_object_index_flags(const sd_object_index* index, int* flags);
+/* New reads of an owners-mode index, asynchronous on `stream`; both return SD_ERR_INVALID on
+ * an index without the flag, and both may run concurrently with the other reads, as
+ * sd_object_index_lookup may.  d_links_out[i] = the link count of the pair (d_keys[i],
+ * d_object_ids[i]), 0 if absent. */
+int sd_object_index_links(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_keys,
+                          const uint64_t* d_object_ids, uint64_t m, uint64_t* d_links_out, void* stream);
+/* The entries in ascending (key, id) order with their link counts, into device arrays of
+ * `capacity` entries (SD_ERR_CAPACITY if smaller than the count). */
+int sd_object_index_export_links(sd_cas_ctx* ctx, const sd_object_index* index, uint64_t* d_keys_out,
+                                 uint64_t* d_ids_out, uint64_t* d_links_out, uint64_t capacity, void* stream);
 /* sd_dedup_owners against the Objects the library already has (mod.rs:168-225, then
  * :229-333 for the rest), per grouped record i:
  *   d_owner[i] = index[cas_id], d_existing[i] = 1     if the index has the record's cas_id;
@@ -525,6 +576,15 @@ int sd_cpu_object_index_lookup(const sd_cpu_object_index* index, const uint64_t*
 int sd_cpu_object_index_count(const sd_cpu_object_index* index, uint64_t* n);
 int sd_cpu_object_index_export(const sd_cpu_object_index* index, uint64_t* keys_out, uint64_t* object_ids_out,
                                uint64_t capacity);
+/* The owners mode of the host twin: the same flag, semantics and layout as
+ * sd_object_index_create_ex / _flags / _links / _export_links, over host arrays; the other
+ * sd_cpu_object_index_* calls follow the mode. */
+int sd_cpu_object_index_create_ex(int nparts, int part, int flags, sd_cpu_object_index** out);
+int sd_cpu_object_index_flags(const sd_cpu_object_index* index, int* flags);
+int sd_cpu_object_index_links(const sd_cpu_object_index* index, const uint64_t* keys, const uint64_t* object_ids,
+                              uint64_t m, uint64_t* links_out);
+int sd_cpu_object_index_export_links(const sd_cpu_object_index* index, uint64_t* keys_out, uint64_t* ids_out,
+                                     uint64_t* links_out, uint64_t capacity);
 int sd_cpu_dedup_owners_indexed(const sd_cpu_object_index* index, const uint64_t* records, uint64_t m,
                                 const uint64_t* rep, uint64_t chunk_size, uint64_t* owner, uint8_t* existing,
                                 uint64_t* new_out, uint64_t* n_new);

@@ -70,6 +70,7 @@ pub const SD_FILE_IO_ERROR: i32 = 2;
 pub const SD_FILE_SHORT_READ: i32 = 3;
 pub const SD_FILE_CHANGED: i32 = 4;
 pub const SD_COMM_ID_BYTES: usize = 128;
+pub const SD_OBJECT_INDEX_OWNERS: c_int = 1;
 
 extern "C" {
     pub fn sd_cas_abi_version() -> c_int;
@@ -168,6 +169,23 @@ extern "C" {
                                   d_object_ids: *mut u64, d_found: *mut u8, stream: *mut c_void) -> c_int;
     pub fn sd_object_index_export(ctx: *mut sd_cas_ctx, index: *const sd_object_index, d_keys_out: *mut u64,
                                   d_object_ids_out: *mut u64, capacity: u64, stream: *mut c_void) -> c_int;
+    // the owners mode (SD_OBJECT_INDEX_OWNERS): one entry per (cas_id, Object) with its link count
+    pub fn sd_object_index_create_ex(ctx: *mut sd_cas_ctx, nparts: c_int, part: c_int, flags: c_int,
+                                     out: *mut *mut sd_object_index) -> c_int;
+    pub fn sd_object_index_flags(index: *const sd_object_index, flags: *mut c_int) -> c_int;
+    pub fn sd_object_index_links(ctx: *mut sd_cas_ctx, index: *const sd_object_index, d_keys: *const u64,
+                                 d_object_ids: *const u64, m: u64, d_links_out: *mut u64,
+                                 stream: *mut c_void) -> c_int;
+    pub fn sd_object_index_export_links(ctx: *mut sd_cas_ctx, index: *const sd_object_index, d_keys_out: *mut u64,
+                                        d_ids_out: *mut u64, d_links_out: *mut u64, capacity: u64,
+                                        stream: *mut c_void) -> c_int;
+    pub fn sd_cpu_object_index_create_ex(nparts: c_int, part: c_int, flags: c_int,
+                                         out: *mut *mut sd_cpu_object_index) -> c_int;
+    pub fn sd_cpu_object_index_flags(index: *const sd_cpu_object_index, flags: *mut c_int) -> c_int;
+    pub fn sd_cpu_object_index_links(index: *const sd_cpu_object_index, keys: *const u64, object_ids: *const u64,
+                                     m: u64, links_out: *mut u64) -> c_int;
+    pub fn sd_cpu_object_index_export_links(index: *const sd_cpu_object_index, keys_out: *mut u64,
+                                            ids_out: *mut u64, links_out: *mut u64, capacity: u64) -> c_int;
     pub fn sd_dedup_owners_indexed(ctx: *mut sd_cas_ctx, index: *const sd_object_index, d_records: *const u64,
                                    m: u64, d_rep: *const u64, chunk_size: u64, d_owner: *mut u64,
                                    d_existing: *mut u8, d_new_out: *mut u64, d_n_new: *mut u64,
@@ -380,6 +398,20 @@ pub fn fingerprints_blocking(data: &[u8], ranges: &[(u64, u64)]) -> Result<Vec<(
 //     sd_object_index_insert_hex(ctx, index, hex17(&rows), object_ids(&rows), rows.len() as u64, &mut taken);
 //
 // A deleted file_path (c, O) is the first and the last line of that hook with c for A.
+//
+// With an owners-mode index (sd_object_index_create_ex(.., SD_OBJECT_INDEX_OWNERS, ..)) none of
+// the hooks asks the DB for owners: the index holds every (cas_id, Object) pair with its count
+// of file_paths, and the first owner of a cas_id is its smallest Object id.
+//
+//     // after a scan: ONE insert of (cas_id, Object id) for every record, linked and created alike
+//     sd_object_index_insert(ctx, index, d_keys, d_object_ids, m, &mut taken, stream);
+//     // a deleted file_path (c, O): one link less; the entry leaves at zero
+//     sd_object_index_remove_hex(ctx, index, hex17(&[c]), [o].as_ptr(), 1, &mut removed);
+//     // the watcher's update hook, A -> B on O
+//     sd_object_index_remove_hex(ctx, index, hex17(&[a]), [o].as_ptr(), 1, &mut removed);
+//     sd_object_index_insert_hex(ctx, index, hex17(&[b]), [o].as_ptr(), 1, &mut taken);
+//     // the orphan remover's hook
+//     sd_object_index_remove_objects(ctx, index, d_ids, ids.len() as u64, std::ptr::null_mut(), 0, &mut removed, stream);
 
 /// libsdcas's RCCL communicator for a multi-GPU library scan (one process per GPU).
 /// A member of an in-process group holds a reference to the group, so the group is

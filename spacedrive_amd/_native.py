@@ -161,7 +161,16 @@ SIGNATURES = [
     ("sd_cpu_object_index_count", I32, [P, PU64]),
     ("sd_cpu_object_index_export", I32, [P, P, P, U64]),
     ("sd_cpu_dedup_owners_indexed", I32, [P, P, U64, P, U64, P, P, P, PU64]),
+    ("sd_object_index_create_ex", I32, [P, I32, I32, I32, ctypes.POINTER(P)]),
+    ("sd_object_index_flags", I32, [P, ctypes.POINTER(I32)]),
+    ("sd_object_index_links", I32, [P, P, P, P, U64, P, P]),
+    ("sd_object_index_export_links", I32, [P, P, P, P, P, U64, P]),
+    ("sd_cpu_object_index_create_ex", I32, [I32, I32, I32, ctypes.POINTER(P)]),
+    ("sd_cpu_object_index_flags", I32, [P, ctypes.POINTER(I32)]),
+    ("sd_cpu_object_index_links", I32, [P, P, P, U64, P]),
+    ("sd_cpu_object_index_export_links", I32, [P, P, P, P, U64]),
 ]
+SD_OBJECT_INDEX_OWNERS = 1
 
 
 def host_cpu_budget() -> dict:

@@ -21,7 +21,13 @@ void check_index(const sd_cas_ctx* ctx, const sd_object_index* index) {
 // number of dropped entries; it is checked against `capacity` BEFORE anything is written, so
 // a short d_removed_out leaves the index (and d_removed_out) as they were.  Then the two-way
 // compaction into the other buffer pair, the swap, and the directory for the new count.
-void finish_remove(sd_object_index* x, uint64_t* d_removed_out, uint64_t capacity, uint64_t* removed, hipStream_t s) {
+// Owners mode: the compaction also carries links[], less `asked` (the links a removal with ids
+// takes from each entry; null otherwise) for the survivors -- written into the other buffer
+// only, after the capacity check, so a refused call leaves every link count as it was.  When no
+// entry leaves (the commonest deletion: the pair keeps other links) nothing is compacted: the
+// links are taken in place, O(log n) per distinct pair, and capacity cannot be short of 0 rows.
+void finish_remove(sd_object_index* x, uint64_t* d_removed_out, uint64_t capacity, uint64_t* removed, hipStream_t s,
+                   const uint64_t* asked = nullptr, uint64_t m = 0) {
     const uint32_t slots = sdk::index_remove_slots(x->n);
     HIP_CHECK(hipMemcpyAsync(x->host.p, x->counts.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
@@ -30,16 +36,69 @@ void finish_remove(sd_object_index* x, uint64_t* d_removed_out, uint64_t capacit
     for (uint32_t k = 0; k < slots; k++) r += c[k];
     if (r > x->n) throw sd_failure(SD_ERR_INTERNAL, "remove: more dropped entries than entries");
     if (removed) *removed = r;
-    if (r == 0) return;
+    if (r == 0) {  // no entry leaves: keys, values and directory stand; a removal with ids (of m
+                   // pairs) takes its links from the index's own array, a pair without an entry none
+        if (asked) {
+            HIP_CHECK(sdk::index_owners_take_links(x->view(), x->scratch.p, m, x->links[x->cur].as<uint64_t>(), s));
+            HIP_CHECK(hipStreamSynchronize(s));
+        }
+        return;
+    }
     if (d_removed_out && capacity < r)
         throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of removed entries");
     const int to = 1 - x->cur;  // both pairs hold `cap` entries since the insert that grew them
-    HIP_CHECK(sdk::index_remove_compact(x->view(), x->scratch.p, x->counts.as<uint64_t>(), x->keys[to].as<uint64_t>(),
-                                        x->vals[to].as<uint64_t>(), d_removed_out, s));
+    if (x->owners())
+        HIP_CHECK(sdk::index_owners_remove_compact(x->view(), x->scratch.p, asked, x->counts.as<uint64_t>(),
+                                                   x->keys[to].as<uint64_t>(), x->vals[to].as<uint64_t>(),
+                                                   x->links[to].as<uint64_t>(), d_removed_out, s));
+    else
+        HIP_CHECK(sdk::index_remove_compact(x->view(), x->scratch.p, x->counts.as<uint64_t>(),
+                                            x->keys[to].as<uint64_t>(), x->vals[to].as<uint64_t>(), d_removed_out, s));
     HIP_CHECK(hipStreamSynchronize(s));  // the compaction read the old buffers
     x->cur = to;
     x->n -= r;
     x->bits = oi_dir_bits(x->n);  // re-chosen for the new count; the directory's buffer never shrinks
+    HIP_CHECK(sdk::index_build_dir(x->keys[to].as<uint64_t>(), x->n, x->bits, x->dir.as<uint64_t>(), s));
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// Owners-mode insert: aggregate the batch, select the absent pairs, merge them in by (key, id)
+// rank with the links beside keys and values, then add the present pairs' multiplicities to
+// their entries (in place when nothing merges).
+void insert_owners(sd_object_index* x, const uint64_t* d_keys, const uint64_t* d_object_ids, uint64_t m,
+                   uint64_t* taken, hipStream_t s) {
+    x->scratch.ensure(sdk::index_owners_insert_scratch(m));
+    const uint64_t *nk = nullptr, *nv = nullptr, *nl = nullptr, *d_total = nullptr;
+    HIP_CHECK(sdk::index_owners_insert_select(x->view(), x->nparts, x->part, d_keys, d_object_ids, m, x->scratch.p,
+                                              x->counts.as<uint64_t>(), &nk, &nv, &nl, &d_total, s));
+    HIP_CHECK(hipMemcpyAsync(x->host.p, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const uint64_t r = *reinterpret_cast<const uint64_t*>(x->host.p);
+    if (r > m) throw sd_failure(SD_ERR_INTERNAL, "insert: more new entries than pairs");
+    if (taken) *taken = r;
+    if (r == 0) {
+        if (x->n)
+            HIP_CHECK(sdk::index_owners_add_links(x->scratch.p, m, nk, nv, 0, x->links[x->cur].as<uint64_t>(), s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        return;
+    }
+    const uint64_t cap = oi_grow_capacity(x->n + r, x->cap);
+    const int to = 1 - x->cur;
+    x->keys[to].ensure(cap * sizeof(uint64_t));
+    x->vals[to].ensure(cap * sizeof(uint64_t));
+    x->links[to].ensure(cap * sizeof(uint64_t));
+    HIP_CHECK(sdk::index_owners_merge(x->view(), nk, nv, nl, r, x->keys[to].as<uint64_t>(), x->vals[to].as<uint64_t>(),
+                                      x->links[to].as<uint64_t>(), s));
+    HIP_CHECK(sdk::index_owners_add_links(x->scratch.p, m, nk, nv, r, x->links[to].as<uint64_t>(), s));
+    HIP_CHECK(hipStreamSynchronize(s));  // the merge read the old buffers and the old directory
+    x->keys[x->cur].ensure(cap * sizeof(uint64_t));
+    x->vals[x->cur].ensure(cap * sizeof(uint64_t));
+    x->links[x->cur].ensure(cap * sizeof(uint64_t));
+    x->cap = cap;
+    x->cur = to;
+    x->n += r;
+    x->bits = oi_dir_bits(x->n);
+    x->dir.ensure(((1ull << x->bits) + 1) * sizeof(uint64_t));
     HIP_CHECK(sdk::index_build_dir(x->keys[to].as<uint64_t>(), x->n, x->bits, x->dir.as<uint64_t>(), s));
     HIP_CHECK(hipStreamSynchronize(s));
 }
@@ -49,19 +108,26 @@ void finish_remove(sd_object_index* x, uint64_t* d_removed_out, uint64_t capacit
 extern "C" {
 
 int sd_object_index_create(sd_cas_ctx* ctx, int nparts, int part, sd_object_index** out) {
+    return sd_object_index_create_ex(ctx, nparts, part, 0, out);
+}
+
+int sd_object_index_create_ex(sd_cas_ctx* ctx, int nparts, int part, int flags, sd_object_index** out) {
     SD_GUARD_BEGIN
     if (!ctx || !out) throw sd_failure(SD_ERR_INVALID, "null argument");
     if (nparts < 1 || nparts > 64 || part < 0 || part >= nparts)
         throw sd_failure(SD_ERR_INVALID, "part / nparts out of range (1..64 parts)");
+    if (flags & ~SD_OBJECT_INDEX_OWNERS) throw sd_failure(SD_ERR_INVALID, "unknown flags");
     *out = nullptr;
     ctx->bind();
     auto x = std::make_unique<sd_object_index>();
     x->ctx = ctx;
     x->nparts = nparts;
     x->part = part;
+    x->flags = flags;
     for (int k = 0; k < 2; k++) {
         x->keys[k].alloc(0);
         x->vals[k].alloc(0);
+        if (x->owners()) x->links[k].alloc(0);
     }
     x->dir.alloc(2 * sizeof(uint64_t));
     HIP_CHECK(hipMemset(x->dir.p, 0, 2 * sizeof(uint64_t)));
@@ -78,6 +144,14 @@ void sd_object_index_destroy(sd_object_index* index) {
         delete index;
     } catch (...) {
     }
+}
+
+int sd_object_index_flags(const sd_object_index* index, int* flags) {
+    SD_GUARD_BEGIN
+    if (!index || !flags) throw sd_failure(SD_ERR_INVALID, "null argument");
+    *flags = index->flags;
+    return SD_OK;
+    SD_GUARD_END
 }
 
 int sd_object_index_count(const sd_object_index* index, uint64_t* n) {
@@ -98,6 +172,10 @@ int sd_object_index_insert(sd_cas_ctx* ctx, sd_object_index* index, const uint64
     ctx->bind();
     hipStream_t s = ctx->pick(stream);
     sd_object_index* x = index;
+    if (x->owners()) {
+        insert_owners(x, d_keys, d_object_ids, m, taken, s);
+        return SD_OK;
+    }
     x->scratch.ensure(sdk::index_insert_scratch(m));
     const uint64_t *nk = nullptr, *nv = nullptr, *d_total = nullptr;
     HIP_CHECK(sdk::index_insert_select(x->view(), x->nparts, x->part, d_keys, d_object_ids, m, x->scratch.p,
@@ -160,6 +238,19 @@ int sd_object_index_remove(sd_cas_ctx* ctx, sd_object_index* index, const uint64
     if (m == 0 || x->n == 0) return SD_OK;
     ctx->bind();
     hipStream_t s = ctx->pick(stream);
+    if (x->owners() && d_object_ids) {  // each pair takes one link; an entry leaves at zero
+        x->scratch.ensure(sdk::index_owners_remove_scratch(x->n, m));
+        HIP_CHECK(sdk::index_owners_remove_flag_pairs(x->view(), d_keys, d_object_ids, m, x->scratch.p,
+                                                      x->counts.as<uint64_t>(), s));
+        finish_remove(x, d_removed_out, capacity, removed, s, sdk::index_owners_asked(x->scratch.p, x->n), m);
+        return SD_OK;
+    }
+    if (x->owners()) {  // every entry of each listed key
+        x->scratch.ensure(sdk::index_remove_scratch(x->n, m));
+        HIP_CHECK(sdk::index_owners_remove_flag_keys(x->view(), d_keys, m, x->scratch.p, x->counts.as<uint64_t>(), s));
+        finish_remove(x, d_removed_out, capacity, removed, s);
+        return SD_OK;
+    }
     x->scratch.ensure(sdk::index_remove_scratch(x->n, 0));
     HIP_CHECK(sdk::index_remove_flag_keys(x->view(), d_keys, d_object_ids, m, x->scratch.p, x->counts.as<uint64_t>(),
                                           s));
@@ -235,6 +326,39 @@ int sd_object_index_export(sd_cas_ctx* ctx, const sd_object_index* index, uint64
     const sdk::oi_view v = index->view();
     HIP_CHECK(hipMemcpyAsync(d_keys_out, v.keys, v.n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_object_ids_out, v.vals, v.n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_object_index_links(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_keys,
+                          const uint64_t* d_object_ids, uint64_t m, uint64_t* d_links_out, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index || (m && (!d_keys || !d_object_ids || !d_links_out)))
+        throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    if (m == 0) return SD_OK;
+    ctx->bind();
+    HIP_CHECK(sdk::index_links(index->view(), d_keys, d_object_ids, m, d_links_out, ctx->pick(stream)));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_object_index_export_links(sd_cas_ctx* ctx, const sd_object_index* index, uint64_t* d_keys_out,
+                                 uint64_t* d_ids_out, uint64_t* d_links_out, uint64_t capacity, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    if (index->n && (!d_keys_out || !d_ids_out || !d_links_out)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (capacity < index->n) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the index's count");
+    if (index->n == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    const sdk::oi_view v = index->view();
+    HIP_CHECK(hipMemcpyAsync(d_keys_out, v.keys, v.n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_ids_out, v.vals, v.n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_links_out, v.links, v.n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
     return SD_OK;
     SD_GUARD_END
 }

@@ -4,7 +4,8 @@
 // Reference semantics: identifier_job_step first finds the Objects the library already has
 // for a step's cas_ids (core/src/object/file_identifier/mod.rs:168-175) and links each file
 // to the first of them (:189-225).  The index is that join's table: keys[n] strictly
-// ascending (the big-endian u64 of the cas_id, dedup.hip cas_key), vals[n] the Object ids,
+// ascending (the big-endian u64 of the cas_id, dedup.hip cas_key; one entry per key -- the
+// owners mode below keeps one per (key, Object id) instead), vals[n] the Object ids,
 // and a prefix directory dir[2^bits + 1]: dir[p] = the first position whose key's top
 // `bits` bits are >= p (dir[2^bits] = n).  cas_ids are uniform hash bits, so a bucket
 // [dir[p], dir[p + 1]) holds ~8-16 keys; the search inside it is a binary search bounded by
@@ -63,6 +64,48 @@ SD_OI_HD bool oi_id_listed(const uint64_t* sorted_ids, uint64_t m, uint64_t id) 
     const uint64_t at = oi_lower_bound(sorted_ids, 0, m, id);
     return at < m && sorted_ids[at] == id;
 }
+
+// ---- owners mode (SD_OBJECT_INDEX_OWNERS), stated once for both paths.  One entry per (key,
+// Object id) pair: keys[n] ascending, no longer strictly; vals[n] strictly ascending (unsigned)
+// within equal keys; links[n] >= 1, the file_paths that link the pair; the same directory over
+// keys.  The FIRST owner of a key is its smallest Object id (mod.rs:168-210: find over a
+// find_many in id order), and oi_find returns a lower bound over keys, so it lands on exactly
+// that entry: lookup, the indexed owner rule, the new heads, the directory and the multi-GPU
+// step serve this mode through the functions above, with no change of rule.  Every entry of a
+// key lies in the key's bucket, so the (key, id) bound inside the bucket is the global one and
+// a run of thousands of owners costs O(log), never a walk.
+// first position in [lo, hi) whose (key, id) is >= (key, id) (hi if none)
+SD_OI_HD uint64_t oi_lower_bound_pair(const uint64_t* keys, const uint64_t* vals, uint64_t lo, uint64_t hi,
+                                      uint64_t key, uint64_t id) {
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        const uint64_t k = keys[mid];
+        if (k < key || (k == key && vals[mid] < id)) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// (key, id) lower bound over the whole index through the directory
+SD_OI_HD uint64_t oi_rank_pair(const uint64_t* keys, const uint64_t* vals, const uint64_t* dir, uint32_t bits,
+                               uint64_t key, uint64_t id) {
+    const uint64_t p = oi_prefix(key, bits);
+    return oi_lower_bound_pair(keys, vals, dir[p], dir[p + 1], key, id);
+}
+
+// position of the entry (key, id), or false (*pos = its rank either way)
+SD_OI_HD bool oi_find_pair(const uint64_t* keys, const uint64_t* vals, const uint64_t* dir, uint32_t bits,
+                           uint64_t key, uint64_t id, uint64_t* pos) {
+    const uint64_t p = oi_prefix(key, bits);
+    const uint64_t hi = dir[p + 1];
+    const uint64_t at = oi_lower_bound_pair(keys, vals, dir[p], hi, key, id);
+    *pos = at;
+    return at < hi && keys[at] == key && vals[at] == id;
+}
+
+// removal with ids: an entry asked for at least as many links as it holds is dropped (asking
+// for more is not an error); asked 0 = no pair named it
+SD_OI_HD bool oi_links_drop(uint64_t held, uint64_t asked) { return asked != 0 && asked >= held; }
 
 // ---- policies (object_index_host.cpp; the device path calls the same functions)
 // directory bits for n entries: ~log2(n / 8), 0 for tiny indexes, at most 24

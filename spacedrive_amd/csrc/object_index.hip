@@ -1,6 +1,8 @@
 // object_index.hip -- the device-resident Object index: lookup, the indexed owner rule with
 // its compacted list of new group heads, insertion (merge by rank + directory rebuild) and
-// removal by key or by Object (flag, two-way ordered compaction, directory rebuild).
+// removal by key or by Object (flag, two-way ordered compaction, directory rebuild); and the
+// owners mode (one entry per (key, Object id) with a link count): the same passes over (key,
+// id), after a batch of pairs has been aggregated to distinct pairs with multiplicities.
 //
 // Reference semantics: identifier_job_step joins a step's cas_ids against the Objects the
 // library already has (core/src/object/file_identifier/mod.rs:168-175), links each file to
@@ -275,7 +277,10 @@ __global__ __launch_bounds__(256) void k_remove_compact(const uint64_t* __restri
                                                         const uint64_t* __restrict__ counts,
                                                         uint64_t* __restrict__ out_keys,
                                                         uint64_t* __restrict__ out_vals,
-                                                        uint64_t* __restrict__ rm_out) {
+                                                        uint64_t* __restrict__ rm_out,
+                                                        const uint64_t* __restrict__ links,
+                                                        const uint64_t* __restrict__ asked,
+                                                        uint64_t* __restrict__ out_links) {
     uint64_t run = block_base(counts, nullptr);
     const oi_slice sl = oi_slice_of(n);
     for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
@@ -288,10 +293,183 @@ __global__ __launch_bounds__(256) void k_remove_compact(const uint64_t* __restri
         if (!flag) {
             out_keys[i - slot] = k;
             out_vals[i - slot] = v;
+            // owners mode: the third array, less the links a removal with ids asked for
+            if (out_links) out_links[i - slot] = links[i] - (asked ? asked[i] : 0);
         } else if (rm_out) {
             rm_out[2 * slot] = k;
             rm_out[2 * slot + 1] = v;
         }
+    }
+}
+
+// ---- owners mode (object_index.h): one entry per (key, Object id) and links[n].
+// A batch of pairs is first aggregated: two stable radix sorts (by id, then by key) leave it
+// in (key, id) order; the heads of the runs of equal pairs are flagged and compacted in order
+// with their positions, so a distinct pair's multiplicity is the distance to the next head
+// (the last one's to m): no lane walks a run, however many copies of one pair there are.
+__global__ __launch_bounds__(256) void k_pair_heads(const uint64_t* __restrict__ sk, const uint64_t* __restrict__ sv,
+                                                    uint64_t m, uint8_t* __restrict__ flags,
+                                                    uint64_t* __restrict__ counts) {
+    const oi_slice sl = oi_slice_of(m);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+        const bool head = i == 0 || sk[i - 1] != sk[i] || sv[i - 1] != sv[i];
+        flags[i] = head ? 1 : 0;
+        mine += head;
+    }
+    block_count(mine, counts);
+}
+
+__global__ __launch_bounds__(256) void k_pair_compact(const uint64_t* __restrict__ sk, const uint64_t* __restrict__ sv,
+                                                      uint64_t m, const uint8_t* __restrict__ flags,
+                                                      const uint64_t* __restrict__ counts,
+                                                      uint64_t* __restrict__ dk, uint64_t* __restrict__ dv,
+                                                      uint64_t* __restrict__ dpos, uint64_t* __restrict__ total) {
+    uint64_t run = block_base(counts, total);
+    const oi_slice sl = oi_slice_of(m);
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool flag = i < sl.hi && flags[i];
+        const uint64_t slot = tile_slot(flag, run);
+        if (flag) {
+            dk[slot] = sk[i];
+            dv[slot] = sv[i];
+            dpos[slot] = i;
+        }
+    }
+}
+
+// Insert: every distinct pair (d = *d_total of them) takes its (key, id) rank in the index and
+// its state: 0 = another shard's key, 1 = absent (merges in at its rank), 2 = present (adds its
+// multiplicity to the entry at its rank).  Counts the absent ones per workgroup slice.
+__global__ __launch_bounds__(256) void k_owners_insert_flag(
+    const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, const uint64_t* __restrict__ dir,
+    uint32_t bits, int nparts, int part, const uint64_t* __restrict__ dk, const uint64_t* __restrict__ dv,
+    const uint64_t* __restrict__ dpos, const uint64_t* __restrict__ d_total, uint64_t m, uint64_t* __restrict__ dcnt,
+    uint64_t* __restrict__ drank, uint8_t* __restrict__ dstate, uint64_t* __restrict__ counts) {
+    const uint64_t d = *d_total;
+    const oi_slice sl = oi_slice_of(d);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+        const uint64_t k = dk[i], v = dv[i];
+        uint64_t at = 0;
+        uint8_t st = 0;
+        if (oi_dest_of(k, nparts) == (uint32_t)part) st = oi_find_pair(keys, vals, dir, bits, k, v, &at) ? 2 : 1;
+        dcnt[i] = (i + 1 < d ? dpos[i + 1] : m) - dpos[i];
+        drank[i] = at;
+        dstate[i] = st;
+        mine += st == 1;
+    }
+    block_count(mine, counts);
+}
+
+__global__ __launch_bounds__(256) void k_owners_insert_compact(
+    const uint64_t* __restrict__ dk, const uint64_t* __restrict__ dv, const uint64_t* __restrict__ dcnt,
+    const uint8_t* __restrict__ dstate, const uint64_t* __restrict__ d_total, const uint64_t* __restrict__ counts,
+    uint64_t* __restrict__ nk, uint64_t* __restrict__ nv, uint64_t* __restrict__ nl, uint64_t* __restrict__ total) {
+    uint64_t run = block_base(counts, total);
+    const oi_slice sl = oi_slice_of(*d_total);
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool flag = i < sl.hi && dstate[i] == 1;
+        const uint64_t slot = tile_slot(flag, run);
+        if (flag) {
+            nk[slot] = dk[i];
+            nv[slot] = dv[i];
+            nl[slot] = dcnt[i];
+        }
+    }
+}
+
+// k_index_merge over (key, id): two sorted runs without common pairs
+__global__ __launch_bounds__(256) void k_owners_merge(
+    const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, const uint64_t* __restrict__ links,
+    const uint64_t* __restrict__ dir, uint32_t bits, uint64_t n, const uint64_t* __restrict__ nk,
+    const uint64_t* __restrict__ nv, const uint64_t* __restrict__ nl, uint64_t r, uint64_t* __restrict__ out_keys,
+    uint64_t* __restrict__ out_vals, uint64_t* __restrict__ out_links) {
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n + r; t += (uint64_t)gridDim.x * blockDim.x) {
+        if (t < r) {
+            const uint64_t k = nk[t], v = nv[t], at = t + oi_rank_pair(keys, vals, dir, bits, k, v);
+            out_keys[at] = k;
+            out_vals[at] = v;
+            out_links[at] = nl[t];
+        } else {
+            const uint64_t i = t - r, k = keys[i], v = vals[i], at = i + oi_lower_bound_pair(nk, nv, 0, r, k, v);
+            out_keys[at] = k;
+            out_vals[at] = v;
+            out_links[at] = links[i];
+        }
+    }
+}
+
+// the present pairs add their multiplicity to their entry, which the merge of r new entries
+// moved up by the new pairs below it; distinct pairs name distinct entries: one writer each
+__global__ __launch_bounds__(256) void k_owners_add_links(
+    const uint64_t* __restrict__ dk, const uint64_t* __restrict__ dv, const uint64_t* __restrict__ dcnt,
+    const uint64_t* __restrict__ drank, const uint8_t* __restrict__ dstate, const uint64_t* __restrict__ d_total,
+    const uint64_t* __restrict__ nk, const uint64_t* __restrict__ nv, uint64_t r, uint64_t* __restrict__ links) {
+    const uint64_t d = *d_total;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d; i += (uint64_t)gridDim.x * blockDim.x) {
+        if (dstate[i] != 2) continue;
+        const uint64_t at = drank[i] + (r ? oi_lower_bound_pair(nk, nv, 0, r, dk[i], dv[i]) : 0);
+        links[at] += dcnt[i];
+    }
+}
+
+// Removal with ids: every distinct pair leaves the links asked at its entry (asked[n], zeroed
+// before; one writer per entry), then the entries asked for at least what they hold are flagged
+__global__ __launch_bounds__(256) void k_owners_remove_ask(
+    const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, const uint64_t* __restrict__ dir,
+    uint32_t bits, const uint64_t* __restrict__ dk, const uint64_t* __restrict__ dv,
+    const uint64_t* __restrict__ dpos, const uint64_t* __restrict__ d_total, uint64_t m,
+    uint64_t* __restrict__ asked) {
+    const uint64_t d = *d_total;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t at;
+        if (oi_find_pair(keys, vals, dir, bits, dk[i], dv[i], &at))
+            asked[at] = (i + 1 < d ? dpos[i + 1] : m) - dpos[i];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_owners_remove_flag(const uint64_t* __restrict__ links,
+                                                            const uint64_t* __restrict__ asked, uint64_t n,
+                                                            uint8_t* __restrict__ flags,
+                                                            uint64_t* __restrict__ counts) {
+    const oi_slice sl = oi_slice_of(n);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+        const bool drop = oi_links_drop(links[i], asked[i]);
+        flags[i] = drop ? 1 : 0;
+        mine += drop;
+    }
+    block_count(mine, counts);
+}
+
+// A removal with ids after which no entry leaves: every distinct pair takes its multiplicity
+// from its entry in place (less than the entry holds, or it would have been flagged); distinct
+// pairs name distinct entries: one writer each
+__global__ __launch_bounds__(256) void k_owners_take_links(
+    const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, const uint64_t* __restrict__ dir,
+    uint32_t bits, const uint64_t* __restrict__ dk, const uint64_t* __restrict__ dv,
+    const uint64_t* __restrict__ dpos, const uint64_t* __restrict__ d_total, uint64_t m,
+    uint64_t* __restrict__ links) {
+    const uint64_t d = *d_total;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t at;
+        if (oi_find_pair(keys, vals, dir, bits, dk[i], dv[i], &at))
+            links[at] -= (i + 1 < d ? dpos[i + 1] : m) - dpos[i];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_index_links(const uint64_t* __restrict__ keys,
+                                                     const uint64_t* __restrict__ vals,
+                                                     const uint64_t* __restrict__ links,
+                                                     const uint64_t* __restrict__ dir, uint32_t bits,
+                                                     const uint64_t* __restrict__ qk, const uint64_t* __restrict__ qv,
+                                                     uint64_t m, uint64_t* __restrict__ out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t at;
+        out[i] = oi_find_pair(keys, vals, dir, bits, qk[i], qv[i], &at) ? links[at] : 0;
     }
 }
 
@@ -310,6 +488,52 @@ size_t remove_sort_bytes(uint64_t m, hipStream_t s) {
 }
 
 size_t remove_flag_bytes(uint64_t n) { return (n + 255) & ~size_t(255); }
+
+size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
+
+// An aggregated batch of m pairs in scratch: a[5][m] u64 (the first sort's ids and keys, later
+// the distinct pairs dk, dv; the second sort's sk, sv, later an insert's nk, nv; dpos), an
+// insert's dcnt, drank, nl [m] u64, heads[m] and dstate[m] u8, the distinct count and an
+// insert's count (u64, 256 bytes apart), then the radix sort's temporary storage.
+struct pair_batch {
+    uint64_t *t0, *t1, *sk, *sv, *dpos, *dcnt, *drank, *nl, *d_total, *r_total;
+    uint8_t *heads, *dstate;
+    void* tmp;
+};
+
+size_t pair_batch_bytes(uint64_t m, bool insert) {
+    return round256((insert ? 8 : 5) * m * sizeof(uint64_t)) + round256(2 * m) + 512 + insert_sort_bytes(m, nullptr) +
+           256;
+}
+
+pair_batch pair_batch_at(void* base, uint64_t m, bool insert) {
+    pair_batch b;
+    uint64_t* u = reinterpret_cast<uint64_t*>(base);
+    b.t0 = u, b.t1 = u + m, b.sk = u + 2 * m, b.sv = u + 3 * m, b.dpos = u + 4 * m;
+    b.dcnt = insert ? u + 5 * m : nullptr, b.drank = insert ? u + 6 * m : nullptr, b.nl = insert ? u + 7 * m : nullptr;
+    uint8_t* p = reinterpret_cast<uint8_t*>(base) + round256((insert ? 8 : 5) * m * sizeof(uint64_t));
+    b.heads = p, b.dstate = p + m;
+    p += round256(2 * m);
+    b.d_total = reinterpret_cast<uint64_t*>(p), b.r_total = reinterpret_cast<uint64_t*>(p + 256);
+    b.tmp = p + 512;
+    return b;
+}
+
+// (key, id) order by two stable sorts, then the distinct pairs (t0 = keys, t1 = ids) with the
+// positions of their runs' heads and their count
+hipError_t aggregate_pairs(const pair_batch& b, const uint64_t* in_keys, const uint64_t* in_ids, uint64_t m,
+                           uint64_t* counts, hipStream_t s) {
+    size_t tb = insert_sort_bytes(m, s);
+    hipError_t e = rocprim::radix_sort_pairs(b.tmp, tb, in_ids, b.t0, in_keys, b.t1, (size_t)m, 0, 64, s);
+    if (e != hipSuccess) return e;
+    e = rocprim::radix_sort_pairs(b.tmp, tb, b.t1, b.sk, b.t0, b.sv, (size_t)m, 0, 64, s);
+    if (e != hipSuccess) return e;
+    const uint32_t g = sliced_grid(m);
+    hipLaunchKernelGGL(k_pair_heads, dim3(g), dim3(256), 0, s, b.sk, b.sv, m, b.heads, counts);
+    hipLaunchKernelGGL(k_pair_compact, dim3(g), dim3(256), 0, s, b.sk, b.sv, m, b.heads, counts, b.t0, b.t1, b.dpos,
+                       b.d_total);
+    return hipGetLastError();
+}
 
 }  // namespace
 
@@ -412,7 +636,111 @@ hipError_t index_remove_flag_objects(const oi_view& x, const uint64_t* ids, uint
 hipError_t index_remove_compact(const oi_view& x, const void* scratch, const uint64_t* counts, uint64_t* out_keys,
                                 uint64_t* out_vals, uint64_t* rm_out, hipStream_t s) {
     hipLaunchKernelGGL(k_remove_compact, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, x.n,
-                       reinterpret_cast<const uint8_t*>(scratch), counts, out_keys, out_vals, rm_out);
+                       reinterpret_cast<const uint8_t*>(scratch), counts, out_keys, out_vals, rm_out, nullptr, nullptr,
+                       nullptr);
+    return hipGetLastError();
+}
+
+// ---- owners mode
+size_t index_owners_insert_scratch(uint64_t m) { return pair_batch_bytes(m, true); }
+
+hipError_t index_owners_insert_select(const oi_view& x, int nparts, int part, const uint64_t* in_keys,
+                                      const uint64_t* in_vals, uint64_t m, void* scratch, uint64_t* counts,
+                                      const uint64_t** nk_out, const uint64_t** nv_out, const uint64_t** nl_out,
+                                      const uint64_t** total_out, hipStream_t s) {
+    const pair_batch b = pair_batch_at(scratch, m, true);
+    hipError_t e = aggregate_pairs(b, in_keys, in_vals, m, counts, s);
+    if (e != hipSuccess) return e;
+    const uint32_t g = sliced_grid(m);
+    hipLaunchKernelGGL(k_owners_insert_flag, dim3(g), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, nparts, part, b.t0,
+                       b.t1, b.dpos, b.d_total, m, b.dcnt, b.drank, b.dstate, counts);
+    hipLaunchKernelGGL(k_owners_insert_compact, dim3(g), dim3(256), 0, s, b.t0, b.t1, b.dcnt, b.dstate, b.d_total,
+                       counts, b.sk, b.sv, b.nl, b.r_total);
+    *nk_out = b.sk;
+    *nv_out = b.sv;
+    *nl_out = b.nl;
+    *total_out = b.r_total;
+    return hipGetLastError();
+}
+
+hipError_t index_owners_merge(const oi_view& x, const uint64_t* nk, const uint64_t* nv, const uint64_t* nl, uint64_t r,
+                              uint64_t* out_keys, uint64_t* out_vals, uint64_t* out_links, hipStream_t s) {
+    if (x.n + r == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_owners_merge, dim3(grid_for(x.n + r)), dim3(256), 0, s, x.keys, x.vals, x.links, x.dir, x.bits,
+                       x.n, nk, nv, nl, r, out_keys, out_vals, out_links);
+    return hipGetLastError();
+}
+
+hipError_t index_owners_add_links(const void* scratch, uint64_t m, const uint64_t* nk, const uint64_t* nv, uint64_t r,
+                                  uint64_t* links, hipStream_t s) {
+    const pair_batch b = pair_batch_at(const_cast<void*>(scratch), m, true);
+    hipLaunchKernelGGL(k_owners_add_links, dim3(grid_for(m)), dim3(256), 0, s, b.t0, b.t1, b.dcnt, b.drank, b.dstate,
+                       b.d_total, nk, nv, r, links);
+    return hipGetLastError();
+}
+
+// scratch: flags[n] (u8), asked[n] (u64), then the aggregated batch
+size_t index_owners_remove_scratch(uint64_t n, uint64_t m) {
+    return remove_flag_bytes(n) + round256(n * sizeof(uint64_t)) + pair_batch_bytes(m, false);
+}
+
+const uint64_t* index_owners_asked(const void* scratch, uint64_t n) {
+    return reinterpret_cast<const uint64_t*>(reinterpret_cast<const uint8_t*>(scratch) + remove_flag_bytes(n));
+}
+
+hipError_t index_owners_remove_flag_pairs(const oi_view& x, const uint64_t* rm_keys, const uint64_t* rm_ids,
+                                          uint64_t m, void* scratch, uint64_t* counts, hipStream_t s) {
+    uint8_t* flags = reinterpret_cast<uint8_t*>(scratch);
+    uint64_t* asked = const_cast<uint64_t*>(index_owners_asked(scratch, x.n));
+    const pair_batch b =
+        pair_batch_at(reinterpret_cast<uint8_t*>(asked) + round256(x.n * sizeof(uint64_t)), m, false);
+    hipError_t e = hipMemsetAsync(asked, 0, x.n * sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    e = aggregate_pairs(b, rm_keys, rm_ids, m, counts, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_owners_remove_ask, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, b.t0,
+                       b.t1, b.dpos, b.d_total, m, asked);
+    hipLaunchKernelGGL(k_owners_remove_flag, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.links, asked, x.n, flags,
+                       counts);
+    return hipGetLastError();
+}
+
+hipError_t index_owners_take_links(const oi_view& x, const void* scratch, uint64_t m, uint64_t* links, hipStream_t s) {
+    const uint8_t* asked = reinterpret_cast<const uint8_t*>(index_owners_asked(scratch, x.n));
+    const pair_batch b = pair_batch_at(const_cast<uint8_t*>(asked) + round256(x.n * sizeof(uint64_t)), m, false);
+    hipLaunchKernelGGL(k_owners_take_links, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, b.t0,
+                       b.t1, b.dpos, b.d_total, m, links);
+    return hipGetLastError();
+}
+
+hipError_t index_owners_remove_flag_keys(const oi_view& x, const uint64_t* rm_keys, uint64_t m, void* scratch,
+                                         uint64_t* counts, hipStream_t s) {
+    uint8_t* flags = reinterpret_cast<uint8_t*>(scratch);
+    uint64_t* sorted = reinterpret_cast<uint64_t*>(flags + remove_flag_bytes(x.n));
+    void* tmp = reinterpret_cast<uint8_t*>(sorted) + round256(m * sizeof(uint64_t));
+    size_t tb = remove_sort_bytes(m, s);
+    hipError_t e = rocprim::radix_sort_keys(tmp, tb, rm_keys, sorted, (size_t)m, 0, 64, s);
+    if (e != hipSuccess) return e;
+    // the entry side searches the sorted keys, as it searches the sorted ids by Object
+    hipLaunchKernelGGL(k_remove_flag_objects, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.n, sorted, m, flags,
+                       counts);
+    return hipGetLastError();
+}
+
+hipError_t index_owners_remove_compact(const oi_view& x, const void* scratch, const uint64_t* asked,
+                                       const uint64_t* counts, uint64_t* out_keys, uint64_t* out_vals,
+                                       uint64_t* out_links, uint64_t* rm_out, hipStream_t s) {
+    hipLaunchKernelGGL(k_remove_compact, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, x.n,
+                       reinterpret_cast<const uint8_t*>(scratch), counts, out_keys, out_vals, rm_out, x.links, asked,
+                       out_links);
+    return hipGetLastError();
+}
+
+hipError_t index_links(const oi_view& x, const uint64_t* q_keys, const uint64_t* q_ids, uint64_t m, uint64_t* out,
+                       hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_index_links, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.links, x.dir, x.bits, q_keys,
+                       q_ids, m, out);
     return hipGetLastError();
 }
 

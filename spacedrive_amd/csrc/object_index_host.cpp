@@ -7,8 +7,11 @@
 // (core/src/object/file_identifier/mod.rs:168-175) and the link to the first of them
 // (:189-225); removal as Objects are deleted (core/src/object/orphan_remover.rs:57-95) and
 // files change (location/manager/watcher/utils.rs:410-494).  No HIP: built with g++ under
-// the sanitizers too (object_index_selftest.cpp, object_index_remove_selftest.cpp; `make
-// sanitize-object-index`, `make sanitize-object-index-remove`).
+// the sanitizers too (object_index_selftest.cpp, object_index_remove_selftest.cpp,
+// object_index_owners_selftest.cpp; `make sanitize-object-index`, `make
+// sanitize-object-index-remove`, `make sanitize-object-index-owners`).  The owners mode
+// (sd_cpu_object_index_create_ex with SD_OBJECT_INDEX_OWNERS) keeps one entry per (key, Object
+// id) with its link count; its rules are those of object_index.h, as the kernels'.
 #include <string.h>
 
 #include <algorithm>
@@ -47,9 +50,12 @@ bool oi_key_from_hex(const char* hex16, uint64_t* key) {
 
 struct sd_cpu_object_index {
     int nparts = 1, part = 0;
+    int flags = 0;  // SD_OBJECT_INDEX_OWNERS: one entry per (key, Object id) and links[]
     uint64_t n = 0, cap = 0;
     uint32_t bits = 0;
     std::vector<uint64_t> keys, vals, keys2, vals2;  // two buffers of `cap`, swapped by an insert or a removal
+    std::vector<uint64_t> links, links2;             // owners mode: the third array beside them
+    bool owners() const { return (flags & SD_OBJECT_INDEX_OWNERS) != 0; }
     std::vector<uint64_t> dir{0, 0};
 };
 
@@ -71,11 +77,17 @@ void build_dir(sd_cpu_object_index* x) {
 // The second half of both removals (object_index.cpp finish_remove): the count against
 // `capacity` before anything is written, the dropped entries in order into removed_out, the
 // survivors in order into the other buffer pair, the swap and the directory.
+// Owners mode: links[] travels with the survivors, less asked[i] (the links a removal with ids
+// takes; null otherwise); nothing is decremented before the capacity check.
 void finish_remove(sd_cpu_object_index* x, const std::vector<uint8_t>& flags, uint64_t* removed_out, uint64_t capacity,
-                   uint64_t* removed) {
+                   uint64_t* removed, const uint64_t* asked = nullptr) {
     const uint64_t r = (uint64_t)std::count(flags.begin(), flags.end(), (uint8_t)1);
     if (removed) *removed = r;
-    if (r == 0) return;
+    if (r == 0) {  // no entry leaves: the links asked are taken in place, the rest stands
+        if (asked)
+            for (uint64_t i = 0; i < x->n; i++) x->links[i] -= asked[i];
+        return;
+    }
     if (removed_out && capacity < r)
         throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of removed entries");
     uint64_t kept = 0, gone = 0;
@@ -83,6 +95,7 @@ void finish_remove(sd_cpu_object_index* x, const std::vector<uint8_t>& flags, ui
         if (!flags[i]) {
             x->keys2[kept] = x->keys[i];
             x->vals2[kept] = x->vals[i];
+            if (x->owners()) x->links2[kept] = x->links[i] - (asked ? asked[i] : 0);
             kept++;
         } else {
             if (removed_out) {
@@ -94,7 +107,75 @@ void finish_remove(sd_cpu_object_index* x, const std::vector<uint8_t>& flags, ui
     }
     x->keys.swap(x->keys2);
     x->vals.swap(x->vals2);
+    x->links.swap(x->links2);
     x->n = kept;
+    build_dir(x);
+}
+
+// A batch of pairs aggregated (object_index.hip aggregate_pairs): ordered by (key, id), each
+// distinct pair once with its multiplicity
+struct pair_batch {
+    std::vector<uint64_t> k, v, cnt;
+};
+pair_batch aggregate_pairs(const uint64_t* keys, const uint64_t* ids, uint64_t m) {
+    std::vector<uint64_t> pos(m);
+    std::iota(pos.begin(), pos.end(), 0);
+    std::sort(pos.begin(), pos.end(), [&](uint64_t a, uint64_t b) {
+        return keys[a] != keys[b] ? keys[a] < keys[b] : ids[a] < ids[b];
+    });
+    pair_batch b;
+    for (uint64_t j = 0; j < m; j++) {
+        const uint64_t k = keys[pos[j]], v = ids[pos[j]];
+        if (j && b.k.back() == k && b.v.back() == v) b.cnt.back()++;
+        else b.k.push_back(k), b.v.push_back(v), b.cnt.push_back(1);
+    }
+    return b;
+}
+
+void grow(sd_cpu_object_index* x, uint64_t need) {
+    const uint64_t cap = oi_grow_capacity(need, x->cap);
+    if (cap == x->cap) return;
+    x->keys.resize(cap), x->vals.resize(cap), x->keys2.resize(cap), x->vals2.resize(cap);
+    if (x->owners()) x->links.resize(cap), x->links2.resize(cap);
+    x->cap = cap;
+}
+
+// Owners-mode insert: every distinct pair of this shard takes its (key, id) rank; the absent
+// ones merge in by rank with their multiplicity as links, the present ones add theirs
+void insert_owners(sd_cpu_object_index* x, const uint64_t* keys, const uint64_t* ids, uint64_t m, uint64_t* taken) {
+    const pair_batch b = aggregate_pairs(keys, ids, m);
+    std::vector<uint64_t> nk, nv, nl, at_old, add;
+    for (size_t j = 0; j < b.k.size(); j++) {
+        if (oi_dest_of(b.k[j], x->nparts) != (uint32_t)x->part) continue;
+        uint64_t at;
+        if (oi_find_pair(x->keys.data(), x->vals.data(), x->dir.data(), x->bits, b.k[j], b.v[j], &at))
+            at_old.push_back(at), add.push_back(b.cnt[j]);
+        else
+            nk.push_back(b.k[j]), nv.push_back(b.v[j]), nl.push_back(b.cnt[j]);
+    }
+    const uint64_t r = nk.size();
+    if (taken) *taken = r;
+    if (r == 0) {
+        for (size_t j = 0; j < at_old.size(); j++) x->links[at_old[j]] += add[j];
+        return;
+    }
+    grow(x, x->n + r);
+    for (uint64_t j = 0; j < r; j++) {
+        const uint64_t at = j + oi_rank_pair(x->keys.data(), x->vals.data(), x->dir.data(), x->bits, nk[j], nv[j]);
+        x->keys2[at] = nk[j], x->vals2[at] = nv[j], x->links2[at] = nl[j];
+    }
+    for (uint64_t i = 0; i < x->n; i++) {
+        const uint64_t at = i + oi_lower_bound_pair(nk.data(), nv.data(), 0, r, x->keys[i], x->vals[i]);
+        x->keys2[at] = x->keys[i], x->vals2[at] = x->vals[i], x->links2[at] = x->links[i];
+    }
+    for (size_t j = 0; j < at_old.size(); j++) {
+        const uint64_t i = at_old[j];
+        x->links2[i + oi_lower_bound_pair(nk.data(), nv.data(), 0, r, x->keys[i], x->vals[i])] += add[j];
+    }
+    x->keys.swap(x->keys2);
+    x->vals.swap(x->vals2);
+    x->links.swap(x->links2);
+    x->n += r;
     build_dir(x);
 }
 
@@ -103,19 +184,33 @@ void finish_remove(sd_cpu_object_index* x, const std::vector<uint8_t>& flags, ui
 extern "C" {
 
 int sd_cpu_object_index_create(int nparts, int part, sd_cpu_object_index** out) {
+    return sd_cpu_object_index_create_ex(nparts, part, 0, out);
+}
+
+int sd_cpu_object_index_create_ex(int nparts, int part, int flags, sd_cpu_object_index** out) {
     SD_GUARD_BEGIN
     if (!out) throw sd_failure(SD_ERR_INVALID, "null argument");
     if (nparts < 1 || nparts > 64 || part < 0 || part >= nparts)
         throw sd_failure(SD_ERR_INVALID, "part / nparts out of range (1..64 parts)");
+    if (flags & ~SD_OBJECT_INDEX_OWNERS) throw sd_failure(SD_ERR_INVALID, "unknown flags");
     auto* x = new sd_cpu_object_index();
     x->nparts = nparts;
     x->part = part;
+    x->flags = flags;
     *out = x;
     return SD_OK;
     SD_GUARD_END
 }
 
 void sd_cpu_object_index_destroy(sd_cpu_object_index* index) { delete index; }
+
+int sd_cpu_object_index_flags(const sd_cpu_object_index* index, int* flags) {
+    SD_GUARD_BEGIN
+    if (!index || !flags) throw sd_failure(SD_ERR_INVALID, "null argument");
+    *flags = index->flags;
+    return SD_OK;
+    SD_GUARD_END
+}
 
 int sd_cpu_object_index_count(const sd_cpu_object_index* index, uint64_t* n) {
     SD_GUARD_BEGIN
@@ -132,6 +227,10 @@ int sd_cpu_object_index_insert(sd_cpu_object_index* index, const uint64_t* keys,
     if (taken) *taken = 0;
     if (m == 0) return SD_OK;
     sd_cpu_object_index* x = index;
+    if (x->owners()) {
+        insert_owners(x, keys, object_ids, m, taken);
+        return SD_OK;
+    }
     // keep first: order the pairs by (key, position), keep each key's first pair, drop the
     // other shards' keys and those the index already has
     std::vector<uint64_t> pos(m);
@@ -150,14 +249,7 @@ int sd_cpu_object_index_insert(sd_cpu_object_index* index, const uint64_t* keys,
     const uint64_t r = nk.size();
     if (taken) *taken = r;
     if (r == 0) return SD_OK;
-    const uint64_t cap = oi_grow_capacity(x->n + r, x->cap);
-    if (cap != x->cap) {
-        x->keys.resize(cap);
-        x->vals.resize(cap);
-        x->keys2.resize(cap);
-        x->vals2.resize(cap);
-        x->cap = cap;
-    }
+    grow(x, x->n + r);
     // merge by rank: a new entry goes to its rank + the old keys below it, an old entry to its
     // position + the new keys below it
     for (uint64_t j = 0; j < r; j++) {
@@ -186,6 +278,25 @@ int sd_cpu_object_index_remove(sd_cpu_object_index* index, const uint64_t* keys,
     sd_cpu_object_index* x = index;
     if (m == 0 || x->n == 0) return SD_OK;
     std::vector<uint8_t> flags(x->n, 0);
+    if (x->owners() && object_ids) {  // each pair takes one link; an entry leaves at zero
+        const pair_batch b = aggregate_pairs(keys, object_ids, m);
+        std::vector<uint64_t> asked(x->n, 0);
+        for (size_t j = 0; j < b.k.size(); j++) {
+            uint64_t at;
+            if (oi_find_pair(x->keys.data(), x->vals.data(), x->dir.data(), x->bits, b.k[j], b.v[j], &at))
+                asked[at] = b.cnt[j];
+        }
+        for (uint64_t i = 0; i < x->n; i++) flags[i] = oi_links_drop(x->links[i], asked[i]) ? 1 : 0;
+        finish_remove(x, flags, removed_out, capacity, removed, asked.data());
+        return SD_OK;
+    }
+    if (x->owners()) {  // every entry of each listed key: the entry side searches the sorted keys
+        std::vector<uint64_t> sorted(keys, keys + m);
+        std::sort(sorted.begin(), sorted.end());
+        for (uint64_t i = 0; i < x->n; i++) flags[i] = oi_id_listed(sorted.data(), m, x->keys[i]) ? 1 : 0;
+        finish_remove(x, flags, removed_out, capacity, removed);
+        return SD_OK;
+    }
     for (uint64_t i = 0; i < m; i++) {
         uint64_t at;
         if (oi_remove_hit(x->keys.data(), x->vals.data(), x->dir.data(), x->bits, keys[i],
@@ -235,6 +346,38 @@ int sd_cpu_object_index_export(const sd_cpu_object_index* index, uint64_t* keys_
     if (index->n) {
         memcpy(keys_out, index->keys.data(), index->n * sizeof(uint64_t));
         memcpy(object_ids_out, index->vals.data(), index->n * sizeof(uint64_t));
+    }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_object_index_links(const sd_cpu_object_index* index, const uint64_t* keys, const uint64_t* object_ids,
+                              uint64_t m, uint64_t* links_out) {
+    SD_GUARD_BEGIN
+    if (!index || (m && (!keys || !object_ids || !links_out))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    for (uint64_t i = 0; i < m; i++) {
+        uint64_t at;
+        links_out[i] = oi_find_pair(index->keys.data(), index->vals.data(), index->dir.data(), index->bits, keys[i],
+                                    object_ids[i], &at)
+                           ? index->links[at]
+                           : 0;
+    }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_object_index_export_links(const sd_cpu_object_index* index, uint64_t* keys_out, uint64_t* ids_out,
+                                     uint64_t* links_out, uint64_t capacity) {
+    SD_GUARD_BEGIN
+    if (!index) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    if (index->n && (!keys_out || !ids_out || !links_out)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (capacity < index->n) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the index's count");
+    if (index->n) {
+        memcpy(keys_out, index->keys.data(), index->n * sizeof(uint64_t));
+        memcpy(ids_out, index->vals.data(), index->n * sizeof(uint64_t));
+        memcpy(links_out, index->links.data(), index->n * sizeof(uint64_t));
     }
     return SD_OK;
     SD_GUARD_END

@@ -209,12 +209,16 @@ struct sd_object_index {
     uint64_t n = 0, cap = 0;
     uint32_t bits = 0;
     int cur = 0;                        // which buffer pair holds the index
+    int flags = 0;                      // SD_OBJECT_INDEX_OWNERS: one entry per (key, Object id) + links
     sdi::DevBuf keys[2], vals[2], dir;  // dir: 2^bits + 1 offsets
+    sdi::DevBuf links[2];               // owners mode: the third array beside keys / vals, grown with them
     sdi::DevBuf counts;                 // OI_COUNT_SLOTS u64, then one device count
     sdi::DevBuf scratch;                // sdk::index_insert_scratch / index_remove_scratch
     sdi::PinnedBuf host;                // an insert's survivor count; a removal's per-slice counts
+    bool owners() const { return (flags & SD_OBJECT_INDEX_OWNERS) != 0; }
     sdk::oi_view view() const {
-        return {keys[cur].as<uint64_t>(), vals[cur].as<uint64_t>(), dir.as<uint64_t>(), n, bits};
+        return {keys[cur].as<uint64_t>(), vals[cur].as<uint64_t>(), dir.as<uint64_t>(), n, bits,
+                owners() ? links[cur].as<uint64_t>() : nullptr};
     }
 };
 

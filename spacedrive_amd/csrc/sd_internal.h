@@ -67,6 +67,7 @@ struct oi_view {
     const uint64_t *keys, *vals, *dir;
     uint64_t n;
     uint32_t bits;
+    const uint64_t* links = nullptr;  // owners mode only: the link count per entry
 };
 constexpr uint32_t OI_COUNT_SLOTS = 1024;  // u64 per-workgroup counts of an ordered compaction
 hipError_t index_lookup(const oi_view& x, const uint64_t* q, uint64_t m, uint64_t* out, uint8_t* found,
@@ -99,5 +100,43 @@ hipError_t index_remove_flag_objects(const oi_view& x, const uint64_t* ids, uint
 // Object id) in order into rm_out (may be null)
 hipError_t index_remove_compact(const oi_view& x, const void* scratch, const uint64_t* counts, uint64_t* out_keys,
                                 uint64_t* out_vals, uint64_t* rm_out, hipStream_t s);
+// ---- owners mode (object_index.h): one entry per (key, Object id) with its link count
+// A batch of m pairs aggregated in `scratch`: ordered by (key, id), each distinct pair once
+// with its multiplicity.  Insert, first half: the distinct pairs this shard lacks (nk, nv, nl =
+// multiplicity) with their count (device u64); the present ones are remembered in `scratch`
+// for index_owners_add_links.  m > 0.
+size_t index_owners_insert_scratch(uint64_t m);
+hipError_t index_owners_insert_select(const oi_view& x, int nparts, int part, const uint64_t* in_keys,
+                                      const uint64_t* in_vals, uint64_t m, void* scratch, uint64_t* counts,
+                                      const uint64_t** nk_out, const uint64_t** nv_out, const uint64_t** nl_out,
+                                      const uint64_t** total_out, hipStream_t s);
+// second half: merge the r new entries with the index x into out_* (n + r entries) ...
+hipError_t index_owners_merge(const oi_view& x, const uint64_t* nk, const uint64_t* nv, const uint64_t* nl, uint64_t r,
+                              uint64_t* out_keys, uint64_t* out_vals, uint64_t* out_links, hipStream_t s);
+// ... and add the present pairs' multiplicities to their entries' links, at their places after
+// the merge of r new entries (r == 0: in the index's own array); one writer per entry
+hipError_t index_owners_add_links(const void* scratch, uint64_t m, const uint64_t* nk, const uint64_t* nv, uint64_t r,
+                                  uint64_t* links, hipStream_t s);
+// removal with ids, first half: asked[n] (the links each entry is asked to give up), flags[n]
+// and the per-slice counts; n > 0, m > 0.  Nothing of the index is written.
+size_t index_owners_remove_scratch(uint64_t n, uint64_t m);
+hipError_t index_owners_remove_flag_pairs(const oi_view& x, const uint64_t* rm_keys, const uint64_t* rm_ids,
+                                          uint64_t m, void* scratch, uint64_t* counts, hipStream_t s);
+// a removal with ids that drops no entry (the counts say so): the links asked leave their
+// entries in place, `links` being the index's own array; keys, values and directory stand
+hipError_t index_owners_take_links(const oi_view& x, const void* scratch, uint64_t m, uint64_t* links, hipStream_t s);
+// removal without ids: every entry whose key is among the m keys (sorted in `scratch`, sized by
+// index_remove_scratch(n, m))
+hipError_t index_owners_remove_flag_keys(const oi_view& x, const uint64_t* rm_keys, uint64_t m, void* scratch,
+                                         uint64_t* counts, hipStream_t s);
+// second half of every owners-mode removal: index_remove_compact carrying the links; `asked`
+// (null except after index_owners_remove_flag_pairs) is taken from the survivors' links
+const uint64_t* index_owners_asked(const void* scratch, uint64_t n);
+hipError_t index_owners_remove_compact(const oi_view& x, const void* scratch, const uint64_t* asked,
+                                       const uint64_t* counts, uint64_t* out_keys, uint64_t* out_vals,
+                                       uint64_t* out_links, uint64_t* rm_out, hipStream_t s);
+// the link count per (key, id) pair, 0 if absent
+hipError_t index_links(const oi_view& x, const uint64_t* q_keys, const uint64_t* q_ids, uint64_t m, uint64_t* out,
+                       hipStream_t s);
 hipError_t index_build_dir(const uint64_t* keys, uint64_t n, uint32_t bits, uint64_t* dir, hipStream_t s);
 }  // namespace sdk

@@ -274,6 +274,89 @@ def index_remove_objects_host(keys: np.ndarray, vals: np.ndarray, ids):
     return _index_drop(keys, vals, drop)
 
 
+# ---- the owners mode (SD_OBJECT_INDEX_OWNERS): an index given as (keys uint64 ascending, vals
+# uint64 ascending within equal keys, links uint64 >= 1), one entry per (key, Object id) pair
+def _pair_codes(*pairs):
+    """(keys, ids) lists -> one int64 code array per list: equal pairs get equal codes, and the
+    codes ascend with (key, id) (unsigned)."""
+    k = np.concatenate([np.asarray(p[0], np.uint64) for p in pairs])
+    v = np.concatenate([np.asarray(p[1], np.uint64) for p in pairs])
+    order = np.lexsort((v, k))
+    ks, vs = k[order], v[order]
+    new = np.ones(len(k), bool)
+    new[1:] = (ks[1:] != ks[:-1]) | (vs[1:] != vs[:-1])
+    code = np.empty(len(k), np.int64)
+    code[order] = np.cumsum(new) - 1
+    cuts = np.cumsum([len(p[0]) for p in pairs])[:-1]
+    return np.split(code, cuts)
+
+
+def owners_insert_host(keys, vals, links, new_keys, new_vals, nparts: int = 1, part: int = 0):
+    """Host mirror of sd_object_index_insert on an owners-mode index: each pair of shard `part`
+    adds one link to (k, v), created at 1 if absent; repeated pairs add up; the order of the
+    pairs does not matter.  Returns (keys, vals, links, entries created)."""
+    keys, vals, links = (np.asarray(a, np.uint64) for a in (keys, vals, links))
+    nk = np.ascontiguousarray(new_keys, dtype=np.uint64).reshape(-1)
+    nv = np.ascontiguousarray(new_vals, dtype=np.uint64).reshape(-1)
+    mine = dest_of(nk, nparts) == part
+    nk, nv = nk[mine], nv[mine]
+    if len(nk) == 0:
+        return keys, vals, links, 0
+    ci, cn = _pair_codes((keys, vals), (nk, nv))
+    u, first, cnt = np.unique(cn, return_index=True, return_counts=True)
+    present = np.isin(u, ci)
+    links = links.copy()
+    links[np.searchsorted(ci, u[present])] += cnt[present].astype(np.uint64)
+    allk = np.concatenate([keys, nk[first[~present]]])
+    allv = np.concatenate([vals, nv[first[~present]]])
+    alll = np.concatenate([links, cnt[~present].astype(np.uint64)])
+    o = np.lexsort((allv, allk))
+    return allk[o], allv[o], alll[o], int((~present).sum())
+
+
+def _owners_drop(keys, vals, links, drop):
+    return keys[~drop], vals[~drop], links[~drop], np.stack([keys[drop], vals[drop]], axis=1)
+
+
+def owners_remove_host(keys, vals, links, rm_keys, rm_ids=None):
+    """Host mirror of sd_object_index_remove on an owners-mode index.  With ids each pair takes
+    one link from (k, v), pairs naming one entry add up, and an entry asked for at least as
+    many links as it has is dropped; without ids every entry of each listed key goes.  Returns
+    (keys, vals, links, removed pairs uint64 [r, 2] in ascending (key, id) order)."""
+    keys, vals, links = (np.asarray(a, np.uint64) for a in (keys, vals, links))
+    rk = np.ascontiguousarray(rm_keys, dtype=np.uint64).reshape(-1)
+    if rm_ids is None:
+        return _owners_drop(keys, vals, links, np.isin(keys, rk))
+    rv = np.ascontiguousarray(rm_ids, dtype=np.uint64).reshape(-1)
+    asked = np.zeros(len(keys), np.uint64)
+    if len(keys) and len(rk):
+        ci, cr = _pair_codes((keys, vals), (rk, rv))
+        u, cnt = np.unique(cr, return_counts=True)
+        present = np.isin(u, ci)
+        asked[np.searchsorted(ci, u[present])] = cnt[present].astype(np.uint64)
+    drop = (asked > 0) & (asked >= links)
+    return _owners_drop(keys, vals, links - np.where(drop, np.uint64(0), asked), drop)
+
+
+def owners_remove_objects_host(keys, vals, links, ids):
+    """Host mirror of sd_object_index_remove_objects on an owners-mode index: every entry whose
+    Object id is listed goes, whatever its links."""
+    keys, vals, links = (np.asarray(a, np.uint64) for a in (keys, vals, links))
+    return _owners_drop(keys, vals, links, np.isin(vals, np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)))
+
+
+def owners_links_host(keys, vals, links, q_keys, q_ids):
+    """Host mirror of sd_object_index_links: the link count per (key, id) pair, 0 if absent."""
+    qk = np.ascontiguousarray(q_keys, dtype=np.uint64).reshape(-1)
+    qv = np.ascontiguousarray(q_ids, dtype=np.uint64).reshape(-1)
+    out = np.zeros(len(qk), np.uint64)
+    if len(qk) and len(keys):
+        ci, cq = _pair_codes((keys, vals), (qk, qv))
+        hit = np.isin(cq, ci)
+        out[hit] = np.asarray(links, np.uint64)[np.searchsorted(ci, cq[hit])]
+    return out
+
+
 def owners_indexed_host(records: np.ndarray, rep: np.ndarray, keys: np.ndarray, vals: np.ndarray,
                         chunk_size: int = 100):
     """Host mirror of sd_dedup_owners_indexed on grouped records (int64 [m, 2] sorted by (key,

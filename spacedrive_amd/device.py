@@ -11,7 +11,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._native import SD_ERR_CAPACITY, Extent, SdCasError, check, lib
+from ._native import SD_ERR_CAPACITY, SD_OBJECT_INDEX_OWNERS, Extent, SdCasError, check, lib
 
 EXTENT_DTYPE = np.dtype([("size", "<u8"), ("msg_offset", "<u8"), ("msg_len", "<u4"), ("kind", "<u4")])
 assert EXTENT_DTYPE.itemsize == ctypes.sizeof(Extent) == 24
@@ -176,13 +176,45 @@ class ObjectIndex:
     """The device-resident Object index (sd_object_index): cas_id key -> the Object of the
     library that already owns it (file_identifier/mod.rs:168-225).  Keys are carried in int64
     tensors (the bit pattern of the u64); Object ids likewise.  Insert is keep-first; insert
-    and the removals are exclusive; lookups may run concurrently (include/sd_cas.h)."""
+    and the removals are exclusive; lookups may run concurrently (include/sd_cas.h).
 
-    def __init__(self, ctx: Context, nparts: int = 1, part: int = 0):
-        self.ctx, self.nparts, self.part = ctx, nparts, part
+    ``owners=True`` (SD_OBJECT_INDEX_OWNERS) keeps one entry per (cas_id, Object) pair with
+    the number of file_paths that link them: insert adds a link per pair, remove with ids
+    takes one, an entry leaves at zero, and the first owner of a key is its smallest Object
+    id -- the host never asks the DB who else owns a cas_id."""
+
+    def __init__(self, ctx: Context, nparts: int = 1, part: int = 0, owners: bool = False):
+        self.ctx, self.nparts, self.part, self.owners_mode = ctx, nparts, part, bool(owners)
         h = ctypes.c_void_p()
-        check(lib().sd_object_index_create(ctx.handle, nparts, part, ctypes.byref(h)))
+        if owners:
+            check(lib().sd_object_index_create_ex(ctx.handle, nparts, part, SD_OBJECT_INDEX_OWNERS, ctypes.byref(h)))
+        else:
+            check(lib().sd_object_index_create(ctx.handle, nparts, part, ctypes.byref(h)))
         self.handle = h
+
+    @property
+    def flags(self) -> int:
+        f = ctypes.c_int(0)
+        check(lib().sd_object_index_flags(self.handle, ctypes.byref(f)))
+        return int(f.value)
+
+    def links(self, d_keys: torch.Tensor, d_object_ids: torch.Tensor, stream=None) -> torch.Tensor:
+        """-> int64 [m]: the link count of each (key, Object id) pair, 0 if absent (owners mode)."""
+        m = int(d_keys.numel())
+        assert d_object_ids.numel() == m and d_keys.dtype == d_object_ids.dtype == torch.int64
+        out = torch.empty(max(m, 1), dtype=torch.int64, device=torch.device("cuda", self.ctx.device))
+        check(lib().sd_object_index_links(self.ctx.handle, self.handle, _ptr(d_keys) if m else None,
+                                          _ptr(d_object_ids) if m else None, m, _ptr(out), _stream(stream)))
+        return out[:m]
+
+    def export_links(self, stream=None):
+        """-> (keys, Object ids, links) int64 [n] in ascending (key, id) order (owners mode)."""
+        n = len(self)
+        dev = torch.device("cuda", self.ctx.device)
+        k, v, c = (torch.empty(max(n, 1), dtype=torch.int64, device=dev) for _ in range(3))
+        check(lib().sd_object_index_export_links(self.ctx.handle, self.handle, _ptr(k), _ptr(v), _ptr(c), max(n, 1),
+                                                 _stream(stream)))
+        return k[:n], v[:n], c[:n]
 
     def __len__(self) -> int:
         n = ctypes.c_uint64(0)
@@ -253,7 +285,9 @@ class ObjectIndex:
         return self._removal(lambda out, cap, removed: lib().sd_object_index_remove(
             self.ctx.handle, self.handle, _ptr(d_keys) if m else None,
             _ptr(d_object_ids) if m and d_object_ids is not None else None, m, out, cap, removed, st),
-            min(m, len(self)), d_removed_out, capacity)
+            # owners mode without ids: a key drops all its owners, so the bound is the entries
+            # (HostObjectIndex.remove sizes its rows the same way)
+            len(self) if self.owners_mode and d_object_ids is None else min(m, len(self)), d_removed_out, capacity)
 
     def remove_objects(self, d_object_ids: torch.Tensor, stream=None, d_removed_out: Optional[torch.Tensor] = None,
                        capacity: Optional[int] = None):
@@ -324,11 +358,37 @@ class HostObjectIndex:
     """The host twin (sd_cpu_object_index): the same index over numpy arrays, for a host
     without a gfx950 device.  Keys and Object ids are uint64 arrays."""
 
-    def __init__(self, nparts: int = 1, part: int = 0):
-        self.nparts, self.part = nparts, part
+    def __init__(self, nparts: int = 1, part: int = 0, owners: bool = False):
+        self.nparts, self.part, self.owners_mode = nparts, part, bool(owners)
         h = ctypes.c_void_p()
-        check(lib().sd_cpu_object_index_create(nparts, part, ctypes.byref(h)))
+        if owners:
+            check(lib().sd_cpu_object_index_create_ex(nparts, part, SD_OBJECT_INDEX_OWNERS, ctypes.byref(h)))
+        else:
+            check(lib().sd_cpu_object_index_create(nparts, part, ctypes.byref(h)))
         self.handle = h
+
+    @property
+    def flags(self) -> int:
+        f = ctypes.c_int(0)
+        check(lib().sd_cpu_object_index_flags(self.handle, ctypes.byref(f)))
+        return int(f.value)
+
+    def links(self, keys, object_ids) -> np.ndarray:
+        """-> uint64 [m]: the link count of each (key, Object id) pair, 0 if absent (owners mode)."""
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        v = np.ascontiguousarray(object_ids, dtype=np.uint64)
+        assert k.size == v.size
+        out = np.zeros(max(k.size, 1), np.uint64)
+        check(lib().sd_cpu_object_index_links(self.handle, _ptr(k) if k.size else None, _ptr(v) if k.size else None,
+                                              k.size, _ptr(out)))
+        return out[:k.size]
+
+    def export_links(self):
+        """-> (keys, Object ids, links) uint64 [n] in ascending (key, id) order (owners mode)."""
+        n = len(self)
+        k, v, c = (np.zeros(max(n, 1), np.uint64) for _ in range(3))
+        check(lib().sd_cpu_object_index_export_links(self.handle, _ptr(k), _ptr(v), _ptr(c), max(n, 1)))
+        return k[:n], v[:n], c[:n]
 
     def __len__(self) -> int:
         n = ctypes.c_uint64(0)
@@ -365,7 +425,7 @@ class HostObjectIndex:
         assert v is None or v.size == k.size
         return self._removal(lambda out, cap, removed: lib().sd_cpu_object_index_remove(
             self.handle, _ptr(k) if k.size else None, _ptr(v) if k.size and v is not None else None, k.size, out, cap,
-            removed), min(k.size, len(self)), capacity)
+            removed), len(self) if self.owners_mode and v is None else min(k.size, len(self)), capacity)
 
     def remove_hex(self, cas_ids, object_ids=None) -> int:
         """remove from the DB's strings; returns the count."""

@@ -23,7 +23,7 @@ from ._native import SD_FILE_OK
 
 
 def scan_library(ctx, paths: Sequence[str], sizes, comm=None, group: Optional[dist.ProcessGroup] = None,
-                 chunk_size: int = 100, nthreads: int = 16, index=None) -> dict:
+                 chunk_size: int = 100, nthreads: int = 16, index=None, object_id_of=None) -> dict:
     """This rank's share of the scan of the whole library (`paths`, `sizes` as the walker's
     metadata reported them; the same lists on every rank).  With `comm` (libsdcas's RCCL
     communicator, dedup.make_comm) the exchange runs inside the library; without it, over
@@ -32,7 +32,10 @@ def scan_library(ctx, paths: Sequence[str], sizes, comm=None, group: Optional[di
     "owner": [m], "n_groups": int}.  With `index` (a device.ObjectIndex of the Objects the
     library already has, sharded as this rank's prefix range) owners of known cas_ids are those Objects' ids, and the result gains "existing"
     (uint8 [m]) and "new_heads" (int64 [n_new, 2]: key, creating file) to insert once the
-    host has given the new Objects their ids."""
+    host has given the new Objects their ids.  With an owners-mode index (ObjectIndex(...,
+    owners=True)) and `object_id_of` (int64 tensor of creating file indices -> int64 tensor of
+    the ids the host gave their Objects) the scan also inserts every record's (key, Object id)
+    pair, and the result gains "object_ids" (int64 [m]) and "inserted" (entries created)."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
@@ -51,6 +54,16 @@ def scan_library(ctx, paths: Sequence[str], sizes, comm=None, group: Optional[di
         else:
             recs, rep, ng, owner, existing, new = dedup.dedup_shard(ctx, d_hash, d_valid, n, lo, group, index=index)
         extra = {"existing": existing, "new_heads": new}
+        if getattr(index, "owners_mode", False) and object_id_of is not None:
+            # owners mode: ONE insert of (key, Object id) for every record, linked and created
+            # alike -- a linked record's owner is an Object id already, a created one's is the
+            # file whose Object the host has just made.  The host's mapping sees the created
+            # records only: a linked owner is an arbitrary u64, not a file index
+            created = ~existing.bool()
+            object_ids = owner.clone()
+            object_ids[created] = object_id_of(owner[created])
+            extra["object_ids"] = object_ids
+            extra["inserted"] = index.insert(recs[:, 0].contiguous(), object_ids.contiguous())
     elif comm is not None:
         runner = dedup.RcclDedup(ctx, comm, dev, capacity=n * 5 // 4 + 4096)
         recs, rep, ng, owner = runner(d_hash, d_valid, n, lo, chunk_size=chunk_size)
