@@ -506,7 +506,7 @@ int sd_object_index_export(sd_cas_ctx* ctx, const sd_object_index* index, uint64
  * as above; the host creates the new heads' Objects) -> ONE insert of (key, Object id) for
  * EVERY record of the scan, linked and created alike; a file_path (c, O) deleted -> remove of
  * the pair (c, O) with the id given; a file_path changed A -> B on O -> remove (A, O), insert
- * (B, O); the orphan remover -> sd_object_index_remove_objects(ids).  No DB query for owners.
+ * (B, O), or both in one sd_object_index_apply (below); the orphan remover -> sd_object_index_remove_objects(ids).  No DB query for owners.
  * Opting in: sd_object_index_create_ex(ctx, nparts, part, flags, &index) with
  *   SD_OBJECT_INDEX_OWNERS (1); flags 0 is sd_object_index_create.  sd_object_index_flags
  *   (index, &flags) reads the mode back.  An index made without the flag behaves bit for bit
@@ -545,6 +545,44 @@ int sd_object_index_links(sd_cas_ctx* ctx, const sd_object_index* index, const u
  * `capacity` entries (SD_ERR_CAPACITY if smaller than the count). */
 int sd_object_index_export_links(sd_cas_ctx* ctx, const sd_object_index* index, uint64_t* d_keys_out,
                                  uint64_t* d_ids_out, uint64_t* d_links_out, uint64_t capacity, void* stream);
+/* APPLY: "these links went, these links came" in one call, for an owners-mode index only.  A
+ * content change moves a file_path from cas_id A to B on its Object (watcher/utils.rs:410-494),
+ * a re-identified location and a burst of watcher events produce pairs that leave and pairs
+ * that enter together; remove then insert rewrites the index twice and shows concurrent
+ * lookups a state between the two.  For every pair p = (key, id) of this shard, with held(p)
+ * its links before the call (0 if absent), asked(p) its multiplicity in the removal list and
+ * added(p) its multiplicity in the insertion list:
+ *   kept(p)  = 0 if held(p) == 0 or asked(p) >= held(p) > 0 with asked(p) > 0, else held(p) - asked(p)
+ *   after(p) = kept(p) + added(p)
+ * which is what sd_object_index_remove with ids followed by sd_object_index_insert leaves:
+ * asking for more than held is not an error, the removals apply before the insertions, the
+ * order inside each list does not matter.  After the call the index is bit-identical to a
+ * fresh owners-mode index holding the `after` relation (ascending (key, id), the same count,
+ * directory bits re-chosen, directory rebuilt), and to a twin given the two calls.
+ * Reports, of the NET effect (not the two calls' counters): *removed (host, may be NULL) = the
+ *   entries present before and absent after; d_removed_out (device, may be NULL; `capacity`
+ *   rows of 2 x u64) receives their (key, id) in ascending (key, id) order, nothing past the
+ *   first *removed rows; *taken (host, may be NULL) = the entries absent before and present
+ *   after.  A pair whose last link is taken and that gains a link in the same call stays with
+ *   links = added and counts in neither.
+ * Pairs of other shards, absent pairs in the removal list and a present key with another id
+ *   are no-ops.  m_rm == 0 is an insert, m_in == 0 a removal with ids, both 0 a no-op.
+ *   d_rm_ids == NULL with m_rm > 0 is SD_ERR_INVALID (every owner of a key: sd_object_index_remove),
+ *   and so is an index without SD_OBJECT_INDEX_OWNERS.
+ * If d_removed_out is given and capacity < *removed: SD_ERR_CAPACITY, *removed = the
+ *   requirement, *taken = 0, and nothing changes: no entry, no link count, no new pair.
+ * Exclusive on the index, runs on `stream` and syncs it, grows the buffers as insert does; not
+ * collective.  When nothing leaves or enters only the link counts change, in place.
+ * sd_object_index_apply_hex: both lists from the DB's strings (hex17 as
+ * sd_object_index_insert_hex takes it) and host ids; a malformed cas_id in either list is
+ * SD_ERR_INVALID with nothing changed. */
+int sd_object_index_apply(sd_cas_ctx* ctx, sd_object_index* index, const uint64_t* d_rm_keys,
+                          const uint64_t* d_rm_ids, uint64_t m_rm, const uint64_t* d_in_keys,
+                          const uint64_t* d_in_ids, uint64_t m_in, uint64_t* d_removed_out, uint64_t capacity,
+                          uint64_t* removed, uint64_t* taken, void* stream);
+int sd_object_index_apply_hex(sd_cas_ctx* ctx, sd_object_index* index, const char* rm_hex17, const uint64_t* rm_ids,
+                              uint64_t m_rm, const char* in_hex17, const uint64_t* in_ids, uint64_t m_in,
+                              uint64_t* removed, uint64_t* taken);
 /* sd_dedup_owners against the Objects the library already has (mod.rs:168-225, then
  * :229-333 for the rest), per grouped record i:
  *   d_owner[i] = index[cas_id], d_existing[i] = 1     if the index has the record's cas_id;
@@ -585,6 +623,10 @@ int sd_cpu_object_index_links(const sd_cpu_object_index* index, const uint64_t* 
                               uint64_t m, uint64_t* links_out);
 int sd_cpu_object_index_export_links(const sd_cpu_object_index* index, uint64_t* keys_out, uint64_t* ids_out,
                                      uint64_t* links_out, uint64_t capacity);
+/* sd_object_index_apply over host arrays: the same rule, reports and refusals. */
+int sd_cpu_object_index_apply(sd_cpu_object_index* index, const uint64_t* rm_keys, const uint64_t* rm_ids,
+                              uint64_t m_rm, const uint64_t* in_keys, const uint64_t* in_ids, uint64_t m_in,
+                              uint64_t* removed_out, uint64_t capacity, uint64_t* removed, uint64_t* taken);
 int sd_cpu_dedup_owners_indexed(const sd_cpu_object_index* index, const uint64_t* records, uint64_t m,
                                 const uint64_t* rep, uint64_t chunk_size, uint64_t* owner, uint8_t* existing,
                                 uint64_t* new_out, uint64_t* n_new);

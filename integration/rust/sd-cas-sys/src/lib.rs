@@ -186,6 +186,18 @@ extern "C" {
                                      m: u64, links_out: *mut u64) -> c_int;
     pub fn sd_cpu_object_index_export_links(index: *const sd_cpu_object_index, keys_out: *mut u64,
                                             ids_out: *mut u64, links_out: *mut u64, capacity: u64) -> c_int;
+    // apply: the links that went, then the links that came, of an owners-mode index in one call
+    pub fn sd_object_index_apply(ctx: *mut sd_cas_ctx, index: *mut sd_object_index, d_rm_keys: *const u64,
+                                 d_rm_ids: *const u64, m_rm: u64, d_in_keys: *const u64, d_in_ids: *const u64,
+                                 m_in: u64, d_removed_out: *mut u64, capacity: u64, removed: *mut u64,
+                                 taken: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_object_index_apply_hex(ctx: *mut sd_cas_ctx, index: *mut sd_object_index, rm_hex17: *const c_char,
+                                     rm_ids: *const u64, m_rm: u64, in_hex17: *const c_char, in_ids: *const u64,
+                                     m_in: u64, removed: *mut u64, taken: *mut u64) -> c_int;
+    pub fn sd_cpu_object_index_apply(index: *mut sd_cpu_object_index, rm_keys: *const u64, rm_ids: *const u64,
+                                     m_rm: u64, in_keys: *const u64, in_ids: *const u64, m_in: u64,
+                                     removed_out: *mut u64, capacity: u64, removed: *mut u64,
+                                     taken: *mut u64) -> c_int;
     pub fn sd_dedup_owners_indexed(ctx: *mut sd_cas_ctx, index: *const sd_object_index, d_records: *const u64,
                                    m: u64, d_rep: *const u64, chunk_size: u64, d_owner: *mut u64,
                                    d_existing: *mut u8, d_new_out: *mut u64, d_n_new: *mut u64,
@@ -377,7 +389,8 @@ pub fn fingerprints_blocking(data: &[u8], ranges: &[(u64, u64)]) -> Result<Vec<(
 
 // Keeping the Object index true while the library changes.  The invariant:
 // index[c] = the first live Object, in DB order, that owns a file_path with cas_id c.  Remove
-// and insert are two calls; both are exclusive on the index.
+// and insert are two calls, because the DB query sits between them; both are exclusive on the
+// index.  (The owners mode further down has them as one call, OwnersIndex::apply.)
 //
 // The orphan remover's hook (orphan_remover.rs:57-95), after its delete_many of <= 512 ids:
 //
@@ -412,6 +425,64 @@ pub fn fingerprints_blocking(data: &[u8], ranges: &[(u64, u64)]) -> Result<Vec<(
 //     sd_object_index_insert_hex(ctx, index, hex17(&[b]), [o].as_ptr(), 1, &mut taken);
 //     // the orphan remover's hook
 //     sd_object_index_remove_objects(ctx, index, d_ids, ids.len() as u64, std::ptr::null_mut(), 0, &mut removed, stream);
+//
+// The update hook and a burst of watcher events are ONE call with `OwnersIndex::apply` below: the
+// links that went, then the links that came, one rewrite of the index and no state in between.
+
+/// An owners-mode Object index on the process's GPU context.
+pub struct OwnersIndex(*mut sd_object_index);
+unsafe impl Send for OwnersIndex {}
+
+impl OwnersIndex {
+    pub fn new(nparts: i32, part: i32) -> Result<Self, io::Error> {
+        let g = ctx()?;
+        let mut p = std::ptr::null_mut();
+        match unsafe { sd_object_index_create_ex(g.0, nparts, part, SD_OBJECT_INDEX_OWNERS, &mut p) } {
+            SD_OK => Ok(OwnersIndex(p)),
+            _ => Err(io::Error::new(io::ErrorKind::Other, last_error())),
+        }
+    }
+
+    /// sd_object_index_apply_hex: `gone` and `came` are (cas_id as 16 lower-case hex digits,
+    /// Object id) of the file_path links that left and that entered since the last call -- a
+    /// content change A -> B on O is `gone = [(A, O)]`, `came = [(B, O)]`; a deleted file_path has
+    /// an empty `came`; a burst passes its coalesced lists (a link that came and went again
+    /// inside the burst is struck from `came`, not added to `gone`).  Returns (entries that
+    /// left the index, entries that entered it): the net effect, not the two lists' lengths.
+    pub fn apply(&mut self, gone: &[(&str, u64)], came: &[(&str, u64)]) -> Result<(u64, u64), io::Error> {
+        fn hex17(rows: &[(&str, u64)]) -> Result<Vec<u8>, io::Error> {
+            let mut buf = Vec::with_capacity(17 * rows.len());
+            for r in rows {
+                if r.0.len() != 16 {
+                    return Err(io::Error::new(io::ErrorKind::InvalidInput, "a cas_id is not 16 characters"));
+                }
+                buf.extend_from_slice(r.0.as_bytes());
+                buf.push(0);
+            }
+            Ok(buf)
+        }
+        let g = ctx()?;
+        let (rm_hex, in_hex) = (hex17(gone)?, hex17(came)?);
+        let rm_ids: Vec<u64> = gone.iter().map(|r| r.1).collect();
+        let in_ids: Vec<u64> = came.iter().map(|r| r.1).collect();
+        let (mut removed, mut taken) = (0u64, 0u64);
+        let rc = unsafe {
+            sd_object_index_apply_hex(g.0, self.0, rm_hex.as_ptr() as *const c_char, rm_ids.as_ptr(), gone.len() as u64,
+                                      in_hex.as_ptr() as *const c_char, in_ids.as_ptr(), came.len() as u64,
+                                      &mut removed, &mut taken)
+        };
+        match rc {
+            SD_OK => Ok((removed, taken)),
+            _ => Err(io::Error::new(io::ErrorKind::Other, last_error())),
+        }
+    }
+}
+
+impl Drop for OwnersIndex {
+    fn drop(&mut self) {
+        unsafe { sd_object_index_destroy(self.0) }
+    }
+}
 
 /// libsdcas's RCCL communicator for a multi-GPU library scan (one process per GPU).
 /// A member of an in-process group holds a reference to the group, so the group is

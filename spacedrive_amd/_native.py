@@ -169,6 +169,9 @@ SIGNATURES = [
     ("sd_cpu_object_index_flags", I32, [P, ctypes.POINTER(I32)]),
     ("sd_cpu_object_index_links", I32, [P, P, P, U64, P]),
     ("sd_cpu_object_index_export_links", I32, [P, P, P, P, U64]),
+    ("sd_object_index_apply", I32, [P, P, P, P, U64, P, P, U64, P, U64, PU64, PU64, P]),
+    ("sd_object_index_apply_hex", I32, [P, P, P, P, U64, P, P, U64, PU64, PU64]),
+    ("sd_cpu_object_index_apply", I32, [P, P, P, U64, P, P, U64, P, U64, PU64, PU64]),
 ]
 SD_OBJECT_INDEX_OWNERS = 1
 

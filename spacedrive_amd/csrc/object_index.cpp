@@ -3,7 +3,8 @@
 // through the DB (core/src/object/file_identifier/mod.rs:168-175) before it links each file
 // to the first such Object (:189-225), and the removals that keep it true while Objects are
 // deleted (core/src/object/orphan_remover.rs:57-95) and files change
-// (location/manager/watcher/utils.rs:410-494).  Kernels: object_index.hip; layout, lookup,
+// (location/manager/watcher/utils.rs:410-494), in the owners mode also both at once
+// (sd_object_index_apply).  Kernels: object_index.hip; layout, lookup,
 // the removal rules and the directory / growth policies: object_index.h,
 // object_index_host.cpp (shared with the sd_cpu_object_index_* mirror).
 #include <vector>
@@ -297,6 +298,109 @@ int sd_object_index_remove_hex(sd_cas_ctx* ctx, sd_object_index* index, const ch
     }
     return sd_object_index_remove(ctx, index, dk.as<uint64_t>(), object_ids ? dv.as<uint64_t>() : nullptr, m, nullptr,
                                   0, removed, nullptr);
+    SD_GUARD_END
+}
+
+// Removals, then insertions, of an owners-mode index in one call (object_index.h
+// oi_links_after): both lists aggregated and every entry and pair classed (nothing of the index
+// written); the per-slice counts of leaving entries and entering pairs in one copy and one
+// sync; `capacity` checked; then either the links in place (nothing leaves or enters) or ONE
+// merge-compaction into the other buffer triple, the swap and the directory.
+int sd_object_index_apply(sd_cas_ctx* ctx, sd_object_index* index, const uint64_t* d_rm_keys, const uint64_t* d_rm_ids,
+                          uint64_t m_rm, const uint64_t* d_in_keys, const uint64_t* d_in_ids, uint64_t m_in,
+                          uint64_t* d_removed_out, uint64_t capacity, uint64_t* removed, uint64_t* taken,
+                          void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index || (m_rm && !d_rm_keys) || (m_in && (!d_in_keys || !d_in_ids)))
+        throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (removed) *removed = 0;
+    if (taken) *taken = 0;
+    sd_object_index* x = index;
+    if (!x->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    if (m_rm && !d_rm_ids)
+        throw sd_failure(SD_ERR_INVALID, "apply takes links of (key, id) pairs; every owner of a key: sd_object_index_remove");
+    if (x->n == 0) m_rm = 0;  // nothing to take from
+    if (m_rm == 0 && m_in == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    x->scratch.ensure(sdk::index_apply_scratch(x->n, m_rm, m_in));
+    HIP_CHECK(sdk::index_apply_flag(x->view(), x->nparts, x->part, d_rm_keys, d_rm_ids, m_rm, d_in_keys, d_in_ids, m_in,
+                                    x->scratch.p, x->counts.as<uint64_t>(), s));
+    uint32_t slots_out = 0, slots_in = 0;
+    sdk::index_apply_slots(x->n, m_in, &slots_out, &slots_in);
+    x->host.ensure(2 * sdk::OI_COUNT_SLOTS * sizeof(uint64_t));
+    HIP_CHECK(hipMemcpyAsync(x->host.p, sdk::index_apply_counts(x->scratch.p, x->n),
+                             (slots_out + slots_in) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const uint64_t* c = reinterpret_cast<const uint64_t*>(x->host.p);
+    uint64_t r_out = 0, r_in = 0;
+    for (uint32_t k = 0; k < slots_out; k++) r_out += c[k];
+    for (uint32_t k = 0; k < slots_in; k++) r_in += c[slots_out + k];
+    if (r_out > x->n || r_in > m_in) throw sd_failure(SD_ERR_INTERNAL, "apply: more leaving or entering than there are");
+    if (removed) *removed = r_out;
+    if (d_removed_out && capacity < r_out)
+        throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of removed entries");
+    if (taken) *taken = r_in;
+    if (r_out == 0 && r_in == 0) {  // keys, values and directory stand
+        HIP_CHECK(sdk::index_apply_in_place(x->view(), x->scratch.p, m_rm, m_in, x->links[x->cur].as<uint64_t>(), s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        return SD_OK;
+    }
+    const uint64_t n_new = x->n - r_out + r_in;
+    const uint64_t cap = oi_grow_capacity(n_new, x->cap);
+    const int to = 1 - x->cur;
+    x->keys[to].ensure(cap * sizeof(uint64_t));
+    x->vals[to].ensure(cap * sizeof(uint64_t));
+    x->links[to].ensure(cap * sizeof(uint64_t));
+    HIP_CHECK(sdk::index_apply_merge(x->view(), x->scratch.p, m_rm, m_in, r_in, x->keys[to].as<uint64_t>(),
+                                     x->vals[to].as<uint64_t>(), x->links[to].as<uint64_t>(), d_removed_out, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // the merge read the old buffers and the old directory
+    x->keys[x->cur].ensure(cap * sizeof(uint64_t));
+    x->vals[x->cur].ensure(cap * sizeof(uint64_t));
+    x->links[x->cur].ensure(cap * sizeof(uint64_t));
+    x->cap = cap;
+    x->cur = to;
+    x->n = n_new;
+    x->bits = oi_dir_bits(x->n);  // rebuilt even at an unchanged count: the keys moved
+    x->dir.ensure(((1ull << x->bits) + 1) * sizeof(uint64_t));
+    HIP_CHECK(sdk::index_build_dir(x->keys[to].as<uint64_t>(), x->n, x->bits, x->dir.as<uint64_t>(), s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_object_index_apply_hex(sd_cas_ctx* ctx, sd_object_index* index, const char* rm_hex17, const uint64_t* rm_ids,
+                              uint64_t m_rm, const char* in_hex17, const uint64_t* in_ids, uint64_t m_in,
+                              uint64_t* removed, uint64_t* taken) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index || (m_rm && !rm_hex17) || (m_in && (!in_hex17 || !in_ids)))
+        throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (removed) *removed = 0;
+    if (taken) *taken = 0;
+    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    if (m_rm && !rm_ids)
+        throw sd_failure(SD_ERR_INVALID, "apply takes links of (key, id) pairs; every owner of a key: sd_object_index_remove_hex");
+    if (m_rm == 0 && m_in == 0) return SD_OK;
+    // both lists are parsed before anything is uploaded: a malformed cas_id changes nothing
+    std::vector<uint64_t> host(2 * (m_rm + m_in));
+    uint64_t *rk = host.data(), *rv = rk + m_rm, *ik = rv + m_rm, *iv = ik + m_in;
+    for (uint64_t i = 0; i < m_rm; i++)
+        if (!oi_key_from_hex(rm_hex17 + 17 * i, &rk[i]))
+            throw sd_failure(SD_ERR_INVALID, "removed cas_id " + std::to_string(i) + " is not 16 lower-case hex digits");
+    for (uint64_t i = 0; i < m_in; i++)
+        if (!oi_key_from_hex(in_hex17 + 17 * i, &ik[i]))
+            throw sd_failure(SD_ERR_INVALID, "inserted cas_id " + std::to_string(i) + " is not 16 lower-case hex digits");
+    for (uint64_t i = 0; i < m_rm; i++) rv[i] = rm_ids[i];
+    for (uint64_t i = 0; i < m_in; i++) iv[i] = in_ids[i];
+    ctx->bind();
+    sdi::DevBuf d;
+    d.alloc(host.size() * sizeof(uint64_t));
+    HIP_CHECK(hipMemcpy(d.p, host.data(), host.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    uint64_t* p = d.as<uint64_t>();
+    return sd_object_index_apply(ctx, index, p, p + m_rm, m_rm, p + 2 * m_rm, p + 2 * m_rm + m_in, m_in, nullptr, 0,
+                                 removed, taken, nullptr);
     SD_GUARD_END
 }
 

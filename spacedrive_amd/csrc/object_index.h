@@ -107,6 +107,17 @@ SD_OI_HD bool oi_find_pair(const uint64_t* keys, const uint64_t* vals, const uin
 // for more is not an error); asked 0 = no pair named it
 SD_OI_HD bool oi_links_drop(uint64_t held, uint64_t asked) { return asked != 0 && asked >= held; }
 
+// apply (removals, then insertions, in one call): the links of a pair afterwards.  held = its
+// links before (0 = absent), asked / added = its multiplicity in the removal / insertion list.
+//   kept  = 0 if held == 0 or oi_links_drop(held, asked), else held - asked
+//   after = kept + added
+// after == 0 with held > 0: the entry leaves; after > 0 with held == 0: the pair enters.  A pair
+// whose last link is taken and that gains one in the same call stays, with links = added.
+SD_OI_HD uint64_t oi_links_after(uint64_t held, uint64_t asked, uint64_t added) {
+    const uint64_t kept = (held == 0 || oi_links_drop(held, asked)) ? 0 : held - asked;
+    return kept + added;
+}
+
 // ---- policies (object_index_host.cpp; the device path calls the same functions)
 // directory bits for n entries: ~log2(n / 8), 0 for tiny indexes, at most 24
 uint32_t oi_dir_bits(uint64_t n);

@@ -2,7 +2,9 @@
 // its compacted list of new group heads, insertion (merge by rank + directory rebuild) and
 // removal by key or by Object (flag, two-way ordered compaction, directory rebuild); and the
 // owners mode (one entry per (key, Object id) with a link count): the same passes over (key,
-// id), after a batch of pairs has been aggregated to distinct pairs with multiplicities.
+// id), after a batch of pairs has been aggregated to distinct pairs with multiplicities; and
+// apply, that mode's removal with ids and insert in one flagging pass and one fused
+// merge-compaction.
 //
 // Reference semantics: identifier_job_step joins a step's cas_ids against the Objects the
 // library already has (core/src/object/file_identifier/mod.rs:168-175), links each file to
@@ -473,6 +475,199 @@ __global__ __launch_bounds__(256) void k_index_links(const uint64_t* __restrict_
     }
 }
 
+// ---- apply (owners mode): a removal list and an insertion list in one call, one rewrite.
+// Both lists are aggregated (above).  A pair absent from the index is untouched by the
+// removal list, so the two lists meet only at present entries: mark[n], one byte per entry,
+//   0 = no pair names it, 1 = it leaves (oi_links_after == 0), 2 = it stays and only the
+//   insertion list names it, 3 = it stays and the removal list names it,
+// and the absent pairs of the insertion list enter at their (key, id) rank.  An entry is named
+// by at most one distinct pair of each list, and the pass over the removal list runs after the
+// pass over the insertion list: one writer per byte per pass, the later pass decides.
+
+// the multiplicity of (key, id) in an aggregated batch (d distinct pairs in (key, id) order
+// with the head positions of their runs among m pairs), 0 if it is not there
+__device__ __forceinline__ uint64_t pair_multiplicity(const uint64_t* __restrict__ dk, const uint64_t* __restrict__ dv,
+                                                      const uint64_t* __restrict__ dpos, uint64_t d, uint64_t m,
+                                                      uint64_t key, uint64_t id) {
+    const uint64_t j = oi_lower_bound_pair(dk, dv, 0, d, key, id);
+    if (j >= d || dk[j] != key || dv[j] != id) return 0;
+    return (j + 1 < d ? dpos[j + 1] : m) - dpos[j];
+}
+
+// k_owners_insert_flag for apply: state, rank and multiplicity of every distinct pair of the
+// insertion list, the entering ones counted per slice; a present pair marks its entry 2.  (A
+// kernel of its own, as k_apply_enter_compact is beside k_owners_insert_compact: the insert's
+// kernels would have to branch on their caller, and its timings are to stay as they are.)
+__global__ __launch_bounds__(256) void k_apply_flag_insertions(
+    const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, const uint64_t* __restrict__ dir,
+    uint32_t bits, int nparts, int part, const uint64_t* __restrict__ dk, const uint64_t* __restrict__ dv,
+    const uint64_t* __restrict__ dpos, const uint64_t* __restrict__ d_total, uint64_t m, uint64_t* __restrict__ dcnt,
+    uint64_t* __restrict__ drank, uint8_t* __restrict__ dstate, uint8_t* __restrict__ mark,
+    uint64_t* __restrict__ counts) {
+    const uint64_t d = *d_total;
+    const oi_slice sl = oi_slice_of(d);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+        const uint64_t k = dk[i], v = dv[i];
+        uint64_t at = 0;
+        uint8_t st = 0;
+        if (oi_dest_of(k, nparts) == (uint32_t)part) st = oi_find_pair(keys, vals, dir, bits, k, v, &at) ? 2 : 1;
+        dcnt[i] = (i + 1 < d ? dpos[i + 1] : m) - dpos[i];
+        drank[i] = at;
+        dstate[i] = st;
+        if (st == 2) mark[at] = 2;
+        mine += st == 1;
+    }
+    block_count(mine, counts);
+}
+
+// every distinct pair of the removal list that names an entry decides it: leaving or staying
+__global__ __launch_bounds__(256) void k_apply_mark_removals(
+    const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, const uint64_t* __restrict__ links,
+    const uint64_t* __restrict__ dir, uint32_t bits, const uint64_t* __restrict__ rk, const uint64_t* __restrict__ rv,
+    const uint64_t* __restrict__ rpos, const uint64_t* __restrict__ r_total, uint64_t m_rm,
+    const uint64_t* __restrict__ ik, const uint64_t* __restrict__ iv, const uint64_t* __restrict__ ipos,
+    const uint64_t* __restrict__ i_total, uint64_t m_in, uint8_t* __restrict__ mark) {
+    const uint64_t d = *r_total, di = *i_total;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t k = rk[i], v = rv[i];
+        uint64_t at;
+        if (!oi_find_pair(keys, vals, dir, bits, k, v, &at)) continue;
+        const uint64_t asked = (i + 1 < d ? rpos[i + 1] : m_rm) - rpos[i];
+        const uint64_t added = pair_multiplicity(ik, iv, ipos, di, m_in, k, v);
+        mark[at] = oi_links_after(links[at], asked, added) == 0 ? 1 : 3;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_apply_count_leaving(const uint8_t* __restrict__ mark, uint64_t n,
+                                                             uint64_t* __restrict__ counts) {
+    const oi_slice sl = oi_slice_of(n);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) mine += mark[i] == 1;
+    block_count(mine, counts);
+}
+
+// the entering pairs in order, with their ranks in the index as it stands (non-decreasing)
+__global__ __launch_bounds__(256) void k_apply_enter_compact(
+    const uint64_t* __restrict__ dk, const uint64_t* __restrict__ dv, const uint64_t* __restrict__ dcnt,
+    const uint64_t* __restrict__ drank, const uint8_t* __restrict__ dstate, const uint64_t* __restrict__ d_total,
+    const uint64_t* __restrict__ counts, uint64_t* __restrict__ nk, uint64_t* __restrict__ nv,
+    uint64_t* __restrict__ nl, uint64_t* __restrict__ nrank) {
+    uint64_t run = block_base(counts, nullptr);
+    const oi_slice sl = oi_slice_of(*d_total);
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool flag = i < sl.hi && dstate[i] == 1;
+        const uint64_t slot = tile_slot(flag, run);
+        if (flag) {
+            nk[slot] = dk[i];
+            nv[slot] = dv[i];
+            nl[slot] = dcnt[i];
+            nrank[slot] = drank[i];
+        }
+    }
+}
+
+// Nothing leaves and nothing enters: the links change at their entries.  Lanes [0, d_rm) take
+// the entries the removal list names (mark 3: both lists' multiplicities), lanes [d_rm, d_rm +
+// d_in) those only the insertion list names (mark 2); one writer per entry.
+__global__ __launch_bounds__(256) void k_apply_links_in_place(
+    const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, const uint64_t* __restrict__ dir,
+    uint32_t bits, const uint64_t* __restrict__ rk, const uint64_t* __restrict__ rv,
+    const uint64_t* __restrict__ rpos, const uint64_t* __restrict__ r_total, uint64_t m_rm,
+    const uint64_t* __restrict__ ik, const uint64_t* __restrict__ iv, const uint64_t* __restrict__ ipos,
+    const uint64_t* __restrict__ icnt, const uint64_t* __restrict__ irank, const uint8_t* __restrict__ istate,
+    const uint64_t* __restrict__ i_total, uint64_t m_in, const uint8_t* __restrict__ mark,
+    uint64_t* __restrict__ links) {
+    const uint64_t d = *r_total, di = *i_total;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < d + di; t += (uint64_t)gridDim.x * blockDim.x) {
+        if (t < d) {
+            const uint64_t k = rk[t], v = rv[t];
+            uint64_t at;
+            if (!oi_find_pair(keys, vals, dir, bits, k, v, &at)) continue;
+            const uint64_t asked = (t + 1 < d ? rpos[t + 1] : m_rm) - rpos[t];
+            links[at] = oi_links_after(links[at], asked, pair_multiplicity(ik, iv, ipos, di, m_in, k, v));
+        } else {
+            const uint64_t j = t - d;
+            if (istate[j] == 2 && mark[irank[j]] == 2) links[irank[j]] += icnt[j];
+        }
+    }
+}
+
+// The one rewrite: k_owners_merge and the owners branch of k_remove_compact in one sliced pass
+// over the entries.  With L(i) the leaving entries before position i (block_base + tile_slot)
+// and E(i) the entering pairs ranked at or before i (a search of nrank[r]):
+//   a staying entry i      -> out[i - L(i) + E(i)], with oi_links_after where a pair names it
+//   a leaving entry i      -> row L(i) of rm_out (may be null)
+//   the entering pair j    -> out[q - L(q) + j], q = nrank[j]: the tile that holds position q
+//                             places it (L inside a tile from LDS); the tile that holds the
+//                             last entry also places the pairs ranked at n
+// n == 0: workgroup 0 copies the entering pairs.
+__global__ __launch_bounds__(256) void k_apply_merge(
+    const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, const uint64_t* __restrict__ links,
+    uint64_t n, const uint8_t* __restrict__ mark, const uint64_t* __restrict__ counts,
+    const uint64_t* __restrict__ rk, const uint64_t* __restrict__ rv, const uint64_t* __restrict__ rpos,
+    const uint64_t* __restrict__ r_total, uint64_t m_rm, const uint64_t* __restrict__ ik,
+    const uint64_t* __restrict__ iv, const uint64_t* __restrict__ ipos, const uint64_t* __restrict__ i_total,
+    uint64_t m_in, const uint64_t* __restrict__ nk, const uint64_t* __restrict__ nv, const uint64_t* __restrict__ nl,
+    const uint64_t* __restrict__ nrank, uint64_t r, uint64_t* __restrict__ out_keys, uint64_t* __restrict__ out_vals,
+    uint64_t* __restrict__ out_links, uint64_t* __restrict__ rm_out) {
+    __shared__ uint32_t before[257];  // leaving entries of the tile before each lane; [256] = all
+    if (n == 0) {
+        if (blockIdx.x == 0)
+            for (uint64_t j = threadIdx.x; j < r; j += blockDim.x) {
+                out_keys[j] = nk[j];
+                out_vals[j] = nv[j];
+                out_links[j] = nl[j];
+            }
+        return;
+    }
+    uint64_t run = block_base(counts, nullptr);
+    const oi_slice sl = oi_slice_of(n);
+    const uint64_t d_rm = *r_total, d_in = *i_total;
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool act = i < sl.hi;
+        const uint8_t mk = act ? mark[i] : 0;
+        const bool leave = mk == 1;
+        const uint64_t tile_run = run;
+        const uint64_t slot = tile_slot(leave, run);
+        const uint64_t end = base + blockDim.x < sl.hi ? base + blockDim.x : sl.hi;
+        // the entering pairs this tile places: ranks in [base, end), and n with the last entry
+        const uint64_t e_lo = oi_lower_bound(nrank, 0, r, base);
+        const uint64_t e_hi = end == n ? r : oi_lower_bound(nrank, e_lo, r, end);
+        if (e_hi > e_lo) {  // the same for every lane
+            before[threadIdx.x] = (uint32_t)(slot - tile_run);
+            if (threadIdx.x == 255) before[256] = (uint32_t)(slot - tile_run) + (leave ? 1 : 0);
+            __syncthreads();
+            for (uint64_t j = e_lo + threadIdx.x; j < e_hi; j += blockDim.x) {
+                const uint64_t q = nrank[j], at = q - (tile_run + before[q - base]) + j;
+                out_keys[at] = nk[j];
+                out_vals[at] = nv[j];
+                out_links[at] = nl[j];
+            }
+            __syncthreads();
+        }
+        if (!act) continue;
+        const uint64_t k = keys[i], v = vals[i];
+        if (leave) {
+            if (rm_out) {
+                rm_out[2 * slot] = k;
+                rm_out[2 * slot + 1] = v;
+            }
+            continue;
+        }
+        const uint64_t at = i - slot + (e_hi > e_lo ? oi_lower_bound(nrank, e_lo, e_hi, i + 1) : e_lo);
+        uint64_t l = links[i];
+        if (mk >= 2)
+            l = oi_links_after(l, mk == 3 ? pair_multiplicity(rk, rv, rpos, d_rm, m_rm, k, v) : 0,
+                               pair_multiplicity(ik, iv, ipos, d_in, m_in, k, v));
+        out_keys[at] = k;
+        out_vals[at] = v;
+        out_links[at] = l;
+    }
+}
+
 size_t insert_sort_bytes(uint64_t m, hipStream_t s) {
     size_t b = 0;
     uint64_t* nul = nullptr;
@@ -733,6 +928,94 @@ hipError_t index_owners_remove_compact(const oi_view& x, const void* scratch, co
     hipLaunchKernelGGL(k_remove_compact, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, x.n,
                        reinterpret_cast<const uint8_t*>(scratch), counts, out_keys, out_vals, rm_out, x.links, asked,
                        out_links);
+    return hipGetLastError();
+}
+
+// ---- apply.  scratch: mark[n] (u8); the per-slice counts of leaving entries, then of entering
+// pairs (u64, index_apply_slots of each, side by side for the host's one copy); the removal
+// list's aggregated batch; the insertion list's, as an insert's; nrank[m_in] (u64)
+namespace {
+struct apply_scratch {
+    uint8_t* mark;
+    uint64_t *leaving, *entering, *nrank;
+    pair_batch rm, in;
+};
+
+apply_scratch apply_scratch_at(void* base, uint64_t n, uint64_t m_rm, uint64_t m_in) {
+    apply_scratch a;
+    uint8_t* p = reinterpret_cast<uint8_t*>(base);
+    a.mark = p;
+    p += remove_flag_bytes(n);
+    a.leaving = reinterpret_cast<uint64_t*>(p);
+    a.entering = a.leaving + sliced_grid(n);
+    p += 2 * OI_BLOCKS * sizeof(uint64_t);
+    a.rm = pair_batch_at(p, m_rm, false);
+    p += pair_batch_bytes(std::max<uint64_t>(m_rm, 1), false);
+    a.in = pair_batch_at(p, m_in, true);
+    p += pair_batch_bytes(std::max<uint64_t>(m_in, 1), true);
+    a.nrank = reinterpret_cast<uint64_t*>(p);
+    return a;
+}
+}  // namespace
+
+size_t index_apply_scratch(uint64_t n, uint64_t m_rm, uint64_t m_in) {
+    return remove_flag_bytes(n) + 2 * OI_BLOCKS * sizeof(uint64_t) + pair_batch_bytes(std::max<uint64_t>(m_rm, 1), false) +
+           pair_batch_bytes(std::max<uint64_t>(m_in, 1), true) + round256(m_in * sizeof(uint64_t)) + 256;
+}
+
+void index_apply_slots(uint64_t n, uint64_t m_in, uint32_t* leaving, uint32_t* entering) {
+    *leaving = sliced_grid(n);
+    *entering = sliced_grid(m_in);
+}
+
+const uint64_t* index_apply_counts(const void* scratch, uint64_t n) {
+    return apply_scratch_at(const_cast<void*>(scratch), n, 0, 0).leaving;
+}
+
+hipError_t index_apply_flag(const oi_view& x, int nparts, int part, const uint64_t* rm_keys, const uint64_t* rm_ids,
+                            uint64_t m_rm, const uint64_t* in_keys, const uint64_t* in_ids, uint64_t m_in,
+                            void* scratch, uint64_t* counts, hipStream_t s) {
+    const apply_scratch a = apply_scratch_at(scratch, x.n, m_rm, m_in);
+    hipError_t e = hipSuccess;
+    if (x.n && (e = hipMemsetAsync(a.mark, 0, x.n, s)) != hipSuccess) return e;
+    // an empty list has no distinct pairs; its arrays are never read
+    if (m_rm) e = aggregate_pairs(a.rm, rm_keys, rm_ids, m_rm, counts, s);
+    else e = hipMemsetAsync(a.rm.d_total, 0, sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    if (m_in) e = aggregate_pairs(a.in, in_keys, in_ids, m_in, counts, s);
+    else e = hipMemsetAsync(a.in.d_total, 0, sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_apply_flag_insertions, dim3(sliced_grid(m_in)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits,
+                       nparts, part, a.in.t0, a.in.t1, a.in.dpos, a.in.d_total, m_in, a.in.dcnt, a.in.drank,
+                       a.in.dstate, a.mark, a.entering);
+    if (m_rm)
+        hipLaunchKernelGGL(k_apply_mark_removals, dim3(grid_for(m_rm)), dim3(256), 0, s, x.keys, x.vals, x.links, x.dir,
+                           x.bits, a.rm.t0, a.rm.t1, a.rm.dpos, a.rm.d_total, m_rm, a.in.t0, a.in.t1, a.in.dpos,
+                           a.in.d_total, m_in, a.mark);
+    hipLaunchKernelGGL(k_apply_count_leaving, dim3(sliced_grid(x.n)), dim3(256), 0, s, a.mark, x.n, a.leaving);
+    return hipGetLastError();
+}
+
+hipError_t index_apply_in_place(const oi_view& x, const void* scratch, uint64_t m_rm, uint64_t m_in, uint64_t* links,
+                                hipStream_t s) {
+    const apply_scratch a = apply_scratch_at(const_cast<void*>(scratch), x.n, m_rm, m_in);
+    hipLaunchKernelGGL(k_apply_links_in_place, dim3(grid_for(m_rm + m_in)), dim3(256), 0, s, x.keys, x.vals, x.dir,
+                       x.bits, a.rm.t0, a.rm.t1, a.rm.dpos, a.rm.d_total, m_rm, a.in.t0, a.in.t1, a.in.dpos, a.in.dcnt,
+                       a.in.drank, a.in.dstate, a.in.d_total, m_in, a.mark, links);
+    return hipGetLastError();
+}
+
+hipError_t index_apply_merge(const oi_view& x, const void* scratch, uint64_t m_rm, uint64_t m_in, uint64_t r_in,
+                             uint64_t* out_keys, uint64_t* out_vals, uint64_t* out_links, uint64_t* rm_out,
+                             hipStream_t s) {
+    const apply_scratch a = apply_scratch_at(const_cast<void*>(scratch), x.n, m_rm, m_in);
+    if (r_in)
+        hipLaunchKernelGGL(k_apply_enter_compact, dim3(sliced_grid(m_in)), dim3(256), 0, s, a.in.t0, a.in.t1, a.in.dcnt,
+                           a.in.drank, a.in.dstate, a.in.d_total, a.entering, a.in.sk, a.in.sv, a.in.nl, a.nrank);
+    hipLaunchKernelGGL(k_apply_merge, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, x.links, x.n, a.mark,
+                       a.leaving, a.rm.t0, a.rm.t1, a.rm.dpos, a.rm.d_total, m_rm, a.in.t0, a.in.t1, a.in.dpos,
+                       a.in.d_total, m_in, a.in.sk, a.in.sv, a.in.nl, a.nrank, r_in, out_keys, out_vals, out_links,
+                       rm_out);
     return hipGetLastError();
 }
 

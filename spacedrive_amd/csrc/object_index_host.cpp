@@ -8,8 +8,9 @@
 // (:189-225); removal as Objects are deleted (core/src/object/orphan_remover.rs:57-95) and
 // files change (location/manager/watcher/utils.rs:410-494).  No HIP: built with g++ under
 // the sanitizers too (object_index_selftest.cpp, object_index_remove_selftest.cpp,
-// object_index_owners_selftest.cpp; `make sanitize-object-index`, `make
-// sanitize-object-index-remove`, `make sanitize-object-index-owners`).  The owners mode
+// object_index_owners_selftest.cpp, object_index_apply_selftest.cpp; `make
+// sanitize-object-index`, `make sanitize-object-index-remove`, `make
+// sanitize-object-index-owners`, `make sanitize-object-index-apply`).  The owners mode
 // (sd_cpu_object_index_create_ex with SD_OBJECT_INDEX_OWNERS) keeps one entry per (key, Object
 // id) with its link count; its rules are those of object_index.h, as the kernels'.
 #include <string.h>
@@ -320,6 +321,73 @@ int sd_cpu_object_index_remove_objects(sd_cpu_object_index* index, const uint64_
     std::vector<uint8_t> flags(x->n);
     for (uint64_t i = 0; i < x->n; i++) flags[i] = oi_id_listed(sorted.data(), m, x->vals[i]) ? 1 : 0;
     finish_remove(x, flags, removed_out, capacity, removed);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+// sd_object_index_apply over host arrays (object_index.cpp): both lists aggregated, asked[] and
+// added[] per entry and the entering pairs with their ranks, the counts against `capacity`
+// before anything is written, then the links in place or one merge into the other buffers.
+int sd_cpu_object_index_apply(sd_cpu_object_index* index, const uint64_t* rm_keys, const uint64_t* rm_ids, uint64_t m_rm,
+                              const uint64_t* in_keys, const uint64_t* in_ids, uint64_t m_in, uint64_t* removed_out,
+                              uint64_t capacity, uint64_t* removed, uint64_t* taken) {
+    SD_GUARD_BEGIN
+    if (!index || (m_rm && !rm_keys) || (m_in && (!in_keys || !in_ids)))
+        throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (removed) *removed = 0;
+    if (taken) *taken = 0;
+    sd_cpu_object_index* x = index;
+    if (!x->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    if (m_rm && !rm_ids)
+        throw sd_failure(SD_ERR_INVALID, "apply takes links of (key, id) pairs; every owner of a key: sd_cpu_object_index_remove");
+    if (x->n == 0) m_rm = 0;
+    if (m_rm == 0 && m_in == 0) return SD_OK;
+    const pair_batch rm = aggregate_pairs(rm_keys, rm_ids, m_rm), in = aggregate_pairs(in_keys, in_ids, m_in);
+    std::vector<uint64_t> asked(x->n, 0), added(x->n, 0), nk, nv, nl, nrank;
+    for (size_t j = 0; j < rm.k.size(); j++) {
+        uint64_t at;
+        if (oi_find_pair(x->keys.data(), x->vals.data(), x->dir.data(), x->bits, rm.k[j], rm.v[j], &at))
+            asked[at] = rm.cnt[j];
+    }
+    for (size_t j = 0; j < in.k.size(); j++) {
+        if (oi_dest_of(in.k[j], x->nparts) != (uint32_t)x->part) continue;
+        uint64_t at;
+        if (oi_find_pair(x->keys.data(), x->vals.data(), x->dir.data(), x->bits, in.k[j], in.v[j], &at))
+            added[at] = in.cnt[j];
+        else
+            nk.push_back(in.k[j]), nv.push_back(in.v[j]), nl.push_back(in.cnt[j]), nrank.push_back(at);
+    }
+    uint64_t r_out = 0;
+    for (uint64_t i = 0; i < x->n; i++) r_out += oi_links_after(x->links[i], asked[i], added[i]) == 0;
+    const uint64_t r_in = nk.size();
+    if (removed) *removed = r_out;
+    if (removed_out && capacity < r_out)
+        throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of removed entries");
+    if (taken) *taken = r_in;
+    if (r_out == 0 && r_in == 0) {  // keys, values and directory stand
+        for (uint64_t i = 0; i < x->n; i++) x->links[i] = oi_links_after(x->links[i], asked[i], added[i]);
+        return SD_OK;
+    }
+    grow(x, x->n - r_out + r_in);
+    uint64_t o = 0, gone = 0, j = 0;
+    for (uint64_t i = 0; i <= x->n; i++) {
+        for (; j < r_in && nrank[j] == i; j++, o++)  // the entering pairs ranked at i go before entry i
+            x->keys2[o] = nk[j], x->vals2[o] = nv[j], x->links2[o] = nl[j];
+        if (i == x->n) break;
+        const uint64_t after = oi_links_after(x->links[i], asked[i], added[i]);
+        if (after == 0) {
+            if (removed_out) removed_out[2 * gone] = x->keys[i], removed_out[2 * gone + 1] = x->vals[i];
+            gone++;
+        } else {
+            x->keys2[o] = x->keys[i], x->vals2[o] = x->vals[i], x->links2[o] = after;
+            o++;
+        }
+    }
+    x->keys.swap(x->keys2);
+    x->vals.swap(x->vals2);
+    x->links.swap(x->links2);
+    x->n = o;
+    build_dir(x);
     return SD_OK;
     SD_GUARD_END
 }

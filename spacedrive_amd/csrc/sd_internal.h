@@ -135,6 +135,26 @@ const uint64_t* index_owners_asked(const void* scratch, uint64_t n);
 hipError_t index_owners_remove_compact(const oi_view& x, const void* scratch, const uint64_t* asked,
                                        const uint64_t* counts, uint64_t* out_keys, uint64_t* out_vals,
                                        uint64_t* out_links, uint64_t* rm_out, hipStream_t s);
+// apply: a removal list (with ids) and an insertion list in one call (object_index.h
+// oi_links_after).  First half: both lists aggregated in `scratch`, every entry marked leaving /
+// staying, every distinct pair of the insertion list classed entering / present / another
+// shard's; index_apply_counts(scratch, n) then holds the per-slice counts of leaving entries
+// (`leaving` slots) followed by those of entering pairs (`entering` slots).  Nothing of the
+// index is written.  m_rm + m_in > 0; either may be 0; `counts`: OI_COUNT_SLOTS u64 of scratch.
+size_t index_apply_scratch(uint64_t n, uint64_t m_rm, uint64_t m_in);
+void index_apply_slots(uint64_t n, uint64_t m_in, uint32_t* leaving, uint32_t* entering);
+const uint64_t* index_apply_counts(const void* scratch, uint64_t n);
+hipError_t index_apply_flag(const oi_view& x, int nparts, int part, const uint64_t* rm_keys, const uint64_t* rm_ids,
+                            uint64_t m_rm, const uint64_t* in_keys, const uint64_t* in_ids, uint64_t m_in,
+                            void* scratch, uint64_t* counts, hipStream_t s);
+// nothing leaves or enters: the new link counts at their entries, `links` being the index's own
+hipError_t index_apply_in_place(const oi_view& x, const void* scratch, uint64_t m_rm, uint64_t m_in, uint64_t* links,
+                                hipStream_t s);
+// otherwise: the staying entries (with their new links) and the r_in entering pairs merged into
+// out_* (n - leaving + r_in entries), the leaving entries in order into rm_out (may be null)
+hipError_t index_apply_merge(const oi_view& x, const void* scratch, uint64_t m_rm, uint64_t m_in, uint64_t r_in,
+                             uint64_t* out_keys, uint64_t* out_vals, uint64_t* out_links, uint64_t* rm_out,
+                             hipStream_t s);
 // the link count per (key, id) pair, 0 if absent
 hipError_t index_links(const oi_view& x, const uint64_t* q_keys, const uint64_t* q_ids, uint64_t m, uint64_t* out,
                        hipStream_t s);

@@ -345,6 +345,33 @@ def owners_remove_objects_host(keys, vals, links, ids):
     return _owners_drop(keys, vals, links, np.isin(vals, np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)))
 
 
+def owners_apply_host(keys, vals, links, rm_keys, rm_ids, in_keys, in_ids, nparts: int = 1, part: int = 0):
+    """Host mirror of sd_object_index_apply on an owners-mode index: for every pair with `held`
+    links, named `asked` times in the removal list and `added` times in the insertion list (of
+    shard `part`), kept = 0 if held == 0 or 0 < held <= asked else held - asked, and after =
+    kept + added.  Returns (keys, vals, links) of the pairs with after > 0, the pairs with held >
+    0 and after == 0 as uint64 [r, 2] in ascending (key, id) order, and taken = the number of
+    pairs with held == 0 and after > 0."""
+    keys, vals, links = (np.asarray(a, np.uint64) for a in (keys, vals, links))
+    rk, rv, ik, iv = (np.ascontiguousarray(a, dtype=np.uint64).reshape(-1) for a in (rm_keys, rm_ids, in_keys, in_ids))
+    mine = dest_of(ik, nparts) == part
+    ik, iv = ik[mine], iv[mine]
+    ci, cr, cn = _pair_codes((keys, vals), (rk, rv), (ik, iv))
+    u = len(keys) + len(rk) + len(ik)  # more than the largest code
+    held = np.zeros(u, np.uint64)
+    held[ci] = links
+    asked = np.bincount(cr, minlength=u).astype(np.uint64)
+    added = np.bincount(cn, minlength=u).astype(np.uint64)
+    drop = (held == 0) | ((asked != 0) & (asked >= held))
+    after = np.where(drop, np.uint64(0), held - np.minimum(asked, held)) + added
+    pk, pv = np.zeros(u, np.uint64), np.zeros(u, np.uint64)  # the pair of each code
+    for c, k, v in ((ci, keys, vals), (cr, rk, rv), (cn, ik, iv)):
+        pk[c], pv[c] = k, v
+    stay, gone = after > 0, (held > 0) & (after == 0)
+    return (pk[stay], pv[stay], after[stay], np.stack([pk[gone], pv[gone]], axis=1),
+            int(((held == 0) & (after > 0)).sum()))
+
+
 def owners_links_host(keys, vals, links, q_keys, q_ids):
     """Host mirror of sd_object_index_links: the link count per (key, id) pair, 0 if absent."""
     qk = np.ascontiguousarray(q_keys, dtype=np.uint64).reshape(-1)

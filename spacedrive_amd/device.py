@@ -314,6 +314,43 @@ class ObjectIndex:
                                                _ptr(ids) if m and ids is not None else None, m, ctypes.byref(removed)))
         return int(removed.value)
 
+    # -------------------------------------------------------------- apply (owners mode)
+    def apply(self, d_rm_keys: torch.Tensor, d_rm_ids: torch.Tensor, d_in_keys: torch.Tensor, d_in_ids: torch.Tensor,
+              stream=None, d_removed_out: Optional[torch.Tensor] = None, capacity: Optional[int] = None):
+        """sd_object_index_apply: the links of the removal list go, then those of the insertion
+        list come, in one call and one rewrite of the index (owners mode).  -> (removed, taken):
+        the pairs int64 [r, 2] present before and absent after, in ascending (key, id) order, and
+        the number of pairs absent before and present after.  d_removed_out / capacity as remove."""
+        m_rm, m_in = int(d_rm_keys.numel()), int(d_in_keys.numel())
+        for t, m in ((d_rm_keys, m_rm), (d_rm_ids, m_rm), (d_in_keys, m_in), (d_in_ids, m_in)):
+            assert t.numel() == m and t.dtype == torch.int64 and (m == 0 or (t.is_cuda and t.is_contiguous()))
+        st = _stream(stream)
+        taken = ctypes.c_uint64(0)
+        pairs, _ = self._removal(lambda out, cap, removed: lib().sd_object_index_apply(
+            self.ctx.handle, self.handle, _ptr(d_rm_keys) if m_rm else None, _ptr(d_rm_ids) if m_rm else None, m_rm,
+            _ptr(d_in_keys) if m_in else None, _ptr(d_in_ids) if m_in else None, m_in, out, cap, removed,
+            ctypes.byref(taken), st), min(m_rm, len(self)), d_removed_out, capacity)
+        return pairs, int(taken.value)
+
+    def apply_hex(self, rm_cas_ids, rm_object_ids, in_cas_ids, in_object_ids):
+        """apply from the DB's strings -> (entries removed, entries taken)."""
+        bufs, ids = [], []
+        for cas, oid in ((rm_cas_ids, rm_object_ids), (in_cas_ids, in_object_ids)):
+            buf = b"".join(c.encode("ascii") + b"\0" for c in cas)
+            if len(buf) != 17 * len(cas):
+                raise ValueError("a cas_id is not 16 characters")
+            a = np.ascontiguousarray(oid, dtype=np.uint64)
+            assert a.size == len(cas)
+            bufs.append(buf), ids.append(a)
+        m_rm, m_in = len(rm_cas_ids), len(in_cas_ids)
+        removed, taken = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        torch.cuda.current_stream().synchronize()
+        check(lib().sd_object_index_apply_hex(self.ctx.handle, self.handle, bufs[0] if m_rm else None,
+                                              _ptr(ids[0]) if m_rm else None, m_rm, bufs[1] if m_in else None,
+                                              _ptr(ids[1]) if m_in else None, m_in, ctypes.byref(removed),
+                                              ctypes.byref(taken)))
+        return int(removed.value), int(taken.value)
+
     def lookup(self, d_keys: torch.Tensor, d_object_ids: torch.Tensor = None, d_found: torch.Tensor = None,
                m: Optional[int] = None, stream=None):
         """-> (object ids int64 [m], found uint8 [m]) for m keys in any order."""
@@ -436,6 +473,18 @@ class HostObjectIndex:
         v = np.ascontiguousarray(object_ids, dtype=np.uint64)
         return self._removal(lambda out, cap, removed: lib().sd_cpu_object_index_remove_objects(
             self.handle, _ptr(v) if v.size else None, v.size, out, cap, removed), len(self), capacity)
+
+    def apply(self, rm_keys, rm_ids, in_keys, in_ids, capacity: Optional[int] = None):
+        """sd_cpu_object_index_apply -> (removed pairs uint64 [r, 2] in ascending (key, id) order,
+        taken), the net effect of the removal list then the insertion list (owners mode)."""
+        rk, rv, ik, iv = (np.ascontiguousarray(a, dtype=np.uint64) for a in (rm_keys, rm_ids, in_keys, in_ids))
+        assert rk.size == rv.size and ik.size == iv.size
+        taken = ctypes.c_uint64(0)
+        pairs, _ = self._removal(lambda out, cap, removed: lib().sd_cpu_object_index_apply(
+            self.handle, _ptr(rk) if rk.size else None, _ptr(rv) if rk.size else None, rk.size,
+            _ptr(ik) if ik.size else None, _ptr(iv) if ik.size else None, ik.size, out, cap, removed,
+            ctypes.byref(taken)), min(rk.size, len(self)), capacity)
+        return pairs, int(taken.value)
 
     def lookup(self, keys):
         k = np.ascontiguousarray(keys, dtype=np.uint64)
