@@ -506,7 +506,8 @@ int sd_object_index_export(sd_cas_ctx* ctx, const sd_object_index* index, uint64
  * as above; the host creates the new heads' Objects) -> ONE insert of (key, Object id) for
  * EVERY record of the scan, linked and created alike; a file_path (c, O) deleted -> remove of
  * the pair (c, O) with the id given; a file_path changed A -> B on O -> remove (A, O), insert
- * (B, O), or both in one sd_object_index_apply (below); the orphan remover -> sd_object_index_remove_objects(ids).  No DB query for owners.
+ * (B, O), or both in one sd_object_index_apply (below); the orphan remover -> sd_object_index_remove_objects(ids),
+ * or, without its DB scan, sd_object_index_orphans over the Objects of the pairs that left (below).  No DB query for owners.
  * Opting in: sd_object_index_create_ex(ctx, nparts, part, flags, &index) with
  *   SD_OBJECT_INDEX_OWNERS (1); flags 0 is sd_object_index_create.  sd_object_index_flags
  *   (index, &flags) reads the mode back.  An index made without the flag behaves bit for bit
@@ -583,6 +584,50 @@ int sd_object_index_apply(sd_cas_ctx* ctx, sd_object_index* index, const uint64_
 int sd_object_index_apply_hex(sd_cas_ctx* ctx, sd_object_index* index, const char* rm_hex17, const uint64_t* rm_ids,
                               uint64_t m_rm, const char* in_hex17, const uint64_t* in_ids, uint64_t m_in,
                               uint64_t* removed, uint64_t* taken);
+/* THE VIEW BY OBJECT of an owners-mode index: per-Object link totals and orphan detection.  The
+ * orphan remover asks the DB, every minute and after every delete job, which Objects have no
+ * file_path any more: `object().find_many(vec![object::file_paths::none(vec![])]).take(512)` in
+ * a loop (core/src/object/orphan_remover.rs:57-95), a scan of the Object table against
+ * file_path.  In the owners mode the answer is a property of the index: an Object whose pairs
+ * have all left has no entry.  For an Object id o and one index (one shard), ids compared
+ * unsigned:
+ *   entries(o) = the number of entries whose Object id is o
+ *   links(o)   = the sum of their link counts, in u64
+ *   o is unowned in this shard iff entries(o) == 0
+ * Both calls take m ids on the device, in any order, repeats allowed; the id of element j is
+ * d_object_ids[j * id_stride].  id_stride is in u64 units and is 1 or 2 (anything else is
+ * SD_ERR_INVALID): stride 2 reads the id column of (key, id) rows, so a caller passes
+ * d_removed_out + 1 of sd_object_index_apply / _remove / _remove_objects and the candidates never
+ * leave the device.  Any u64 is a legal id.  m == 0 and an empty index are valid: with m == 0
+ * nothing is written and *count = 0; on an empty index every total is 0 and every distinct id an
+ * orphan.  An index without SD_OBJECT_INDEX_OWNERS is SD_ERR_INVALID.
+ * Both only read the index and may run beside sd_object_index_lookup / _links / _export*,
+ * sd_dedup_owners_indexed and sd_cas_dedup_mgpu_indexed (they share no buffer with those); they
+ * are exclusive with insert, remove and apply, as every read is.  Unlike lookups they are NOT
+ * free to run beside each other: they sort the ids and keep their totals in scratch owned by the
+ * index, so ONE call by Object is in flight per index.  sd_object_index_object_links is
+ * asynchronous: the next call by Object on that index goes to the same stream or waits for it;
+ * nothing checks this.
+ * Neither is collective: on a sharded index each rank answers for its shard; the host adds the
+ * links and entries rows across ranks, and an id is an orphan iff every shard lists it.
+ * The limit: the index knows only links that have a cas_id.  An empty file has no cas_id
+ * (file_identifier/mod.rs:80-88) and still gets an Object (mod.rs:233-333), so the host keeps,
+ * per Object, the count of its file_paths without a cas_id and deletes an Object iff the index
+ * lists it as an orphan AND that count is zero.
+ * sd_object_index_object_links (orphan_remover.rs:57-95): d_links_out[j] = links(id j),
+ *   d_entries_out[j] = entries(id j); either output may be NULL.  Asynchronous on `stream`. */
+int sd_object_index_object_links(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_object_ids,
+                                 uint64_t id_stride, uint64_t m, uint64_t* d_links_out, uint64_t* d_entries_out,
+                                 void* stream);
+/* sd_object_index_orphans (orphan_remover.rs:57-95): the DISTINCT listed ids that have no entry
+ *   in this index, ascending (unsigned), into d_orphans_out (device, may be NULL; `capacity`
+ *   u64); *count (host, may be NULL) = how many.  If d_orphans_out is given and `capacity` is
+ *   smaller than the count: SD_ERR_CAPACITY with *count = the requirement and nothing written to
+ *   d_orphans_out (the convention of d_removed_out).  Nothing past the first *count elements is
+ *   written.  Runs on `stream` and syncs it. */
+int sd_object_index_orphans(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_object_ids,
+                            uint64_t id_stride, uint64_t m, uint64_t* d_orphans_out, uint64_t capacity,
+                            uint64_t* count, void* stream);
 /* sd_dedup_owners against the Objects the library already has (mod.rs:168-225, then
  * :229-333 for the rest), per grouped record i:
  *   d_owner[i] = index[cas_id], d_existing[i] = 1     if the index has the record's cas_id;
@@ -627,6 +672,12 @@ int sd_cpu_object_index_export_links(const sd_cpu_object_index* index, uint64_t*
 int sd_cpu_object_index_apply(sd_cpu_object_index* index, const uint64_t* rm_keys, const uint64_t* rm_ids,
                               uint64_t m_rm, const uint64_t* in_keys, const uint64_t* in_ids, uint64_t m_in,
                               uint64_t* removed_out, uint64_t capacity, uint64_t* removed, uint64_t* taken);
+/* sd_object_index_object_links / _orphans over host arrays (orphan_remover.rs:57-95): the same
+ * rule, strides, reports and refusals. */
+int sd_cpu_object_index_object_links(const sd_cpu_object_index* index, const uint64_t* object_ids,
+                                     uint64_t id_stride, uint64_t m, uint64_t* links_out, uint64_t* entries_out);
+int sd_cpu_object_index_orphans(const sd_cpu_object_index* index, const uint64_t* object_ids, uint64_t id_stride,
+                                uint64_t m, uint64_t* orphans_out, uint64_t capacity, uint64_t* count);
 int sd_cpu_dedup_owners_indexed(const sd_cpu_object_index* index, const uint64_t* records, uint64_t m,
                                 const uint64_t* rep, uint64_t chunk_size, uint64_t* owner, uint8_t* existing,
                                 uint64_t* new_out, uint64_t* n_new);

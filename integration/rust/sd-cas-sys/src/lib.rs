@@ -198,6 +198,24 @@ extern "C" {
                                      m_rm: u64, in_keys: *const u64, in_ids: *const u64, m_in: u64,
                                      removed_out: *mut u64, capacity: u64, removed: *mut u64,
                                      taken: *mut u64) -> c_int;
+    // the view by Object of an owners-mode index: per-Object link totals and the orphans among
+    // listed ids, without the DB scan of orphan_remover.rs:57-95
+    pub fn sd_object_index_object_links(ctx: *mut sd_cas_ctx, index: *const sd_object_index,
+                                        d_object_ids: *const u64, id_stride: u64, m: u64, d_links_out: *mut u64,
+                                        d_entries_out: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_object_index_orphans(ctx: *mut sd_cas_ctx, index: *const sd_object_index, d_object_ids: *const u64,
+                                   id_stride: u64, m: u64, d_orphans_out: *mut u64, capacity: u64, count: *mut u64,
+                                   stream: *mut c_void) -> c_int;
+    pub fn sd_cpu_object_index_object_links(index: *const sd_cpu_object_index, object_ids: *const u64,
+                                            id_stride: u64, m: u64, links_out: *mut u64,
+                                            entries_out: *mut u64) -> c_int;
+    pub fn sd_cpu_object_index_orphans(index: *const sd_cpu_object_index, object_ids: *const u64, id_stride: u64,
+                                       m: u64, orphans_out: *mut u64, capacity: u64, count: *mut u64) -> c_int;
+    // device buffers for callers that hold their lists on the host (sd_memcpy syncs `stream`)
+    pub fn sd_device_malloc(ctx: *mut sd_cas_ctx, bytes: u64, out: *mut *mut c_void) -> c_int;
+    pub fn sd_device_free(ctx: *mut sd_cas_ctx, p: *mut c_void);
+    pub fn sd_memcpy(ctx: *mut sd_cas_ctx, dst: *mut c_void, src: *const c_void, bytes: u64,
+                     stream: *mut c_void) -> c_int;
     pub fn sd_dedup_owners_indexed(ctx: *mut sd_cas_ctx, index: *const sd_object_index, d_records: *const u64,
                                    m: u64, d_rep: *const u64, chunk_size: u64, d_owner: *mut u64,
                                    d_existing: *mut u8, d_new_out: *mut u64, d_n_new: *mut u64,
@@ -423,8 +441,13 @@ pub fn fingerprints_blocking(data: &[u8], ranges: &[(u64, u64)]) -> Result<Vec<(
 //     // the watcher's update hook, A -> B on O
 //     sd_object_index_remove_hex(ctx, index, hex17(&[a]), [o].as_ptr(), 1, &mut removed);
 //     sd_object_index_insert_hex(ctx, index, hex17(&[b]), [o].as_ptr(), 1, &mut taken);
-//     // the orphan remover's hook
+//     // the orphan remover's hook, after a DB scan for the ids (orphan_remover.rs:57-95)
 //     sd_object_index_remove_objects(ctx, index, d_ids, ids.len() as u64, std::ptr::null_mut(), 0, &mut removed, stream);
+//     // ... or without that scan: the candidates are the Object ids of the (key, id) rows the calls
+//     // above reported in d_removed_out, plus the Objects that lost a file_path without a cas_id;
+//     // the orphans among them own nothing in the index and need no remove_objects call
+//     sd_object_index_orphans(ctx, index, d_removed.add(1), 2, removed, d_orphans, capacity, &mut count, stream);
+//     // delete from the DB those whose count of cas-less file_paths (kept by the host) is zero
 //
 // The update hook and a burst of watcher events are ONE call with `OwnersIndex::apply` below: the
 // links that went, then the links that came, one rewrite of the index and no state in between.
@@ -475,6 +498,49 @@ impl OwnersIndex {
             SD_OK => Ok((removed, taken)),
             _ => Err(io::Error::new(io::ErrorKind::Other, last_error())),
         }
+    }
+
+    /// sd_object_index_orphans: the distinct Objects among `candidates` that own nothing in the
+    /// index any more, ascending -- the orphan remover's query (orphan_remover.rs:57-95) without
+    /// its scan of the Object table.  `candidates` are the Object ids of the pairs that left the
+    /// index since the last pass (the reports of apply and remove) and every Object that lost a
+    /// file_path without a cas_id.  The index knows only links that have a cas_id: the caller
+    /// deletes an Object iff it is returned here AND its count of file_paths without a cas_id
+    /// (kept by the host) is zero.  No remove_objects call follows: an orphan
+    /// holds no entry.
+    pub fn orphans(&self, candidates: &[u64]) -> Result<Vec<u64>, io::Error> {
+        let m = candidates.len();
+        if m == 0 {
+            return Ok(Vec::new());
+        }
+        let g = ctx()?;
+        let fail = || io::Error::new(io::ErrorKind::Other, last_error());
+        let bytes = (8 * m) as u64;
+        let mut buf: *mut c_void = std::ptr::null_mut();
+        // ids in the first half, the orphans (m at most) in the second
+        if unsafe { sd_device_malloc(g.0, 2 * bytes, &mut buf) } != SD_OK {
+            return Err(fail());
+        }
+        let d_ids = buf as *mut u64;
+        let d_out = unsafe { d_ids.add(m) };
+        let mut out = vec![0u64; m];
+        let mut count = 0u64;
+        let null = std::ptr::null_mut();
+        let rc = unsafe {
+            let mut rc = sd_memcpy(g.0, buf, candidates.as_ptr() as *const c_void, bytes, null);
+            if rc == SD_OK {
+                rc = sd_object_index_orphans(g.0, self.0, d_ids, 1, m as u64, d_out, m as u64, &mut count, null);
+            }
+            if rc == SD_OK && count > 0 {
+                rc = sd_memcpy(g.0, out.as_mut_ptr() as *mut c_void, d_out as *const c_void, 8 * count, null);
+            }
+            rc
+        };
+        let res = if rc == SD_OK { Ok(()) } else { Err(fail()) };
+        unsafe { sd_device_free(g.0, buf) };
+        res?;
+        out.truncate(count as usize);
+        Ok(out)
     }
 }
 

@@ -4,7 +4,9 @@
 // to the first such Object (:189-225), and the removals that keep it true while Objects are
 // deleted (core/src/object/orphan_remover.rs:57-95) and files change
 // (location/manager/watcher/utils.rs:410-494), in the owners mode also both at once
-// (sd_object_index_apply).  Kernels: object_index.hip; layout, lookup,
+// (sd_object_index_apply), and that mode's read-only view by Object, which answers the orphan
+// remover's own query (sd_object_index_object_links, sd_object_index_orphans).  Kernels:
+// object_index.hip; layout, lookup,
 // the removal rules and the directory / growth policies: object_index.h,
 // object_index_host.cpp (shared with the sd_cpu_object_index_* mirror).
 #include <vector>
@@ -16,6 +18,17 @@ namespace {
 
 void check_index(const sd_cas_ctx* ctx, const sd_object_index* index) {
     if (index->ctx != ctx) throw sd_failure(SD_ERR_INVALID, "the index belongs to another context");
+}
+
+// the checks both reads by Object share; the index comes back writable for its scratch alone:
+// keys, values, links and directory are only read
+sd_object_index* objects_query(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_object_ids,
+                               uint64_t id_stride, uint64_t m) {
+    if (!ctx || !index || (m && !d_object_ids)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    if (id_stride != 1 && id_stride != 2) throw sd_failure(SD_ERR_INVALID, "id_stride is 1 or 2 (u64 units)");
+    return const_cast<sd_object_index*>(index);
 }
 
 // The second half of both removals, after the flagging pass: the per-slice counts give the
@@ -463,6 +476,58 @@ int sd_object_index_export_links(sd_cas_ctx* ctx, const sd_object_index* index, 
     HIP_CHECK(hipMemcpyAsync(d_keys_out, v.keys, v.n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_ids_out, v.vals, v.n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_links_out, v.links, v.n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+// The view by Object of an owners-mode index (object_index.h oi_object_slot / oi_unowned): what
+// the orphan remover asks the DB with `object().find_many(file_paths::none)` per 512 Objects
+// (core/src/object/orphan_remover.rs:57-95).  The entries are only read; the sorted ids and the
+// totals, the per-slice counts and the host's copy of them are the index's own but belong to these
+// two calls alone (not `counts` and `host`, which sd_dedup_owners_indexed and
+// sd_cas_dedup_mgpu_indexed use): they may run beside every other read, and one at a time.
+int sd_object_index_object_links(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_object_ids,
+                                 uint64_t id_stride, uint64_t m, uint64_t* d_links_out, uint64_t* d_entries_out,
+                                 void* stream) {
+    SD_GUARD_BEGIN
+    sd_object_index* x = objects_query(ctx, index, d_object_ids, id_stride, m);
+    if (m == 0 || (!d_links_out && !d_entries_out)) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    x->scratch.ensure(sdk::index_objects_scratch(m));
+    HIP_CHECK(sdk::index_objects_totals(x->view(), d_object_ids, id_stride, m, true, x->scratch.p, s));
+    HIP_CHECK(sdk::index_objects_scatter(x->scratch.p, m, d_links_out, d_entries_out, s));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_object_index_orphans(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_object_ids,
+                            uint64_t id_stride, uint64_t m, uint64_t* d_orphans_out, uint64_t capacity,
+                            uint64_t* count, void* stream) {
+    SD_GUARD_BEGIN
+    sd_object_index* x = objects_query(ctx, index, d_object_ids, id_stride, m);
+    if (count) *count = 0;
+    if (m == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    x->scratch.ensure(sdk::index_objects_scratch(m));
+    HIP_CHECK(sdk::index_objects_totals(x->view(), d_object_ids, id_stride, m, false, x->scratch.p, s));
+    HIP_CHECK(sdk::index_orphans_flag(x->scratch.p, m, s));
+    // the count in one copy and one sync, checked against `capacity` before anything is written
+    const uint32_t slots = sdk::index_objects_slots(m);
+    x->objects_host.ensure(sdk::OI_COUNT_SLOTS * sizeof(uint64_t));
+    HIP_CHECK(hipMemcpyAsync(x->objects_host.p, sdk::index_objects_counts(x->scratch.p, m), slots * sizeof(uint64_t),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const uint64_t* c = reinterpret_cast<const uint64_t*>(x->objects_host.p);
+    uint64_t r = 0;
+    for (uint32_t k = 0; k < slots; k++) r += c[k];
+    if (r > m) throw sd_failure(SD_ERR_INTERNAL, "orphans: more orphans than listed ids");
+    if (count) *count = r;
+    if (!d_orphans_out || r == 0) return SD_OK;
+    if (capacity < r) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of orphans");
+    HIP_CHECK(sdk::index_orphans_compact(x->scratch.p, m, d_orphans_out, s));
+    HIP_CHECK(hipStreamSynchronize(s));
     return SD_OK;
     SD_GUARD_END
 }

@@ -65,6 +65,21 @@ SD_OI_HD bool oi_id_listed(const uint64_t* sorted_ids, uint64_t m, uint64_t id) 
     return at < m && sorted_ids[at] == id;
 }
 
+// By Object, read-only (owners mode; sd_object_index_object_links, sd_object_index_orphans): the
+// orphan remover asks the DB which Objects have no file_path (orphan_remover.rs:57-95).  For an
+// Object id o and one index (one shard), ids compared unsigned:
+//   entries(o) = the number of entries with vals[i] == o
+//   links(o)   = the sum of links[i] over those entries, in u64
+//   o is UNOWNED IN THIS SHARD iff entries(o) == 0
+// Both paths search the listed ids, sorted and made distinct, from the entry side: the slot of
+// vals[i] among them, or false; an entry adds (links[i], 1) to its slot's two totals.
+SD_OI_HD bool oi_object_slot(const uint64_t* distinct_ids, uint64_t d, uint64_t id, uint64_t* slot) {
+    const uint64_t at = oi_lower_bound(distinct_ids, 0, d, id);
+    *slot = at;
+    return at < d && distinct_ids[at] == id;
+}
+SD_OI_HD bool oi_unowned(uint64_t entries) { return entries == 0; }
+
 // ---- owners mode (SD_OBJECT_INDEX_OWNERS), stated once for both paths.  One entry per (key,
 // Object id) pair: keys[n] ascending, no longer strictly; vals[n] strictly ascending (unsigned)
 // within equal keys; links[n] >= 1, the file_paths that link the pair; the same directory over

@@ -4,7 +4,8 @@
 // owners mode (one entry per (key, Object id) with a link count): the same passes over (key,
 // id), after a batch of pairs has been aggregated to distinct pairs with multiplicities; and
 // apply, that mode's removal with ids and insert in one flagging pass and one fused
-// merge-compaction.
+// merge-compaction; and that mode's read-only view by Object: the link totals of listed ids and
+// the orphans among them, in one pass over the entries.
 //
 // Reference semantics: identifier_job_step joins a step's cas_ids against the Objects the
 // library already has (core/src/object/file_identifier/mod.rs:168-175), links each file to
@@ -20,6 +21,8 @@
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 #include "object_index.h"
 #include "sd_internal.h"
@@ -668,6 +671,208 @@ __global__ __launch_bounds__(256) void k_apply_merge(
     }
 }
 
+// ---- by Object, read-only (owners mode): per-Object link totals and the orphans among listed
+// ids (object_index.h oi_object_slot / oi_unowned; orphan_remover.rs:57-95 asks the DB which
+// Objects have no file_path).  The listed ids are sorted with their positions (the strided
+// read is the sort's input iterator), the heads of the runs of equal ids compacted in order to
+// the distinct ids u[d], and every position keeps its run's slot, so repeats share one answer.
+struct strided_ids {
+    const uint64_t* p;
+    uint64_t stride;
+    __host__ __device__ uint64_t operator()(uint64_t j) const { return p[j * stride]; }
+};
+
+__global__ __launch_bounds__(256) void k_ids_heads(const uint64_t* __restrict__ sid, uint64_t m,
+                                                   uint8_t* __restrict__ flags, uint64_t* __restrict__ counts) {
+    const oi_slice sl = oi_slice_of(m);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+        const bool head = i == 0 || sid[i - 1] != sid[i];
+        flags[i] = head ? 1 : 0;
+        mine += head;
+    }
+    block_count(mine, counts);
+}
+
+// u[slot] = the run's id; pslot[position] = the slot of the position's id: tile_slot counts the
+// heads before a lane, which is a head's own slot and one more than a follower's
+__global__ __launch_bounds__(256) void k_ids_compact(const uint64_t* __restrict__ sid, const uint64_t* __restrict__ spos,
+                                                     uint64_t m, const uint8_t* __restrict__ flags,
+                                                     const uint64_t* __restrict__ counts, uint64_t* __restrict__ u,
+                                                     uint64_t* __restrict__ pslot, uint64_t* __restrict__ total) {
+    uint64_t run = block_base(counts, total);
+    const oi_slice sl = oi_slice_of(m);
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool act = i < sl.hi;
+        const bool flag = act && flags[i];
+        const uint64_t slot = tile_slot(flag, run);
+        if (!act) continue;
+        if (flag) u[slot] = sid[i];
+        pslot[spos[i]] = flag ? slot : slot - 1;  // position 0 is a head: a follower has one before it
+    }
+}
+
+// The one pass over the entries, from the entry side: vals[i] (8 B per entry, coalesced) is
+// searched among the distinct ids -- staged in LDS when the list is at most OI_LDS_IDS ids -- and
+// only a hit reads links[i].  tot[2 * slot] = links, tot[2 * slot + 1] = entries, zeroed before.
+// SUMS: a lane keeps the totals of the slot it hit last in registers (one Object owning a large
+// share of the entries adds up there, not at one address); lanes that meet another slot first
+// add what they hold combined by equal slot within the wave (wave_flush).  With the ids in LDS
+// those adds go to per-slot totals of the workgroup in LDS (16 KB), which leave for global
+// memory once, at the end of the slice: one pair of global adds per workgroup and slot, however
+// many heavy Objects alternate along the entries.  Without (more than OI_LDS_IDS ids) they go to
+// global memory, and what the lanes hold at the end of the slice is combined by equal slot
+// across the workgroup (two rounds: the slots most lanes hold; the rest add alone).  Integer
+// sums: any order is exact.
+// !SUMS (orphans): a hit stores 1 at tot[2 * slot + 1]; every writer writes the same value.
+constexpr uint32_t OI_LDS_IDS = 1024;
+
+__device__ __forceinline__ void add_totals(uint64_t* __restrict__ tot, uint64_t slot, uint64_t links, uint64_t entries) {
+    atomicAdd(reinterpret_cast<unsigned long long*>(tot + 2 * slot), (unsigned long long)links);
+    atomicAdd(reinterpret_cast<unsigned long long*>(tot + 2 * slot + 1), (unsigned long long)entries);
+}
+
+// The lanes of one wave with `pend` add (sum, cnt) to their slot `cur` and clear them: twice the
+// lanes that hold the slot of the first pending lane add as one (a shuffle reduction, one lane
+// adds), the rest add alone.  `tot` is global memory or the workgroup's table in LDS.  Called
+// by every lane of the wave.
+__device__ __forceinline__ void wave_flush(uint64_t* __restrict__ tot, bool pend, uint64_t cur, uint64_t& sum,
+                                           uint64_t& cnt) {
+    const uint32_t lane = threadIdx.x & 63;
+    for (int round = 0; round < 2; round++) {
+        const uint64_t bal = __ballot(pend);
+        if (!bal) return;  // the same for every lane
+        const int leader = __ffsll((unsigned long long)bal) - 1;
+        const uint64_t chosen = __shfl(cur, leader);
+        const bool same = pend && cur == chosen;
+        uint64_t l = same ? sum : 0, e = same ? cnt : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            l += __shfl_xor(l, o);
+            e += __shfl_xor(e, o);
+        }
+        if (lane == (uint32_t)leader) add_totals(tot, chosen, l, e);
+        if (same) sum = cnt = 0;
+        pend = pend && !same;
+    }
+    if (pend) {
+        add_totals(tot, cur, sum, cnt);
+        sum = cnt = 0;
+    }
+}
+
+template <bool LDS, bool SUMS>
+__global__ __launch_bounds__(256) void k_object_totals(const uint64_t* __restrict__ vals,
+                                                       const uint64_t* __restrict__ links, uint64_t n,
+                                                       const uint64_t* __restrict__ u,
+                                                       const uint64_t* __restrict__ d_total,
+                                                       uint64_t* __restrict__ tot) {
+    __shared__ uint64_t su[LDS ? OI_LDS_IDS : 1];
+    __shared__ uint64_t lt[LDS && SUMS ? 2 * OI_LDS_IDS : 1];  // the workgroup's totals per slot
+    __shared__ uint64_t pick, wl[4], we[4];
+    const uint64_t d = *d_total;  // <= the listed count, which chose LDS
+    if (LDS) {
+        for (uint64_t j = threadIdx.x; j < d && j < OI_LDS_IDS; j += blockDim.x) {
+            su[j] = u[j];
+            if (SUMS) lt[2 * j] = lt[2 * j + 1] = 0;
+        }
+        __syncthreads();
+    }
+    const uint64_t* ids = LDS ? su : u;
+    uint64_t* acc = LDS && SUMS ? lt : tot;  // where a lane that changes slots adds what it holds
+    const oi_slice sl = oi_slice_of(n);
+    bool have = false;
+    uint64_t cur = 0, sum = 0, cnt = 0;
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {  // whole tiles: the same trips for every lane
+        const uint64_t i = base + threadIdx.x;
+        uint64_t slot = 0;
+        const bool hit = i < sl.hi && oi_object_slot(ids, d, vals[i], &slot);
+        if (!SUMS) {
+            if (hit) tot[2 * slot + 1] = 1;
+            continue;
+        }
+        // lanes that meet another slot give up what they hold, combined by equal slot in the wave
+        const bool change = hit && have && slot != cur;
+        if (__any(change)) wave_flush(acc, change, cur, sum, cnt);
+        if (hit) {
+            have = true;
+            cur = slot;
+            sum += links[i];
+            cnt++;
+        }
+    }
+    if (!SUMS) return;
+    if (LDS) {  // the workgroup's totals leave LDS once: one pair of global adds per slot it hit
+        wave_flush(acc, have, cur, sum, cnt);
+        __syncthreads();
+        for (uint64_t j = threadIdx.x; j < d && j < OI_LDS_IDS; j += blockDim.x)
+            if (lt[2 * j + 1]) add_totals(tot, j, lt[2 * j], lt[2 * j + 1]);
+        return;
+    }
+    bool pend = have;
+    for (int round = 0; round < 2; round++) {
+        if (!__syncthreads_or(pend)) break;  // the same for every lane
+        if (pend) pick = cur;                // any one of the pending slots
+        __syncthreads();
+        const uint64_t chosen = pick;
+        const bool same = pend && cur == chosen;
+        uint64_t l = same ? sum : 0, e = same ? cnt : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            l += __shfl_xor(l, o);
+            e += __shfl_xor(e, o);
+        }
+        if ((threadIdx.x & 63) == 0) wl[threadIdx.x >> 6] = l, we[threadIdx.x >> 6] = e;
+        __syncthreads();
+        if (threadIdx.x == 0) add_totals(tot, chosen, wl[0] + wl[1] + wl[2] + wl[3], we[0] + we[1] + we[2] + we[3]);
+        pend = pend && !same;
+    }
+    if (pend) add_totals(tot, cur, sum, cnt);
+}
+
+// the totals of every position's slot, to the caller's order (either output may be null)
+__global__ __launch_bounds__(256) void k_object_scatter(const uint64_t* __restrict__ pslot,
+                                                        const uint64_t* __restrict__ tot, uint64_t m,
+                                                        uint64_t* __restrict__ links_out,
+                                                        uint64_t* __restrict__ entries_out) {
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t slot = pslot[j];
+        if (links_out) links_out[j] = tot[2 * slot];
+        if (entries_out) entries_out[j] = tot[2 * slot + 1];
+    }
+}
+
+// orphans: the distinct ids without an entry, flagged and counted per slice, then compacted in
+// order (ascending, as u is) once the host has checked the count against the capacity
+__global__ __launch_bounds__(256) void k_orphans_flag(const uint64_t* __restrict__ tot,
+                                                      const uint64_t* __restrict__ d_total,
+                                                      uint8_t* __restrict__ flags, uint64_t* __restrict__ counts) {
+    const oi_slice sl = oi_slice_of(*d_total);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+        const bool orphan = oi_unowned(tot[2 * i + 1]);
+        flags[i] = orphan ? 1 : 0;
+        mine += orphan;
+    }
+    block_count(mine, counts);
+}
+
+__global__ __launch_bounds__(256) void k_orphans_compact(const uint64_t* __restrict__ u,
+                                                         const uint64_t* __restrict__ d_total,
+                                                         const uint8_t* __restrict__ flags,
+                                                         const uint64_t* __restrict__ counts,
+                                                         uint64_t* __restrict__ out) {
+    uint64_t run = block_base(counts, nullptr);
+    const oi_slice sl = oi_slice_of(*d_total);
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool flag = i < sl.hi && flags[i];
+        const uint64_t slot = tile_slot(flag, run);
+        if (flag) out[slot] = u[i];
+    }
+}
+
 size_t insert_sort_bytes(uint64_t m, hipStream_t s) {
     size_t b = 0;
     uint64_t* nul = nullptr;
@@ -1024,6 +1229,103 @@ hipError_t index_links(const oi_view& x, const uint64_t* q_keys, const uint64_t*
     if (m == 0) return hipSuccess;
     hipLaunchKernelGGL(k_index_links, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.links, x.dir, x.bits, q_keys,
                        q_ids, m, out);
+    return hipGetLastError();
+}
+
+// ---- by Object, read-only.  scratch: sid[m], spos[m], u[m], pslot[m], tot[2 * m] (u64),
+// flags[m] (u8), the distinct count (u64), the per-slice counts of the two ordered compactions
+// (OI_BLOCKS u64: the calls by Object share no count slot with sd_dedup_owners_indexed, which
+// uses the index's own), then the radix sort's temporary storage
+namespace {
+struct objects_scratch {
+    uint64_t *sid, *spos, *u, *pslot, *tot, *d_total, *counts;
+    uint8_t* flags;
+    void* tmp;
+};
+
+// the sort of (listed id, position): the ids read through their stride, the positions counted
+hipError_t objects_sort(void* tmp, size_t& bytes, const uint64_t* ids, uint64_t stride, uint64_t m, uint64_t* sid,
+                        uint64_t* spos, hipStream_t s) {
+    const rocprim::counting_iterator<uint64_t> pos(0);
+    return rocprim::radix_sort_pairs(tmp, bytes, rocprim::make_transform_iterator(pos, strided_ids{ids, stride}), sid,
+                                     pos, spos, (size_t)m, 0, 64, s);
+}
+
+size_t objects_sort_bytes(uint64_t m) {
+    size_t b = 0;
+    uint64_t* nul = nullptr;
+    if (objects_sort(nullptr, b, nul, 1, m, nul, nul, nullptr) != hipSuccess) return 0;
+    return round256(b);
+}
+
+objects_scratch objects_scratch_at(void* base, uint64_t m) {
+    objects_scratch q;
+    uint64_t* p = reinterpret_cast<uint64_t*>(base);
+    q.sid = p, q.spos = p + m, q.u = p + 2 * m, q.pslot = p + 3 * m, q.tot = p + 4 * m;
+    uint8_t* b = reinterpret_cast<uint8_t*>(base) + round256(6 * m * sizeof(uint64_t));
+    q.flags = b;
+    b += round256(m);
+    q.d_total = reinterpret_cast<uint64_t*>(b);
+    q.counts = reinterpret_cast<uint64_t*>(b + 256);
+    q.tmp = b + 256 + OI_BLOCKS * sizeof(uint64_t);
+    return q;
+}
+}  // namespace
+
+size_t index_objects_scratch(uint64_t m) {
+    return round256(6 * m * sizeof(uint64_t)) + round256(m) + 256 + OI_BLOCKS * sizeof(uint64_t) + objects_sort_bytes(m) + 256;
+}
+
+uint32_t index_objects_slots(uint64_t m) { return sliced_grid(m); }
+
+// m > 0.  After it tot[2 * slot], tot[2 * slot + 1] hold links and entries of the distinct ids
+// (sums), or 0 and entries != 0 (!sums: what the orphans need).  Nothing of the index is written.
+hipError_t index_objects_totals(const oi_view& x, const uint64_t* ids, uint64_t stride, uint64_t m, bool sums,
+                                void* scratch, hipStream_t s) {
+    const objects_scratch q = objects_scratch_at(scratch, m);
+    size_t tb = objects_sort_bytes(m);
+    hipError_t e = objects_sort(q.tmp, tb, ids, stride, m, q.sid, q.spos, s);
+    if (e != hipSuccess) return e;
+    if ((e = hipMemsetAsync(q.tot, 0, 2 * m * sizeof(uint64_t), s)) != hipSuccess) return e;
+    const uint32_t g = sliced_grid(m);
+    hipLaunchKernelGGL(k_ids_heads, dim3(g), dim3(256), 0, s, q.sid, m, q.flags, q.counts);
+    hipLaunchKernelGGL(k_ids_compact, dim3(g), dim3(256), 0, s, q.sid, q.spos, m, q.flags, q.counts, q.u, q.pslot,
+                       q.d_total);
+    if (x.n) {
+        const dim3 ge(sliced_grid(x.n)), b(256);
+        if (m <= OI_LDS_IDS) {
+            if (sums) hipLaunchKernelGGL((k_object_totals<true, true>), ge, b, 0, s, x.vals, x.links, x.n, q.u, q.d_total, q.tot);
+            else hipLaunchKernelGGL((k_object_totals<true, false>), ge, b, 0, s, x.vals, x.links, x.n, q.u, q.d_total, q.tot);
+        } else {
+            if (sums) hipLaunchKernelGGL((k_object_totals<false, true>), ge, b, 0, s, x.vals, x.links, x.n, q.u, q.d_total, q.tot);
+            else hipLaunchKernelGGL((k_object_totals<false, false>), ge, b, 0, s, x.vals, x.links, x.n, q.u, q.d_total, q.tot);
+        }
+    }
+    return hipGetLastError();
+}
+
+hipError_t index_objects_scatter(const void* scratch, uint64_t m, uint64_t* links_out, uint64_t* entries_out,
+                                 hipStream_t s) {
+    const objects_scratch q = objects_scratch_at(const_cast<void*>(scratch), m);
+    hipLaunchKernelGGL(k_object_scatter, dim3(grid_for(m)), dim3(256), 0, s, q.pslot, q.tot, m, links_out, entries_out);
+    return hipGetLastError();
+}
+
+// the orphans counted per slice in index_objects_counts(scratch, m)[0 .. index_objects_slots(m)),
+// then compacted
+const uint64_t* index_objects_counts(const void* scratch, uint64_t m) {
+    return objects_scratch_at(const_cast<void*>(scratch), m).counts;
+}
+
+hipError_t index_orphans_flag(const void* scratch, uint64_t m, hipStream_t s) {
+    const objects_scratch q = objects_scratch_at(const_cast<void*>(scratch), m);
+    hipLaunchKernelGGL(k_orphans_flag, dim3(sliced_grid(m)), dim3(256), 0, s, q.tot, q.d_total, q.flags, q.counts);
+    return hipGetLastError();
+}
+
+hipError_t index_orphans_compact(const void* scratch, uint64_t m, uint64_t* out, hipStream_t s) {
+    const objects_scratch q = objects_scratch_at(const_cast<void*>(scratch), m);
+    hipLaunchKernelGGL(k_orphans_compact, dim3(sliced_grid(m)), dim3(256), 0, s, q.u, q.d_total, q.flags, q.counts, out);
     return hipGetLastError();
 }
 

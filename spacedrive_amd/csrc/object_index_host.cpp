@@ -8,9 +8,10 @@
 // (:189-225); removal as Objects are deleted (core/src/object/orphan_remover.rs:57-95) and
 // files change (location/manager/watcher/utils.rs:410-494).  No HIP: built with g++ under
 // the sanitizers too (object_index_selftest.cpp, object_index_remove_selftest.cpp,
-// object_index_owners_selftest.cpp, object_index_apply_selftest.cpp; `make
-// sanitize-object-index`, `make sanitize-object-index-remove`, `make
-// sanitize-object-index-owners`, `make sanitize-object-index-apply`).  The owners mode
+// object_index_owners_selftest.cpp, object_index_apply_selftest.cpp,
+// object_index_orphans_selftest.cpp; `make sanitize-object-index`, `make
+// sanitize-object-index-remove`, `make sanitize-object-index-owners`, `make
+// sanitize-object-index-apply`, `make sanitize-object-index-orphans`).  The owners mode
 // (sd_cpu_object_index_create_ex with SD_OBJECT_INDEX_OWNERS) keeps one entry per (key, Object
 // id) with its link count; its rules are those of object_index.h, as the kernels'.
 #include <string.h>
@@ -180,6 +181,29 @@ void insert_owners(sd_cpu_object_index* x, const uint64_t* keys, const uint64_t*
     build_dir(x);
 }
 
+
+// The view by Object of object_index.cpp over host arrays (orphan_remover.rs:57-95): the listed
+// ids sorted and made distinct, one pass over the entries from the entry side (oi_object_slot),
+// the two totals per distinct id.
+struct object_totals {
+    std::vector<uint64_t> u, links, entries;
+};
+object_totals totals_by_object(const sd_cpu_object_index* x, const uint64_t* object_ids, uint64_t id_stride, uint64_t m) {
+    if (!x || (m && !object_ids)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (!x->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    if (id_stride != 1 && id_stride != 2) throw sd_failure(SD_ERR_INVALID, "id_stride is 1 or 2 (u64 units)");
+    object_totals t;
+    t.u.resize(m);
+    for (uint64_t j = 0; j < m; j++) t.u[j] = object_ids[j * id_stride];
+    std::sort(t.u.begin(), t.u.end());
+    t.u.erase(std::unique(t.u.begin(), t.u.end()), t.u.end());
+    t.links.assign(t.u.size(), 0), t.entries.assign(t.u.size(), 0);
+    for (uint64_t i = 0; i < x->n; i++) {
+        uint64_t slot;
+        if (oi_object_slot(t.u.data(), t.u.size(), x->vals[i], &slot)) t.links[slot] += x->links[i], t.entries[slot]++;
+    }
+    return t;
+}
 }  // namespace
 
 extern "C" {
@@ -447,6 +471,37 @@ int sd_cpu_object_index_export_links(const sd_cpu_object_index* index, uint64_t*
         memcpy(ids_out, index->vals.data(), index->n * sizeof(uint64_t));
         memcpy(links_out, index->links.data(), index->n * sizeof(uint64_t));
     }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_object_index_object_links(const sd_cpu_object_index* index, const uint64_t* object_ids, uint64_t id_stride,
+                                     uint64_t m, uint64_t* links_out, uint64_t* entries_out) {
+    SD_GUARD_BEGIN
+    const object_totals t = totals_by_object(index, object_ids, id_stride, m);
+    for (uint64_t j = 0; j < m; j++) {
+        uint64_t slot = 0;
+        (void)oi_object_slot(t.u.data(), t.u.size(), object_ids[j * id_stride], &slot);  // every listed id has one
+        if (links_out) links_out[j] = t.links[slot];
+        if (entries_out) entries_out[j] = t.entries[slot];
+    }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_object_index_orphans(const sd_cpu_object_index* index, const uint64_t* object_ids, uint64_t id_stride,
+                                uint64_t m, uint64_t* orphans_out, uint64_t capacity, uint64_t* count) {
+    SD_GUARD_BEGIN
+    if (count) *count = 0;
+    const object_totals t = totals_by_object(index, object_ids, id_stride, m);
+    uint64_t r = 0;
+    for (size_t s = 0; s < t.u.size(); s++) r += oi_unowned(t.entries[s]);
+    if (count) *count = r;
+    if (!orphans_out || r == 0) return SD_OK;
+    if (capacity < r) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of orphans");
+    uint64_t o = 0;
+    for (size_t s = 0; s < t.u.size(); s++)
+        if (oi_unowned(t.entries[s])) orphans_out[o++] = t.u[s];
     return SD_OK;
     SD_GUARD_END
 }

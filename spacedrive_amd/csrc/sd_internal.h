@@ -158,5 +158,22 @@ hipError_t index_apply_merge(const oi_view& x, const void* scratch, uint64_t m_r
 // the link count per (key, id) pair, 0 if absent
 hipError_t index_links(const oi_view& x, const uint64_t* q_keys, const uint64_t* q_ids, uint64_t m, uint64_t* out,
                        hipStream_t s);
+// By Object, read-only (owners mode; object_index.h oi_object_slot): the m listed ids (element j at
+// ids[j * stride]) sorted and made distinct in `scratch` (index_objects_scratch(m) bytes), then
+// one pass over the entries that leaves, per distinct id, its links and entries (`sums`) or only
+// whether it has an entry (the orphans).  m > 0.  The per-slice counts of their ordered
+// compactions live in `scratch` too, not in the index's count slots.
+size_t index_objects_scratch(uint64_t m);
+uint32_t index_objects_slots(uint64_t m);
+hipError_t index_objects_totals(const oi_view& x, const uint64_t* ids, uint64_t stride, uint64_t m, bool sums,
+                                void* scratch, hipStream_t s);
+// the totals to the m listed positions (either output may be null)
+hipError_t index_objects_scatter(const void* scratch, uint64_t m, uint64_t* links_out, uint64_t* entries_out,
+                                 hipStream_t s);
+// the distinct ids without an entry: counted per slice in index_objects_counts(scratch, m)[0 ..
+// index_objects_slots(m)), then written ascending to `out` (as many as the counts add up to)
+const uint64_t* index_objects_counts(const void* scratch, uint64_t m);
+hipError_t index_orphans_flag(const void* scratch, uint64_t m, hipStream_t s);
+hipError_t index_orphans_compact(const void* scratch, uint64_t m, uint64_t* out, hipStream_t s);
 hipError_t index_build_dir(const uint64_t* keys, uint64_t n, uint32_t bits, uint64_t* dir, hipStream_t s);
 }  // namespace sdk

@@ -384,6 +384,55 @@ def owners_links_host(keys, vals, links, q_keys, q_ids):
     return out
 
 
+def owners_object_links_host(vals, links, ids):
+    """Host mirror of sd_object_index_object_links on an owners-mode index given by its Object
+    ids and link counts: per listed id (any order, repeats allowed) the sum of links[i] over the
+    entries with vals[i] == id, in u64, and the number of those entries.  Returns (links,
+    entries) uint64 [m]."""
+    vals, links = np.asarray(vals, np.uint64), np.asarray(links, np.uint64)
+    q = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+    u, inv = np.unique(q, return_inverse=True)
+    tl, te = np.zeros(len(u), np.uint64), np.zeros(len(u), np.uint64)
+    if len(u) and len(vals):
+        at = np.minimum(np.searchsorted(u, vals), len(u) - 1)
+        hit = u[at] == vals
+        np.add.at(tl, at[hit], links[hit])
+        np.add.at(te, at[hit], np.uint64(1))
+    return tl[inv.reshape(-1)], te[inv.reshape(-1)]
+
+
+def owners_orphans_host(vals, ids):
+    """Host mirror of sd_object_index_orphans: the distinct listed ids that no entry names,
+    ascending (unsigned)."""
+    u = np.unique(np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1))
+    return u[~np.isin(u, np.asarray(vals, np.uint64))]
+
+
+def host_u64(a) -> np.ndarray:
+    """a uint64 numpy array, or an int64 tensor carrying u64 bit patterns, as uint64 on the host"""
+    if isinstance(a, np.ndarray):
+        return a.view(np.uint64) if a.dtype == np.int64 else a.astype(np.uint64, copy=False)
+    return a.detach().cpu().numpy().view(np.uint64)
+
+
+def combine_object_links(per_shard):
+    """The shards' answers of object_links for one id list -> the library's: per_shard is a list
+    of (links, entries) arrays, one per rank; the totals add up."""
+    ls = [np.asarray(host_u64(p[0])) for p in per_shard]
+    es = [np.asarray(host_u64(p[1])) for p in per_shard]
+    return np.sum(ls, axis=0, dtype=np.uint64), np.sum(es, axis=0, dtype=np.uint64)
+
+
+def combine_orphans(per_shard):
+    """The shards' orphan lists for one id list -> the library's: an id is an orphan iff every
+    shard lists it.  Ascending (unsigned)."""
+    out = None
+    for p in per_shard:
+        p = np.asarray(host_u64(p))
+        out = p if out is None else np.intersect1d(out, p)
+    return np.zeros(0, np.uint64) if out is None else np.sort(out)
+
+
 def owners_indexed_host(records: np.ndarray, rep: np.ndarray, keys: np.ndarray, vals: np.ndarray,
                         chunk_size: int = 100):
     """Host mirror of sd_dedup_owners_indexed on grouped records (int64 [m, 2] sorted by (key,

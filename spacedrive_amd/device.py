@@ -181,7 +181,9 @@ class ObjectIndex:
     ``owners=True`` (SD_OBJECT_INDEX_OWNERS) keeps one entry per (cas_id, Object) pair with
     the number of file_paths that link them: insert adds a link per pair, remove with ids
     takes one, an entry leaves at zero, and the first owner of a key is its smallest Object
-    id -- the host never asks the DB who else owns a cas_id."""
+    id -- the host never asks the DB who else owns a cas_id.  Its view by Object
+    (``object_links``, ``orphans``; ``apply(..., orphans=True)``) answers the orphan remover's
+    query too: which of these Objects own nothing any more (orphan_remover.rs:57-95)."""
 
     def __init__(self, ctx: Context, nparts: int = 1, part: int = 0, owners: bool = False):
         self.ctx, self.nparts, self.part, self.owners_mode = ctx, nparts, part, bool(owners)
@@ -271,34 +273,38 @@ class ObjectIndex:
         raise RuntimeError("sd_object_index_remove: capacity still short after regrowing")
 
     def remove(self, d_keys: torch.Tensor, d_object_ids: Optional[torch.Tensor] = None, stream=None,
-               d_removed_out: Optional[torch.Tensor] = None, capacity: Optional[int] = None):
+               d_removed_out: Optional[torch.Tensor] = None, capacity: Optional[int] = None, orphans: bool = False):
         """Drop entry (k, v) iff some pair i has d_keys[i] == k and (d_object_ids is None or
         d_object_ids[i] == v).  -> (removed pairs int64 [r, 2] = (key, Object id) in ascending
         key order, r).  With d_removed_out (int64, `capacity` rows of 2) too small the call
-        raises SdCasError (SD_ERR_CAPACITY, ``.needed`` rows) and the index is unchanged."""
+        raises SdCasError (SD_ERR_CAPACITY, ``.needed`` rows) and the index is unchanged.
+        ``orphans=True`` (owners mode) appends the Objects of the removed pairs that now own
+        nothing in this index (_orphans_of)."""
         m = int(d_keys.numel())
         assert d_keys.dtype == torch.int64 and (m == 0 or (d_keys.is_cuda and d_keys.is_contiguous()))
         if d_object_ids is not None:
             assert d_object_ids.numel() == m and d_object_ids.dtype == torch.int64
             assert m == 0 or (d_object_ids.is_cuda and d_object_ids.is_contiguous())
         st = _stream(stream)
-        return self._removal(lambda out, cap, removed: lib().sd_object_index_remove(
+        res = self._removal(lambda out, cap, removed: lib().sd_object_index_remove(
             self.ctx.handle, self.handle, _ptr(d_keys) if m else None,
             _ptr(d_object_ids) if m and d_object_ids is not None else None, m, out, cap, removed, st),
             # owners mode without ids: a key drops all its owners, so the bound is the entries
             # (HostObjectIndex.remove sizes its rows the same way)
             len(self) if self.owners_mode and d_object_ids is None else min(m, len(self)), d_removed_out, capacity)
+        return res + (self._orphans_of(res[0], stream),) if orphans else res
 
     def remove_objects(self, d_object_ids: torch.Tensor, stream=None, d_removed_out: Optional[torch.Tensor] = None,
-                       capacity: Optional[int] = None):
+                       capacity: Optional[int] = None, orphans: bool = False):
         """Drop every entry whose Object id is among d_object_ids (orphan_remover.rs:57-95).
-        -> (removed pairs int64 [r, 2], r), as remove."""
+        -> (removed pairs int64 [r, 2], r), as remove; ``orphans`` as remove."""
         m = int(d_object_ids.numel())
         assert d_object_ids.dtype == torch.int64 and (m == 0 or (d_object_ids.is_cuda and d_object_ids.is_contiguous()))
         st = _stream(stream)
-        return self._removal(lambda out, cap, removed: lib().sd_object_index_remove_objects(
+        res = self._removal(lambda out, cap, removed: lib().sd_object_index_remove_objects(
             self.ctx.handle, self.handle, _ptr(d_object_ids) if m else None, m, out, cap, removed, st),
             min(len(self), max(4 * m, 1024)) if m else 0, d_removed_out, capacity)
+        return res + (self._orphans_of(res[0], stream),) if orphans else res
 
     def remove_hex(self, cas_ids, object_ids=None) -> int:
         """remove from the DB's strings (object_ids None: unconditional); returns the count."""
@@ -316,11 +322,14 @@ class ObjectIndex:
 
     # -------------------------------------------------------------- apply (owners mode)
     def apply(self, d_rm_keys: torch.Tensor, d_rm_ids: torch.Tensor, d_in_keys: torch.Tensor, d_in_ids: torch.Tensor,
-              stream=None, d_removed_out: Optional[torch.Tensor] = None, capacity: Optional[int] = None):
+              stream=None, d_removed_out: Optional[torch.Tensor] = None, capacity: Optional[int] = None,
+              orphans: bool = False):
         """sd_object_index_apply: the links of the removal list go, then those of the insertion
         list come, in one call and one rewrite of the index (owners mode).  -> (removed, taken):
         the pairs int64 [r, 2] present before and absent after, in ascending (key, id) order, and
-        the number of pairs absent before and present after.  d_removed_out / capacity as remove."""
+        the number of pairs absent before and present after.  d_removed_out / capacity as remove.
+        ``orphans=True`` appends the Objects of the removed pairs that now own nothing in this
+        index (_orphans_of): the orphan remover's candidates, found without a DB scan."""
         m_rm, m_in = int(d_rm_keys.numel()), int(d_in_keys.numel())
         for t, m in ((d_rm_keys, m_rm), (d_rm_ids, m_rm), (d_in_keys, m_in), (d_in_ids, m_in)):
             assert t.numel() == m and t.dtype == torch.int64 and (m == 0 or (t.is_cuda and t.is_contiguous()))
@@ -330,7 +339,53 @@ class ObjectIndex:
             self.ctx.handle, self.handle, _ptr(d_rm_keys) if m_rm else None, _ptr(d_rm_ids) if m_rm else None, m_rm,
             _ptr(d_in_keys) if m_in else None, _ptr(d_in_ids) if m_in else None, m_in, out, cap, removed,
             ctypes.byref(taken), st), min(m_rm, len(self)), d_removed_out, capacity)
+        if orphans:
+            return pairs, int(taken.value), self._orphans_of(pairs, stream)
         return pairs, int(taken.value)
+
+    # -------------------------------------------------------------- the view by Object (owners mode)
+    def object_links(self, d_object_ids: torch.Tensor, stream=None, stride: int = 1, m: Optional[int] = None):
+        """sd_object_index_object_links -> (links, entries) int64 [m]: per listed Object id (any
+        order, repeats allowed) the sum of its entries' link counts and the number of its
+        entries in this index.  ``stride`` (1 or 2, in elements): the id of element j is
+        d_object_ids[j * stride], so the id column of (key, id) rows is rows.reshape(-1)[1:]
+        with stride 2 and m = the rows."""
+        m = (int(d_object_ids.numel()) + stride - 1) // max(stride, 1) if m is None else int(m)
+        assert d_object_ids.dtype == torch.int64 and (m == 0 or (d_object_ids.is_cuda and d_object_ids.is_contiguous()))
+        assert m == 0 or stride not in (1, 2) or (m - 1) * stride < d_object_ids.numel()
+        dev = torch.device("cuda", self.ctx.device)
+        links, entries = (torch.empty(max(m, 1), dtype=torch.int64, device=dev) for _ in range(2))
+        check(lib().sd_object_index_object_links(self.ctx.handle, self.handle, _ptr(d_object_ids) if m else None, stride,
+                                                 m, _ptr(links), _ptr(entries), _stream(stream)))
+        return links[:m], entries[:m]
+
+    def orphans(self, d_object_ids: torch.Tensor, stream=None, stride: int = 1, m: Optional[int] = None,
+                d_orphans_out: Optional[torch.Tensor] = None, capacity: Optional[int] = None) -> torch.Tensor:
+        """sd_object_index_orphans -> int64 [count]: the distinct listed Object ids that have no
+        entry in this index, ascending as u64 (orphan_remover.rs:57-95 without the DB scan).
+        ``stride`` / ``m`` as object_links.  With d_orphans_out (int64, `capacity` elements)
+        too small the call raises SdCasError (SD_ERR_CAPACITY, ``.needed``) and writes nothing."""
+        m = (int(d_object_ids.numel()) + stride - 1) // max(stride, 1) if m is None else int(m)
+        assert d_object_ids.dtype == torch.int64 and (m == 0 or (d_object_ids.is_cuda and d_object_ids.is_contiguous()))
+        assert m == 0 or stride not in (1, 2) or (m - 1) * stride < d_object_ids.numel()
+        if d_orphans_out is None:  # the distinct ids are m at most: never short
+            d_orphans_out = torch.empty(max(m, 1), dtype=torch.int64, device=torch.device("cuda", self.ctx.device))
+            capacity = max(m, 1)
+        cap = int(d_orphans_out.numel() if capacity is None else capacity)
+        count = ctypes.c_uint64(0)
+        try:
+            check(lib().sd_object_index_orphans(self.ctx.handle, self.handle, _ptr(d_object_ids) if m else None, stride,
+                                                m, _ptr(d_orphans_out), cap, ctypes.byref(count), _stream(stream)))
+        except SdCasError as e:
+            e.needed = int(count.value)
+            raise
+        return d_orphans_out[:int(count.value)]
+
+    def _orphans_of(self, pairs: torch.Tensor, stream=None) -> torch.Tensor:
+        """The orphans among the Objects of removed (key, id) rows: their id column read at
+        stride 2 on the device."""
+        r = int(pairs.shape[0])
+        return self.orphans(pairs.reshape(-1)[1:] if r else pairs.reshape(-1), stream, stride=2, m=r)
 
     def apply_hex(self, rm_cas_ids, rm_object_ids, in_cas_ids, in_object_ids):
         """apply from the DB's strings -> (entries removed, entries taken)."""
@@ -453,30 +508,69 @@ class HostObjectIndex:
         r = int(removed.value)
         return out[:r], r
 
-    def remove(self, keys, object_ids=None, capacity: Optional[int] = None):
+    def remove(self, keys, object_ids=None, capacity: Optional[int] = None, orphans: bool = False):
         """sd_cpu_object_index_remove -> (removed pairs uint64 [r, 2] ascending by key, r);
         `capacity` (rows) below the count raises SdCasError (SD_ERR_CAPACITY, ``.needed``)
-        and leaves the index unchanged."""
+        and leaves the index unchanged.  ``orphans=True`` appends the Objects of the removed
+        pairs that now own nothing in this index."""
         k = np.ascontiguousarray(keys, dtype=np.uint64)
         v = None if object_ids is None else np.ascontiguousarray(object_ids, dtype=np.uint64)
         assert v is None or v.size == k.size
-        return self._removal(lambda out, cap, removed: lib().sd_cpu_object_index_remove(
+        res = self._removal(lambda out, cap, removed: lib().sd_cpu_object_index_remove(
             self.handle, _ptr(k) if k.size else None, _ptr(v) if k.size and v is not None else None, k.size, out, cap,
             removed), len(self) if self.owners_mode and v is None else min(k.size, len(self)), capacity)
+        return res + (self._orphans_of(res[0]),) if orphans else res
 
     def remove_hex(self, cas_ids, object_ids=None) -> int:
         """remove from the DB's strings; returns the count."""
         return self.remove(np.array([int(c, 16) for c in cas_ids], dtype=np.uint64), object_ids)[1]
 
-    def remove_objects(self, object_ids, capacity: Optional[int] = None):
-        """sd_cpu_object_index_remove_objects -> (removed pairs uint64 [r, 2], r)."""
+    def remove_objects(self, object_ids, capacity: Optional[int] = None, orphans: bool = False):
+        """sd_cpu_object_index_remove_objects -> (removed pairs uint64 [r, 2], r); ``orphans`` as
+        remove."""
         v = np.ascontiguousarray(object_ids, dtype=np.uint64)
-        return self._removal(lambda out, cap, removed: lib().sd_cpu_object_index_remove_objects(
+        res = self._removal(lambda out, cap, removed: lib().sd_cpu_object_index_remove_objects(
             self.handle, _ptr(v) if v.size else None, v.size, out, cap, removed), len(self), capacity)
+        return res + (self._orphans_of(res[0]),) if orphans else res
 
-    def apply(self, rm_keys, rm_ids, in_keys, in_ids, capacity: Optional[int] = None):
+    def object_links(self, object_ids, stride: int = 1, m: Optional[int] = None):
+        """sd_cpu_object_index_object_links -> (links, entries) uint64 [m] per listed Object id;
+        ``stride`` / ``m`` as ObjectIndex.object_links."""
+        v = np.ascontiguousarray(object_ids, dtype=np.uint64).reshape(-1)
+        m = (v.size + stride - 1) // max(stride, 1) if m is None else int(m)
+        assert m == 0 or stride not in (1, 2) or (m - 1) * stride < v.size
+        links, entries = np.zeros(max(m, 1), np.uint64), np.zeros(max(m, 1), np.uint64)
+        check(lib().sd_cpu_object_index_object_links(self.handle, _ptr(v) if m else None, stride, m, _ptr(links),
+                                                     _ptr(entries)))
+        return links[:m], entries[:m]
+
+    def orphans(self, object_ids, stride: int = 1, m: Optional[int] = None, capacity: Optional[int] = None):
+        """sd_cpu_object_index_orphans -> uint64 [count]: the distinct listed ids without an entry
+        in this index, ascending; `capacity` below the count raises SdCasError (SD_ERR_CAPACITY,
+        ``.needed``)."""
+        v = np.ascontiguousarray(object_ids, dtype=np.uint64).reshape(-1)
+        m = (v.size + stride - 1) // max(stride, 1) if m is None else int(m)
+        assert m == 0 or stride not in (1, 2) or (m - 1) * stride < v.size
+        cap = max(m, 1) if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 1), np.uint64)
+        count = ctypes.c_uint64(0)
+        try:
+            check(lib().sd_cpu_object_index_orphans(self.handle, _ptr(v) if m else None, stride, m, _ptr(out), cap,
+                                                    ctypes.byref(count)))
+        except SdCasError as e:
+            e.needed = int(count.value)
+            raise
+        return out[:int(count.value)]
+
+    def _orphans_of(self, pairs: np.ndarray) -> np.ndarray:
+        r = len(pairs)
+        flat = np.ascontiguousarray(pairs).reshape(-1)
+        return self.orphans(flat[1:] if r else flat, stride=2, m=r)
+
+    def apply(self, rm_keys, rm_ids, in_keys, in_ids, capacity: Optional[int] = None, orphans: bool = False):
         """sd_cpu_object_index_apply -> (removed pairs uint64 [r, 2] in ascending (key, id) order,
-        taken), the net effect of the removal list then the insertion list (owners mode)."""
+        taken), the net effect of the removal list then the insertion list (owners mode);
+        ``orphans=True`` appends the Objects of those pairs that now own nothing in this index."""
         rk, rv, ik, iv = (np.ascontiguousarray(a, dtype=np.uint64) for a in (rm_keys, rm_ids, in_keys, in_ids))
         assert rk.size == rv.size and ik.size == iv.size
         taken = ctypes.c_uint64(0)
@@ -484,6 +578,8 @@ class HostObjectIndex:
             self.handle, _ptr(rk) if rk.size else None, _ptr(rv) if rk.size else None, rk.size,
             _ptr(ik) if ik.size else None, _ptr(iv) if ik.size else None, ik.size, out, cap, removed,
             ctypes.byref(taken)), min(rk.size, len(self)), capacity)
+        if orphans:
+            return pairs, int(taken.value), self._orphans_of(pairs)
         return pairs, int(taken.value)
 
     def lookup(self, keys):
