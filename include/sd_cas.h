@@ -605,7 +605,8 @@ int sd_object_index_apply_hex(sd_cas_ctx* ctx, sd_object_index* index, const cha
  * sd_dedup_owners_indexed and sd_cas_dedup_mgpu_indexed (they share no buffer with those); they
  * are exclusive with insert, remove and apply, as every read is.  Unlike lookups they are NOT
  * free to run beside each other: they sort the ids and keep their totals in scratch owned by the
- * index, so ONE call by Object is in flight per index.  sd_object_index_object_links is
+ * index, so ONE call by Object (or of the view by key below, which shares that scratch) is in
+ * flight per index.  sd_object_index_object_links is
  * asynchronous: the next call by Object on that index goes to the same stream or waits for it;
  * nothing checks this.
  * Neither is collective: on a sharded index each rank answers for its shard; the host adds the
@@ -628,6 +629,68 @@ int sd_object_index_object_links(sd_cas_ctx* ctx, const sd_object_index* index, 
 int sd_object_index_orphans(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_object_ids,
                             uint64_t id_stride, uint64_t m, uint64_t* d_orphans_out, uint64_t capacity,
                             uint64_t* count, void* stream);
+/* THE VIEW BY KEY of an owners-mode index: the duplicate groups per cas_id.  The reference plans
+ * a duplicate finder and has not built it (a disabled "Duplicates" sidebar entry,
+ * interface/app/$libraryId/Layout/Sidebar/Contents.tsx:58-62; an empty guide,
+ * docs/product/guides/discover-duplicates.mdx; docs/changelog/alpha/0.1.0.mdx:45); against its DB
+ * the question is a GROUP BY cas_id HAVING COUNT(*) > 1 over file_path, whose cas_id has no
+ * index (core/prisma/schema.prisma:162, :196-199).  In the owners mode the answer is a property
+ * of the index: entries with equal keys are adjacent.  Both kinds of duplicate are there:
+ * same-step duplicates each get an Object (file_identifier/mod.rs:229-333), so one cas_id has
+ * several owners; later duplicates link to an existing Object (mod.rs:189-225), so one pair
+ * carries several links.  For one index (one shard) and a key k that has at least one entry:
+ *   owners(k) = the number of entries with key k
+ *   links(k)  = the sum of their link counts, in u64
+ *   first(k)  = the smallest Object id among them (what sd_object_index_lookup answers with)
+ *   k QUALIFIES under (min_links, min_owners) iff links(k) >= min_links and owners(k) >=
+ *   min_owners; 0 means 1 for both, so every key qualifies.
+ * min_links = 2 selects content that more than one file_path has; min_owners = 2 selects content
+ * split over several Objects, the merge candidates of mod.rs:229-333.
+ * An index without SD_OBJECT_INDEX_OWNERS, an index of another context and a NULL d_keys with
+ * m > 0 are SD_ERR_INVALID.  m == 0 and an empty index are valid: counts are 0, stats all 0,
+ * nothing is written.  All four only read the index: they are exclusive with insert, remove and
+ * apply, as every read is.  sd_object_index_key_links needs no scratch and may run beside every
+ * other read.  The three group calls keep their group totals in scratch owned by the index,
+ * shared with the calls by Object above: ONE call by Object or of this view is in flight per
+ * index (the next goes to the same stream or waits; nothing checks this); beside lookups,
+ * _links, _export*, _key_links and sd_dedup_owners_indexed they are free to run.  That scratch
+ * is grow-only: 18 bytes per entry and 17 KiB (never more than 32 bytes per entry above 1300
+ * entries).
+ * None is collective.  sd_dedup_partition's destination is monotone in the key, so the shards'
+ * groups are disjoint and the shards' rows concatenated in rank order are the library's answer,
+ * still ascending; stats rows add up over shards ([7] takes the maximum); key_links rows add up
+ * (a key lives in one shard).
+ * The limits: a cas_id samples files over 100 KiB (core/src/object/cas.rs:30-58), so a group is
+ * a candidate set that sd_file_checksums confirms; the index knows no paths and no sizes (the
+ * host joins them from the DB by cas_id: the key's 16 hex digits); files without a cas_id are
+ * invisible.
+ * sd_object_index_key_links (mod.rs:189-225, :229-333): per listed key (any order, repeats
+ *   allowed) d_links_out[j] = links(k), d_owners_out[j] = owners(k); 0 and 0 for a key the index
+ *   does not hold (absent, or of another shard).  Either output may be NULL.  Asynchronous. */
+int sd_object_index_key_links(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_keys, uint64_t m,
+                              uint64_t* d_links_out, uint64_t* d_owners_out, void* stream);
+/* sd_object_index_duplicates (mod.rs:189-225, :229-333): one row per qualifying key, ascending:
+ *   key, first(k), links(k), owners(k) (device, `capacity` u64 each; each may be NULL); *count
+ *   (host, may be NULL) = the qualifying keys.  If any output is given and `capacity` is smaller
+ *   than the count: SD_ERR_CAPACITY with *count = the requirement and nothing written.  Nothing
+ *   past the first *count rows is ever written; with every output NULL the call only counts.
+ *   Runs on `stream` and syncs it. */
+int sd_object_index_duplicates(sd_cas_ctx* ctx, const sd_object_index* index, uint64_t min_links, uint64_t min_owners,
+                               uint64_t* d_keys_out, uint64_t* d_first_out, uint64_t* d_links_out,
+                               uint64_t* d_owners_out, uint64_t capacity, uint64_t* count, void* stream);
+/* sd_object_index_duplicate_entries (mod.rs:189-225, :229-333): the ENTRIES of the qualifying
+ *   keys, ascending (key, id), with their link counts: the members of each duplicate group.
+ *   sd_object_index_export_links filtered; with (0, 0) equal to it, row for row.  *count = the
+ *   entries; outputs, capacity and sync as sd_object_index_duplicates. */
+int sd_object_index_duplicate_entries(sd_cas_ctx* ctx, const sd_object_index* index, uint64_t min_links,
+                                      uint64_t min_owners, uint64_t* d_keys_out, uint64_t* d_ids_out,
+                                      uint64_t* d_links_out, uint64_t capacity, uint64_t* count, void* stream);
+/* sd_object_index_duplicate_stats (mod.rs:189-225, :229-333): out[8] (host): [0] keys, [1]
+ *   entries, [2] links, [3] keys with links(k) >= 2, [4] the links of those keys, [5] keys with
+ *   owners(k) >= 2, [6] the entries of those keys, [7] the largest links(k) (0 on an empty
+ *   index).  Redundant file_paths = [4] - [3]; surplus Objects = [6] - [5].  Runs on `stream` and
+ *   syncs it. */
+int sd_object_index_duplicate_stats(sd_cas_ctx* ctx, const sd_object_index* index, uint64_t out[8], void* stream);
 /* sd_dedup_owners against the Objects the library already has (mod.rs:168-225, then
  * :229-333 for the rest), per grouped record i:
  *   d_owner[i] = index[cas_id], d_existing[i] = 1     if the index has the record's cas_id;
@@ -678,6 +741,17 @@ int sd_cpu_object_index_object_links(const sd_cpu_object_index* index, const uin
                                      uint64_t id_stride, uint64_t m, uint64_t* links_out, uint64_t* entries_out);
 int sd_cpu_object_index_orphans(const sd_cpu_object_index* index, const uint64_t* object_ids, uint64_t id_stride,
                                 uint64_t m, uint64_t* orphans_out, uint64_t capacity, uint64_t* count);
+/* sd_object_index_key_links / _duplicates / _duplicate_entries / _duplicate_stats over host arrays
+ * (mod.rs:189-225, :229-333): the same rule, reports and refusals. */
+int sd_cpu_object_index_key_links(const sd_cpu_object_index* index, const uint64_t* keys, uint64_t m,
+                                  uint64_t* links_out, uint64_t* owners_out);
+int sd_cpu_object_index_duplicates(const sd_cpu_object_index* index, uint64_t min_links, uint64_t min_owners,
+                                   uint64_t* keys_out, uint64_t* first_out, uint64_t* links_out, uint64_t* owners_out,
+                                   uint64_t capacity, uint64_t* count);
+int sd_cpu_object_index_duplicate_entries(const sd_cpu_object_index* index, uint64_t min_links, uint64_t min_owners,
+                                          uint64_t* keys_out, uint64_t* ids_out, uint64_t* links_out,
+                                          uint64_t capacity, uint64_t* count);
+int sd_cpu_object_index_duplicate_stats(const sd_cpu_object_index* index, uint64_t out[8]);
 int sd_cpu_dedup_owners_indexed(const sd_cpu_object_index* index, const uint64_t* records, uint64_t m,
                                 const uint64_t* rep, uint64_t chunk_size, uint64_t* owner, uint8_t* existing,
                                 uint64_t* new_out, uint64_t* n_new);

@@ -211,6 +211,20 @@ extern "C" {
                                             entries_out: *mut u64) -> c_int;
     pub fn sd_cpu_object_index_orphans(index: *const sd_cpu_object_index, object_ids: *const u64, id_stride: u64,
                                        m: u64, orphans_out: *mut u64, capacity: u64, count: *mut u64) -> c_int;
+    // the view by key of an owners-mode index: the duplicate groups per cas_id (mod.rs:189-225,
+    // :229-333), without a GROUP BY over file_path
+    pub fn sd_object_index_key_links(ctx: *mut sd_cas_ctx, index: *const sd_object_index, d_keys: *const u64, m: u64,
+                                     d_links_out: *mut u64, d_owners_out: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_object_index_duplicates(ctx: *mut sd_cas_ctx, index: *const sd_object_index, min_links: u64,
+                                      min_owners: u64, d_keys_out: *mut u64, d_first_out: *mut u64,
+                                      d_links_out: *mut u64, d_owners_out: *mut u64, capacity: u64,
+                                      count: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_object_index_duplicate_entries(ctx: *mut sd_cas_ctx, index: *const sd_object_index, min_links: u64,
+                                             min_owners: u64, d_keys_out: *mut u64, d_ids_out: *mut u64,
+                                             d_links_out: *mut u64, capacity: u64, count: *mut u64,
+                                             stream: *mut c_void) -> c_int;
+    pub fn sd_object_index_duplicate_stats(ctx: *mut sd_cas_ctx, index: *const sd_object_index, out: *mut u64,
+                                           stream: *mut c_void) -> c_int;
     // device buffers for callers that hold their lists on the host (sd_memcpy syncs `stream`)
     pub fn sd_device_malloc(ctx: *mut sd_cas_ctx, bytes: u64, out: *mut *mut c_void) -> c_int;
     pub fn sd_device_free(ctx: *mut sd_cas_ctx, p: *mut c_void);

@@ -176,6 +176,14 @@ SIGNATURES = [
     ("sd_object_index_orphans", I32, [P, P, P, U64, U64, P, U64, PU64, P]),
     ("sd_cpu_object_index_object_links", I32, [P, P, U64, U64, P, P]),
     ("sd_cpu_object_index_orphans", I32, [P, P, U64, U64, P, U64, PU64]),
+    ("sd_object_index_key_links", I32, [P, P, P, U64, P, P, P]),
+    ("sd_object_index_duplicates", I32, [P, P, U64, U64, P, P, P, P, U64, PU64, P]),
+    ("sd_object_index_duplicate_entries", I32, [P, P, U64, U64, P, P, P, U64, PU64, P]),
+    ("sd_object_index_duplicate_stats", I32, [P, P, P, P]),
+    ("sd_cpu_object_index_key_links", I32, [P, P, U64, P, P]),
+    ("sd_cpu_object_index_duplicates", I32, [P, U64, U64, P, P, P, P, U64, PU64]),
+    ("sd_cpu_object_index_duplicate_entries", I32, [P, U64, U64, P, P, P, U64, PU64]),
+    ("sd_cpu_object_index_duplicate_stats", I32, [P, P]),
 ]
 SD_OBJECT_INDEX_OWNERS = 1
 

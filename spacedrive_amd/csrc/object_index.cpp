@@ -5,7 +5,9 @@
 // deleted (core/src/object/orphan_remover.rs:57-95) and files change
 // (location/manager/watcher/utils.rs:410-494), in the owners mode also both at once
 // (sd_object_index_apply), and that mode's read-only view by Object, which answers the orphan
-// remover's own query (sd_object_index_object_links, sd_object_index_orphans).  Kernels:
+// remover's own query (sd_object_index_object_links, sd_object_index_orphans), and its view by
+// key, the duplicate groups per cas_id (sd_object_index_key_links, _duplicates,
+// _duplicate_entries, _duplicate_stats).  Kernels:
 // object_index.hip; layout, lookup,
 // the removal rules and the directory / growth policies: object_index.h,
 // object_index_host.cpp (shared with the sd_cpu_object_index_* mirror).
@@ -29,6 +31,41 @@ sd_object_index* objects_query(sd_cas_ctx* ctx, const sd_object_index* index, co
     if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
     if (id_stride != 1 && id_stride != 2) throw sd_failure(SD_ERR_INVALID, "id_stride is 1 or 2 (u64 units)");
     return const_cast<sd_object_index*>(index);
+}
+
+// the checks the three group calls share; the index comes back writable for its scratch alone
+sd_object_index* groups_query(sd_cas_ctx* ctx, const sd_object_index* index) {
+    if (!ctx || !index) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    return const_cast<sd_object_index*>(index);
+}
+
+// Both selections after the group totals: flag, the count in one copy and one sync, the capacity
+// checked BEFORE anything is written, then the ordered compaction.
+template <class Compact>
+void groups_select(sd_object_index* x, uint64_t min_links, uint64_t min_owners, bool entries, bool any_output,
+                   uint64_t capacity, uint64_t* count, hipStream_t s, Compact compact) {
+    if (count) *count = 0;
+    if (x->n == 0) return;
+    x->scratch.ensure(sdk::index_groups_scratch(x->n));
+    const sdk::oi_view v = x->view();
+    HIP_CHECK(sdk::index_groups_totals(v, x->scratch.p, s));
+    HIP_CHECK(sdk::index_groups_flag(v, x->scratch.p, min_links, min_owners, entries, s));
+    const uint32_t slots = sdk::index_groups_slots(x->n);
+    x->objects_host.ensure(sdk::OI_COUNT_SLOTS * sizeof(uint64_t));
+    HIP_CHECK(hipMemcpyAsync(x->objects_host.p, sdk::index_groups_counts(x->scratch.p, x->n), slots * sizeof(uint64_t),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const uint64_t* c = reinterpret_cast<const uint64_t*>(x->objects_host.p);
+    uint64_t r = 0;
+    for (uint32_t k = 0; k < slots; k++) r += c[k];
+    if (r > x->n) throw sd_failure(SD_ERR_INTERNAL, "duplicates: more rows than entries");
+    if (count) *count = r;
+    if (!any_output || r == 0) return;
+    if (capacity < r) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of rows");
+    HIP_CHECK(compact(v, x->scratch.p));
+    HIP_CHECK(hipStreamSynchronize(s));
 }
 
 // The second half of both removals, after the flagging pass: the per-slice counts give the
@@ -528,6 +565,75 @@ int sd_object_index_orphans(sd_cas_ctx* ctx, const sd_object_index* index, const
     if (capacity < r) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of orphans");
     HIP_CHECK(sdk::index_orphans_compact(x->scratch.p, m, d_orphans_out, s));
     HIP_CHECK(hipStreamSynchronize(s));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+// The view by key of an owners-mode index (object_index.h oi_key_run / oi_qualifies): which
+// content exists more than once (later duplicates link to an Object, mod.rs:189-225) and which is
+// split over several Objects (same-step duplicates, mod.rs:229-333).  key_links is a plain read.
+// The three group calls keep the group totals, flags and per-slice counts in the index's scratch
+// and use the by-Object calls' host buffer: ONE call by Object or of this view per index.
+int sd_object_index_key_links(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_keys, uint64_t m,
+                              uint64_t* d_links_out, uint64_t* d_owners_out, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index || (m && !d_keys)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    if (m == 0) return SD_OK;
+    ctx->bind();
+    HIP_CHECK(sdk::index_key_links(index->view(), d_keys, m, d_links_out, d_owners_out, ctx->pick(stream)));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_object_index_duplicates(sd_cas_ctx* ctx, const sd_object_index* index, uint64_t min_links, uint64_t min_owners,
+                               uint64_t* d_keys_out, uint64_t* d_first_out, uint64_t* d_links_out,
+                               uint64_t* d_owners_out, uint64_t capacity, uint64_t* count, void* stream) {
+    SD_GUARD_BEGIN
+    sd_object_index* x = groups_query(ctx, index);
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    groups_select(x, min_links, min_owners, false, d_keys_out || d_first_out || d_links_out || d_owners_out, capacity,
+                  count, s, [&](const sdk::oi_view& v, const void* scratch) {
+                      return sdk::index_groups_compact(v, scratch, d_keys_out, d_first_out, d_links_out, d_owners_out, s);
+                  });
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_object_index_duplicate_entries(sd_cas_ctx* ctx, const sd_object_index* index, uint64_t min_links,
+                                      uint64_t min_owners, uint64_t* d_keys_out, uint64_t* d_ids_out,
+                                      uint64_t* d_links_out, uint64_t capacity, uint64_t* count, void* stream) {
+    SD_GUARD_BEGIN
+    sd_object_index* x = groups_query(ctx, index);
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    groups_select(x, min_links, min_owners, true, d_keys_out || d_ids_out || d_links_out, capacity, count, s,
+                  [&](const sdk::oi_view& v, const void* scratch) {
+                      return sdk::index_groups_compact_entries(v, scratch, d_keys_out, d_ids_out, d_links_out, s);
+                  });
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_object_index_duplicate_stats(sd_cas_ctx* ctx, const sd_object_index* index, uint64_t out[8], void* stream) {
+    SD_GUARD_BEGIN
+    if (!out) throw sd_failure(SD_ERR_INVALID, "null argument");
+    sd_object_index* x = groups_query(ctx, index);
+    for (int k = 0; k < 8; k++) out[k] = 0;
+    if (x->n == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    x->scratch.ensure(sdk::index_groups_scratch(x->n));
+    const sdk::oi_view v = x->view();
+    HIP_CHECK(sdk::index_groups_totals(v, x->scratch.p, s));
+    HIP_CHECK(sdk::index_groups_stats(v, x->scratch.p, s));
+    x->objects_host.ensure(sdk::OI_COUNT_SLOTS * sizeof(uint64_t));
+    HIP_CHECK(hipMemcpyAsync(x->objects_host.p, sdk::index_groups_stats_at(x->scratch.p, x->n), 8 * sizeof(uint64_t),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (int k = 0; k < 8; k++) out[k] = reinterpret_cast<const uint64_t*>(x->objects_host.p)[k];
     return SD_OK;
     SD_GUARD_END
 }

@@ -133,6 +133,40 @@ SD_OI_HD uint64_t oi_links_after(uint64_t held, uint64_t asked, uint64_t added) 
     return kept + added;
 }
 
+// ---- by key, read-only (owners mode; sd_object_index_key_links, _duplicates, _duplicate_entries,
+// _duplicate_stats): the duplicates the library exists to find -- content that more than one
+// file_path has (mod.rs:189-225 links later copies to an existing Object) and content split over
+// several Objects (mod.rs:229-333 gives same-step duplicates an Object each).  For one index (one
+// shard) and a key k that has at least one entry -- the entries of a key are adjacent:
+//   owners(k) = the number of entries with key k
+//   links(k)  = the sum of their link counts, in u64
+//   first(k)  = the smallest Object id among them: the run's first entry, which lookup answers with
+//   k QUALIFIES under (min_links, min_owners) iff links(k) >= min_links and owners(k) >= min_owners;
+//   0 means 1 for both, so every key qualifies.
+// first position in [lo, hi) whose key is > key (hi if none): the run's end without key + 1,
+// since 2^64 - 1 is a legal key
+SD_OI_HD uint64_t oi_upper_bound(const uint64_t* keys, uint64_t lo, uint64_t hi, uint64_t key) {
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] <= key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the run [*lo, *hi) of `key` (empty if absent): two binary searches inside the key's bucket
+SD_OI_HD void oi_key_run(const uint64_t* keys, const uint64_t* dir, uint32_t bits, uint64_t key, uint64_t* lo,
+                         uint64_t* hi) {
+    const uint64_t p = oi_prefix(key, bits);
+    const uint64_t end = dir[p + 1];
+    *lo = oi_lower_bound(keys, dir[p], end, key);
+    *hi = oi_upper_bound(keys, *lo, end, key);
+}
+
+SD_OI_HD bool oi_qualifies(uint64_t links, uint64_t owners, uint64_t min_links, uint64_t min_owners) {
+    return links >= (min_links ? min_links : 1) && owners >= (min_owners ? min_owners : 1);
+}
+
 // ---- policies (object_index_host.cpp; the device path calls the same functions)
 // directory bits for n entries: ~log2(n / 8), 0 for tiny indexes, at most 24
 uint32_t oi_dir_bits(uint64_t n);

@@ -5,7 +5,9 @@
 // id), after a batch of pairs has been aggregated to distinct pairs with multiplicities; and
 // apply, that mode's removal with ids and insert in one flagging pass and one fused
 // merge-compaction; and that mode's read-only view by Object: the link totals of listed ids and
-// the orphans among them, in one pass over the entries.
+// the orphans among them, in one pass over the entries; and its read-only view by key: the
+// duplicate groups (the runs of equal keys) with their link and owner totals, selected by
+// thresholds and compacted in order.
 //
 // Reference semantics: identifier_job_step joins a step's cas_ids against the Objects the
 // library already has (core/src/object/file_identifier/mod.rs:168-175), links each file to
@@ -873,6 +875,253 @@ __global__ __launch_bounds__(256) void k_orphans_compact(const uint64_t* __restr
     }
 }
 
+// ---- by key, read-only (owners mode): the duplicate groups (object_index.h oi_key_run /
+// oi_qualifies; mod.rs:189-225 links later copies to an Object, :229-333 gives same-step
+// duplicates an Object each).  The index is sorted, so a group is a run of equal keys and its
+// slot is the number of heads before it (block_base + tile_slot over the head flags).
+//
+// key_links: per listed key the run's bounds by two searches in its bucket.  A run of at most
+// OI_RUN_SERIAL entries is summed by its lane; longer ones are summed by the whole wave, one run
+// after the other (64 * OI_RUN_LOADS consecutive links per step, OI_RUN_LOADS loads in flight per
+// lane: one wave is bound by the memory's latency, not its bandwidth), so RUN owners of one key
+// cost RUN / 512 steps.
+constexpr uint64_t OI_RUN_SERIAL = 64;
+constexpr uint32_t OI_RUN_LOADS = 8;
+
+template <bool SUMS>
+__global__ __launch_bounds__(256) void k_key_links(const uint64_t* __restrict__ keys,
+                                                   const uint64_t* __restrict__ links,
+                                                   const uint64_t* __restrict__ dir, uint32_t bits,
+                                                   const uint64_t* __restrict__ q, uint64_t m,
+                                                   uint64_t* __restrict__ links_out,
+                                                   uint64_t* __restrict__ owners_out) {
+    const uint32_t lane = threadIdx.x & 63;
+    // whole tiles: the same trips for every lane of a wave
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < m; base += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool act = i < m;
+        uint64_t lo = 0, hi = 0;
+        if (act) oi_key_run(keys, dir, bits, q[i], &lo, &hi);
+        if (act && owners_out) owners_out[i] = hi - lo;
+        if (!SUMS) continue;
+        uint64_t sum = 0;
+        const bool wide = hi - lo > OI_RUN_SERIAL;
+        if (!wide)
+            for (uint64_t j = lo; j < hi; j++) sum += links[j];
+        uint64_t todo = __ballot(wide);
+        while (todo) {  // the same for every lane
+            const int leader = __ffsll((unsigned long long)todo) - 1;
+            todo &= todo - 1;
+            const uint64_t l0 = __shfl(lo, leader), h0 = __shfl(hi, leader);
+            uint64_t p[OI_RUN_LOADS] = {};  // that many loads in flight per lane
+            for (uint64_t j = l0 + lane; j < h0; j += 64 * OI_RUN_LOADS) {
+                // every load is issued before the first add waits for one: a lane past the run's end
+                // reads the run's last link and adds 0
+                uint64_t v[OI_RUN_LOADS];
+#pragma unroll
+                for (uint32_t u = 0; u < OI_RUN_LOADS; u++) v[u] = links[j + 64 * u < h0 ? j + 64 * u : h0 - 1];
+#pragma unroll
+                for (uint32_t u = 0; u < OI_RUN_LOADS; u++) p[u] += j + 64 * u < h0 ? v[u] : 0;
+            }
+            uint64_t part = 0;
+#pragma unroll
+            for (uint32_t u = 0; u < OI_RUN_LOADS; u++) part += p[u];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+            if (lane == (uint32_t)leader) sum = part;
+        }
+        if (act) links_out[i] = sum;
+    }
+}
+
+// the heads of the runs of equal keys, counted per workgroup slice
+__global__ __launch_bounds__(256) void k_group_heads(const uint64_t* __restrict__ keys, uint64_t n,
+                                                     uint64_t* __restrict__ counts) {
+    const oi_slice sl = oi_slice_of(n);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) mine += i == 0 || keys[i - 1] != keys[i];
+    block_count(mine, counts);
+}
+
+// Group totals.  Every entry learns its group's slot; a head stores its position at hpos[slot],
+// so owners(slot) = hpos[slot + 1] - hpos[slot] (the last one's from n) with no sum at all.
+// links: a segmented sum by slot inside the wave (the lanes of one run are neighbours; each step
+// takes the partial sum `o` lanes down unless that lane lies before the run's first lane in this
+// wave), which leaves the run's sum over this wave at the run's last lane here.  A run that
+// begins and ends inside the wave -- most do -- costs one plain store; a run that crosses a wave,
+// tile or slice border costs one u64 add per wave it touches into gl[slot] (zeroed before;
+// integer sums are exact in any order), so a run of many slices combines across workgroups and no
+// lane walks anything.  A slot is written either by one store or by adds, never both.
+__global__ __launch_bounds__(256) void k_group_totals(const uint64_t* __restrict__ keys,
+                                                      const uint64_t* __restrict__ links, uint64_t n,
+                                                      const uint64_t* __restrict__ counts,
+                                                      uint64_t* __restrict__ hpos, uint64_t* __restrict__ gl,
+                                                      uint64_t* __restrict__ g_total) {
+    uint64_t run = block_base(counts, g_total);
+    const oi_slice sl = oi_slice_of(n);
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool act = i < sl.hi;
+        const uint64_t key = act ? keys[i] : 0;
+        const bool head = act && (i == 0 || keys[i - 1] != key);
+        const uint64_t slot = tile_slot(head, run);
+        if (head) hpos[slot] = i;
+        // a segment of the wave begins at lane 0, at a head and at every inactive lane
+        const uint64_t starts = __ballot(lane == 0 || head || !act);
+        const uint64_t heads = __ballot(head);
+        const uint64_t upto = lane == 63 ? ~0ull : (2ull << lane) - 1;
+        const uint32_t first = 63 - (uint32_t)__clzll((long long)(starts & upto));  // bit 0 is set
+        uint64_t sum = act ? links[i] : 0;
+#pragma unroll
+        for (uint32_t o = 1; o < 64; o <<= 1) {
+            const uint64_t below = __shfl_up(sum, o);
+            if (lane >= first + o) sum += below;
+        }
+        const bool last = act && (lane == 63 || ((starts >> (lane + 1)) & 1));
+        if (!last) continue;
+        const uint64_t gs = head ? slot : slot - 1;  // position 0 is a head: a follower has one before it
+        const bool opens = (heads >> first) & 1;
+        const bool closes = i + 1 == n || keys[i + 1] != key;
+        if (opens && closes) gl[gs] = sum;
+        else atomicAdd(reinterpret_cast<unsigned long long*>(gl + gs), (unsigned long long)sum);
+    }
+}
+
+__device__ __forceinline__ uint64_t group_owners(const uint64_t* __restrict__ hpos, uint64_t g, uint64_t groups,
+                                                 uint64_t n) {
+    return (g + 1 < groups ? hpos[g + 1] : n) - hpos[g];
+}
+
+// Selection per group: gflags[g] = the group qualifies, counted per workgroup slice of the groups
+__global__ __launch_bounds__(256) void k_group_flag(const uint64_t* __restrict__ hpos,
+                                                    const uint64_t* __restrict__ gl,
+                                                    const uint64_t* __restrict__ g_total, uint64_t n,
+                                                    uint64_t min_links, uint64_t min_owners,
+                                                    uint8_t* __restrict__ gflags, uint64_t* __restrict__ counts) {
+    const uint64_t groups = *g_total;
+    const oi_slice sl = oi_slice_of(groups);
+    uint32_t mine = 0;
+    for (uint64_t g = sl.lo + threadIdx.x; g < sl.hi; g += blockDim.x) {
+        const bool ok = oi_qualifies(gl[g], group_owners(hpos, g, groups, n), min_links, min_owners);
+        gflags[g] = ok ? 1 : 0;
+        mine += ok;
+    }
+    block_count(mine, counts);
+}
+
+// one row per qualifying group in group order = ascending key order; key and first owner are
+// read at the head's position (every output may be null)
+__global__ __launch_bounds__(256) void k_group_compact(const uint64_t* __restrict__ keys,
+                                                       const uint64_t* __restrict__ vals,
+                                                       const uint64_t* __restrict__ hpos,
+                                                       const uint64_t* __restrict__ gl,
+                                                       const uint64_t* __restrict__ g_total, uint64_t n,
+                                                       const uint8_t* __restrict__ gflags,
+                                                       const uint64_t* __restrict__ counts,
+                                                       uint64_t* __restrict__ keys_out,
+                                                       uint64_t* __restrict__ first_out,
+                                                       uint64_t* __restrict__ links_out,
+                                                       uint64_t* __restrict__ owners_out) {
+    uint64_t run = block_base(counts, nullptr);
+    const uint64_t groups = *g_total;
+    const oi_slice sl = oi_slice_of(groups);
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t g = base + threadIdx.x;
+        const bool flag = g < sl.hi && gflags[g];
+        const uint64_t slot = tile_slot(flag, run);
+        if (!flag) continue;
+        const uint64_t at = hpos[g];
+        if (keys_out) keys_out[slot] = keys[at];
+        if (first_out) first_out[slot] = vals[at];
+        if (links_out) links_out[slot] = gl[g];
+        if (owners_out) owners_out[slot] = group_owners(hpos, g, groups, n);
+    }
+}
+
+// Selection per entry: an entry is selected iff its group is.  The group's slot is found again as
+// in k_group_totals (the head counts per slice are still there); eflags[i] and the selected
+// entries per slice are left for the compaction.
+__global__ __launch_bounds__(256) void k_entry_flag(const uint64_t* __restrict__ keys, uint64_t n,
+                                                    const uint64_t* __restrict__ head_counts,
+                                                    const uint8_t* __restrict__ gflags,
+                                                    uint8_t* __restrict__ eflags, uint64_t* __restrict__ counts) {
+    uint64_t run = block_base(head_counts, nullptr);
+    const oi_slice sl = oi_slice_of(n);
+    uint32_t mine = 0;
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool act = i < sl.hi;
+        const bool head = act && (i == 0 || keys[i - 1] != keys[i]);
+        const uint64_t slot = tile_slot(head, run);
+        if (!act) continue;
+        const bool sel = gflags[head ? slot : slot - 1] != 0;
+        eflags[i] = sel ? 1 : 0;
+        mine += sel;
+    }
+    block_count(mine, counts);
+}
+
+__global__ __launch_bounds__(256) void k_entry_compact(const uint64_t* __restrict__ keys,
+                                                       const uint64_t* __restrict__ vals,
+                                                       const uint64_t* __restrict__ links, uint64_t n,
+                                                       const uint8_t* __restrict__ eflags,
+                                                       const uint64_t* __restrict__ counts,
+                                                       uint64_t* __restrict__ keys_out,
+                                                       uint64_t* __restrict__ ids_out,
+                                                       uint64_t* __restrict__ links_out) {
+    uint64_t run = block_base(counts, nullptr);
+    const oi_slice sl = oi_slice_of(n);
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool flag = i < sl.hi && eflags[i];
+        const uint64_t slot = tile_slot(flag, run);
+        if (!flag) continue;
+        if (keys_out) keys_out[slot] = keys[i];
+        if (ids_out) ids_out[slot] = vals[i];
+        if (links_out) links_out[slot] = links[i];
+    }
+}
+
+// Stats: one reduction over the group totals.  A lane sums its groups in registers, the wave by
+// shuffles, the workgroup through LDS; one workgroup adds seven sums and one maximum to st[8]
+// (zeroed before).  st[0] (the groups) and st[1] (the entries) are known and set by workgroup 0.
+__global__ __launch_bounds__(256) void k_group_stats(const uint64_t* __restrict__ hpos,
+                                                     const uint64_t* __restrict__ gl,
+                                                     const uint64_t* __restrict__ g_total, uint64_t n,
+                                                     uint64_t* __restrict__ st) {
+    __shared__ uint64_t ws[4][6];
+    const uint64_t groups = *g_total;
+    const oi_slice sl = oi_slice_of(groups);
+    uint64_t v[6] = {0, 0, 0, 0, 0, 0};  // v[k] is st[2 + k]; v[5] = the largest links(k)
+    for (uint64_t g = sl.lo + threadIdx.x; g < sl.hi; g += blockDim.x) {
+        const uint64_t l = gl[g], o = group_owners(hpos, g, groups, n);
+        v[0] += l;
+        if (l >= 2) v[1] += 1, v[2] += l;
+        if (o >= 2) v[3] += 1, v[4] += o;
+        if (l > v[5]) v[5] = l;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) v[k] += __shfl_xor(v[k], o);
+        const uint64_t other = __shfl_xor(v[5], o);
+        if (other > v[5]) v[5] = other;
+    }
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < 6; k++) ws[threadIdx.x >> 6][k] = v[k];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int k = 0; k < 5; k++) {
+        const uint64_t t = ws[0][k] + ws[1][k] + ws[2][k] + ws[3][k];
+        if (t) atomicAdd(reinterpret_cast<unsigned long long*>(st + 2 + k), (unsigned long long)t);
+    }
+    uint64_t mx = ws[0][5];
+    for (int w = 1; w < 4; w++) mx = ws[w][5] > mx ? ws[w][5] : mx;
+    if (mx)atomicMax(reinterpret_cast<unsigned long long*>(st + 7), (unsigned long long)mx);
+    if (blockIdx.x == 0) st[0] = groups, st[1] = n;
+}
+
 size_t insert_sort_bytes(uint64_t m, hipStream_t s) {
     size_t b = 0;
     uint64_t* nul = nullptr;
@@ -1327,6 +1576,109 @@ hipError_t index_orphans_compact(const void* scratch, uint64_t m, uint64_t* out,
     const objects_scratch q = objects_scratch_at(const_cast<void*>(scratch), m);
     hipLaunchKernelGGL(k_orphans_compact, dim3(sliced_grid(m)), dim3(256), 0, s, q.u, q.d_total, q.flags, q.counts, out);
     return hipGetLastError();
+}
+
+// ---- by key, read-only
+hipError_t index_key_links(const oi_view& x, const uint64_t* q_keys, uint64_t m, uint64_t* links_out,
+                           uint64_t* owners_out, hipStream_t s) {
+    if (m == 0 || (!links_out && !owners_out)) return hipSuccess;
+    if (x.n == 0) {  // no run to search: every answer is 0
+        hipError_t e = links_out ? hipMemsetAsync(links_out, 0, m * sizeof(uint64_t), s) : hipSuccess;
+        if (e == hipSuccess && owners_out) e = hipMemsetAsync(owners_out, 0, m * sizeof(uint64_t), s);
+        return e;
+    }
+    const dim3 g(grid_for(m)), b(256);
+    if (links_out) hipLaunchKernelGGL((k_key_links<true>), g, b, 0, s, x.keys, x.links, x.dir, x.bits, q_keys, m, links_out, owners_out);
+    else hipLaunchKernelGGL((k_key_links<false>), g, b, 0, s, x.keys, x.links, x.dir, x.bits, q_keys, m, links_out, owners_out);
+    return hipGetLastError();
+}
+
+// The group calls' scratch for n entries: hpos[n], gl[n] (u64), gflags[n], eflags[n] (u8), the
+// group count and the eight stats (u64, 256 bytes apart), the head counts and the selection
+// counts per slice (OI_BLOCKS u64 each): 18 B per entry and 17 KiB.
+namespace {
+struct groups_scratch {
+    uint64_t *hpos, *gl, *g_total, *stats, *head_counts, *sel_counts;
+    uint8_t *gflags, *eflags;
+};
+
+groups_scratch groups_scratch_at(void* base, uint64_t n) {
+    groups_scratch q;
+    uint64_t* p = reinterpret_cast<uint64_t*>(base);
+    q.hpos = p, q.gl = p + n;
+    uint8_t* b = reinterpret_cast<uint8_t*>(base) + round256(2 * n * sizeof(uint64_t));
+    q.gflags = b, q.eflags = b + round256(n);
+    b += 2 * round256(n);
+    q.g_total = reinterpret_cast<uint64_t*>(b);
+    q.stats = reinterpret_cast<uint64_t*>(b + 256);
+    q.head_counts = reinterpret_cast<uint64_t*>(b + 512);
+    q.sel_counts = q.head_counts + OI_BLOCKS;
+    return q;
+}
+}  // namespace
+
+size_t index_groups_scratch(uint64_t n) {
+    return round256(2 * n * sizeof(uint64_t)) + 2 * round256(n) + 512 + 2 * OI_BLOCKS * sizeof(uint64_t);
+}
+
+uint32_t index_groups_slots(uint64_t n) { return sliced_grid(n); }
+
+// n > 0.  After it hpos[g] and gl[g] hold the head position and links of every group g, and
+// *g_total the groups.  Nothing of the index is written.
+hipError_t index_groups_totals(const oi_view& x, void* scratch, hipStream_t s) {
+    const groups_scratch q = groups_scratch_at(scratch, x.n);
+    hipError_t e = hipMemsetAsync(q.gl, 0, x.n * sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    const dim3 g(sliced_grid(x.n)), b(256);
+    hipLaunchKernelGGL(k_group_heads, g, b, 0, s, x.keys, x.n, q.head_counts);
+    hipLaunchKernelGGL(k_group_totals, g, b, 0, s, x.keys, x.links, x.n, q.head_counts, q.hpos, q.gl, q.g_total);
+    return hipGetLastError();
+}
+
+// the qualifying groups, or (entries) the entries of the qualifying groups, counted per slice in
+// index_groups_counts(scratch, n)[0 .. index_groups_slots(n))
+hipError_t index_groups_flag(const oi_view& x, void* scratch, uint64_t min_links, uint64_t min_owners, bool entries,
+                             hipStream_t s) {
+    const groups_scratch q = groups_scratch_at(scratch, x.n);
+    const dim3 g(sliced_grid(x.n)), b(256);  // groups <= n: the slices past the groups are empty
+    hipLaunchKernelGGL(k_group_flag, g, b, 0, s, q.hpos, q.gl, q.g_total, x.n, min_links, min_owners, q.gflags,
+                       q.sel_counts);
+    if (entries)
+        hipLaunchKernelGGL(k_entry_flag, g, b, 0, s, x.keys, x.n, q.head_counts, q.gflags, q.eflags, q.sel_counts);
+    return hipGetLastError();
+}
+
+const uint64_t* index_groups_counts(const void* scratch, uint64_t n) {
+    return groups_scratch_at(const_cast<void*>(scratch), n).sel_counts;
+}
+
+hipError_t index_groups_compact(const oi_view& x, const void* scratch, uint64_t* keys_out, uint64_t* first_out,
+                                uint64_t* links_out, uint64_t* owners_out, hipStream_t s) {
+    const groups_scratch q = groups_scratch_at(const_cast<void*>(scratch), x.n);
+    hipLaunchKernelGGL(k_group_compact, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, q.hpos, q.gl, q.g_total,
+                       x.n, q.gflags, q.sel_counts, keys_out, first_out, links_out, owners_out);
+    return hipGetLastError();
+}
+
+hipError_t index_groups_compact_entries(const oi_view& x, const void* scratch, uint64_t* keys_out, uint64_t* ids_out,
+                                        uint64_t* links_out, hipStream_t s) {
+    const groups_scratch q = groups_scratch_at(const_cast<void*>(scratch), x.n);
+    hipLaunchKernelGGL(k_entry_compact, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, x.links, x.n, q.eflags,
+                       q.sel_counts, keys_out, ids_out, links_out);
+    return hipGetLastError();
+}
+
+// the eight stats of sd_object_index_duplicate_stats in index_groups_stats_at(scratch, n)
+hipError_t index_groups_stats(const oi_view& x, void* scratch, hipStream_t s) {
+    const groups_scratch q = groups_scratch_at(scratch, x.n);
+    hipError_t e = hipMemsetAsync(q.stats, 0, 8 * sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_group_stats, dim3(sliced_grid(x.n)), dim3(256), 0, s, q.hpos, q.gl, q.g_total, x.n, q.stats);
+    return hipGetLastError();
+}
+
+const uint64_t* index_groups_stats_at(const void* scratch, uint64_t n) {
+    return groups_scratch_at(const_cast<void*>(scratch), n).stats;
 }
 
 hipError_t index_build_dir(const uint64_t* keys, uint64_t n, uint32_t bits, uint64_t* dir, hipStream_t s) {

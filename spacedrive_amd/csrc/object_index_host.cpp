@@ -9,9 +9,10 @@
 // files change (location/manager/watcher/utils.rs:410-494).  No HIP: built with g++ under
 // the sanitizers too (object_index_selftest.cpp, object_index_remove_selftest.cpp,
 // object_index_owners_selftest.cpp, object_index_apply_selftest.cpp,
-// object_index_orphans_selftest.cpp; `make sanitize-object-index`, `make
-// sanitize-object-index-remove`, `make sanitize-object-index-owners`, `make
-// sanitize-object-index-apply`, `make sanitize-object-index-orphans`).  The owners mode
+// object_index_orphans_selftest.cpp, object_index_duplicates_selftest.cpp; `make
+// sanitize-object-index`, `make sanitize-object-index-remove`, `make
+// sanitize-object-index-owners`, `make sanitize-object-index-apply`, `make
+// sanitize-object-index-orphans`, `make sanitize-object-index-duplicates`).  The owners mode
 // (sd_cpu_object_index_create_ex with SD_OBJECT_INDEX_OWNERS) keeps one entry per (key, Object
 // id) with its link count; its rules are those of object_index.h, as the kernels'.
 #include <string.h>
@@ -204,6 +205,23 @@ object_totals totals_by_object(const sd_cpu_object_index* x, const uint64_t* obj
     }
     return t;
 }
+
+// The groups of an owners-mode index (object_index.h, by key): head[s] = the position of run s's
+// first entry, links[s] = links(k); owners = the distance to the next head.
+struct groups_of {
+    std::vector<uint64_t> head, links;
+    uint64_t n = 0;
+    explicit groups_of(const sd_cpu_object_index* x) {
+        if (!x) throw sd_failure(SD_ERR_INVALID, "null argument");
+        if (!x->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+        n = x->n;
+        for (uint64_t i = 0; i < n; i++) {
+            if (i == 0 || x->keys[i - 1] != x->keys[i]) head.push_back(i), links.push_back(0);
+            links.back() += x->links[i];
+        }
+    }
+    uint64_t owners(size_t s) const { return (s + 1 < head.size() ? head[s + 1] : n) - head[s]; }
+};
 }  // namespace
 
 extern "C" {
@@ -502,6 +520,90 @@ int sd_cpu_object_index_orphans(const sd_cpu_object_index* index, const uint64_t
     uint64_t o = 0;
     for (size_t s = 0; s < t.u.size(); s++)
         if (oi_unowned(t.entries[s])) orphans_out[o++] = t.u[s];
+    return SD_OK;
+    SD_GUARD_END
+}
+
+// The view by key of object_index.cpp over host arrays (mod.rs:189-225, :229-333): the runs of
+// equal keys walked once (oi_qualifies), key_links through the directory (oi_key_run).
+int sd_cpu_object_index_key_links(const sd_cpu_object_index* index, const uint64_t* keys, uint64_t m,
+                                  uint64_t* links_out, uint64_t* owners_out) {
+    SD_GUARD_BEGIN
+    if (!index || (m && !keys)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    for (uint64_t j = 0; j < m; j++) {
+        uint64_t lo, hi, sum = 0;
+        oi_key_run(index->keys.data(), index->dir.data(), index->bits, keys[j], &lo, &hi);
+        for (uint64_t i = lo; i < hi; i++) sum += index->links[i];
+        if (links_out) links_out[j] = sum;
+        if (owners_out) owners_out[j] = hi - lo;
+    }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_object_index_duplicates(const sd_cpu_object_index* index, uint64_t min_links, uint64_t min_owners,
+                                   uint64_t* keys_out, uint64_t* first_out, uint64_t* links_out, uint64_t* owners_out,
+                                   uint64_t capacity, uint64_t* count) {
+    SD_GUARD_BEGIN
+    if (count) *count = 0;
+    const groups_of g(index);
+    uint64_t r = 0;
+    for (size_t s = 0; s < g.head.size(); s++) r += oi_qualifies(g.links[s], g.owners(s), min_links, min_owners);
+    if (count) *count = r;
+    if ((!keys_out && !first_out && !links_out && !owners_out) || r == 0) return SD_OK;
+    if (capacity < r) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of rows");
+    uint64_t o = 0;
+    for (size_t s = 0; s < g.head.size(); s++) {
+        if (!oi_qualifies(g.links[s], g.owners(s), min_links, min_owners)) continue;
+        if (keys_out) keys_out[o] = index->keys[g.head[s]];
+        if (first_out) first_out[o] = index->vals[g.head[s]];
+        if (links_out) links_out[o] = g.links[s];
+        if (owners_out) owners_out[o] = g.owners(s);
+        o++;
+    }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_object_index_duplicate_entries(const sd_cpu_object_index* index, uint64_t min_links, uint64_t min_owners,
+                                          uint64_t* keys_out, uint64_t* ids_out, uint64_t* links_out,
+                                          uint64_t capacity, uint64_t* count) {
+    SD_GUARD_BEGIN
+    if (count) *count = 0;
+    const groups_of g(index);
+    uint64_t r = 0;
+    for (size_t s = 0; s < g.head.size(); s++)
+        if (oi_qualifies(g.links[s], g.owners(s), min_links, min_owners)) r += g.owners(s);
+    if (count) *count = r;
+    if ((!keys_out && !ids_out && !links_out) || r == 0) return SD_OK;
+    if (capacity < r) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of rows");
+    uint64_t o = 0;
+    for (size_t s = 0; s < g.head.size(); s++) {
+        if (!oi_qualifies(g.links[s], g.owners(s), min_links, min_owners)) continue;
+        for (uint64_t i = g.head[s]; i < g.head[s] + g.owners(s); i++, o++) {
+            if (keys_out) keys_out[o] = index->keys[i];
+            if (ids_out) ids_out[o] = index->vals[i];
+            if (links_out) links_out[o] = index->links[i];
+        }
+    }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_object_index_duplicate_stats(const sd_cpu_object_index* index, uint64_t out[8]) {
+    SD_GUARD_BEGIN
+    if (!out) throw sd_failure(SD_ERR_INVALID, "null argument");
+    const groups_of g(index);
+    for (int k = 0; k < 8; k++) out[k] = 0;
+    out[0] = g.head.size(), out[1] = index->n;
+    for (size_t s = 0; s < g.head.size(); s++) {
+        const uint64_t l = g.links[s], o = g.owners(s);
+        out[2] += l;
+        if (l >= 2) out[3] += 1, out[4] += l;
+        if (o >= 2) out[5] += 1, out[6] += o;
+        if (l > out[7]) out[7] = l;
+    }
     return SD_OK;
     SD_GUARD_END
 }

@@ -215,8 +215,9 @@ struct sd_object_index {
     sdi::DevBuf counts;                 // OI_COUNT_SLOTS u64, then one device count
     sdi::DevBuf scratch;                // sdk::index_insert_scratch / index_remove_scratch
     sdi::PinnedBuf host;                // an insert's survivor count; a removal's per-slice counts
-    sdi::PinnedBuf objects_host;        // sd_object_index_orphans' per-slice counts: a read of its own, which may
-                                        // run beside sd_cas_dedup_mgpu_indexed's use of `host`
+    sdi::PinnedBuf objects_host;        // sd_object_index_orphans' per-slice counts, and those and the stats of
+                                        // the view by key: reads of their own, which may run beside
+                                        // sd_cas_dedup_mgpu_indexed's use of `host`
     bool owners() const { return (flags & SD_OBJECT_INDEX_OWNERS) != 0; }
     sdk::oi_view view() const {
         return {keys[cur].as<uint64_t>(), vals[cur].as<uint64_t>(), dir.as<uint64_t>(), n, bits,

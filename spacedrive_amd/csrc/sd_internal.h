@@ -175,5 +175,28 @@ hipError_t index_objects_scatter(const void* scratch, uint64_t m, uint64_t* link
 const uint64_t* index_objects_counts(const void* scratch, uint64_t m);
 hipError_t index_orphans_flag(const void* scratch, uint64_t m, hipStream_t s);
 hipError_t index_orphans_compact(const void* scratch, uint64_t m, uint64_t* out, hipStream_t s);
+// By key, read-only (owners mode; object_index.h oi_key_run / oi_qualifies).  links(k) and
+// owners(k) per listed key, 0 and 0 for a key the index does not hold (either output may be
+// null); no scratch.
+hipError_t index_key_links(const oi_view& x, const uint64_t* q_keys, uint64_t m, uint64_t* links_out,
+                           uint64_t* owners_out, hipStream_t s);
+// The duplicate groups of an index of n > 0 entries in `scratch` (index_groups_scratch(n) bytes,
+// 18 B per entry and 17 KiB): the totals of every run of equal keys; then the qualifying groups
+// (or, `entries`, the entries of the qualifying groups) flagged and counted per slice in
+// index_groups_counts(scratch, n)[0 .. index_groups_slots(n)); then, once the host has checked
+// the count, one row per flagged group / entry in order (every output may be null); or the
+// eight stats of sd_object_index_duplicate_stats at index_groups_stats_at(scratch, n).
+size_t index_groups_scratch(uint64_t n);
+uint32_t index_groups_slots(uint64_t n);
+hipError_t index_groups_totals(const oi_view& x, void* scratch, hipStream_t s);
+hipError_t index_groups_flag(const oi_view& x, void* scratch, uint64_t min_links, uint64_t min_owners, bool entries,
+                             hipStream_t s);
+const uint64_t* index_groups_counts(const void* scratch, uint64_t n);
+hipError_t index_groups_compact(const oi_view& x, const void* scratch, uint64_t* keys_out, uint64_t* first_out,
+                                uint64_t* links_out, uint64_t* owners_out, hipStream_t s);
+hipError_t index_groups_compact_entries(const oi_view& x, const void* scratch, uint64_t* keys_out, uint64_t* ids_out,
+                                        uint64_t* links_out, hipStream_t s);
+hipError_t index_groups_stats(const oi_view& x, void* scratch, hipStream_t s);
+const uint64_t* index_groups_stats_at(const void* scratch, uint64_t n);
 hipError_t index_build_dir(const uint64_t* keys, uint64_t n, uint32_t bits, uint64_t* dir, hipStream_t s);
 }  // namespace sdk

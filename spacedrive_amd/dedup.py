@@ -433,6 +433,81 @@ def combine_orphans(per_shard):
     return np.zeros(0, np.uint64) if out is None else np.sort(out)
 
 
+def owners_groups_host(keys, vals, links):
+    """The duplicate groups of an owners-mode index given by its entries in (key, id) order (what
+    export_links returns): (group keys ascending, first owner, links(k), owners(k)), uint64 each.
+    The group-by a user of export_links runs on the host: np.unique and np.add.reduceat."""
+    keys, vals, links = (np.asarray(a, np.uint64).reshape(-1) for a in (keys, vals, links))
+    if len(keys) == 0:
+        return tuple(np.zeros(0, np.uint64) for _ in range(4))
+    gk, head, owners = np.unique(keys, return_index=True, return_counts=True)
+    return gk, vals[head], np.add.reduceat(links, head).astype(np.uint64), owners.astype(np.uint64)
+
+
+def _qualifies(gl, go, min_links, min_owners):
+    return (gl >= np.uint64(max(int(min_links), 1))) & (go >= np.uint64(max(int(min_owners), 1)))
+
+
+def owners_duplicates_host(keys, vals, links, min_links=0, min_owners=0):
+    """Host mirror of sd_object_index_duplicates: one row (key, first, links, owners) per key with
+    links(k) >= min_links and owners(k) >= min_owners (0 means 1), ascending."""
+    gk, gf, gl, go = owners_groups_host(keys, vals, links)
+    sel = _qualifies(gl, go, min_links, min_owners)
+    return gk[sel], gf[sel], gl[sel], go[sel]
+
+
+def owners_duplicate_entries_host(keys, vals, links, min_links=0, min_owners=0):
+    """Host mirror of sd_object_index_duplicate_entries: the entries (key, id, links) of the
+    qualifying keys, in (key, id) order."""
+    keys, vals, links = (np.asarray(a, np.uint64).reshape(-1) for a in (keys, vals, links))
+    _, _, gl, go = owners_groups_host(keys, vals, links)
+    sel = np.repeat(_qualifies(gl, go, min_links, min_owners), go.astype(np.int64))
+    return keys[sel], vals[sel], links[sel]
+
+
+def owners_key_links_host(keys, vals, links, q_keys):
+    """Host mirror of sd_object_index_key_links: (links(k), owners(k)) per listed key, 0 and 0 for
+    a key without an entry."""
+    gk, _, gl, go = owners_groups_host(keys, vals, links)
+    q = np.ascontiguousarray(q_keys, dtype=np.uint64).reshape(-1)
+    if len(gk) == 0:
+        return np.zeros(len(q), np.uint64), np.zeros(len(q), np.uint64)
+    at = np.minimum(np.searchsorted(gk, q), len(gk) - 1)
+    hit = gk[at] == q
+    return np.where(hit, gl[at], np.uint64(0)), np.where(hit, go[at], np.uint64(0))
+
+
+def owners_duplicate_stats_host(keys, vals, links):
+    """Host mirror of sd_object_index_duplicate_stats: uint64 [8] = keys, entries, links, keys
+    with links >= 2, their links, keys with owners >= 2, their entries, the largest links(k)."""
+    _, _, gl, go = owners_groups_host(keys, vals, links)
+    l2, o2 = gl >= np.uint64(2), go >= np.uint64(2)
+    return np.array([len(gl), int(go.sum()), int(gl.sum()), int(l2.sum()), int(gl[l2].sum()), int(o2.sum()),
+                     int(go[o2].sum()), int(gl.max()) if len(gl) else 0], dtype=np.uint64)
+
+
+def combine_duplicates(per_shard):
+    """The shards' rows of duplicates (or duplicate_entries) -> the library's: per_shard is a list
+    of column tuples, one per rank IN RANK ORDER.  sd_dedup_partition's destination is monotone in
+    the key, so the shards' groups are disjoint and their rows concatenated are still ascending."""
+    cols = list(zip(*[[np.asarray(host_u64(c)) for c in p] for p in per_shard]))
+    return tuple(np.concatenate(c) for c in cols)
+
+
+def combine_duplicate_stats(per_shard):
+    """The shards' duplicate_stats -> the library's: the rows add up, [7] takes the maximum."""
+    s = np.stack([np.asarray(p, np.uint64) for p in per_shard])
+    out = s.sum(axis=0, dtype=np.uint64)
+    out[7] = s[:, 7].max()
+    return out
+
+
+def combine_key_links(per_shard):
+    """The shards' answers of key_links for one key list -> the library's: a key lives in one
+    shard, so the rows add up."""
+    return combine_object_links(per_shard)
+
+
 def owners_indexed_host(records: np.ndarray, rep: np.ndarray, keys: np.ndarray, vals: np.ndarray,
                         chunk_size: int = 100):
     """Host mirror of sd_dedup_owners_indexed on grouped records (int64 [m, 2] sorted by (key,

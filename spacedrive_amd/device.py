@@ -183,7 +183,9 @@ class ObjectIndex:
     takes one, an entry leaves at zero, and the first owner of a key is its smallest Object
     id -- the host never asks the DB who else owns a cas_id.  Its view by Object
     (``object_links``, ``orphans``; ``apply(..., orphans=True)``) answers the orphan remover's
-    query too: which of these Objects own nothing any more (orphan_remover.rs:57-95)."""
+    query too: which of these Objects own nothing any more (orphan_remover.rs:57-95).  Its view
+    by key (``key_links``, ``duplicates``, ``duplicate_entries``, ``duplicate_stats``) lists the
+    cas_ids that several file_paths have or that are split over several Objects."""
 
     def __init__(self, ctx: Context, nparts: int = 1, part: int = 0, owners: bool = False):
         self.ctx, self.nparts, self.part, self.owners_mode = ctx, nparts, part, bool(owners)
@@ -387,6 +389,61 @@ class ObjectIndex:
         r = int(pairs.shape[0])
         return self.orphans(pairs.reshape(-1)[1:] if r else pairs.reshape(-1), stream, stride=2, m=r)
 
+    # -------------------------------------------------------------- the view by key (owners mode)
+    def key_links(self, d_keys: torch.Tensor, stream=None):
+        """sd_object_index_key_links -> (links, owners) int64 [m]: per listed key (any order,
+        repeats allowed) the sum of its entries' link counts and the number of its entries
+        (Objects) in this index; 0 and 0 for a key it does not hold."""
+        m = int(d_keys.numel())
+        assert d_keys.dtype == torch.int64 and (m == 0 or (d_keys.is_cuda and d_keys.is_contiguous()))
+        dev = torch.device("cuda", self.ctx.device)
+        links, owners = (torch.empty(max(m, 1), dtype=torch.int64, device=dev) for _ in range(2))
+        check(lib().sd_object_index_key_links(self.ctx.handle, self.handle, _ptr(d_keys) if m else None, m,
+                                              _ptr(links), _ptr(owners), _stream(stream)))
+        return links[:m], owners[:m]
+
+    def _group_rows(self, fn, ncols: int, min_links: int, min_owners: int, stream, out, capacity):
+        """The capacity convention of the two group calls: without `out` the rows are counted
+        first (every output NULL) and then written into tensors of exactly that many rows; with
+        `out` (ncols int64 tensors, None for a column not wanted) and `capacity` short, the call
+        raises SdCasError (SD_ERR_CAPACITY, ``.needed`` rows) and writes nothing."""
+        st = _stream(stream)
+        count = ctypes.c_uint64(0)
+        if out is None:
+            check(fn(self.ctx.handle, self.handle, min_links, min_owners, *([None] * ncols), 0, ctypes.byref(count), st))
+            capacity = int(count.value)
+            dev = torch.device("cuda", self.ctx.device)
+            out = tuple(torch.empty(max(capacity, 1), dtype=torch.int64, device=dev) for _ in range(ncols))
+        assert len(out) == ncols and all(t is None or (t.dtype == torch.int64 and t.is_cuda and t.is_contiguous()) for t in out)
+        cap = int(min(t.numel() for t in out if t is not None) if capacity is None else capacity)
+        try:
+            check(fn(self.ctx.handle, self.handle, min_links, min_owners, *(None if t is None else _ptr(t) for t in out),
+                     cap, ctypes.byref(count), st))
+        except SdCasError as e:
+            e.needed = int(count.value)
+            raise
+        return tuple(None if t is None else t[:int(count.value)] for t in out)
+
+    def duplicates(self, min_links: int = 0, min_owners: int = 0, stream=None, out=None, capacity: Optional[int] = None):
+        """sd_object_index_duplicates -> (keys, first, links, owners) int64 [count]: one row per key
+        with links(k) >= min_links and owners(k) >= min_owners (0 means 1), ascending as u64.
+        min_links=2: content more than one file_path has; min_owners=2: content split over
+        several Objects.  `out` / `capacity` as _group_rows."""
+        return self._group_rows(lib().sd_object_index_duplicates, 4, min_links, min_owners, stream, out, capacity)
+
+    def duplicate_entries(self, min_links: int = 0, min_owners: int = 0, stream=None, out=None,
+                          capacity: Optional[int] = None):
+        """sd_object_index_duplicate_entries -> (keys, ids, links) int64 [count]: the entries of the
+        qualifying keys in (key, id) order -- export_links filtered to the duplicate groups."""
+        return self._group_rows(lib().sd_object_index_duplicate_entries, 3, min_links, min_owners, stream, out, capacity)
+
+    def duplicate_stats(self, stream=None) -> np.ndarray:
+        """sd_object_index_duplicate_stats -> uint64 [8]: keys, entries, links, keys with links >= 2,
+        their links, keys with owners >= 2, their entries, the largest links(k)."""
+        out = np.zeros(8, np.uint64)
+        check(lib().sd_object_index_duplicate_stats(self.ctx.handle, self.handle, _ptr(out), _stream(stream)))
+        return out
+
     def apply_hex(self, rm_cas_ids, rm_object_ids, in_cas_ids, in_object_ids):
         """apply from the DB's strings -> (entries removed, entries taken)."""
         bufs, ids = [], []
@@ -561,6 +618,43 @@ class HostObjectIndex:
             e.needed = int(count.value)
             raise
         return out[:int(count.value)]
+
+    def key_links(self, keys):
+        """sd_cpu_object_index_key_links -> (links, owners) uint64 [m] per listed key."""
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        links, owners = np.zeros(max(k.size, 1), np.uint64), np.zeros(max(k.size, 1), np.uint64)
+        check(lib().sd_cpu_object_index_key_links(self.handle, _ptr(k) if k.size else None, k.size, _ptr(links),
+                                                  _ptr(owners)))
+        return links[:k.size], owners[:k.size]
+
+    def _group_rows(self, fn, ncols: int, min_links: int, min_owners: int, capacity):
+        count = ctypes.c_uint64(0)
+        if capacity is None:  # count first, then exactly that many rows
+            check(fn(self.handle, min_links, min_owners, *([None] * ncols), 0, ctypes.byref(count)))
+            capacity = int(count.value)
+        out = tuple(np.zeros(max(int(capacity), 1), np.uint64) for _ in range(ncols))
+        try:
+            check(fn(self.handle, min_links, min_owners, *(_ptr(a) for a in out), int(capacity), ctypes.byref(count)))
+        except SdCasError as e:
+            e.needed = int(count.value)
+            raise
+        return tuple(a[:int(count.value)] for a in out)
+
+    def duplicates(self, min_links: int = 0, min_owners: int = 0, capacity: Optional[int] = None):
+        """sd_cpu_object_index_duplicates -> (keys, first, links, owners) uint64 [count], ascending;
+        `capacity` (rows) below the count raises SdCasError (SD_ERR_CAPACITY, ``.needed``)."""
+        return self._group_rows(lib().sd_cpu_object_index_duplicates, 4, min_links, min_owners, capacity)
+
+    def duplicate_entries(self, min_links: int = 0, min_owners: int = 0, capacity: Optional[int] = None):
+        """sd_cpu_object_index_duplicate_entries -> (keys, ids, links) uint64 [count] in (key, id)
+        order; `capacity` as duplicates."""
+        return self._group_rows(lib().sd_cpu_object_index_duplicate_entries, 3, min_links, min_owners, capacity)
+
+    def duplicate_stats(self) -> np.ndarray:
+        """sd_cpu_object_index_duplicate_stats -> uint64 [8], as ObjectIndex.duplicate_stats."""
+        out = np.zeros(8, np.uint64)
+        check(lib().sd_cpu_object_index_duplicate_stats(self.handle, _ptr(out)))
+        return out
 
     def _orphans_of(self, pairs: np.ndarray) -> np.ndarray:
         r = len(pairs)
