@@ -22,13 +22,60 @@ void check_index(const sd_cas_ctx* ctx, const sd_object_index* index) {
     if (index->ctx != ctx) throw sd_failure(SD_ERR_INVALID, "the index belongs to another context");
 }
 
+void require_owners(const sd_object_index* index) {
+    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+}
+
+// m cas_ids of 17 bytes each as keys; `what` names the list in the error ("cas_id", ...)
+void keys_from_hex(const char* hex17, uint64_t m, const char* what, uint64_t* keys) {
+    for (uint64_t i = 0; i < m; i++)
+        if (!oi_key_from_hex(hex17 + 17 * i, &keys[i]))
+            throw sd_failure(SD_ERR_INVALID, std::string(what) + " " + std::to_string(i) + " is not 16 lower-case hex digits");
+}
+
+// the per-slice counts of a flagging pass in one copy and one sync, summed
+uint64_t sum_slots(const uint64_t* dev_counts, uint32_t slots, const sdi::PinnedBuf& host_buf, hipStream_t s) {
+    HIP_CHECK(hipMemcpyAsync(host_buf.p, dev_counts, slots * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const uint64_t* c = reinterpret_cast<const uint64_t*>(host_buf.p);
+    uint64_t r = 0;
+    for (uint32_t k = 0; k < slots; k++) r += c[k];
+    return r;
+}
+
+// Every rewrite goes into the other buffer pair (triple in the owners mode) and swaps: before
+// the kernel, grow_other makes that side hold `cap` entries (grow-only); after it, swap_in waits
+// for the kernel (it read the old buffers and the old directory), grows the old side too, swaps,
+// and rebuilds the directory for the new count (bits re-chosen; rebuilt even at an unchanged
+// count: the keys moved; the directory's buffer never shrinks).
+void grow_other(sd_object_index* x, uint64_t cap) {
+    const int to = 1 - x->cur;
+    x->keys[to].ensure(cap * sizeof(uint64_t));
+    x->vals[to].ensure(cap * sizeof(uint64_t));
+    if (x->owners()) x->links[to].ensure(cap * sizeof(uint64_t));
+}
+
+void swap_in(sd_object_index* x, int to, uint64_t cap, uint64_t n_new, hipStream_t s) {
+    HIP_CHECK(hipStreamSynchronize(s));
+    x->keys[x->cur].ensure(cap * sizeof(uint64_t));
+    x->vals[x->cur].ensure(cap * sizeof(uint64_t));
+    if (x->owners()) x->links[x->cur].ensure(cap * sizeof(uint64_t));
+    x->cap = cap;
+    x->cur = to;
+    x->n = n_new;
+    x->bits = oi_dir_bits(x->n);
+    x->dir.ensure(((1ull << x->bits) + 1) * sizeof(uint64_t));
+    HIP_CHECK(sdk::index_build_dir(x->keys[to].as<uint64_t>(), x->n, x->bits, x->dir.as<uint64_t>(), s));
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
 // the checks both reads by Object share; the index comes back writable for its scratch alone:
 // keys, values, links and directory are only read
 sd_object_index* objects_query(sd_cas_ctx* ctx, const sd_object_index* index, const uint64_t* d_object_ids,
                                uint64_t id_stride, uint64_t m) {
     if (!ctx || !index || (m && !d_object_ids)) throw sd_failure(SD_ERR_INVALID, "null argument");
     check_index(ctx, index);
-    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    require_owners(index);
     if (id_stride != 1 && id_stride != 2) throw sd_failure(SD_ERR_INVALID, "id_stride is 1 or 2 (u64 units)");
     return const_cast<sd_object_index*>(index);
 }
@@ -37,7 +84,7 @@ sd_object_index* objects_query(sd_cas_ctx* ctx, const sd_object_index* index, co
 sd_object_index* groups_query(sd_cas_ctx* ctx, const sd_object_index* index) {
     if (!ctx || !index) throw sd_failure(SD_ERR_INVALID, "null argument");
     check_index(ctx, index);
-    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    require_owners(index);
     return const_cast<sd_object_index*>(index);
 }
 
@@ -52,14 +99,9 @@ void groups_select(sd_object_index* x, uint64_t min_links, uint64_t min_owners, 
     const sdk::oi_view v = x->view();
     HIP_CHECK(sdk::index_groups_totals(v, x->scratch.p, s));
     HIP_CHECK(sdk::index_groups_flag(v, x->scratch.p, min_links, min_owners, entries, s));
-    const uint32_t slots = sdk::index_groups_slots(x->n);
     x->objects_host.ensure(sdk::OI_COUNT_SLOTS * sizeof(uint64_t));
-    HIP_CHECK(hipMemcpyAsync(x->objects_host.p, sdk::index_groups_counts(x->scratch.p, x->n), slots * sizeof(uint64_t),
-                             hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    const uint64_t* c = reinterpret_cast<const uint64_t*>(x->objects_host.p);
-    uint64_t r = 0;
-    for (uint32_t k = 0; k < slots; k++) r += c[k];
+    const uint64_t r =
+        sum_slots(sdk::index_groups_counts(x->scratch.p, x->n), sdk::index_slots(x->n), x->objects_host, s);
     if (r > x->n) throw sd_failure(SD_ERR_INTERNAL, "duplicates: more rows than entries");
     if (count) *count = r;
     if (!any_output || r == 0) return;
@@ -79,12 +121,7 @@ void groups_select(sd_object_index* x, uint64_t min_links, uint64_t min_owners, 
 // links are taken in place, O(log n) per distinct pair, and capacity cannot be short of 0 rows.
 void finish_remove(sd_object_index* x, uint64_t* d_removed_out, uint64_t capacity, uint64_t* removed, hipStream_t s,
                    const uint64_t* asked = nullptr, uint64_t m = 0) {
-    const uint32_t slots = sdk::index_remove_slots(x->n);
-    HIP_CHECK(hipMemcpyAsync(x->host.p, x->counts.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    const uint64_t* c = reinterpret_cast<const uint64_t*>(x->host.p);
-    uint64_t r = 0;
-    for (uint32_t k = 0; k < slots; k++) r += c[k];
+    const uint64_t r = sum_slots(x->counts.as<uint64_t>(), sdk::index_slots(x->n), x->host, s);
     if (r > x->n) throw sd_failure(SD_ERR_INTERNAL, "remove: more dropped entries than entries");
     if (removed) *removed = r;
     if (r == 0) {  // no entry leaves: keys, values and directory stand; a removal with ids (of m
@@ -105,12 +142,7 @@ void finish_remove(sd_object_index* x, uint64_t* d_removed_out, uint64_t capacit
     else
         HIP_CHECK(sdk::index_remove_compact(x->view(), x->scratch.p, x->counts.as<uint64_t>(),
                                             x->keys[to].as<uint64_t>(), x->vals[to].as<uint64_t>(), d_removed_out, s));
-    HIP_CHECK(hipStreamSynchronize(s));  // the compaction read the old buffers
-    x->cur = to;
-    x->n -= r;
-    x->bits = oi_dir_bits(x->n);  // re-chosen for the new count; the directory's buffer never shrinks
-    HIP_CHECK(sdk::index_build_dir(x->keys[to].as<uint64_t>(), x->n, x->bits, x->dir.as<uint64_t>(), s));
-    HIP_CHECK(hipStreamSynchronize(s));
+    swap_in(x, to, x->cap, x->n - r, s);
 }
 
 // Owners-mode insert: aggregate the batch, select the absent pairs, merge them in by (key, id)
@@ -135,23 +167,11 @@ void insert_owners(sd_object_index* x, const uint64_t* d_keys, const uint64_t* d
     }
     const uint64_t cap = oi_grow_capacity(x->n + r, x->cap);
     const int to = 1 - x->cur;
-    x->keys[to].ensure(cap * sizeof(uint64_t));
-    x->vals[to].ensure(cap * sizeof(uint64_t));
-    x->links[to].ensure(cap * sizeof(uint64_t));
+    grow_other(x, cap);
     HIP_CHECK(sdk::index_owners_merge(x->view(), nk, nv, nl, r, x->keys[to].as<uint64_t>(), x->vals[to].as<uint64_t>(),
                                       x->links[to].as<uint64_t>(), s));
     HIP_CHECK(sdk::index_owners_add_links(x->scratch.p, m, nk, nv, r, x->links[to].as<uint64_t>(), s));
-    HIP_CHECK(hipStreamSynchronize(s));  // the merge read the old buffers and the old directory
-    x->keys[x->cur].ensure(cap * sizeof(uint64_t));
-    x->vals[x->cur].ensure(cap * sizeof(uint64_t));
-    x->links[x->cur].ensure(cap * sizeof(uint64_t));
-    x->cap = cap;
-    x->cur = to;
-    x->n += r;
-    x->bits = oi_dir_bits(x->n);
-    x->dir.ensure(((1ull << x->bits) + 1) * sizeof(uint64_t));
-    HIP_CHECK(sdk::index_build_dir(x->keys[to].as<uint64_t>(), x->n, x->bits, x->dir.as<uint64_t>(), s));
-    HIP_CHECK(hipStreamSynchronize(s));
+    swap_in(x, to, cap, x->n + r, s);
 }
 
 }  // namespace
@@ -240,19 +260,9 @@ int sd_object_index_insert(sd_cas_ctx* ctx, sd_object_index* index, const uint64
     // merge into the other buffer pair (grown first if short; grow-only), then swap
     const uint64_t cap = oi_grow_capacity(x->n + r, x->cap);
     const int to = 1 - x->cur;
-    x->keys[to].ensure(cap * sizeof(uint64_t));
-    x->vals[to].ensure(cap * sizeof(uint64_t));
+    grow_other(x, cap);
     HIP_CHECK(sdk::index_merge(x->view(), nk, nv, r, x->keys[to].as<uint64_t>(), x->vals[to].as<uint64_t>(), s));
-    HIP_CHECK(hipStreamSynchronize(s));  // the merge read the old buffers and the old directory
-    x->keys[x->cur].ensure(cap * sizeof(uint64_t));
-    x->vals[x->cur].ensure(cap * sizeof(uint64_t));
-    x->cap = cap;
-    x->cur = to;
-    x->n += r;
-    x->bits = oi_dir_bits(x->n);  // re-chosen when n crosses a power of two
-    x->dir.ensure(((1ull << x->bits) + 1) * sizeof(uint64_t));
-    HIP_CHECK(sdk::index_build_dir(x->keys[to].as<uint64_t>(), x->n, x->bits, x->dir.as<uint64_t>(), s));
-    HIP_CHECK(hipStreamSynchronize(s));
+    swap_in(x, to, cap, x->n + r, s);
     return SD_OK;
     SD_GUARD_END
 }
@@ -265,9 +275,7 @@ int sd_object_index_insert_hex(sd_cas_ctx* ctx, sd_object_index* index, const ch
     if (taken) *taken = 0;
     if (m == 0) return SD_OK;
     std::vector<uint64_t> keys(m);
-    for (uint64_t i = 0; i < m; i++)
-        if (!oi_key_from_hex(hex17 + 17 * i, &keys[i]))
-            throw sd_failure(SD_ERR_INVALID, "cas_id " + std::to_string(i) + " is not 16 lower-case hex digits");
+    keys_from_hex(hex17, m, "cas_id", keys.data());
     ctx->bind();
     sdi::DevBuf dk, dv;
     dk.alloc(m * sizeof(uint64_t));
@@ -335,9 +343,7 @@ int sd_object_index_remove_hex(sd_cas_ctx* ctx, sd_object_index* index, const ch
     if (removed) *removed = 0;
     if (m == 0) return SD_OK;
     std::vector<uint64_t> keys(m);
-    for (uint64_t i = 0; i < m; i++)
-        if (!oi_key_from_hex(hex17 + 17 * i, &keys[i]))
-            throw sd_failure(SD_ERR_INVALID, "cas_id " + std::to_string(i) + " is not 16 lower-case hex digits");
+    keys_from_hex(hex17, m, "cas_id", keys.data());
     ctx->bind();
     sdi::DevBuf dk, dv;
     dk.alloc(m * sizeof(uint64_t));
@@ -367,7 +373,7 @@ int sd_object_index_apply(sd_cas_ctx* ctx, sd_object_index* index, const uint64_
     if (removed) *removed = 0;
     if (taken) *taken = 0;
     sd_object_index* x = index;
-    if (!x->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    require_owners(x);
     if (m_rm && !d_rm_ids)
         throw sd_failure(SD_ERR_INVALID, "apply takes links of (key, id) pairs; every owner of a key: sd_object_index_remove");
     if (x->n == 0) m_rm = 0;  // nothing to take from
@@ -377,8 +383,7 @@ int sd_object_index_apply(sd_cas_ctx* ctx, sd_object_index* index, const uint64_
     x->scratch.ensure(sdk::index_apply_scratch(x->n, m_rm, m_in));
     HIP_CHECK(sdk::index_apply_flag(x->view(), x->nparts, x->part, d_rm_keys, d_rm_ids, m_rm, d_in_keys, d_in_ids, m_in,
                                     x->scratch.p, x->counts.as<uint64_t>(), s));
-    uint32_t slots_out = 0, slots_in = 0;
-    sdk::index_apply_slots(x->n, m_in, &slots_out, &slots_in);
+    const uint32_t slots_out = sdk::index_slots(x->n), slots_in = sdk::index_slots(m_in);
     x->host.ensure(2 * sdk::OI_COUNT_SLOTS * sizeof(uint64_t));
     HIP_CHECK(hipMemcpyAsync(x->host.p, sdk::index_apply_counts(x->scratch.p, x->n),
                              (slots_out + slots_in) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -400,22 +405,10 @@ int sd_object_index_apply(sd_cas_ctx* ctx, sd_object_index* index, const uint64_
     const uint64_t n_new = x->n - r_out + r_in;
     const uint64_t cap = oi_grow_capacity(n_new, x->cap);
     const int to = 1 - x->cur;
-    x->keys[to].ensure(cap * sizeof(uint64_t));
-    x->vals[to].ensure(cap * sizeof(uint64_t));
-    x->links[to].ensure(cap * sizeof(uint64_t));
+    grow_other(x, cap);
     HIP_CHECK(sdk::index_apply_merge(x->view(), x->scratch.p, m_rm, m_in, r_in, x->keys[to].as<uint64_t>(),
                                      x->vals[to].as<uint64_t>(), x->links[to].as<uint64_t>(), d_removed_out, s));
-    HIP_CHECK(hipStreamSynchronize(s));  // the merge read the old buffers and the old directory
-    x->keys[x->cur].ensure(cap * sizeof(uint64_t));
-    x->vals[x->cur].ensure(cap * sizeof(uint64_t));
-    x->links[x->cur].ensure(cap * sizeof(uint64_t));
-    x->cap = cap;
-    x->cur = to;
-    x->n = n_new;
-    x->bits = oi_dir_bits(x->n);  // rebuilt even at an unchanged count: the keys moved
-    x->dir.ensure(((1ull << x->bits) + 1) * sizeof(uint64_t));
-    HIP_CHECK(sdk::index_build_dir(x->keys[to].as<uint64_t>(), x->n, x->bits, x->dir.as<uint64_t>(), s));
-    HIP_CHECK(hipStreamSynchronize(s));
+    swap_in(x, to, cap, n_new, s);
     return SD_OK;
     SD_GUARD_END
 }
@@ -429,19 +422,15 @@ int sd_object_index_apply_hex(sd_cas_ctx* ctx, sd_object_index* index, const cha
     check_index(ctx, index);
     if (removed) *removed = 0;
     if (taken) *taken = 0;
-    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    require_owners(index);
     if (m_rm && !rm_ids)
         throw sd_failure(SD_ERR_INVALID, "apply takes links of (key, id) pairs; every owner of a key: sd_object_index_remove_hex");
     if (m_rm == 0 && m_in == 0) return SD_OK;
     // both lists are parsed before anything is uploaded: a malformed cas_id changes nothing
     std::vector<uint64_t> host(2 * (m_rm + m_in));
     uint64_t *rk = host.data(), *rv = rk + m_rm, *ik = rv + m_rm, *iv = ik + m_in;
-    for (uint64_t i = 0; i < m_rm; i++)
-        if (!oi_key_from_hex(rm_hex17 + 17 * i, &rk[i]))
-            throw sd_failure(SD_ERR_INVALID, "removed cas_id " + std::to_string(i) + " is not 16 lower-case hex digits");
-    for (uint64_t i = 0; i < m_in; i++)
-        if (!oi_key_from_hex(in_hex17 + 17 * i, &ik[i]))
-            throw sd_failure(SD_ERR_INVALID, "inserted cas_id " + std::to_string(i) + " is not 16 lower-case hex digits");
+    keys_from_hex(rm_hex17, m_rm, "removed cas_id", rk);
+    keys_from_hex(in_hex17, m_in, "inserted cas_id", ik);
     for (uint64_t i = 0; i < m_rm; i++) rv[i] = rm_ids[i];
     for (uint64_t i = 0; i < m_in; i++) iv[i] = in_ids[i];
     ctx->bind();
@@ -490,7 +479,7 @@ int sd_object_index_links(sd_cas_ctx* ctx, const sd_object_index* index, const u
     if (!ctx || !index || (m && (!d_keys || !d_object_ids || !d_links_out)))
         throw sd_failure(SD_ERR_INVALID, "null argument");
     check_index(ctx, index);
-    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    require_owners(index);
     if (m == 0) return SD_OK;
     ctx->bind();
     HIP_CHECK(sdk::index_links(index->view(), d_keys, d_object_ids, m, d_links_out, ctx->pick(stream)));
@@ -503,7 +492,7 @@ int sd_object_index_export_links(sd_cas_ctx* ctx, const sd_object_index* index, 
     SD_GUARD_BEGIN
     if (!ctx || !index) throw sd_failure(SD_ERR_INVALID, "null argument");
     check_index(ctx, index);
-    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    require_owners(index);
     if (index->n && (!d_keys_out || !d_ids_out || !d_links_out)) throw sd_failure(SD_ERR_INVALID, "null argument");
     if (capacity < index->n) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the index's count");
     if (index->n == 0) return SD_OK;
@@ -551,14 +540,8 @@ int sd_object_index_orphans(sd_cas_ctx* ctx, const sd_object_index* index, const
     HIP_CHECK(sdk::index_objects_totals(x->view(), d_object_ids, id_stride, m, false, x->scratch.p, s));
     HIP_CHECK(sdk::index_orphans_flag(x->scratch.p, m, s));
     // the count in one copy and one sync, checked against `capacity` before anything is written
-    const uint32_t slots = sdk::index_objects_slots(m);
     x->objects_host.ensure(sdk::OI_COUNT_SLOTS * sizeof(uint64_t));
-    HIP_CHECK(hipMemcpyAsync(x->objects_host.p, sdk::index_objects_counts(x->scratch.p, m), slots * sizeof(uint64_t),
-                             hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    const uint64_t* c = reinterpret_cast<const uint64_t*>(x->objects_host.p);
-    uint64_t r = 0;
-    for (uint32_t k = 0; k < slots; k++) r += c[k];
+    const uint64_t r = sum_slots(sdk::index_objects_counts(x->scratch.p, m), sdk::index_slots(m), x->objects_host, s);
     if (r > m) throw sd_failure(SD_ERR_INTERNAL, "orphans: more orphans than listed ids");
     if (count) *count = r;
     if (!d_orphans_out || r == 0) return SD_OK;
@@ -579,7 +562,7 @@ int sd_object_index_key_links(sd_cas_ctx* ctx, const sd_object_index* index, con
     SD_GUARD_BEGIN
     if (!ctx || !index || (m && !d_keys)) throw sd_failure(SD_ERR_INVALID, "null argument");
     check_index(ctx, index);
-    if (!index->owners()) throw sd_failure(SD_ERR_INVALID, "the index was not created with SD_OBJECT_INDEX_OWNERS");
+    require_owners(index);
     if (m == 0) return SD_OK;
     ctx->bind();
     HIP_CHECK(sdk::index_key_links(index->view(), d_keys, m, d_links_out, d_owners_out, ctx->pick(stream)));

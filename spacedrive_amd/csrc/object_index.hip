@@ -15,11 +15,15 @@
 // lookup: object_index.h (shared with the host mirror, object_index_host.cpp).
 //
 // Ordered compaction (new heads; an insert's surviving pairs; a removal's survivors and its
-// dropped entries) without atomics on the data path: a fixed grid in which workgroup b
-// owns the contiguous slice b of the input; the
-// flagging pass leaves one count per workgroup, and the compaction pass gives each
-// workgroup the sum of the counts before it, then ranks its flags in order (ballot /
-// popcount inside a wave, LDS counts across the four waves).
+// dropped entries; distinct pairs, ids and groups) without atomics on the data path: a fixed
+// grid in which workgroup b owns the contiguous slice b of the input.  Two kernel skeletons hold
+// the slice and tile arithmetic, and every such pass is a functor of a few lines over one of them:
+//   sliced_flag     a predicate per position -> flags[i] and one count per workgroup
+//   sliced_compact  each workgroup takes the sum of the counts before it, ranks its flags in
+//                   order (ballot / popcount inside a wave, LDS counts across the four waves)
+//                   and hands every position its slot
+// k_apply_merge, k_group_totals, k_entry_flag, k_object_totals, k_key_links and k_group_stats use
+// the slices in ways of their own and stand alone.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -95,6 +99,78 @@ __device__ __forceinline__ uint64_t tile_slot(bool flag, uint64_t& run) {
     return slot;
 }
 
+// The flagging skeleton: workgroup b passes every position i of its slice of [0, n) and n to the
+// functor, stores the answer at flags[i] (unless flags is null: a count-only pass) and leaves
+// its count of true answers at counts[b].  n is *d_n if d_n is set (a count the host never
+// waited for), else the value.  The functor may write side outputs of its own.
+template <class F>
+__global__ __launch_bounds__(256) void sliced_flag(F f, const uint64_t* __restrict__ d_n, uint64_t n,
+                                                   uint8_t* __restrict__ flags, uint64_t* __restrict__ counts) {
+    if (d_n) n = *d_n;
+    const oi_slice sl = oi_slice_of(n);
+    uint32_t mine = 0;
+    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+        const bool flag = f(i, n);
+        if (flags) flags[i] = flag ? 1 : 0;
+        mine += flag;
+    }
+    block_count(mine, counts);
+}
+
+// The compaction skeleton over the same slices: slot = the flagged positions before i (counts[]
+// of the flagging pass before this workgroup, tile_slot inside it), which is a flagged
+// position's row of the output, and taken from i an unflagged position's rank among the
+// unflagged.  Whole tiles: every lane of the workgroup makes the same trips (tile_slot has
+// barriers); the lanes past the slice's end are unflagged and emit nothing.  f.flag(i) says
+// whether i is flagged, f.emit(i, flag, slot, n) writes; *total (may be null) takes the count.
+template <class F>
+__global__ __launch_bounds__(256) void sliced_compact(F f, const uint64_t* __restrict__ d_n, uint64_t n,
+                                                      const uint64_t* __restrict__ counts,
+                                                      uint64_t* __restrict__ total) {
+    uint64_t run = block_base(counts, total);
+    if (d_n) n = *d_n;
+    const oi_slice sl = oi_slice_of(n);
+    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
+        const uint64_t i = base + threadIdx.x;
+        const bool act = i < sl.hi;
+        const bool flag = act && f.flag(i);
+        const uint64_t slot = tile_slot(flag, run);
+        if (act) f.emit(i, flag, slot, n);
+    }
+}
+
+// the flags of a sliced_flag pass, for the compactions that read them
+struct from_flags {
+    const uint8_t* __restrict__ flags;
+    __device__ bool flag(uint64_t i) const { return flags[i] != 0; }
+};
+
+template <class F>
+void launch_flag(uint32_t grid, hipStream_t s, F f, const uint64_t* d_n, uint64_t n, uint8_t* flags,
+                 uint64_t* counts) {
+    hipLaunchKernelGGL(sliced_flag<F>, dim3(grid), dim3(256), 0, s, f, d_n, n, flags, counts);
+}
+
+template <class F>
+void launch_compact(uint32_t grid, hipStream_t s, F f, const uint64_t* d_n, uint64_t n, const uint64_t* counts,
+                    uint64_t* total) {
+    hipLaunchKernelGGL(sliced_compact<F>, dim3(grid), dim3(256), 0, s, f, d_n, n, counts, total);
+}
+
+// the first of a run of equal values in a sorted array: the listed ids by Object, the groups
+// (runs of equal keys) of the index
+struct run_head {
+    const uint64_t* __restrict__ a;
+    __device__ bool operator()(uint64_t i, uint64_t) const { return i == 0 || a[i - 1] != a[i]; }
+};
+
+// bytes already written, counted per slice: the marks of k_remove_mark (0 or 1), apply's
+// leaving entries (mark 1)
+struct marked {
+    const uint8_t* __restrict__ mark;
+    __device__ bool operator()(uint64_t i, uint64_t) const { return mark[i] == 1; }
+};
+
 __global__ __launch_bounds__(256) void k_index_lookup(const uint64_t* __restrict__ keys,
                                                       const uint64_t* __restrict__ vals,
                                                       const uint64_t* __restrict__ dir, uint32_t bits,
@@ -111,48 +187,38 @@ __global__ __launch_bounds__(256) void k_index_lookup(const uint64_t* __restrict
 // The indexed owner rule per grouped record (sorted by (key, index): neighbouring lanes read
 // neighbouring index lines).  existing[i] = 1 if owner[i] is an Object id of the index, else
 // owner[i] is what k_owners writes; bit 1 of existing[i] carries the new-head flag (a group's
-// first record whose key the index does not have) to k_heads_compact, which clears it.
-__global__ __launch_bounds__(256) void k_owners_indexed(const uint64_t* __restrict__ keys,
-                                                        const uint64_t* __restrict__ vals,
-                                                        const uint64_t* __restrict__ dir, uint32_t bits,
-                                                        const uint64_t* __restrict__ rec, uint64_t m,
-                                                        const uint64_t* __restrict__ rep, uint64_t chunk,
-                                                        uint64_t* __restrict__ owner, uint8_t* __restrict__ existing,
-                                                        uint64_t* __restrict__ counts) {
-    const oi_slice sl = oi_slice_of(m);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+// first record whose key the index does not have) to heads_out, which clears it.
+struct owners_indexed_rule {
+    const uint64_t *__restrict__ keys, *__restrict__ vals, *__restrict__ dir;
+    uint32_t bits;
+    const uint64_t *__restrict__ rec, *__restrict__ rep;
+    uint64_t chunk;
+    uint64_t* __restrict__ owner;
+    uint8_t* __restrict__ existing;
+    __device__ bool operator()(uint64_t i, uint64_t) const {
         const uint64_t key = rec[2 * i], idx = rec[2 * i + 1], r = rep[i];
         uint64_t at;
         const bool f = oi_find(keys, dir, bits, key, &at);
         const bool head = !f && (i == 0 || rec[2 * (i - 1)] != key);
         owner[i] = f ? vals[at] : (idx / chunk == r / chunk ? idx : r);
         existing[i] = (uint8_t)((f ? 1 : 0) | (head ? 2 : 0));
-        mine += head;
+        return head;
     }
-    block_count(mine, counts);
-}
+};
 
 // (key, index) of the flagged heads, in record order = ascending key order
-__global__ __launch_bounds__(256) void k_heads_compact(const uint64_t* __restrict__ rec, uint64_t m,
-                                                       uint8_t* __restrict__ existing,
-                                                       const uint64_t* __restrict__ counts,
-                                                       uint64_t* __restrict__ new_out, uint64_t* __restrict__ n_new) {
-    uint64_t run = block_base(counts, n_new);
-    const oi_slice sl = oi_slice_of(m);
-    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
-        const uint64_t i = base + threadIdx.x;
-        const bool act = i < sl.hi;
-        const uint8_t e = act ? existing[i] : 0;
-        const bool flag = (e & 2) != 0;
-        const uint64_t slot = tile_slot(flag, run);
-        if (flag) {
-            new_out[2 * slot] = rec[2 * i];
-            new_out[2 * slot + 1] = rec[2 * i + 1];
-            existing[i] = e & 1;
-        }
+struct heads_out {
+    const uint64_t* __restrict__ rec;
+    uint8_t* __restrict__ existing;
+    uint64_t* __restrict__ new_out;
+    __device__ bool flag(uint64_t i) const { return (existing[i] & 2) != 0; }
+    __device__ void emit(uint64_t i, bool flag, uint64_t slot, uint64_t) const {
+        if (!flag) return;
+        new_out[2 * slot] = rec[2 * i];
+        new_out[2 * slot + 1] = rec[2 * i + 1];
+        existing[i] = 0;  // a head's key is not in the index: bit 0 is clear
     }
-}
+};
 
 __global__ __launch_bounds__(256) void k_iota(uint64_t* __restrict__ p, uint64_t m) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x)
@@ -161,44 +227,28 @@ __global__ __launch_bounds__(256) void k_iota(uint64_t* __restrict__ p, uint64_t
 
 // an insert's pairs sorted by (key, position): a pair survives if it is its key's first, its
 // key belongs to this shard and the index does not have it
-__global__ __launch_bounds__(256) void k_insert_flag(const uint64_t* __restrict__ keys,
-                                                     const uint64_t* __restrict__ dir, uint32_t bits, int nparts,
-                                                     int part, const uint64_t* __restrict__ sk, uint64_t m,
-                                                     uint8_t* __restrict__ flags, uint64_t* __restrict__ counts) {
-    const oi_slice sl = oi_slice_of(m);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+struct insert_keep {
+    const uint64_t *__restrict__ keys, *__restrict__ dir;
+    uint32_t bits;
+    int nparts, part;
+    const uint64_t* __restrict__ sk;
+    __device__ bool operator()(uint64_t i, uint64_t) const {
         const uint64_t k = sk[i];
-        bool keep = (i == 0 || sk[i - 1] != k) && oi_dest_of(k, nparts) == (uint32_t)part;
-        if (keep) {
-            uint64_t at;
-            keep = !oi_find(keys, dir, bits, k, &at);
-        }
-        flags[i] = keep ? 1 : 0;
-        mine += keep;
+        if ((i != 0 && sk[i - 1] == k) || oi_dest_of(k, nparts) != (uint32_t)part) return false;
+        uint64_t at;
+        return !oi_find(keys, dir, bits, k, &at);
     }
-    block_count(mine, counts);
-}
+};
 
-__global__ __launch_bounds__(256) void k_insert_compact(const uint64_t* __restrict__ sk,
-                                                        const uint64_t* __restrict__ spos,
-                                                        const uint64_t* __restrict__ in_vals, uint64_t m,
-                                                        const uint8_t* __restrict__ flags,
-                                                        const uint64_t* __restrict__ counts,
-                                                        uint64_t* __restrict__ nk, uint64_t* __restrict__ nv,
-                                                        uint64_t* __restrict__ total) {
-    uint64_t run = block_base(counts, total);
-    const oi_slice sl = oi_slice_of(m);
-    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
-        const uint64_t i = base + threadIdx.x;
-        const bool flag = i < sl.hi && flags[i];
-        const uint64_t slot = tile_slot(flag, run);
-        if (flag) {
-            nk[slot] = sk[i];
-            nv[slot] = in_vals[spos[i]];
-        }
+struct insert_out : from_flags {
+    const uint64_t *__restrict__ sk, *__restrict__ spos, *__restrict__ in_vals;
+    uint64_t *__restrict__ nk, *__restrict__ nv;
+    __device__ void emit(uint64_t i, bool flag, uint64_t slot, uint64_t) const {
+        if (!flag) return;
+        nk[slot] = sk[i];
+        nv[slot] = in_vals[spos[i]];
     }
-}
+};
 
 // Merge by rank of two sorted runs without common keys: lanes [0, r) place the new entries
 // (rank + the old keys below, through the old directory), lanes [r, r + n) the old ones
@@ -251,51 +301,22 @@ __global__ __launch_bounds__(256) void k_remove_mark(const uint64_t* __restrict_
     }
 }
 
-// the marks of k_remove_mark counted per workgroup slice
-__global__ __launch_bounds__(256) void k_remove_count(const uint8_t* __restrict__ flags, uint64_t n,
-                                                      uint64_t* __restrict__ counts) {
-    const oi_slice sl = oi_slice_of(n);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) mine += flags[i];
-    block_count(mine, counts);
-}
-
 // By Object: an entry goes if its value is among the ids (sorted ascending)
-__global__ __launch_bounds__(256) void k_remove_flag_objects(const uint64_t* __restrict__ vals, uint64_t n,
-                                                             const uint64_t* __restrict__ sorted_ids, uint64_t m,
-                                                             uint8_t* __restrict__ flags,
-                                                             uint64_t* __restrict__ counts) {
-    const oi_slice sl = oi_slice_of(n);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
-        const bool drop = oi_id_listed(sorted_ids, m, vals[i]);
-        flags[i] = drop ? 1 : 0;
-        mine += drop;
-    }
-    block_count(mine, counts);
-}
+struct listed {
+    const uint64_t *__restrict__ vals, *__restrict__ sorted_ids;
+    uint64_t m;
+    __device__ bool operator()(uint64_t i, uint64_t) const { return oi_id_listed(sorted_ids, m, vals[i]); }
+};
 
-// Two-way ordered compaction: tile_slot gives every lane the number of dropped entries before
-// it, which is a dropped entry's row of rm_out (may be null) and, taken from its position, a
+// Two-way ordered compaction: the slot is the number of dropped entries before the position,
+// which is a dropped entry's row of rm_out (may be null) and, taken from its position, a
 // survivor's place in the other buffer pair.
-__global__ __launch_bounds__(256) void k_remove_compact(const uint64_t* __restrict__ keys,
-                                                        const uint64_t* __restrict__ vals, uint64_t n,
-                                                        const uint8_t* __restrict__ flags,
-                                                        const uint64_t* __restrict__ counts,
-                                                        uint64_t* __restrict__ out_keys,
-                                                        uint64_t* __restrict__ out_vals,
-                                                        uint64_t* __restrict__ rm_out,
-                                                        const uint64_t* __restrict__ links,
-                                                        const uint64_t* __restrict__ asked,
-                                                        uint64_t* __restrict__ out_links) {
-    uint64_t run = block_base(counts, nullptr);
-    const oi_slice sl = oi_slice_of(n);
-    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
-        const uint64_t i = base + threadIdx.x;
-        const bool act = i < sl.hi;
-        const bool flag = act && flags[i];
-        const uint64_t slot = tile_slot(flag, run);
-        if (!act) continue;
+struct remove_out : from_flags {
+    const uint64_t *__restrict__ keys, *__restrict__ vals;
+    uint64_t *__restrict__ out_keys, *__restrict__ out_vals, *__restrict__ rm_out;
+    const uint64_t *__restrict__ links, *__restrict__ asked;
+    uint64_t* __restrict__ out_links;
+    __device__ void emit(uint64_t i, bool flag, uint64_t slot, uint64_t) const {
         const uint64_t k = keys[i], v = vals[i];
         if (!flag) {
             out_keys[i - slot] = k;
@@ -307,86 +328,79 @@ __global__ __launch_bounds__(256) void k_remove_compact(const uint64_t* __restri
             rm_out[2 * slot + 1] = v;
         }
     }
-}
+};
 
 // ---- owners mode (object_index.h): one entry per (key, Object id) and links[n].
 // A batch of pairs is first aggregated: two stable radix sorts (by id, then by key) leave it
 // in (key, id) order; the heads of the runs of equal pairs are flagged and compacted in order
 // with their positions, so a distinct pair's multiplicity is the distance to the next head
 // (the last one's to m): no lane walks a run, however many copies of one pair there are.
-__global__ __launch_bounds__(256) void k_pair_heads(const uint64_t* __restrict__ sk, const uint64_t* __restrict__ sv,
-                                                    uint64_t m, uint8_t* __restrict__ flags,
-                                                    uint64_t* __restrict__ counts) {
-    const oi_slice sl = oi_slice_of(m);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
-        const bool head = i == 0 || sk[i - 1] != sk[i] || sv[i - 1] != sv[i];
-        flags[i] = head ? 1 : 0;
-        mine += head;
+struct pair_head {
+    const uint64_t *__restrict__ sk, *__restrict__ sv;
+    __device__ bool operator()(uint64_t i, uint64_t) const {
+        return i == 0 || sk[i - 1] != sk[i] || sv[i - 1] != sv[i];
     }
-    block_count(mine, counts);
+};
+
+struct pair_out : from_flags {
+    const uint64_t *__restrict__ sk, *__restrict__ sv;
+    uint64_t *__restrict__ dk, *__restrict__ dv, *__restrict__ dpos;
+    __device__ void emit(uint64_t i, bool flag, uint64_t slot, uint64_t) const {
+        if (!flag) return;
+        dk[slot] = sk[i];
+        dv[slot] = sv[i];
+        dpos[slot] = i;
+    }
+};
+
+// the multiplicity of distinct pair i of d: from its run's head to the next one's (the last
+// one's to m, the pairs of the batch)
+__device__ __forceinline__ uint64_t run_length(const uint64_t* __restrict__ dpos, uint64_t i, uint64_t d, uint64_t m) {
+    return (i + 1 < d ? dpos[i + 1] : m) - dpos[i];
 }
 
-__global__ __launch_bounds__(256) void k_pair_compact(const uint64_t* __restrict__ sk, const uint64_t* __restrict__ sv,
-                                                      uint64_t m, const uint8_t* __restrict__ flags,
-                                                      const uint64_t* __restrict__ counts,
-                                                      uint64_t* __restrict__ dk, uint64_t* __restrict__ dv,
-                                                      uint64_t* __restrict__ dpos, uint64_t* __restrict__ total) {
-    uint64_t run = block_base(counts, total);
-    const oi_slice sl = oi_slice_of(m);
-    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
-        const uint64_t i = base + threadIdx.x;
-        const bool flag = i < sl.hi && flags[i];
-        const uint64_t slot = tile_slot(flag, run);
-        if (flag) {
-            dk[slot] = sk[i];
-            dv[slot] = sv[i];
-            dpos[slot] = i;
-        }
-    }
-}
-
-// Insert: every distinct pair (d = *d_total of them) takes its (key, id) rank in the index and
-// its state: 0 = another shard's key, 1 = absent (merges in at its rank), 2 = present (adds its
-// multiplicity to the entry at its rank).  Counts the absent ones per workgroup slice.
-__global__ __launch_bounds__(256) void k_owners_insert_flag(
-    const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, const uint64_t* __restrict__ dir,
-    uint32_t bits, int nparts, int part, const uint64_t* __restrict__ dk, const uint64_t* __restrict__ dv,
-    const uint64_t* __restrict__ dpos, const uint64_t* __restrict__ d_total, uint64_t m, uint64_t* __restrict__ dcnt,
-    uint64_t* __restrict__ drank, uint8_t* __restrict__ dstate, uint64_t* __restrict__ counts) {
-    const uint64_t d = *d_total;
-    const oi_slice sl = oi_slice_of(d);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
+// Insert: every distinct pair (d of them, the pass's bound) takes its (key, id) rank in the
+// index and its state: 0 = another shard's key, 1 = absent (merges in at its rank), 2 = present
+// (adds its multiplicity to the entry at its rank).  Flags the absent ones.  MARK (apply): a
+// present pair also marks its entry 2.
+template <bool MARK>
+struct pair_state {
+    const uint64_t *__restrict__ keys, *__restrict__ vals, *__restrict__ dir;
+    uint32_t bits;
+    int nparts, part;
+    const uint64_t *__restrict__ dk, *__restrict__ dv, *__restrict__ dpos;
+    uint64_t m;
+    uint64_t *__restrict__ dcnt, *__restrict__ drank;
+    uint8_t *__restrict__ dstate, *__restrict__ mark;
+    __device__ bool operator()(uint64_t i, uint64_t d) const {
         const uint64_t k = dk[i], v = dv[i];
         uint64_t at = 0;
         uint8_t st = 0;
         if (oi_dest_of(k, nparts) == (uint32_t)part) st = oi_find_pair(keys, vals, dir, bits, k, v, &at) ? 2 : 1;
-        dcnt[i] = (i + 1 < d ? dpos[i + 1] : m) - dpos[i];
+        dcnt[i] = run_length(dpos, i, d, m);
         drank[i] = at;
         dstate[i] = st;
-        mine += st == 1;
+        if (MARK && st == 2) mark[at] = 2;
+        return st == 1;
     }
-    block_count(mine, counts);
-}
+};
 
-__global__ __launch_bounds__(256) void k_owners_insert_compact(
-    const uint64_t* __restrict__ dk, const uint64_t* __restrict__ dv, const uint64_t* __restrict__ dcnt,
-    const uint8_t* __restrict__ dstate, const uint64_t* __restrict__ d_total, const uint64_t* __restrict__ counts,
-    uint64_t* __restrict__ nk, uint64_t* __restrict__ nv, uint64_t* __restrict__ nl, uint64_t* __restrict__ total) {
-    uint64_t run = block_base(counts, total);
-    const oi_slice sl = oi_slice_of(*d_total);
-    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
-        const uint64_t i = base + threadIdx.x;
-        const bool flag = i < sl.hi && dstate[i] == 1;
-        const uint64_t slot = tile_slot(flag, run);
-        if (flag) {
-            nk[slot] = dk[i];
-            nv[slot] = dv[i];
-            nl[slot] = dcnt[i];
-        }
+// the absent pairs in order; RANK (apply): with their ranks in the index as it stands
+// (non-decreasing)
+template <bool RANK>
+struct enter_out {
+    const uint64_t *__restrict__ dk, *__restrict__ dv, *__restrict__ dcnt, *__restrict__ drank;
+    const uint8_t* __restrict__ dstate;
+    uint64_t *__restrict__ nk, *__restrict__ nv, *__restrict__ nl, *__restrict__ nrank;
+    __device__ bool flag(uint64_t i) const { return dstate[i] == 1; }
+    __device__ void emit(uint64_t i, bool flag, uint64_t slot, uint64_t) const {
+        if (!flag) return;
+        nk[slot] = dk[i];
+        nv[slot] = dv[i];
+        nl[slot] = dcnt[i];
+        if (RANK) nrank[slot] = drank[i];
     }
-}
+};
 
 // k_index_merge over (key, id): two sorted runs without common pairs
 __global__ __launch_bounds__(256) void k_owners_merge(
@@ -434,23 +448,14 @@ __global__ __launch_bounds__(256) void k_owners_remove_ask(
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d; i += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t at;
         if (oi_find_pair(keys, vals, dir, bits, dk[i], dv[i], &at))
-            asked[at] = (i + 1 < d ? dpos[i + 1] : m) - dpos[i];
+            asked[at] = run_length(dpos, i, d, m);
     }
 }
 
-__global__ __launch_bounds__(256) void k_owners_remove_flag(const uint64_t* __restrict__ links,
-                                                            const uint64_t* __restrict__ asked, uint64_t n,
-                                                            uint8_t* __restrict__ flags,
-                                                            uint64_t* __restrict__ counts) {
-    const oi_slice sl = oi_slice_of(n);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
-        const bool drop = oi_links_drop(links[i], asked[i]);
-        flags[i] = drop ? 1 : 0;
-        mine += drop;
-    }
-    block_count(mine, counts);
-}
+struct links_drop {
+    const uint64_t *__restrict__ links, *__restrict__ asked;
+    __device__ bool operator()(uint64_t i, uint64_t) const { return oi_links_drop(links[i], asked[i]); }
+};
 
 // A removal with ids after which no entry leaves: every distinct pair takes its multiplicity
 // from its entry in place (less than the entry holds, or it would have been flagged); distinct
@@ -464,7 +469,7 @@ __global__ __launch_bounds__(256) void k_owners_take_links(
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d; i += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t at;
         if (oi_find_pair(keys, vals, dir, bits, dk[i], dv[i], &at))
-            links[at] -= (i + 1 < d ? dpos[i + 1] : m) - dpos[i];
+            links[at] -= run_length(dpos, i, d, m);
     }
 }
 
@@ -496,35 +501,11 @@ __device__ __forceinline__ uint64_t pair_multiplicity(const uint64_t* __restrict
                                                       uint64_t key, uint64_t id) {
     const uint64_t j = oi_lower_bound_pair(dk, dv, 0, d, key, id);
     if (j >= d || dk[j] != key || dv[j] != id) return 0;
-    return (j + 1 < d ? dpos[j + 1] : m) - dpos[j];
+    return run_length(dpos, j, d, m);
 }
 
-// k_owners_insert_flag for apply: state, rank and multiplicity of every distinct pair of the
-// insertion list, the entering ones counted per slice; a present pair marks its entry 2.  (A
-// kernel of its own, as k_apply_enter_compact is beside k_owners_insert_compact: the insert's
-// kernels would have to branch on their caller, and its timings are to stay as they are.)
-__global__ __launch_bounds__(256) void k_apply_flag_insertions(
-    const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, const uint64_t* __restrict__ dir,
-    uint32_t bits, int nparts, int part, const uint64_t* __restrict__ dk, const uint64_t* __restrict__ dv,
-    const uint64_t* __restrict__ dpos, const uint64_t* __restrict__ d_total, uint64_t m, uint64_t* __restrict__ dcnt,
-    uint64_t* __restrict__ drank, uint8_t* __restrict__ dstate, uint8_t* __restrict__ mark,
-    uint64_t* __restrict__ counts) {
-    const uint64_t d = *d_total;
-    const oi_slice sl = oi_slice_of(d);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
-        const uint64_t k = dk[i], v = dv[i];
-        uint64_t at = 0;
-        uint8_t st = 0;
-        if (oi_dest_of(k, nparts) == (uint32_t)part) st = oi_find_pair(keys, vals, dir, bits, k, v, &at) ? 2 : 1;
-        dcnt[i] = (i + 1 < d ? dpos[i + 1] : m) - dpos[i];
-        drank[i] = at;
-        dstate[i] = st;
-        if (st == 2) mark[at] = 2;
-        mine += st == 1;
-    }
-    block_count(mine, counts);
-}
+// (The insertion list's pass is pair_state<true>, its compaction enter_out<true>: the insert's
+// own instantiations carry neither the mark nor the rank.)
 
 // every distinct pair of the removal list that names an entry decides it: leaving or staying
 __global__ __launch_bounds__(256) void k_apply_mark_removals(
@@ -538,38 +519,9 @@ __global__ __launch_bounds__(256) void k_apply_mark_removals(
         const uint64_t k = rk[i], v = rv[i];
         uint64_t at;
         if (!oi_find_pair(keys, vals, dir, bits, k, v, &at)) continue;
-        const uint64_t asked = (i + 1 < d ? rpos[i + 1] : m_rm) - rpos[i];
+        const uint64_t asked = run_length(rpos, i, d, m_rm);
         const uint64_t added = pair_multiplicity(ik, iv, ipos, di, m_in, k, v);
         mark[at] = oi_links_after(links[at], asked, added) == 0 ? 1 : 3;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_apply_count_leaving(const uint8_t* __restrict__ mark, uint64_t n,
-                                                             uint64_t* __restrict__ counts) {
-    const oi_slice sl = oi_slice_of(n);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) mine += mark[i] == 1;
-    block_count(mine, counts);
-}
-
-// the entering pairs in order, with their ranks in the index as it stands (non-decreasing)
-__global__ __launch_bounds__(256) void k_apply_enter_compact(
-    const uint64_t* __restrict__ dk, const uint64_t* __restrict__ dv, const uint64_t* __restrict__ dcnt,
-    const uint64_t* __restrict__ drank, const uint8_t* __restrict__ dstate, const uint64_t* __restrict__ d_total,
-    const uint64_t* __restrict__ counts, uint64_t* __restrict__ nk, uint64_t* __restrict__ nv,
-    uint64_t* __restrict__ nl, uint64_t* __restrict__ nrank) {
-    uint64_t run = block_base(counts, nullptr);
-    const oi_slice sl = oi_slice_of(*d_total);
-    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
-        const uint64_t i = base + threadIdx.x;
-        const bool flag = i < sl.hi && dstate[i] == 1;
-        const uint64_t slot = tile_slot(flag, run);
-        if (flag) {
-            nk[slot] = dk[i];
-            nv[slot] = dv[i];
-            nl[slot] = dcnt[i];
-            nrank[slot] = drank[i];
-        }
     }
 }
 
@@ -590,7 +542,7 @@ __global__ __launch_bounds__(256) void k_apply_links_in_place(
             const uint64_t k = rk[t], v = rv[t];
             uint64_t at;
             if (!oi_find_pair(keys, vals, dir, bits, k, v, &at)) continue;
-            const uint64_t asked = (t + 1 < d ? rpos[t + 1] : m_rm) - rpos[t];
+            const uint64_t asked = run_length(rpos, t, d, m_rm);
             links[at] = oi_links_after(links[at], asked, pair_multiplicity(ik, iv, ipos, di, m_in, k, v));
         } else {
             const uint64_t j = t - d;
@@ -599,7 +551,7 @@ __global__ __launch_bounds__(256) void k_apply_links_in_place(
     }
 }
 
-// The one rewrite: k_owners_merge and the owners branch of k_remove_compact in one sliced pass
+// The one rewrite: k_owners_merge and the owners branch of remove_out in one sliced pass
 // over the entries.  With L(i) the leaving entries before position i (block_base + tile_slot)
 // and E(i) the entering pairs ranked at or before i (a search of nrank[r]):
 //   a staying entry i      -> out[i - L(i) + E(i)], with oi_links_after where a pair names it
@@ -684,36 +636,17 @@ struct strided_ids {
     __host__ __device__ uint64_t operator()(uint64_t j) const { return p[j * stride]; }
 };
 
-__global__ __launch_bounds__(256) void k_ids_heads(const uint64_t* __restrict__ sid, uint64_t m,
-                                                   uint8_t* __restrict__ flags, uint64_t* __restrict__ counts) {
-    const oi_slice sl = oi_slice_of(m);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
-        const bool head = i == 0 || sid[i - 1] != sid[i];
-        flags[i] = head ? 1 : 0;
-        mine += head;
-    }
-    block_count(mine, counts);
-}
-
-// u[slot] = the run's id; pslot[position] = the slot of the position's id: tile_slot counts the
-// heads before a lane, which is a head's own slot and one more than a follower's
-__global__ __launch_bounds__(256) void k_ids_compact(const uint64_t* __restrict__ sid, const uint64_t* __restrict__ spos,
-                                                     uint64_t m, const uint8_t* __restrict__ flags,
-                                                     const uint64_t* __restrict__ counts, uint64_t* __restrict__ u,
-                                                     uint64_t* __restrict__ pslot, uint64_t* __restrict__ total) {
-    uint64_t run = block_base(counts, total);
-    const oi_slice sl = oi_slice_of(m);
-    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
-        const uint64_t i = base + threadIdx.x;
-        const bool act = i < sl.hi;
-        const bool flag = act && flags[i];
-        const uint64_t slot = tile_slot(flag, run);
-        if (!act) continue;
+// (The heads are run_head over the sorted ids.)  u[slot] = the run's id; pslot[position] = the
+// slot of the position's id: the slot counts the heads before a position, which is a head's own
+// slot and one more than a follower's
+struct ids_out : from_flags {
+    const uint64_t *__restrict__ sid, *__restrict__ spos;
+    uint64_t *__restrict__ u, *__restrict__ pslot;
+    __device__ void emit(uint64_t i, bool flag, uint64_t slot, uint64_t) const {
         if (flag) u[slot] = sid[i];
         pslot[spos[i]] = flag ? slot : slot - 1;  // position 0 is a head: a follower has one before it
     }
-}
+};
 
 // The one pass over the entries, from the entry side: vals[i] (8 B per entry, coalesced) is
 // searched among the distinct ids -- staged in LDS when the list is at most OI_LDS_IDS ids -- and
@@ -847,33 +780,18 @@ __global__ __launch_bounds__(256) void k_object_scatter(const uint64_t* __restri
 
 // orphans: the distinct ids without an entry, flagged and counted per slice, then compacted in
 // order (ascending, as u is) once the host has checked the count against the capacity
-__global__ __launch_bounds__(256) void k_orphans_flag(const uint64_t* __restrict__ tot,
-                                                      const uint64_t* __restrict__ d_total,
-                                                      uint8_t* __restrict__ flags, uint64_t* __restrict__ counts) {
-    const oi_slice sl = oi_slice_of(*d_total);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
-        const bool orphan = oi_unowned(tot[2 * i + 1]);
-        flags[i] = orphan ? 1 : 0;
-        mine += orphan;
-    }
-    block_count(mine, counts);
-}
+struct unowned {
+    const uint64_t* __restrict__ tot;
+    __device__ bool operator()(uint64_t i, uint64_t) const { return oi_unowned(tot[2 * i + 1]); }
+};
 
-__global__ __launch_bounds__(256) void k_orphans_compact(const uint64_t* __restrict__ u,
-                                                         const uint64_t* __restrict__ d_total,
-                                                         const uint8_t* __restrict__ flags,
-                                                         const uint64_t* __restrict__ counts,
-                                                         uint64_t* __restrict__ out) {
-    uint64_t run = block_base(counts, nullptr);
-    const oi_slice sl = oi_slice_of(*d_total);
-    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
-        const uint64_t i = base + threadIdx.x;
-        const bool flag = i < sl.hi && flags[i];
-        const uint64_t slot = tile_slot(flag, run);
+struct orphans_out : from_flags {
+    const uint64_t* __restrict__ u;
+    uint64_t* __restrict__ out;
+    __device__ void emit(uint64_t i, bool flag, uint64_t slot, uint64_t) const {
         if (flag) out[slot] = u[i];
     }
-}
+};
 
 // ---- by key, read-only (owners mode): the duplicate groups (object_index.h oi_key_run /
 // oi_qualifies; mod.rs:189-225 links later copies to an Object, :229-333 gives same-step
@@ -934,15 +852,7 @@ __global__ __launch_bounds__(256) void k_key_links(const uint64_t* __restrict__ 
     }
 }
 
-// the heads of the runs of equal keys, counted per workgroup slice
-__global__ __launch_bounds__(256) void k_group_heads(const uint64_t* __restrict__ keys, uint64_t n,
-                                                     uint64_t* __restrict__ counts) {
-    const oi_slice sl = oi_slice_of(n);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) mine += i == 0 || keys[i - 1] != keys[i];
-    block_count(mine, counts);
-}
-
+// (The heads of the runs of equal keys are counted per workgroup slice by run_head.)
 // Group totals.  Every entry learns its group's slot; a head stores its position at hpos[slot],
 // so owners(slot) = hpos[slot + 1] - hpos[slot] (the last one's from n) with no sum at all.
 // links: a segmented sum by slot inside the wave (the lanes of one run are neighbours; each step
@@ -993,51 +903,30 @@ __device__ __forceinline__ uint64_t group_owners(const uint64_t* __restrict__ hp
     return (g + 1 < groups ? hpos[g + 1] : n) - hpos[g];
 }
 
-// Selection per group: gflags[g] = the group qualifies, counted per workgroup slice of the groups
-__global__ __launch_bounds__(256) void k_group_flag(const uint64_t* __restrict__ hpos,
-                                                    const uint64_t* __restrict__ gl,
-                                                    const uint64_t* __restrict__ g_total, uint64_t n,
-                                                    uint64_t min_links, uint64_t min_owners,
-                                                    uint8_t* __restrict__ gflags, uint64_t* __restrict__ counts) {
-    const uint64_t groups = *g_total;
-    const oi_slice sl = oi_slice_of(groups);
-    uint32_t mine = 0;
-    for (uint64_t g = sl.lo + threadIdx.x; g < sl.hi; g += blockDim.x) {
-        const bool ok = oi_qualifies(gl[g], group_owners(hpos, g, groups, n), min_links, min_owners);
-        gflags[g] = ok ? 1 : 0;
-        mine += ok;
+// Selection per group (the pass's bound is the groups): gflags[g] = the group qualifies
+struct group_ok {
+    const uint64_t *__restrict__ hpos, *__restrict__ gl;
+    uint64_t n, min_links, min_owners;
+    __device__ bool operator()(uint64_t g, uint64_t groups) const {
+        return oi_qualifies(gl[g], group_owners(hpos, g, groups, n), min_links, min_owners);
     }
-    block_count(mine, counts);
-}
+};
 
 // one row per qualifying group in group order = ascending key order; key and first owner are
 // read at the head's position (every output may be null)
-__global__ __launch_bounds__(256) void k_group_compact(const uint64_t* __restrict__ keys,
-                                                       const uint64_t* __restrict__ vals,
-                                                       const uint64_t* __restrict__ hpos,
-                                                       const uint64_t* __restrict__ gl,
-                                                       const uint64_t* __restrict__ g_total, uint64_t n,
-                                                       const uint8_t* __restrict__ gflags,
-                                                       const uint64_t* __restrict__ counts,
-                                                       uint64_t* __restrict__ keys_out,
-                                                       uint64_t* __restrict__ first_out,
-                                                       uint64_t* __restrict__ links_out,
-                                                       uint64_t* __restrict__ owners_out) {
-    uint64_t run = block_base(counts, nullptr);
-    const uint64_t groups = *g_total;
-    const oi_slice sl = oi_slice_of(groups);
-    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
-        const uint64_t g = base + threadIdx.x;
-        const bool flag = g < sl.hi && gflags[g];
-        const uint64_t slot = tile_slot(flag, run);
-        if (!flag) continue;
+struct group_out : from_flags {
+    const uint64_t *__restrict__ keys, *__restrict__ vals, *__restrict__ hpos, *__restrict__ gl;
+    uint64_t n;
+    uint64_t *__restrict__ keys_out, *__restrict__ first_out, *__restrict__ links_out, *__restrict__ owners_out;
+    __device__ void emit(uint64_t g, bool flag, uint64_t slot, uint64_t groups) const {
+        if (!flag) return;
         const uint64_t at = hpos[g];
         if (keys_out) keys_out[slot] = keys[at];
         if (first_out) first_out[slot] = vals[at];
         if (links_out) links_out[slot] = gl[g];
         if (owners_out) owners_out[slot] = group_owners(hpos, g, groups, n);
     }
-}
+};
 
 // Selection per entry: an entry is selected iff its group is.  The group's slot is found again as
 // in k_group_totals (the head counts per slice are still there); eflags[i] and the selected
@@ -1062,26 +951,16 @@ __global__ __launch_bounds__(256) void k_entry_flag(const uint64_t* __restrict__
     block_count(mine, counts);
 }
 
-__global__ __launch_bounds__(256) void k_entry_compact(const uint64_t* __restrict__ keys,
-                                                       const uint64_t* __restrict__ vals,
-                                                       const uint64_t* __restrict__ links, uint64_t n,
-                                                       const uint8_t* __restrict__ eflags,
-                                                       const uint64_t* __restrict__ counts,
-                                                       uint64_t* __restrict__ keys_out,
-                                                       uint64_t* __restrict__ ids_out,
-                                                       uint64_t* __restrict__ links_out) {
-    uint64_t run = block_base(counts, nullptr);
-    const oi_slice sl = oi_slice_of(n);
-    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
-        const uint64_t i = base + threadIdx.x;
-        const bool flag = i < sl.hi && eflags[i];
-        const uint64_t slot = tile_slot(flag, run);
-        if (!flag) continue;
+struct entry_out : from_flags {
+    const uint64_t *__restrict__ keys, *__restrict__ vals, *__restrict__ links;
+    uint64_t *__restrict__ keys_out, *__restrict__ ids_out, *__restrict__ links_out;
+    __device__ void emit(uint64_t i, bool flag, uint64_t slot, uint64_t) const {
+        if (!flag) return;
         if (keys_out) keys_out[slot] = keys[i];
         if (ids_out) ids_out[slot] = vals[i];
         if (links_out) links_out[slot] = links[i];
     }
-}
+};
 
 // Stats: one reduction over the group totals.  A lane sums its groups in registers, the wave by
 // shuffles, the workgroup through LDS; one workgroup adds seven sums and one maximum to st[8]
@@ -1122,23 +1001,21 @@ __global__ __launch_bounds__(256) void k_group_stats(const uint64_t* __restrict_
     if (blockIdx.x == 0) st[0] = groups, st[1] = n;
 }
 
+size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
+
 size_t insert_sort_bytes(uint64_t m, hipStream_t s) {
     size_t b = 0;
     uint64_t* nul = nullptr;
     if (rocprim::radix_sort_pairs(nullptr, b, nul, nul, nul, nul, (size_t)m, 0, 64, s) != hipSuccess) return 0;
-    return (b + 255) & ~size_t(255);
+    return round256(b);
 }
 
 size_t remove_sort_bytes(uint64_t m, hipStream_t s) {
     size_t b = 0;
     uint64_t* nul = nullptr;
     if (rocprim::radix_sort_keys(nullptr, b, nul, nul, (size_t)m, 0, 64, s) != hipSuccess) return 0;
-    return (b + 255) & ~size_t(255);
+    return round256(b);
 }
-
-size_t remove_flag_bytes(uint64_t n) { return (n + 255) & ~size_t(255); }
-
-size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
 
 // An aggregated batch of m pairs in scratch: a[5][m] u64 (the first sort's ids and keys, later
 // the distinct pairs dk, dv; the second sort's sk, sv, later an insert's nk, nv; dpos), an
@@ -1178,15 +1055,16 @@ hipError_t aggregate_pairs(const pair_batch& b, const uint64_t* in_keys, const u
     e = rocprim::radix_sort_pairs(b.tmp, tb, b.t1, b.sk, b.t0, b.sv, (size_t)m, 0, 64, s);
     if (e != hipSuccess) return e;
     const uint32_t g = sliced_grid(m);
-    hipLaunchKernelGGL(k_pair_heads, dim3(g), dim3(256), 0, s, b.sk, b.sv, m, b.heads, counts);
-    hipLaunchKernelGGL(k_pair_compact, dim3(g), dim3(256), 0, s, b.sk, b.sv, m, b.heads, counts, b.t0, b.t1, b.dpos,
-                       b.d_total);
+    launch_flag(g, s, pair_head{b.sk, b.sv}, nullptr, m, b.heads, counts);
+    launch_compact(g, s, pair_out{{b.heads}, b.sk, b.sv, b.t0, b.t1, b.dpos}, nullptr, m, counts, b.d_total);
     return hipGetLastError();
 }
 
 }  // namespace
 
 namespace sdk {
+
+uint32_t index_slots(uint64_t n) { return sliced_grid(n); }
 
 hipError_t index_lookup(const oi_view& x, const uint64_t* q, uint64_t m, uint64_t* out, uint8_t* found,
                         hipStream_t s) {
@@ -1201,16 +1079,16 @@ hipError_t owners_indexed(const oi_view& x, const uint64_t* records, uint64_t m,
                           hipStream_t s) {
     if (m == 0) return hipMemsetAsync(n_new, 0, sizeof(uint64_t), s);
     const uint32_t g = sliced_grid(m);
-    hipLaunchKernelGGL(k_owners_indexed, dim3(g), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, records, m, rep,
-                       chunk, owner, existing, counts);
-    hipLaunchKernelGGL(k_heads_compact, dim3(g), dim3(256), 0, s, records, m, existing, counts, new_out, n_new);
+    launch_flag(g, s, owners_indexed_rule{x.keys, x.vals, x.dir, x.bits, records, rep, chunk, owner, existing}, nullptr,
+                m, nullptr, counts);
+    launch_compact(g, s, heads_out{records, existing, new_out}, nullptr, m, counts, n_new);
     return hipGetLastError();
 }
 
 // scratch: sk[m], spos[m], pos[m], nk[m], nv[m] (u64), flags[m] (u8), total (u64), then the
 // radix sort's temporary storage
 size_t index_insert_scratch(uint64_t m) {
-    return ((5 * m * sizeof(uint64_t) + m + 255) & ~size_t(255)) + 256 + insert_sort_bytes(m, nullptr) + 256;
+    return round256(5 * m * sizeof(uint64_t) + m) + 256 + insert_sort_bytes(m, nullptr) + 256;
 }
 
 hipError_t index_insert_select(const oi_view& x, int nparts, int part, const uint64_t* in_keys,
@@ -1223,7 +1101,7 @@ hipError_t index_insert_select(const oi_view& x, int nparts, int part, const uin
     uint64_t* nk = pos + m;
     uint64_t* nv = nk + m;
     uint8_t* flags = reinterpret_cast<uint8_t*>(nv + m);
-    uint64_t* total = reinterpret_cast<uint64_t*>(((uintptr_t)(flags + m) + 255) & ~uintptr_t(255));
+    uint64_t* total = reinterpret_cast<uint64_t*>(round256((uintptr_t)(flags + m)));
     void* tmp = reinterpret_cast<uint8_t*>(total) + 256;
     size_t tb = insert_sort_bytes(m, s);
     hipLaunchKernelGGL(k_iota, dim3(grid_for(m)), dim3(256), 0, s, pos, m);
@@ -1231,9 +1109,8 @@ hipError_t index_insert_select(const oi_view& x, int nparts, int part, const uin
     hipError_t e = rocprim::radix_sort_pairs(tmp, tb, in_keys, sk, pos, spos, (size_t)m, 0, 64, s);
     if (e != hipSuccess) return e;
     const uint32_t g = sliced_grid(m);
-    hipLaunchKernelGGL(k_insert_flag, dim3(g), dim3(256), 0, s, x.keys, x.dir, x.bits, nparts, part, sk, m, flags,
-                       counts);
-    hipLaunchKernelGGL(k_insert_compact, dim3(g), dim3(256), 0, s, sk, spos, in_vals, m, flags, counts, nk, nv, total);
+    launch_flag(g, s, insert_keep{x.keys, x.dir, x.bits, nparts, part, sk}, nullptr, m, flags, counts);
+    launch_compact(g, s, insert_out{{flags}, sk, spos, in_vals, nk, nv}, nullptr, m, counts, total);
     *nk_out = nk;
     *nv_out = nv;
     *total_out = total;
@@ -1251,12 +1128,10 @@ hipError_t index_merge(const oi_view& x, const uint64_t* nk, const uint64_t* nv,
 // scratch: flags[n] (u8), then for a removal by Object the sorted ids[m_ids] (u64) and the
 // radix sort's temporary storage
 size_t index_remove_scratch(uint64_t n, uint64_t m_ids) {
-    size_t b = remove_flag_bytes(n) + 256;
-    if (m_ids) b += ((m_ids * sizeof(uint64_t) + 255) & ~size_t(255)) + remove_sort_bytes(m_ids, nullptr) + 256;
+    size_t b = round256(n) + 256;
+    if (m_ids) b += round256(m_ids * sizeof(uint64_t)) + remove_sort_bytes(m_ids, nullptr) + 256;
     return b;
 }
-
-uint32_t index_remove_slots(uint64_t n) { return sliced_grid(n); }
 
 hipError_t index_remove_flag_keys(const oi_view& x, const uint64_t* rm_keys, const uint64_t* rm_ids, uint64_t m,
                                   void* scratch, uint64_t* counts, hipStream_t s) {
@@ -1265,29 +1140,34 @@ hipError_t index_remove_flag_keys(const oi_view& x, const uint64_t* rm_keys, con
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_remove_mark, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, rm_keys,
                        rm_ids, m, flags);
-    hipLaunchKernelGGL(k_remove_count, dim3(sliced_grid(x.n)), dim3(256), 0, s, flags, x.n, counts);
+    launch_flag(sliced_grid(x.n), s, marked{flags}, nullptr, x.n, nullptr, counts);
     return hipGetLastError();
 }
 
+namespace {
+// the entries whose `field` (values by Object; keys in the owners mode) is among the m listed,
+// which are sorted into the scratch behind flags[n]
+hipError_t remove_flag_listed(const oi_view& x, const uint64_t* field, const uint64_t* list, uint64_t m, void* scratch,
+                              uint64_t* counts, hipStream_t s) {
+    uint8_t* flags = reinterpret_cast<uint8_t*>(scratch);
+    uint64_t* sorted = reinterpret_cast<uint64_t*>(flags + round256(x.n));
+    void* tmp = reinterpret_cast<uint8_t*>(sorted) + round256(m * sizeof(uint64_t));
+    size_t tb = remove_sort_bytes(m, s);
+    hipError_t e = rocprim::radix_sort_keys(tmp, tb, list, sorted, (size_t)m, 0, 64, s);
+    if (e != hipSuccess) return e;
+    launch_flag(sliced_grid(x.n), s, listed{field, sorted, m}, nullptr, x.n, flags, counts);
+    return hipGetLastError();
+}
+}  // namespace
+
 hipError_t index_remove_flag_objects(const oi_view& x, const uint64_t* ids, uint64_t m, void* scratch,
                                      uint64_t* counts, hipStream_t s) {
-    uint8_t* flags = reinterpret_cast<uint8_t*>(scratch);
-    uint64_t* sorted = reinterpret_cast<uint64_t*>(flags + remove_flag_bytes(x.n));
-    void* tmp = reinterpret_cast<uint8_t*>(sorted) + ((m * sizeof(uint64_t) + 255) & ~size_t(255));
-    size_t tb = remove_sort_bytes(m, s);
-    hipError_t e = rocprim::radix_sort_keys(tmp, tb, ids, sorted, (size_t)m, 0, 64, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_remove_flag_objects, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.vals, x.n, sorted, m, flags,
-                       counts);
-    return hipGetLastError();
+    return remove_flag_listed(x, x.vals, ids, m, scratch, counts, s);
 }
 
 hipError_t index_remove_compact(const oi_view& x, const void* scratch, const uint64_t* counts, uint64_t* out_keys,
                                 uint64_t* out_vals, uint64_t* rm_out, hipStream_t s) {
-    hipLaunchKernelGGL(k_remove_compact, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, x.n,
-                       reinterpret_cast<const uint8_t*>(scratch), counts, out_keys, out_vals, rm_out, nullptr, nullptr,
-                       nullptr);
-    return hipGetLastError();
+    return index_owners_remove_compact(x, scratch, nullptr, counts, out_keys, out_vals, nullptr, rm_out, s);
 }
 
 // ---- owners mode
@@ -1301,10 +1181,12 @@ hipError_t index_owners_insert_select(const oi_view& x, int nparts, int part, co
     hipError_t e = aggregate_pairs(b, in_keys, in_vals, m, counts, s);
     if (e != hipSuccess) return e;
     const uint32_t g = sliced_grid(m);
-    hipLaunchKernelGGL(k_owners_insert_flag, dim3(g), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, nparts, part, b.t0,
-                       b.t1, b.dpos, b.d_total, m, b.dcnt, b.drank, b.dstate, counts);
-    hipLaunchKernelGGL(k_owners_insert_compact, dim3(g), dim3(256), 0, s, b.t0, b.t1, b.dcnt, b.dstate, b.d_total,
-                       counts, b.sk, b.sv, b.nl, b.r_total);
+    launch_flag(g, s,
+                pair_state<false>{x.keys, x.vals, x.dir, x.bits, nparts, part, b.t0, b.t1, b.dpos, m, b.dcnt, b.drank,
+                                  b.dstate, nullptr},
+                b.d_total, 0, nullptr, counts);
+    launch_compact(g, s, enter_out<false>{b.t0, b.t1, b.dcnt, b.drank, b.dstate, b.sk, b.sv, b.nl, nullptr}, b.d_total,
+                   0, counts, b.r_total);
     *nk_out = b.sk;
     *nv_out = b.sv;
     *nl_out = b.nl;
@@ -1330,11 +1212,11 @@ hipError_t index_owners_add_links(const void* scratch, uint64_t m, const uint64_
 
 // scratch: flags[n] (u8), asked[n] (u64), then the aggregated batch
 size_t index_owners_remove_scratch(uint64_t n, uint64_t m) {
-    return remove_flag_bytes(n) + round256(n * sizeof(uint64_t)) + pair_batch_bytes(m, false);
+    return round256(n) + round256(n * sizeof(uint64_t)) + pair_batch_bytes(m, false);
 }
 
 const uint64_t* index_owners_asked(const void* scratch, uint64_t n) {
-    return reinterpret_cast<const uint64_t*>(reinterpret_cast<const uint8_t*>(scratch) + remove_flag_bytes(n));
+    return reinterpret_cast<const uint64_t*>(reinterpret_cast<const uint8_t*>(scratch) + round256(n));
 }
 
 hipError_t index_owners_remove_flag_pairs(const oi_view& x, const uint64_t* rm_keys, const uint64_t* rm_ids,
@@ -1349,8 +1231,7 @@ hipError_t index_owners_remove_flag_pairs(const oi_view& x, const uint64_t* rm_k
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_owners_remove_ask, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, b.t0,
                        b.t1, b.dpos, b.d_total, m, asked);
-    hipLaunchKernelGGL(k_owners_remove_flag, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.links, asked, x.n, flags,
-                       counts);
+    launch_flag(sliced_grid(x.n), s, links_drop{x.links, asked}, nullptr, x.n, flags, counts);
     return hipGetLastError();
 }
 
@@ -1364,29 +1245,22 @@ hipError_t index_owners_take_links(const oi_view& x, const void* scratch, uint64
 
 hipError_t index_owners_remove_flag_keys(const oi_view& x, const uint64_t* rm_keys, uint64_t m, void* scratch,
                                          uint64_t* counts, hipStream_t s) {
-    uint8_t* flags = reinterpret_cast<uint8_t*>(scratch);
-    uint64_t* sorted = reinterpret_cast<uint64_t*>(flags + remove_flag_bytes(x.n));
-    void* tmp = reinterpret_cast<uint8_t*>(sorted) + round256(m * sizeof(uint64_t));
-    size_t tb = remove_sort_bytes(m, s);
-    hipError_t e = rocprim::radix_sort_keys(tmp, tb, rm_keys, sorted, (size_t)m, 0, 64, s);
-    if (e != hipSuccess) return e;
     // the entry side searches the sorted keys, as it searches the sorted ids by Object
-    hipLaunchKernelGGL(k_remove_flag_objects, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.n, sorted, m, flags,
-                       counts);
-    return hipGetLastError();
+    return remove_flag_listed(x, x.keys, rm_keys, m, scratch, counts, s);
 }
 
 hipError_t index_owners_remove_compact(const oi_view& x, const void* scratch, const uint64_t* asked,
                                        const uint64_t* counts, uint64_t* out_keys, uint64_t* out_vals,
                                        uint64_t* out_links, uint64_t* rm_out, hipStream_t s) {
-    hipLaunchKernelGGL(k_remove_compact, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, x.n,
-                       reinterpret_cast<const uint8_t*>(scratch), counts, out_keys, out_vals, rm_out, x.links, asked,
-                       out_links);
+    launch_compact(sliced_grid(x.n), s,
+                   remove_out{{reinterpret_cast<const uint8_t*>(scratch)}, x.keys, x.vals, out_keys, out_vals, rm_out,
+                              x.links, asked, out_links},
+                   nullptr, x.n, counts, nullptr);
     return hipGetLastError();
 }
 
 // ---- apply.  scratch: mark[n] (u8); the per-slice counts of leaving entries, then of entering
-// pairs (u64, index_apply_slots of each, side by side for the host's one copy); the removal
+// pairs (u64, index_slots(n) then index_slots(m_in), side by side for the host's one copy); the removal
 // list's aggregated batch; the insertion list's, as an insert's; nrank[m_in] (u64)
 namespace {
 struct apply_scratch {
@@ -1399,7 +1273,7 @@ apply_scratch apply_scratch_at(void* base, uint64_t n, uint64_t m_rm, uint64_t m
     apply_scratch a;
     uint8_t* p = reinterpret_cast<uint8_t*>(base);
     a.mark = p;
-    p += remove_flag_bytes(n);
+    p += round256(n);
     a.leaving = reinterpret_cast<uint64_t*>(p);
     a.entering = a.leaving + sliced_grid(n);
     p += 2 * OI_BLOCKS * sizeof(uint64_t);
@@ -1413,13 +1287,8 @@ apply_scratch apply_scratch_at(void* base, uint64_t n, uint64_t m_rm, uint64_t m
 }  // namespace
 
 size_t index_apply_scratch(uint64_t n, uint64_t m_rm, uint64_t m_in) {
-    return remove_flag_bytes(n) + 2 * OI_BLOCKS * sizeof(uint64_t) + pair_batch_bytes(std::max<uint64_t>(m_rm, 1), false) +
+    return round256(n) + 2 * OI_BLOCKS * sizeof(uint64_t) + pair_batch_bytes(std::max<uint64_t>(m_rm, 1), false) +
            pair_batch_bytes(std::max<uint64_t>(m_in, 1), true) + round256(m_in * sizeof(uint64_t)) + 256;
-}
-
-void index_apply_slots(uint64_t n, uint64_t m_in, uint32_t* leaving, uint32_t* entering) {
-    *leaving = sliced_grid(n);
-    *entering = sliced_grid(m_in);
 }
 
 const uint64_t* index_apply_counts(const void* scratch, uint64_t n) {
@@ -1439,14 +1308,15 @@ hipError_t index_apply_flag(const oi_view& x, int nparts, int part, const uint64
     if (m_in) e = aggregate_pairs(a.in, in_keys, in_ids, m_in, counts, s);
     else e = hipMemsetAsync(a.in.d_total, 0, sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_apply_flag_insertions, dim3(sliced_grid(m_in)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits,
-                       nparts, part, a.in.t0, a.in.t1, a.in.dpos, a.in.d_total, m_in, a.in.dcnt, a.in.drank,
-                       a.in.dstate, a.mark, a.entering);
+    launch_flag(sliced_grid(m_in), s,
+                pair_state<true>{x.keys, x.vals, x.dir, x.bits, nparts, part, a.in.t0, a.in.t1, a.in.dpos, m_in,
+                                 a.in.dcnt, a.in.drank, a.in.dstate, a.mark},
+                a.in.d_total, 0, nullptr, a.entering);
     if (m_rm)
         hipLaunchKernelGGL(k_apply_mark_removals, dim3(grid_for(m_rm)), dim3(256), 0, s, x.keys, x.vals, x.links, x.dir,
                            x.bits, a.rm.t0, a.rm.t1, a.rm.dpos, a.rm.d_total, m_rm, a.in.t0, a.in.t1, a.in.dpos,
                            a.in.d_total, m_in, a.mark);
-    hipLaunchKernelGGL(k_apply_count_leaving, dim3(sliced_grid(x.n)), dim3(256), 0, s, a.mark, x.n, a.leaving);
+    launch_flag(sliced_grid(x.n), s, marked{a.mark}, nullptr, x.n, nullptr, a.leaving);
     return hipGetLastError();
 }
 
@@ -1464,8 +1334,10 @@ hipError_t index_apply_merge(const oi_view& x, const void* scratch, uint64_t m_r
                              hipStream_t s) {
     const apply_scratch a = apply_scratch_at(const_cast<void*>(scratch), x.n, m_rm, m_in);
     if (r_in)
-        hipLaunchKernelGGL(k_apply_enter_compact, dim3(sliced_grid(m_in)), dim3(256), 0, s, a.in.t0, a.in.t1, a.in.dcnt,
-                           a.in.drank, a.in.dstate, a.in.d_total, a.entering, a.in.sk, a.in.sv, a.in.nl, a.nrank);
+        launch_compact(sliced_grid(m_in), s,
+                       enter_out<true>{a.in.t0, a.in.t1, a.in.dcnt, a.in.drank, a.in.dstate, a.in.sk, a.in.sv, a.in.nl,
+                                       a.nrank},
+                       a.in.d_total, 0, a.entering, nullptr);
     hipLaunchKernelGGL(k_apply_merge, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, x.links, x.n, a.mark,
                        a.leaving, a.rm.t0, a.rm.t1, a.rm.dpos, a.rm.d_total, m_rm, a.in.t0, a.in.t1, a.in.dpos,
                        a.in.d_total, m_in, a.in.sk, a.in.sv, a.in.nl, a.nrank, r_in, out_keys, out_vals, out_links,
@@ -1525,8 +1397,6 @@ size_t index_objects_scratch(uint64_t m) {
     return round256(6 * m * sizeof(uint64_t)) + round256(m) + 256 + OI_BLOCKS * sizeof(uint64_t) + objects_sort_bytes(m) + 256;
 }
 
-uint32_t index_objects_slots(uint64_t m) { return sliced_grid(m); }
-
 // m > 0.  After it tot[2 * slot], tot[2 * slot + 1] hold links and entries of the distinct ids
 // (sums), or 0 and entries != 0 (!sums: what the orphans need).  Nothing of the index is written.
 hipError_t index_objects_totals(const oi_view& x, const uint64_t* ids, uint64_t stride, uint64_t m, bool sums,
@@ -1537,9 +1407,8 @@ hipError_t index_objects_totals(const oi_view& x, const uint64_t* ids, uint64_t 
     if (e != hipSuccess) return e;
     if ((e = hipMemsetAsync(q.tot, 0, 2 * m * sizeof(uint64_t), s)) != hipSuccess) return e;
     const uint32_t g = sliced_grid(m);
-    hipLaunchKernelGGL(k_ids_heads, dim3(g), dim3(256), 0, s, q.sid, m, q.flags, q.counts);
-    hipLaunchKernelGGL(k_ids_compact, dim3(g), dim3(256), 0, s, q.sid, q.spos, m, q.flags, q.counts, q.u, q.pslot,
-                       q.d_total);
+    launch_flag(g, s, run_head{q.sid}, nullptr, m, q.flags, q.counts);
+    launch_compact(g, s, ids_out{{q.flags}, q.sid, q.spos, q.u, q.pslot}, nullptr, m, q.counts, q.d_total);
     if (x.n) {
         const dim3 ge(sliced_grid(x.n)), b(256);
         if (m <= OI_LDS_IDS) {
@@ -1560,7 +1429,7 @@ hipError_t index_objects_scatter(const void* scratch, uint64_t m, uint64_t* link
     return hipGetLastError();
 }
 
-// the orphans counted per slice in index_objects_counts(scratch, m)[0 .. index_objects_slots(m)),
+// the orphans counted per slice in index_objects_counts(scratch, m)[0 .. index_slots(m)),
 // then compacted
 const uint64_t* index_objects_counts(const void* scratch, uint64_t m) {
     return objects_scratch_at(const_cast<void*>(scratch), m).counts;
@@ -1568,13 +1437,13 @@ const uint64_t* index_objects_counts(const void* scratch, uint64_t m) {
 
 hipError_t index_orphans_flag(const void* scratch, uint64_t m, hipStream_t s) {
     const objects_scratch q = objects_scratch_at(const_cast<void*>(scratch), m);
-    hipLaunchKernelGGL(k_orphans_flag, dim3(sliced_grid(m)), dim3(256), 0, s, q.tot, q.d_total, q.flags, q.counts);
+    launch_flag(sliced_grid(m), s, unowned{q.tot}, q.d_total, 0, q.flags, q.counts);
     return hipGetLastError();
 }
 
 hipError_t index_orphans_compact(const void* scratch, uint64_t m, uint64_t* out, hipStream_t s) {
     const objects_scratch q = objects_scratch_at(const_cast<void*>(scratch), m);
-    hipLaunchKernelGGL(k_orphans_compact, dim3(sliced_grid(m)), dim3(256), 0, s, q.u, q.d_total, q.flags, q.counts, out);
+    launch_compact(sliced_grid(m), s, orphans_out{{q.flags}, q.u, out}, q.d_total, 0, q.counts, nullptr);
     return hipGetLastError();
 }
 
@@ -1621,8 +1490,6 @@ size_t index_groups_scratch(uint64_t n) {
     return round256(2 * n * sizeof(uint64_t)) + 2 * round256(n) + 512 + 2 * OI_BLOCKS * sizeof(uint64_t);
 }
 
-uint32_t index_groups_slots(uint64_t n) { return sliced_grid(n); }
-
 // n > 0.  After it hpos[g] and gl[g] hold the head position and links of every group g, and
 // *g_total the groups.  Nothing of the index is written.
 hipError_t index_groups_totals(const oi_view& x, void* scratch, hipStream_t s) {
@@ -1630,19 +1497,18 @@ hipError_t index_groups_totals(const oi_view& x, void* scratch, hipStream_t s) {
     hipError_t e = hipMemsetAsync(q.gl, 0, x.n * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
     const dim3 g(sliced_grid(x.n)), b(256);
-    hipLaunchKernelGGL(k_group_heads, g, b, 0, s, x.keys, x.n, q.head_counts);
+    launch_flag(g.x, s, run_head{x.keys}, nullptr, x.n, nullptr, q.head_counts);
     hipLaunchKernelGGL(k_group_totals, g, b, 0, s, x.keys, x.links, x.n, q.head_counts, q.hpos, q.gl, q.g_total);
     return hipGetLastError();
 }
 
 // the qualifying groups, or (entries) the entries of the qualifying groups, counted per slice in
-// index_groups_counts(scratch, n)[0 .. index_groups_slots(n))
+// index_groups_counts(scratch, n)[0 .. index_slots(n))
 hipError_t index_groups_flag(const oi_view& x, void* scratch, uint64_t min_links, uint64_t min_owners, bool entries,
                              hipStream_t s) {
     const groups_scratch q = groups_scratch_at(scratch, x.n);
     const dim3 g(sliced_grid(x.n)), b(256);  // groups <= n: the slices past the groups are empty
-    hipLaunchKernelGGL(k_group_flag, g, b, 0, s, q.hpos, q.gl, q.g_total, x.n, min_links, min_owners, q.gflags,
-                       q.sel_counts);
+    launch_flag(g.x, s, group_ok{q.hpos, q.gl, x.n, min_links, min_owners}, q.g_total, 0, q.gflags, q.sel_counts);
     if (entries)
         hipLaunchKernelGGL(k_entry_flag, g, b, 0, s, x.keys, x.n, q.head_counts, q.gflags, q.eflags, q.sel_counts);
     return hipGetLastError();
@@ -1655,16 +1521,17 @@ const uint64_t* index_groups_counts(const void* scratch, uint64_t n) {
 hipError_t index_groups_compact(const oi_view& x, const void* scratch, uint64_t* keys_out, uint64_t* first_out,
                                 uint64_t* links_out, uint64_t* owners_out, hipStream_t s) {
     const groups_scratch q = groups_scratch_at(const_cast<void*>(scratch), x.n);
-    hipLaunchKernelGGL(k_group_compact, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, q.hpos, q.gl, q.g_total,
-                       x.n, q.gflags, q.sel_counts, keys_out, first_out, links_out, owners_out);
+    launch_compact(sliced_grid(x.n), s,
+                   group_out{{q.gflags}, x.keys, x.vals, q.hpos, q.gl, x.n, keys_out, first_out, links_out, owners_out},
+                   q.g_total, 0, q.sel_counts, nullptr);
     return hipGetLastError();
 }
 
 hipError_t index_groups_compact_entries(const oi_view& x, const void* scratch, uint64_t* keys_out, uint64_t* ids_out,
                                         uint64_t* links_out, hipStream_t s) {
     const groups_scratch q = groups_scratch_at(const_cast<void*>(scratch), x.n);
-    hipLaunchKernelGGL(k_entry_compact, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, x.links, x.n, q.eflags,
-                       q.sel_counts, keys_out, ids_out, links_out);
+    launch_compact(sliced_grid(x.n), s, entry_out{{q.eflags}, x.keys, x.vals, x.links, keys_out, ids_out, links_out},
+                   nullptr, x.n, q.sel_counts, nullptr);
     return hipGetLastError();
 }
 

@@ -70,6 +70,8 @@ struct oi_view {
     const uint64_t* links = nullptr;  // owners mode only: the link count per entry
 };
 constexpr uint32_t OI_COUNT_SLOTS = 1024;  // u64 per-workgroup counts of an ordered compaction
+// the count slots a sliced pass over n positions fills: one per workgroup, at most OI_COUNT_SLOTS
+uint32_t index_slots(uint64_t n);
 hipError_t index_lookup(const oi_view& x, const uint64_t* q, uint64_t m, uint64_t* out, uint8_t* found,
                         hipStream_t s);
 // the indexed owner rule + the compacted new heads (2 x u64 each, ascending key) and their
@@ -88,10 +90,9 @@ hipError_t index_insert_select(const oi_view& x, int nparts, int part, const uin
 hipError_t index_merge(const oi_view& x, const uint64_t* nk, const uint64_t* nv, uint64_t r, uint64_t* out_keys,
                        uint64_t* out_vals, hipStream_t s);
 // removal, first half: flags[n] in `scratch` (1 = the entry goes) and one count per workgroup
-// slice in counts[0 .. index_remove_slots(n)); n > 0, m > 0.  By key (rm_ids may be null:
+// slice in counts[0 .. index_slots(n)); n > 0, m > 0.  By key (rm_ids may be null:
 // unconditional) or by Object (m_ids = m sizes the scratch for the sorted ids).
 size_t index_remove_scratch(uint64_t n, uint64_t m_ids);
-uint32_t index_remove_slots(uint64_t n);
 hipError_t index_remove_flag_keys(const oi_view& x, const uint64_t* rm_keys, const uint64_t* rm_ids, uint64_t m,
                                   void* scratch, uint64_t* counts, hipStream_t s);
 hipError_t index_remove_flag_objects(const oi_view& x, const uint64_t* ids, uint64_t m, void* scratch,
@@ -139,10 +140,9 @@ hipError_t index_owners_remove_compact(const oi_view& x, const void* scratch, co
 // oi_links_after).  First half: both lists aggregated in `scratch`, every entry marked leaving /
 // staying, every distinct pair of the insertion list classed entering / present / another
 // shard's; index_apply_counts(scratch, n) then holds the per-slice counts of leaving entries
-// (`leaving` slots) followed by those of entering pairs (`entering` slots).  Nothing of the
+// (index_slots(n)) followed by those of entering pairs (index_slots(m_in)).  Nothing of the
 // index is written.  m_rm + m_in > 0; either may be 0; `counts`: OI_COUNT_SLOTS u64 of scratch.
 size_t index_apply_scratch(uint64_t n, uint64_t m_rm, uint64_t m_in);
-void index_apply_slots(uint64_t n, uint64_t m_in, uint32_t* leaving, uint32_t* entering);
 const uint64_t* index_apply_counts(const void* scratch, uint64_t n);
 hipError_t index_apply_flag(const oi_view& x, int nparts, int part, const uint64_t* rm_keys, const uint64_t* rm_ids,
                             uint64_t m_rm, const uint64_t* in_keys, const uint64_t* in_ids, uint64_t m_in,
@@ -164,14 +164,13 @@ hipError_t index_links(const oi_view& x, const uint64_t* q_keys, const uint64_t*
 // whether it has an entry (the orphans).  m > 0.  The per-slice counts of their ordered
 // compactions live in `scratch` too, not in the index's count slots.
 size_t index_objects_scratch(uint64_t m);
-uint32_t index_objects_slots(uint64_t m);
 hipError_t index_objects_totals(const oi_view& x, const uint64_t* ids, uint64_t stride, uint64_t m, bool sums,
                                 void* scratch, hipStream_t s);
 // the totals to the m listed positions (either output may be null)
 hipError_t index_objects_scatter(const void* scratch, uint64_t m, uint64_t* links_out, uint64_t* entries_out,
                                  hipStream_t s);
 // the distinct ids without an entry: counted per slice in index_objects_counts(scratch, m)[0 ..
-// index_objects_slots(m)), then written ascending to `out` (as many as the counts add up to)
+// index_slots(m)), then written ascending to `out` (as many as the counts add up to)
 const uint64_t* index_objects_counts(const void* scratch, uint64_t m);
 hipError_t index_orphans_flag(const void* scratch, uint64_t m, hipStream_t s);
 hipError_t index_orphans_compact(const void* scratch, uint64_t m, uint64_t* out, hipStream_t s);
@@ -183,11 +182,10 @@ hipError_t index_key_links(const oi_view& x, const uint64_t* q_keys, uint64_t m,
 // The duplicate groups of an index of n > 0 entries in `scratch` (index_groups_scratch(n) bytes,
 // 18 B per entry and 17 KiB): the totals of every run of equal keys; then the qualifying groups
 // (or, `entries`, the entries of the qualifying groups) flagged and counted per slice in
-// index_groups_counts(scratch, n)[0 .. index_groups_slots(n)); then, once the host has checked
+// index_groups_counts(scratch, n)[0 .. index_slots(n)); then, once the host has checked
 // the count, one row per flagged group / entry in order (every output may be null); or the
 // eight stats of sd_object_index_duplicate_stats at index_groups_stats_at(scratch, n).
 size_t index_groups_scratch(uint64_t n);
-uint32_t index_groups_slots(uint64_t n);
 hipError_t index_groups_totals(const oi_view& x, void* scratch, hipStream_t s);
 hipError_t index_groups_flag(const oi_view& x, void* scratch, uint64_t min_links, uint64_t min_owners, bool entries,
                              hipStream_t s);
