@@ -469,8 +469,9 @@ def test_dedup_group_edge_sizes(ctx, dedup_variant):
 
 
 def test_dedup_group_large_groups(ctx, dedup_variant):
-    """Duplicate groups larger than a wave's LDS bucket (512): 3000 files and 40 groups of
-    600..1500 go to the workgroup sort (k_gb_sort_big); 5000 exceed it (radix fallback)."""
+    """Duplicate groups larger than a wave's LDS bucket (GB_CAP = 128): 3000 files and 40 groups
+    of 600..1500 go to the workgroup sort (k_gb_sort_big, up to 4096); 5000 exceed it (radix
+    fallback)."""
     rng = np.random.default_rng(8)
     m = 200000
     keys = rng.integers(-2**63, 2**63 - 1, m, dtype=np.int64)
@@ -1276,6 +1277,37 @@ def test_dedup_mgpu_through_rccl_single_rank(ctx, rccl_comm):
     # the torch.distributed exchange path gives the same outputs
     r2, rep2, ng2, own2 = dedup.dedup_shard(ctx, d_hash, d_valid, n, base)
     assert ng2 == gng and np.array_equal(r2.cpu().numpy(), gr) and np.array_equal(own2.cpu().numpy(), want_owner)
+
+
+def test_dedup_mgpu_bucket_overflow_single_rank(ctx, rccl_comm, dedup_variant):
+    """sd_cas_dedup_mgpu passes SD_DEDUP_INDEX_SORTED and an owner chunk to the grouping.  With a
+    bucket of 4097 records (shape_cases.bucket_case) the LDS-bucket path overflows after the
+    owners kernel already ran on its permuted records: the host has to drop the flag, group on
+    the radix path and run the owners again.  With one of 129 (k_gb_sort_big) the first,
+    speculative owners stand.  Records, representatives, group count and owners against
+    group_host and object_owners."""
+    from spacedrive_amd import dedup
+    from spacedrive_amd.identifier import object_owners
+    from tests import shape_cases as sc
+    base, chunk = 7_000_000, 100
+    compared = 0
+    for s, layout in ((4097, "late"), (129, "pairs_shifted")):
+        keys = np.ascontiguousarray(sc.bucket_case(s, layout, True)[:, 0]).view(np.uint64)
+        n = len(keys)
+        d_hash = torch.from_numpy(sc.hashes_from_keys(keys, s)).cuda()
+        d_valid = torch.ones(n, dtype=torch.uint8, device="cuda")
+        gr, grep, gng = group_host(np.stack([keys.view(np.int64), np.arange(base, base + n)], axis=1))
+        want_owner = object_owners(torch.from_numpy(gr[:, 1].copy()), torch.from_numpy(grep), chunk).numpy()
+        assert (want_owner != gr[:, 1]).sum() >= s // 4  # many records link to an earlier step's Object
+        runner = dedup.RcclDedup(ctx, rccl_comm, d_hash.device, capacity=n)
+        recs, rep, ng, owner = runner(d_hash, d_valid, n, base, chunk_size=chunk)
+        torch.cuda.synchronize()
+        assert ng == gng, s
+        assert np.array_equal(recs.cpu().numpy(), gr), s
+        assert np.array_equal(rep.cpu().numpy(), grep), s
+        assert np.array_equal(owner.cpu().numpy(), want_owner), s
+        compared += n
+    assert compared == (4097 + 202) + (129 + 202)
 
 
 def test_dedup_mgpu_bounded_wait_breaks_the_comm(ctx):

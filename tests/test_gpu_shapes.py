@@ -401,8 +401,9 @@ def group_records(m: int, seed: int) -> np.ndarray:
 
 
 def test_dedup_group_writes_only_m_rows(ctx, dedup_variant):
-    """sd_dedup_group sorts d_records[m] in place and writes d_rep[m]: sizes around the wave,
-    the LDS bucket (512) and none at all, the rows past m guarded."""
+    """sd_dedup_group sorts d_records[m] in place and writes d_rep[m]: record counts m around
+    64 and 512 and none at all, the rows past m guarded.  (Uniform keys: no bucket grows past a
+    wave here; test_dedup_group_bucket_sizes sweeps the bucket sizes.)"""
     compared = 0
     for m in sc.GROUP_M:
         recs = group_records(m, 40 + m)
@@ -416,6 +417,67 @@ def test_dedup_group_writes_only_m_rows(ctx, dedup_variant):
         assert np.array_equal(d_rep.host().view(np.int64).reshape(m), grep), m
         compared += 1
     assert compared == 10
+
+
+def group_guarded(ctx, recs: np.ndarray, index_sorted: bool, what, fill_rep=None):
+    """sd_dedup_group on guarded record and rep rows: records, representatives and the group
+    count bit-exact against group_host, the guards intact."""
+    m = len(recs)
+    gr, grep, gng = group_host(recs)
+    d_recs, d_rep = Guarded(m, 16, torch.int64), Guarded(m, 8, torch.int64)
+    d_recs.inner.copy_(torch.from_numpy(np.ascontiguousarray(recs).reshape(-1)))
+    if fill_rep is not None:
+        d_rep.raw[G * 8:(G + m) * 8] = fill_rep
+    ng = ctx.dedup_group(d_recs.inner, m, d_rep.inner, index_sorted=index_sorted)
+    assert d_recs.guards_intact() and d_rep.guards_intact(), what
+    assert ng == gng, what
+    got = d_recs.host().view(np.int64).reshape(m, 2)
+    bad = np.nonzero((got != gr.reshape(m, 2)).any(axis=1))[0]
+    assert len(bad) == 0, (what, "records", bad[:8].tolist())
+    bad = np.nonzero(d_rep.host().view(np.int64).reshape(m) != grep)[0]
+    assert len(bad) == 0, (what, "rep", bad[:8].tolist())
+
+
+@pytest.mark.parametrize("layout", list(sc.BUCKET_LAYOUTS))
+def test_dedup_group_bucket_sizes(ctx, dedup_variant, layout):
+    """Every branch of the LDS-bucket grouping on the size s of a bucket, one size either side of
+    each border: registers (s <= 64), one wave in LDS with a carry between its two 64-record
+    chunks (<= 128), k_gb_sort_big with wmax[] across waves, carry_s across 1024-record chunks
+    and two pairs per lane at P = 4096 (<= 4096), and the overflow to the radix path (4097, also
+    with index_sorted, which the host has to drop).  One bucket of exactly s records per case
+    (shape_cases.bucket_case), its runs of equal keys by `layout`: a head at 0, a late head, a
+    head on every 64-multiple, a group across every 64-multiple."""
+    compared = 0
+    for s, srt, recs in sc.bucket_cases(layout):
+        group_guarded(ctx, recs, srt, (layout, s, srt))
+        compared += 1
+    assert compared == 2 * sc.BUCKET_CASES_PER_LAYOUT[layout]
+
+
+def test_dedup_group_many_big_buckets(ctx, dedup_variant):
+    """More big buckets (130) than k_gb_sort_big has workgroups (128): two workgroups take a
+    second bucket; and m = 129 x 64 records all in buckets of 129, the most big[] can be asked to
+    list for its m."""
+    compared = 0
+    for name, gen in (("many", sc.many_big_case), ("all", sc.all_big_case)):
+        for srt in (False, True):
+            group_guarded(ctx, gen(srt), srt, (name, srt))
+            compared += 1
+    assert compared == 4
+
+
+def test_dedup_group_spans_and_lg_borders(ctx, dedup_variant):
+    """(key - kmin) >> shift for key spans of 0..3, either side of 2^lg, 2^32 and 2^63, and all of
+    u64, from kmin 0, 1, a high prefix and the largest that fits; and record counts either side
+    of the first steps of gb_lg."""
+    compared = 0
+    for span, kmin, srt, recs in sc.span_cases():
+        group_guarded(ctx, recs, srt, ("span", span, kmin, srt))
+        compared += 1
+    for m, srt, recs in sc.lg_border_cases():
+        group_guarded(ctx, recs, srt, ("m", m, srt))
+        compared += 1
+    assert compared == 45 + 6
 
 
 def test_dedup_owners_writes_only_m_rows(ctx):
@@ -477,6 +539,18 @@ def test_checksum_batches_do_not_lean_on_stale_scratch(ctx, oracle_native):
         assert len(bad_rows(got, want_checksums(oracle_native, lens, cids, twins))) == 0, lens
         compared += len(lens)
     assert compared == 4 + 6 + 4
+
+
+def test_dedup_group_not_leaning_on_stale_scratch(ctx, dedup_variant):
+    """The grouping's state lives in scratch the context keeps between calls: an overflowing
+    bucket (4097: `overflow` set, one big[] entry), then one wave-LDS bucket (65: no big bucket
+    at all), then one big bucket (129), each into rep rows of 0xFF.  An `overflow`, `nbig` or
+    big[] entry left from the call before would send a call down the wrong path."""
+    compared = 0
+    for s, layout, srt in ((4097, "late", True), (65, "pairs_shifted", False), (129, "late5", True)):
+        group_guarded(ctx, sc.bucket_case(s, layout, srt), srt, (s, layout, srt), fill_rep=0xFF)
+        compared += 1
+    assert compared == 3
 
 
 # ----------------------------------------------------- F: sd_dedup_partition sweep

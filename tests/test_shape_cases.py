@@ -1,14 +1,19 @@
 """The shape sweeps of tests/shape_cases.py without a device: the generators' own counts,
 the library's CPU path (the staged and range entry points of spacedrive_amd/cpu.py) and the
-Python spec against the C oracle at those shapes, and the host mirror of
-sd_dedup_partition at the extremes of its key range.  tests/test_gpu_shapes.py runs the
-same lists through the kernels."""
+Python spec against the C oracle at those shapes, the host mirror of
+sd_dedup_partition at the extremes of its key range, and the bucket-size cases of
+sd_dedup_group: their own assertions, group_host against a brute-force grouping, and the
+bucket constants against dedup.hip.  tests/test_gpu_shapes.py runs the same lists through
+the kernels."""
+import os
+import re
+
 import numpy as np
 
 from oracle import cas_spec as cs
 from spacedrive_amd import cpu
 from spacedrive_amd._native import check, lib
-from spacedrive_amd.dedup import dest_of, partition_host
+from spacedrive_amd.dedup import dest_of, group_host, partition_host
 from spacedrive_amd.device import stage_plan
 from tests import shape_cases as sc
 
@@ -92,6 +97,80 @@ def test_sweep_a_small_python_spec_pins_oracle(oracle_native):
         assert cs.generate_cas_id(cs.synth_reader(int(cids[i])), int(sizes[i])) == ids[i].tobytes().hex(), (C, r)
         n += 1
     assert n == 62
+
+
+def test_bucket_generators_count_their_cases():
+    """Every list of section D2 built once: each generator asserts, through the numpy mirror of
+    the bucket arithmetic, the bucket sizes it exists for."""
+    n = 0
+    for layout in sc.BUCKET_LAYOUTS:
+        cases = sc.bucket_cases(layout)
+        assert all(len(r) == s + 202 for s, _, r in cases)
+        n += len(cases)
+    assert n == 2 * 126
+    assert len(sc.many_big_case()) == 130 * 129 + 2 and len(sc.many_big_case(True)) == 130 * 129 + 2
+    assert len(sc.all_big_case()) == 64 * 129 and len(sc.all_big_case(True)) == 64 * 129
+    assert len(sc.span_cases()) == 45 and len(sc.lg_border_cases()) == 6
+    assert [sc.gb_lg(m) for m in (1, 96, 97, 192, 193, 1000, 48 << 23, (48 << 23) + 1, 1 << 40)] == [1, 1, 2, 2, 3, 5, 23, 24, 24]
+    # the mirror on keys a hand can follow: span 2^32 at m = 97 (lg 2) shifts by 33 - 2
+    bk, (lg, shift) = sc.gb_buckets(np.array([5] * 95 + [5 + (1 << 32), 5 + (1 << 31)], np.uint64))
+    assert (lg, shift) == (2, 31) and bk.tolist() == [0] * 95 + [2, 1]
+
+
+def brute_group(recs: np.ndarray):
+    """sd_dedup_group's rule with no sort network and no scan: a dict from key to its smallest
+    index, and Python's sort of (key, index) tuples -- all as unsigned Python integers."""
+    pairs = [(int(k), int(i)) for k, i in zip(recs[:, 0].view(np.uint64), recs[:, 1].view(np.uint64))]
+    least = {}
+    for k, i in pairs:
+        least[k] = min(i, least.get(k, i))
+    pairs.sort()
+    return pairs, [least[k] for k, _ in pairs], len(least)
+
+
+def test_group_host_vs_brute_force():
+    """group_host (the GPU sweeps' expected value) against brute_group at the one-wave LDS size
+    and past a 1024-lane chunk, for the layouts with a head off position 0."""
+    n = 0
+    for s in (65, 1025):
+        for layout in ("singles", "late", "pairs_shifted"):
+            for srt in (False, True):
+                recs = sc.bucket_case(s, layout, srt)
+                gr, grep, gng = group_host(recs)
+                pairs, reps, ng = brute_group(recs)
+                assert gng == ng
+                assert list(zip(gr[:, 0].view(np.uint64).tolist(), gr[:, 1].tolist())) == pairs
+                assert grep.tolist() == reps
+                # the records that are not their group's representative
+                assert (grep != gr[:, 1]).sum() == {"singles": 0, "late": s - 2, "pairs_shifted": (s - 1) // 2}[layout]
+                n += 1
+    assert n == 12
+
+
+def parse_gb_constants(path: str) -> dict:
+    """GB_CAP, GB_BIG_CAP and GB_BIG_GRID from their constexpr lines, and the records per bucket
+    and the lg cap from gb_lg's loop, of a dedup.hip."""
+    src = open(path).read()
+    out = {}
+    for name in ("GB_CAP", "GB_BIG_CAP", "GB_BIG_GRID"):
+        found = re.findall(r"^constexpr\s+uint32_t\s+" + name + r"\s*=\s*(\d+)\s*;", src, re.M)
+        assert len(found) == 1, name
+        out[name] = int(found[0])
+    body = re.search(r"static\s+uint32_t\s+gb_lg\(uint64_t m\)\s*\{(.*?)\n\}", src, re.S)
+    assert body, "gb_lg"
+    loop = re.findall(r"while\s*\(lg\s*<\s*(\d+)\s*&&\s*\(\(uint64_t\)\s*(\d+)\s*<<\s*lg\)\s*<\s*m\)", body.group(1))
+    assert len(loop) == 1, "gb_lg's loop"
+    out["GB_LG_MAX"], out["GB_PER_BUCKET"] = int(loop[0][0]), int(loop[0][1])
+    return out
+
+
+def test_bucket_constants_match_the_kernels():
+    """shape_cases' restatement of the bucket arithmetic uses dedup.hip's constants: a retune of
+    the kernels fails here instead of moving a branch out from under the bucket-size sweep."""
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "spacedrive_amd", "csrc", "dedup.hip")
+    assert parse_gb_constants(path) == {"GB_CAP": sc.GB_CAP, "GB_BIG_CAP": sc.GB_BIG_CAP, "GB_BIG_GRID": sc.GB_BIG_GRID,
+                                        "GB_LG_MAX": sc.GB_LG_MAX, "GB_PER_BUCKET": sc.GB_PER_BUCKET}
+    assert (sc.GB_LG_MAX, sc.GB_PER_BUCKET) == (24, 48)
 
 
 def test_partition_host_vs_python_loop():
