@@ -414,6 +414,56 @@ int sd_dedup_group(sd_cas_ctx* ctx, uint64_t* d_records, uint64_t m, int flags, 
  * step links to it).  Asynchronous on `stream`; no host sync. */
 int sd_dedup_owners(sd_cas_ctx* ctx, const uint64_t* d_records, uint64_t m, const uint64_t* d_rep,
                     uint64_t chunk_size, uint64_t* d_owner, void* stream);
+/* Confirm candidate groups by full checksum.  A cas_id samples files over 100 KiB
+ * (core/src/object/cas.rs:30-58): equal cas_ids mean equal size, head, four samples and tail,
+ * not equal bytes; file_checksum (core/src/object/validation/hash.rs:10-24) hashes every byte.
+ * d_keys[m]: the cas key of file i (the big-endian u64 of the first 8 cas hash bytes, as in
+ * d_records and the index); d_hash32: m x 32 bytes of full checksum per file, 8-byte aligned
+ * (what sd_fingerprint_batch_run leaves in d_checksum32); d_valid: m bytes, may be NULL (every
+ * file valid), 0 = a file whose checksum could not be computed.  Per valid file i:
+ *   group(i) = the valid j with keys[j] == keys[i]
+ *   class(i) = the valid j with keys[j] == keys[i] and hash32[j] == hash32[i] over all 32 bytes
+ * (equal checksums under different keys are different classes).
+ *   d_rep[i]        = the smallest member of class(i)          UINT64_MAX for an invalid file
+ *   d_class_size[i] = the size of class(i)                     0
+ *   d_verdict[i]    = SD_CONFIRM_SINGLE / _CONFIRMED / _REFUTED   SD_CONFIRM_INVALID
+ * An invalid file is never a representative and never counted, even with the smallest index of
+ * its key.  Any of the three may be NULL.
+ * d_sets_out (3 x u64 per row): one row (key, rep, size) per class of at least 2 members,
+ * ascending by key, within a key ascending by the 32 checksum bytes as memcmp compares them;
+ * *n_sets (host, may be NULL) = the rows.  If d_sets_out is given and capacity < *n_sets: the
+ * call returns SD_ERR_CAPACITY with *n_sets = the requirement and nothing written to
+ * d_sets_out; the per-file outputs and stats do not depend on capacity and are written in full
+ * then too.  Nothing past the first *n_sets rows is ever written; with d_sets_out NULL the call
+ * only counts.
+ * stats[8] (host, may be NULL): [0] valid files, [1] groups, [2] candidate groups (at least 2
+ * files), [3] classes, [4] confirmed classes (size at least 2; == *n_sets), [5] files in
+ * confirmed classes, [6] refuted files, [7] candidate groups that hold at least 2 classes: the
+ * cas_ids that lied.  Confirmed redundant files = [5] - [4]; [0] == ([1] - [2]) + [5] + [6] and
+ * [3] == ([1] - [2]) + [4] + [6].
+ * m == 0 is valid: counts are 0, nothing is written.  A NULL d_keys or d_hash32 with m > 0 is
+ * SD_ERR_INVALID.  Runs on `stream` and syncs it; scratch comes from the context's pooled slot
+ * (grow-only: 49 bytes per file plus the radix sort's; no allocation in a call whose m fits what
+ * the slot holds), so concurrent calls on one context are as safe as sd_dedup_group's.  Not
+ * collective: a key lives in one shard of sd_dedup_partition, so per-shard answers concatenate.
+ * rep is a position in the call's arrays; the caller maps it to its own file ids.
+ * Two paths, equal answers ("confirm_full_sort", sd_cas_set_tuning): a sort by (key, first 8
+ * checksum bytes) whose head pass compares the other 24 through the permutation, and, only when
+ * some run of equal (key, first 8 bytes) holds unequal tails, a sort over all 40 bytes. */
+#define SD_CONFIRM_INVALID   0  /* d_valid[i] == 0: not looked at */
+#define SD_CONFIRM_SINGLE    1  /* the only valid file of its key: nothing to confirm */
+#define SD_CONFIRM_CONFIRMED 2  /* another valid file has the same key AND the same 32 bytes */
+#define SD_CONFIRM_REFUTED   3  /* shares its key with other valid files, its checksum with none */
+int sd_dedup_confirm(sd_cas_ctx* ctx, const uint64_t* d_keys, const uint8_t* d_hash32, const uint8_t* d_valid,
+                     uint64_t m, uint64_t* d_rep, uint64_t* d_class_size, uint8_t* d_verdict,
+                     uint64_t* d_sets_out, uint64_t capacity, uint64_t* n_sets, uint64_t stats[8], void* stream);
+/* out[0] = the sd_dedup_confirm calls of this context that finished on the prefix path, out[1] =
+ * those that took the full-width path (m == 0 takes neither). */
+int sd_dedup_confirm_stats(sd_cas_ctx* ctx, uint64_t out[2]);
+/* The same over host arrays, without a context or a device (hash.rs:10-24; cas.rs:30-58). */
+int sd_cpu_dedup_confirm(const uint64_t* keys, const uint8_t* hash32, const uint8_t* valid, uint64_t m,
+                         uint64_t* rep, uint64_t* class_size, uint8_t* verdict, uint64_t* sets_out,
+                         uint64_t capacity, uint64_t* n_sets, uint64_t stats[8]);
 
 /* ---------------------------------------------------------------- Object index */
 /* Which Object of the library already owns a cas_id: the join identifier_job_step does per
@@ -661,7 +711,8 @@ int sd_object_index_orphans(sd_cas_ctx* ctx, const sd_object_index* index, const
  * still ascending; stats rows add up over shards ([7] takes the maximum); key_links rows add up
  * (a key lives in one shard).
  * The limits: a cas_id samples files over 100 KiB (core/src/object/cas.rs:30-58), so a group is
- * a candidate set that sd_file_checksums confirms; the index knows no paths and no sizes (the
+ * a candidate set until sd_dedup_confirm (or sd_cpu_dedup_confirm, over sd_file_checksums'
+ * output) has split it by full checksum; the index knows no paths and no sizes (the
  * host joins them from the DB by cas_id: the key's 16 hex digits); files without a cas_id are
  * invisible.
  * sd_object_index_key_links (mod.rs:189-225, :229-333): per listed key (any order, repeats
@@ -926,7 +977,9 @@ int sd_checksum_batch_time(sd_cas_ctx* ctx, const sd_checksum_batch* batch, cons
  * RCCL peers (0 = no bound); "fingerprint_window_mb" (256): the device window of ranges
  * sd_fingerprints uploads at once (a longer range streams); "index_dir_max_bits" (24): the
  * most prefix-directory bits an Object-index insert chooses (0 = no directory: every lookup is
- * a binary search over the whole key array).  Unknown keys fail with SD_ERR_INVALID. */
+ * a binary search over the whole key array); "confirm_full_sort" (0): sd_dedup_confirm sorts by
+ * (key, first 8 checksum bytes) and takes the full-width sort only on a tie with unequal tails
+ * (1 = always the full-width sort).  Unknown keys fail with SD_ERR_INVALID. */
 int sd_cas_set_tuning(const char* key, int value);
 int sd_cas_get_tuning(const char* key, int* value);
 /* Read-only probe over d_buf[0, bytes) (bytes a multiple of 4096) for calibrating the

@@ -71,6 +71,11 @@ pub const SD_FILE_SHORT_READ: i32 = 3;
 pub const SD_FILE_CHANGED: i32 = 4;
 pub const SD_COMM_ID_BYTES: usize = 128;
 pub const SD_OBJECT_INDEX_OWNERS: c_int = 1;
+// sd_dedup_confirm's verdict per file
+pub const SD_CONFIRM_INVALID: u8 = 0;
+pub const SD_CONFIRM_SINGLE: u8 = 1;
+pub const SD_CONFIRM_CONFIRMED: u8 = 2;
+pub const SD_CONFIRM_REFUTED: u8 = 3;
 
 extern "C" {
     pub fn sd_cas_abi_version() -> c_int;
@@ -225,6 +230,16 @@ extern "C" {
                                              stream: *mut c_void) -> c_int;
     pub fn sd_object_index_duplicate_stats(ctx: *mut sd_cas_ctx, index: *const sd_object_index, out: *mut u64,
                                            stream: *mut c_void) -> c_int;
+    // a duplicate group is a candidate set (cas.rs:30-58 samples): split by full checksum
+    // (hash.rs:10-24) on the device, or over host arrays without one
+    pub fn sd_dedup_confirm(ctx: *mut sd_cas_ctx, d_keys: *const u64, d_hash32: *const u8, d_valid: *const u8,
+                            m: u64, d_rep: *mut u64, d_class_size: *mut u64, d_verdict: *mut u8,
+                            d_sets_out: *mut u64, capacity: u64, n_sets: *mut u64, stats: *mut u64,
+                            stream: *mut c_void) -> c_int;
+    pub fn sd_dedup_confirm_stats(ctx: *mut sd_cas_ctx, out: *mut u64) -> c_int;
+    pub fn sd_cpu_dedup_confirm(keys: *const u64, hash32: *const u8, valid: *const u8, m: u64, rep: *mut u64,
+                                class_size: *mut u64, verdict: *mut u8, sets_out: *mut u64, capacity: u64,
+                                n_sets: *mut u64, stats: *mut u64) -> c_int;
     // device buffers for callers that hold their lists on the host (sd_memcpy syncs `stream`)
     pub fn sd_device_malloc(ctx: *mut sd_cas_ctx, bytes: u64, out: *mut *mut c_void) -> c_int;
     pub fn sd_device_free(ctx: *mut sd_cas_ctx, p: *mut c_void);

@@ -184,7 +184,11 @@ SIGNATURES = [
     ("sd_cpu_object_index_duplicates", I32, [P, U64, U64, P, P, P, P, U64, PU64]),
     ("sd_cpu_object_index_duplicate_entries", I32, [P, U64, U64, P, P, P, U64, PU64]),
     ("sd_cpu_object_index_duplicate_stats", I32, [P, P]),
+    ("sd_dedup_confirm", I32, [P, P, P, P, U64, P, P, P, P, U64, PU64, P, P]),
+    ("sd_dedup_confirm_stats", I32, [P, P]),
+    ("sd_cpu_dedup_confirm", I32, [P, P, P, U64, P, P, P, P, U64, PU64, P]),
 ]
+SD_CONFIRM_INVALID, SD_CONFIRM_SINGLE, SD_CONFIRM_CONFIRMED, SD_CONFIRM_REFUTED = 0, 1, 2, 3
 SD_OBJECT_INDEX_OWNERS = 1
 
 

@@ -94,6 +94,39 @@ def fingerprints(data, offsets, lens, nthreads: int = THREADS):
     return _split_hex(o17, 16, n), _split_hex(o65, 64, n)
 
 
+def confirm(keys, hash32, valid=None, capacity: Optional[int] = None, want_sets: bool = True):
+    """sd_cpu_dedup_confirm: candidate groups (keys uint64 [m]) split into classes of equal
+    checksums (hash32 uint8 [m, 32]); valid uint8 [m] or None.  Returns (rep uint64 [m],
+    class_size uint64 [m], verdict uint8 [m], sets uint64 [n_sets, 3], stats uint64 [8]).
+    `capacity` (default m // 2, always enough) short of the sets raises SdCasError
+    (SD_ERR_CAPACITY) with ``.needed``; want_sets=False only counts (sets comes back empty)."""
+    from ._native import SdCasError
+    k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+    m = len(k)
+    h = np.ascontiguousarray(hash32, dtype=np.uint8).reshape(-1)
+    if h.size != 32 * m:
+        raise ValueError("hash32 is not m x 32 bytes")
+    v = None if valid is None else np.ascontiguousarray(np.asarray(valid).reshape(-1) != 0, dtype=np.uint8)
+    if v is not None and v.size != m:
+        raise ValueError("valid is not m bytes")
+    rep, size = np.zeros(max(m, 1), np.uint64), np.zeros(max(m, 1), np.uint64)
+    verdict = np.zeros(max(m, 1), np.uint8)
+    cap = m // 2 if capacity is None else int(capacity)
+    sets = np.zeros((max(cap, 1), 3), np.uint64)
+    n_sets = ctypes.c_uint64(0)
+    stats = np.zeros(8, np.uint64)
+    rc = lib().sd_cpu_dedup_confirm(k.ctypes.data if m else None, h.ctypes.data if m else None,
+                                    None if v is None else v.ctypes.data, m, rep.ctypes.data, size.ctypes.data,
+                                    verdict.ctypes.data, sets.ctypes.data if want_sets else None, cap,
+                                    ctypes.byref(n_sets), stats.ctypes.data)
+    try:
+        check(rc)
+    except SdCasError as e:
+        e.needed = int(n_sets.value)
+        raise
+    return rep[:m], size[:m], verdict[:m], sets[:int(n_sets.value) if want_sets else 0], stats
+
+
 def blake3(data: bytes) -> bytes:
     """Full 32-byte BLAKE3 of a host buffer (sd_cpu_checksums of one range)."""
     buf = np.frombuffer(bytes(data) + bytes(64), np.uint8)

@@ -273,6 +273,8 @@ struct sd_cas_ctx {
     std::atomic<uint64_t> checksums_gpu_bytes{0}, checksums_host_bytes{0};  // sd_checksums: who hashed
     // sd_fingerprints: bytes sent H2D, files gathered on the device, large ranges
     std::atomic<uint64_t> fp_h2d_bytes{0}, fp_gathered{0}, fp_large{0};
+    // sd_dedup_confirm: calls that finished on the prefix path, calls that took the full-width path
+    std::atomic<uint64_t> confirm_calls_prefix{0}, confirm_calls_full{0};
     std::mutex split_mu;
     SplitRoutes split_routes;  // sd_file_checksums: the split or the CPU path, learned (sd_host.h)
     uint64_t split_routes_gen = 0;  // split_route_tuning_gen() the rates were learned under

@@ -763,6 +763,59 @@ int sd_dedup_owners(sd_cas_ctx* ctx, const uint64_t* d_records, uint64_t m, cons
     SD_GUARD_END
 }
 
+// Candidate groups split into classes of equal checksums (dedup_confirm.hip).  The prefix path is
+// queued whole, its state read once; only when it reports a (key, h0) run with unequal tails --
+// its kernels then wrote no output -- the full-width path runs.  Scratch: the pooled slot's, as
+// sd_dedup_group's.
+int sd_dedup_confirm(sd_cas_ctx* ctx, const uint64_t* d_keys, const uint8_t* d_hash32, const uint8_t* d_valid,
+                     uint64_t m, uint64_t* d_rep, uint64_t* d_class_size, uint8_t* d_verdict,
+                     uint64_t* d_sets_out, uint64_t capacity, uint64_t* n_sets, uint64_t stats[8], void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || (m && (!d_keys || !d_hash32))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (reinterpret_cast<uintptr_t>(d_hash32) % 8) throw sd_failure(SD_ERR_INVALID, "d_hash32 must be 8-byte aligned");
+    if (n_sets) *n_sets = 0;
+    if (stats) memset(stats, 0, 8 * sizeof(uint64_t));
+    if (m == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    auto slot = ctx->acquire();
+    struct Rel {
+        sd_cas_ctx* c;
+        std::unique_ptr<Slot>* s;
+        ~Rel() { c->release(std::move(*s)); }
+    } rel{ctx, &slot};
+    slot->staged.ensure(sdk::dedup_confirm_scratch(m));
+    slot->hashes.ensure(sdk::DEDUP_CONFIRM_STATE * sizeof(uint64_t));
+    slot->host_hashes.ensure(sdk::DEDUP_CONFIRM_STATE * sizeof(uint64_t));
+    const uint64_t* st = reinterpret_cast<const uint64_t*>(slot->host_hashes.p);
+    bool full = tuning_get(SD_TUNE_CONFIRM_FULL_SORT) != 0;
+    for (;;) {
+        HIP_CHECK(sdk::dedup_confirm(d_keys, d_hash32, d_valid, m, full, d_rep, d_class_size, d_verdict, d_sets_out,
+                                     capacity, slot->hashes.as<uint64_t>(), slot->staged.p, slot->staged.bytes, s));
+        HIP_CHECK(hipMemcpyAsync(slot->host_hashes.p, slot->hashes.p, sdk::DEDUP_CONFIRM_STATE * sizeof(uint64_t),
+                                 hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (full || st[8] == 0) break;
+        full = true;
+    }
+    (full ? ctx->confirm_calls_full : ctx->confirm_calls_prefix).fetch_add(1, std::memory_order_relaxed);
+    if (st[0] > m || st[4] > st[3] || st[3] > st[0]) throw sd_failure(SD_ERR_INTERNAL, "confirm: inconsistent totals");
+    if (n_sets) *n_sets = st[4];
+    if (stats) memcpy(stats, st, 8 * sizeof(uint64_t));
+    if (d_sets_out && capacity < st[4]) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of sets");
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_dedup_confirm_stats(sd_cas_ctx* ctx, uint64_t out[2]) {
+    SD_GUARD_BEGIN
+    if (!ctx || !out) throw sd_failure(SD_ERR_INVALID, "null argument");
+    out[0] = ctx->confirm_calls_prefix.load(std::memory_order_relaxed);
+    out[1] = ctx->confirm_calls_full.load(std::memory_order_relaxed);
+    return SD_OK;
+    SD_GUARD_END
+}
+
 // ----------------------------------------------------------------- synthetic data
 int sd_synth_stage_cas(sd_cas_ctx* ctx, const uint64_t* d_sizes, const uint64_t* d_cids, const uint32_t* d_twins,
                        const sd_extent* d_extents, size_t n, uint8_t* d_staged, void* stream) {

@@ -47,7 +47,7 @@ thread_local std::string g_err;
 // 5-minute bound on every wait of the RCCL exchange for its peers (torch's own NCCL watchdog
 // waits 10); the Object index's prefix directory up to 2^24 buckets (0 = none: a binary search
 // over the whole key array, the A/B of DESIGN.md §5)
-std::atomic<int> g_tune[SD_TUNE_NKEYS] = {{200}, {4096}, {32}, {1}, {16}, {16}, {6144}, {512}, {4096}, {4}, {2147483647}, {1}, {6}, {15}, {0}, {1}, {0}, {256}, {1}, {8}, {300000}, {256}, {24}};
+std::atomic<int> g_tune[SD_TUNE_NKEYS] = {{200}, {4096}, {32}, {1}, {16}, {16}, {6144}, {512}, {4096}, {4}, {2147483647}, {1}, {6}, {15}, {0}, {1}, {0}, {256}, {1}, {8}, {300000}, {256}, {24}, {0}};
 const char* const TUNE_NAMES[SD_TUNE_NKEYS] = {"coalesce_window_us", "coalesce_max",    "files_window_mb",
                                                "dedup_variant",      "latency_cpu_max", "read_threads",
                                                "sampled_wave_max",   "whole_wave_max",  "batch_cpu_max",
@@ -56,7 +56,8 @@ const char* const TUNE_NAMES[SD_TUNE_NKEYS] = {"coalesce_window_us", "coalesce_m
                                                "host_cpu_budget",    "checksum_stage_hot", "numa_pin",
                                                "cpu_read_piece_kib", "checksum_split_blocks",
                                                "checksum_split_adapt", "comm_timeout_ms",
-                                               "fingerprint_window_mb", "index_dir_max_bits"};
+                                               "fingerprint_window_mb", "index_dir_max_bits",
+                                               "confirm_full_sort"};
 
 bool read_small(const std::string& path, char* buf, size_t cap) {
     FILE* f = fopen(path.c_str(), "re");

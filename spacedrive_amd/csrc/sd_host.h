@@ -80,7 +80,8 @@ enum sd_tune_key {
     SD_TUNE_COMM_TIMEOUT_MS = 20,          // sd_cas_dedup_mgpu over RCCL: longest wait for the peers (0 = none)
     SD_TUNE_FINGERPRINT_WINDOW_MB = 21,    // sd_fingerprints: device window of ranges per upload (MiB)
     SD_TUNE_INDEX_DIR_MAX_BITS = 22,       // Object index: most directory bits an insert chooses (0 = no directory)
-    SD_TUNE_NKEYS = 23
+    SD_TUNE_CONFIRM_FULL_SORT = 23,        // sd_dedup_confirm: 0 = the prefix path first, 1 = always the full-width path
+    SD_TUNE_NKEYS = 24
 };
 int tuning_get(int key);
 

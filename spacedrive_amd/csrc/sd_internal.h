@@ -62,6 +62,15 @@ hipError_t dedup_group_buckets(uint64_t* records, uint64_t m, uint64_t* rep, uin
                                size_t scratch_bytes, hipStream_t s);
 hipError_t dedup_owners(const uint64_t* records, uint64_t m, const uint64_t* rep, uint64_t chunk, uint64_t* owner,
                         hipStream_t s);
+// sd_dedup_confirm (dedup_confirm.hip), one pass queued on s: the prefix path, or (full) the
+// full-width path.  state: DEDUP_CONFIRM_STATE device u64, [0..7] = the stats, [8] = nonzero when
+// the prefix path met a (key, h0) run with unequal tails -- then this pass wrote no output and
+// the pass with full = true must run.  Every output may be null; m > 0.
+constexpr uint32_t DEDUP_CONFIRM_STATE = 16;
+size_t dedup_confirm_scratch(uint64_t m);
+hipError_t dedup_confirm(const uint64_t* keys, const uint8_t* hash32, const uint8_t* valid, uint64_t m, bool full,
+                         uint64_t* rep, uint64_t* class_size, uint8_t* verdict, uint64_t* sets, uint64_t capacity,
+                         uint64_t* state, void* scratch, size_t scratch_bytes, hipStream_t s);
 // Object index (object_index.hip; layout in object_index.h): the current device arrays
 struct oi_view {
     const uint64_t *keys, *vals, *dir;

@@ -86,6 +86,46 @@ def group_device(ctx, records: torch.Tensor, index_sorted: bool = False) -> Tupl
     return records, rep[:m], ng
 
 
+def keys_from_hashes_device(d_cas_hash32: torch.Tensor, ctx=None) -> torch.Tensor:
+    """keys_from_hashes on the device: the cas key (int64 carrying the big-endian u64 of the
+    first 8 bytes) of every row of d_cas_hash32 (uint8 [n, 32], e.g. what
+    sd_fingerprint_batch_run leaves in d_cas_hash32), in row order.  It is sd_dedup_partition
+    over one destination: stable, so the records' key column is the answer."""
+    from .device import default_context
+    n = int(d_cas_hash32.numel() // 32)
+    dev = d_cas_hash32.device
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int64, device=dev)
+    assert d_cas_hash32.dtype == torch.uint8 and d_cas_hash32.is_cuda and d_cas_hash32.is_contiguous()
+    ctx = default_context(dev.index) if ctx is None else ctx
+    counts = torch.empty(1, dtype=torch.int64, device=dev)
+    recs = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    nv = ctx.dedup_partition(d_cas_hash32, None, n, 0, 1, counts, recs)
+    assert nv == n
+    return recs[:, 0].contiguous()
+
+
+def confirm_device(ctx, d_keys: torch.Tensor, d_hash32: torch.Tensor, d_valid: Optional[torch.Tensor] = None,
+                   stream=None):
+    """sd_dedup_confirm: the candidate groups of m files (d_keys int64 [m] cas keys, d_hash32 uint8
+    [m, 32] full checksums, d_valid uint8 [m] or None) split into classes of equal checksums.
+    Returns (rep int64 [m], class_size int64 [m], verdict uint8 [m], sets int64 [n_sets, 3] =
+    (key, rep, size) ascending by (key, checksum), stats uint64 [8]); include/sd_cas.h has the
+    rules.  A class has at least two members, so m // 2 rows always hold the sets."""
+    m = int(d_keys.numel())
+    dev = d_hash32.device if m else torch.device("cuda", ctx.device)
+    assert m == 0 or (d_keys.dtype == torch.int64 and d_keys.is_cuda and d_keys.is_contiguous())
+    assert m == 0 or (d_hash32.dtype == torch.uint8 and d_hash32.is_contiguous() and d_hash32.numel() == 32 * m)
+    assert d_valid is None or (d_valid.dtype == torch.uint8 and d_valid.is_contiguous() and d_valid.numel() >= m)
+    rep = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+    size = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+    verdict = torch.empty(max(m, 1), dtype=torch.uint8, device=dev)
+    cap = m // 2
+    sets = torch.empty((max(cap, 1), 3), dtype=torch.int64, device=dev)
+    n_sets, stats = ctx.dedup_confirm(d_keys, d_hash32, d_valid if m else None, m, rep, size, verdict, sets, cap, stream)
+    return rep[:m], size[:m], verdict[:m], sets[:n_sets], stats
+
+
 def shards_ascend(n_local: int, global_base: int, group: Optional[dist.ProcessGroup] = None,
                    device=None) -> bool:
     """True when every rank's index range [base, base + n) ends before the next rank's
@@ -225,6 +265,46 @@ def group_host(records: np.ndarray):
     head[1:] = ks[1:] != ks[:-1]
     head_pos = np.maximum.accumulate(np.where(head, np.arange(len(r)), 0))
     return r, r[head_pos, 1], int(head.sum())
+
+
+def confirm_host(keys, hash32, valid=None):
+    """Host mirror of sd_dedup_confirm in numpy: keys uint64 [m], hash32 uint8 [m, 32], valid
+    uint8 / bool [m] or None.  Returns (rep uint64 [m], class_size uint64 [m], verdict uint8 [m],
+    sets uint64 [n_sets, 3], stats uint64 [8]).  The order is one lexsort by (key, the four
+    checksum words as big-endian numbers, position) over the valid files."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+    m = len(keys)
+    h = np.ascontiguousarray(hash32, dtype=np.uint8).reshape(m, 32)
+    ok = np.ones(m, bool) if valid is None else np.asarray(valid).reshape(-1)[:m] != 0
+    rep = np.full(m, np.iinfo(np.uint64).max, np.uint64)
+    size = np.zeros(m, np.uint64)
+    verdict = np.zeros(m, np.uint8)
+    stats = np.zeros(8, np.uint64)
+    pos = np.flatnonzero(ok).astype(np.uint64)
+    v = len(pos)
+    if v == 0:
+        return rep, size, verdict, np.zeros((0, 3), np.uint64), stats
+    w = h[ok].copy().view(">u8").astype(np.uint64)  # [v, 4]
+    k = keys[ok]
+    order = np.lexsort((pos, w[:, 3], w[:, 2], w[:, 1], w[:, 0], k))
+    ks, ws, ps = k[order], w[order], pos[order]
+    ghead = np.ones(v, bool)
+    ghead[1:] = ks[1:] != ks[:-1]
+    chead = ghead.copy()
+    chead[1:] |= (ws[1:] != ws[:-1]).any(axis=1)
+    cstart, gstart = np.flatnonzero(chead), np.flatnonzero(ghead)
+    csize = np.diff(np.append(cstart, v)).astype(np.uint64)
+    gsize = np.diff(np.append(gstart, v)).astype(np.uint64)
+    cof, gof = np.cumsum(chead) - 1, np.cumsum(ghead) - 1  # class / group of every sorted place
+    rep[ps] = ps[cstart][cof]
+    size[ps] = csize[cof]
+    verdict[ps] = np.where(gsize[gof] == 1, 1, np.where(csize[cof] >= 2, 2, 3)).astype(np.uint8)
+    conf = csize >= 2
+    sets = np.stack([ks[cstart][conf], ps[cstart][conf], csize[conf]], axis=1).astype(np.uint64)
+    classes_in_group = np.add.reduceat(chead.astype(np.int64), gstart)
+    stats[:] = [v, len(gstart), int((gsize >= 2).sum()), len(cstart), int(conf.sum()), int(csize[conf].sum()),
+                int((verdict == 3).sum()), int(((gsize >= 2) & (classes_in_group >= 2)).sum())]
+    return rep, size, verdict, sets.reshape(-1, 3), stats
 
 
 def index_insert_host(keys: np.ndarray, vals: np.ndarray, new_keys, new_vals, nparts: int = 1, part: int = 0):

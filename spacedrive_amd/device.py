@@ -134,6 +134,33 @@ class Context:
         check(lib().sd_dedup_owners(self.handle, _ptr(d_records), m, _ptr(d_rep), chunk_size, _ptr(d_owner),
                                     _stream(stream)))
 
+    def dedup_confirm(self, d_keys, d_hash32, d_valid, m: int, d_rep=None, d_class_size=None, d_verdict=None,
+                      d_sets_out=None, capacity: int = 0, stream=None):
+        """sd_dedup_confirm: the candidate groups of m files (cas keys int64 [m], checksums uint8
+        [m, 32], d_valid uint8 [m] or None) split into classes of equal checksums.  Writes the
+        outputs given (rep, class_size int64 [m]; verdict uint8 [m]; sets int64 [capacity, 3]) and
+        returns (n_sets, stats uint64 [8]); a short `capacity` raises SdCasError (SD_ERR_CAPACITY,
+        ``.needed`` rows, ``.stats``) with the per-file outputs complete and no set row written."""
+        n_sets = ctypes.c_uint64(0)
+        stats = np.zeros(8, np.uint64)
+        rc = lib().sd_dedup_confirm(self.handle, _ptr(d_keys) if m else None, _ptr(d_hash32) if m else None,
+                                    _ptr(d_valid), m, _ptr(d_rep), _ptr(d_class_size), _ptr(d_verdict),
+                                    _ptr(d_sets_out), capacity, ctypes.byref(n_sets), _ptr(stats), _stream(stream))
+        try:
+            check(rc)
+        except SdCasError as e:
+            e.needed = int(n_sets.value)
+            e.stats = stats
+            raise
+        return int(n_sets.value), stats
+
+    def dedup_confirm_stats(self) -> dict:
+        """sd_dedup_confirm_stats: the calls that finished on the prefix path and those that took
+        the full-width path, since the context was created."""
+        v = np.zeros(2, np.uint64)
+        check(lib().sd_dedup_confirm_stats(self.handle, _ptr(v)))
+        return {"prefix": int(v[0]), "full": int(v[1])}
+
     def dedup_mgpu(self, comm: "Comm", d_hash32, d_valid, n: int, base: int, d_records, d_rep, d_owner,
                    capacity: int, chunk_size: int = 100, stream=None):
         """sd_cas_dedup_mgpu: partition -> RCCL all-to-all -> group -> owners on this rank.

@@ -22,6 +22,35 @@ from .cas import _status_error
 from ._native import SD_FILE_OK
 
 
+def confirm_duplicates(ctx, paths: Sequence[str], cas_ids: Sequence[str], nthreads: int = 16) -> dict:
+    """The file route of the confirm step: the members of duplicate groups (`paths` with their
+    16-hex `cas_ids`, e.g. the duplicate entries joined with the DB) hashed in full
+    (file_checksum, validation/hash.rs:10-24) and split into classes of equal checksums
+    (sd_cpu_dedup_confirm: the checksums arrive on the host, so no device is needed for this
+    half).  `ctx` None hashes on the CPU path, else through sd_file_checksums on ctx's device.
+    A file whose checksum fails is invalid.  Returns {"verdict": uint8 [n] (SD_CONFIRM_*),
+    "rep": uint64 [n] (an index into `paths`; UINT64_MAX when invalid), "class_size": uint64
+    [n], "checksums": [str | OSError], "sets": [(cas_id, [path indices])] confirmed, ascending by
+    (cas_id, checksum), "stats": uint64 [8]}."""
+    from . import cas, cpu
+    n = len(paths)
+    if n != len(cas_ids):
+        raise ValueError("paths and cas_ids differ in length")
+    sums = cpu.file_checksums(paths, nthreads) if ctx is None else cas.file_checksums(paths, ctx.device)
+    valid = np.array([isinstance(s, str) for s in sums], dtype=np.uint8)
+    keys = np.array([int(c, 16) for c in cas_ids], dtype=np.uint64)
+    h = np.zeros((n, 32), np.uint8)
+    for i, s in enumerate(sums):
+        if valid[i]:
+            h[i] = np.frombuffer(bytes.fromhex(s), np.uint8)
+    rep, size, verdict, sets, stats = cpu.confirm(keys, h, valid)
+    members = {}
+    for i in np.flatnonzero(verdict == 2):
+        members.setdefault(int(rep[i]), []).append(int(i))
+    return {"verdict": verdict, "rep": rep, "class_size": size, "checksums": sums,
+            "sets": [(cas_ids[int(r)], members[int(r)]) for _, r, _ in sets], "stats": stats}
+
+
 def scan_library(ctx, paths: Sequence[str], sizes, comm=None, group: Optional[dist.ProcessGroup] = None,
                  chunk_size: int = 100, nthreads: int = 16, index=None, object_id_of=None) -> dict:
     """This rank's share of the scan of the whole library (`paths`, `sizes` as the walker's
