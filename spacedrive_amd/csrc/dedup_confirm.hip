@@ -16,10 +16,12 @@
 // h0) run differ in their last 24 bytes: adjacency then proves nothing (tails A, B, A), the later
 // kernels of that pass write nothing and the host runs the full-width path.
 //
-// After the heads, over a fixed grid in which workgroup b owns the contiguous slice b of the
-// sorted order (whole tiles of 256): the heads before a position are the counts of the slices
-// before it plus a ballot / popcount rank inside the wave and LDS counts across the four waves,
-// which gives every position its class and group slot and every head its row in cpos / gpos.  A
+// After the heads, sliced passes (sliced.h: a fixed grid in which workgroup b owns the contiguous
+// slice b of the sorted order, in whole tiles): the heads before a position are the counts of the
+// slices before it (slice_bases) plus its rank inside the tile (tile_slot), which gives every
+// position its class and group slot and every head its row in cpos / gpos.  The kernels stand
+// alone on that header's primitives: three counters per pass, the tie early-out and the capacity
+// early-out do not fit its two skeletons.  A
 // class's size is the distance to the next class head, its representative the position at its
 // head.  One pass scatters rep, class_size and verdict to file order and reduces the totals (the
 // only atomics: a few adds per workgroup); one more compacts the confirmed classes in order.
@@ -30,39 +32,18 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "sd_internal.h"
+#include "sliced.h"
+
+using namespace sliced;
 
 namespace {
-
-constexpr uint32_t DC_BLOCKS = 1024;  // most workgroups of a sliced pass (= the count slots per counter)
-constexpr uint32_t DC_TILE = 256;     // lanes of a workgroup = positions of a tile
 
 // flags[j] of sorted position j
 constexpr uint8_t DC_VALID = 1, DC_GHEAD = 2, DC_CHEAD = 4;
 // state (device u64): the eight stats, then
 constexpr uint32_t DC_ST_TIE = 8;  // a (key, h0) run with unequal tails (prefix path only)
 
-struct dc_slice { uint64_t lo, hi; };
-__device__ __forceinline__ dc_slice dc_slice_of(uint64_t n) {
-    const uint64_t per = ((n + gridDim.x - 1) / gridDim.x + DC_TILE - 1) / DC_TILE * DC_TILE;  // whole tiles
-    uint64_t lo = (uint64_t)blockIdx.x * per, hi = lo + per;
-    if (lo > n) lo = n;
-    if (hi > n) hi = n;
-    return {lo, hi};
-}
-
-uint32_t dc_grid(uint64_t n) {
-    uint64_t g = (n + DC_TILE - 1) / DC_TILE;
-    if (g < 1) g = 1;
-    if (g > DC_BLOCKS) g = DC_BLOCKS;
-    return (uint32_t)g;
-}
-
 __device__ __forceinline__ uint64_t be64(uint64_t v) { return __builtin_bswap64(v); }
-
-__global__ __launch_bounds__(256) void k_dc_iota(uint64_t* __restrict__ p, uint64_t m) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x)
-        p[i] = i;
-}
 
 // the sort word of every position of the permutation: 0..3 = that checksum word as a big-endian
 // number (the byte-swapped load: memcmp order), 4 = the key, 5 = 1 for an invalid file
@@ -77,16 +58,15 @@ __global__ __launch_bounds__(256) void k_dc_word(const uint64_t* __restrict__ ke
 }
 
 // Heads of the sorted order -> flags[j]; per slice the valid files, group heads and class heads
-// -> counts[{0, 1, 2} * DC_BLOCKS + blockIdx.x].  A valid position's predecessor is valid (the
+// -> counts[{0, 1, 2} * BLOCKS + blockIdx.x].  A valid position's predecessor is valid (the
 // invalid files sort last).  `detect`: raise st[DC_ST_TIE] on unequal tails inside a (key, h0) run.
 __global__ __launch_bounds__(256) void k_dc_heads(const uint64_t* __restrict__ keys,
                                                   const uint64_t* __restrict__ hash, const uint8_t* __restrict__ valid,
                                                   const uint64_t* __restrict__ perm, uint64_t m, int detect,
                                                   uint8_t* __restrict__ flags, uint64_t* __restrict__ counts,
                                                   uint64_t* __restrict__ st) {
-    __shared__ uint32_t ws[4][4];
-    const dc_slice sl = dc_slice_of(m);
-    uint32_t nv = 0, ng = 0, nc = 0, tie = 0;
+    const slice sl = slice_of(m);
+    uint32_t v[4] = {0, 0, 0, 0};  // valid files, group heads, class heads, ties
     for (uint64_t j = sl.lo + threadIdx.x; j < sl.hi; j += blockDim.x) {
         const uint64_t p = perm[j];
         uint8_t f = 0;
@@ -100,80 +80,19 @@ __global__ __launch_bounds__(256) void k_dc_heads(const uint64_t* __restrict__ k
                 const bool tail_eq = hash[4 * q + 1] == hash[4 * p + 1] && hash[4 * q + 2] == hash[4 * p + 2] &&
                                      hash[4 * q + 3] == hash[4 * p + 3];
                 chead = ghead || !h0_eq || !tail_eq;
-                tie |= !ghead && h0_eq && !tail_eq;
+                v[3] += !ghead && h0_eq && !tail_eq;
             }
             f |= (ghead ? DC_GHEAD : 0) | (chead ? DC_CHEAD : 0);
-            nv++;
-            ng += ghead;
-            nc += chead;
+            v[0]++;
+            v[1] += ghead;
+            v[2] += chead;
         }
         flags[j] = f;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        nv += __shfl_xor(nv, o);
-        ng += __shfl_xor(ng, o);
-        nc += __shfl_xor(nc, o);
-        tie |= __shfl_xor(tie, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        const uint32_t w = threadIdx.x >> 6;
-        ws[w][0] = nv, ws[w][1] = ng, ws[w][2] = nc, ws[w][3] = tie;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3)
-        counts[threadIdx.x * DC_BLOCKS + blockIdx.x] =
-            (uint64_t)ws[0][threadIdx.x] + ws[1][threadIdx.x] + ws[2][threadIdx.x] + ws[3][threadIdx.x];
-    if (threadIdx.x == 3 && detect && (ws[0][3] | ws[1][3] | ws[2][3] | ws[3][3])) st[DC_ST_TIE] = 1;  // same value from all
-}
-
-// sums of counts[c * DC_BLOCKS + k] over the slices k before this workgroup's (base[c]) and over
-// all of them (all[c]), c < NC, for every lane
-template <int NC>
-__device__ __forceinline__ void dc_bases(const uint64_t* __restrict__ counts, uint64_t (&base)[NC], uint64_t (&all)[NC]) {
-    __shared__ uint64_t ws[4][2 * NC];
-    uint64_t v[2 * NC];
-#pragma unroll
-    for (int c = 0; c < 2 * NC; c++) v[c] = 0;
-    for (uint32_t k = threadIdx.x; k < gridDim.x; k += blockDim.x) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            const uint64_t x = counts[c * DC_BLOCKS + k];
-            v[NC + c] += x;
-            if (k < blockIdx.x) v[c] += x;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 2 * NC; c++) v[c] += __shfl_xor(v[c], o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 2 * NC; c++) ws[threadIdx.x >> 6][c] = v[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        base[c] = ws[0][c] + ws[1][c] + ws[2][c] + ws[3][c];
-        all[c] = ws[0][NC + c] + ws[1][NC + c] + ws[2][NC + c] + ws[3][NC + c];
-    }
-    __syncthreads();
-}
-
-// this lane's slot among the flagged lanes of the tile, in lane order; `run` (the slot of the
-// tile's first flagged lane) advances by the tile's count.  `wcnt`: 4 u32 of LDS of this call site.
-__device__ __forceinline__ uint64_t dc_tile_slot(bool flag, uint64_t& run, uint32_t* wcnt) {
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint64_t bal = __ballot(flag);
-    if (lane == 0) wcnt[w] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint64_t slot = run + __popcll(bal & ((1ull << lane) - 1));
-    for (uint32_t k = 0; k < w; k++) slot += wcnt[k];
-    const uint32_t all = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-    __syncthreads();
-    run += all;
-    return slot;
+    block_sum(v);
+    if (threadIdx.x != 0) return;
+    for (int c = 0; c < 3; c++) counts[c * BLOCKS + blockIdx.x] = v[c];
+    if (detect && v[3]) st[DC_ST_TIE] = 1;  // same value from all
 }
 
 // Every valid position's class and group slot (the heads at or before it, less one) -> cslot,
@@ -183,17 +102,16 @@ __global__ __launch_bounds__(256) void k_dc_rank(const uint8_t* __restrict__ fla
                                                  const uint64_t* __restrict__ counts, uint64_t* __restrict__ cslot,
                                                  uint64_t* __restrict__ gslot, uint64_t* __restrict__ cpos,
                                                  uint64_t* __restrict__ gpos, uint64_t* __restrict__ st) {
-    __shared__ uint32_t wg[4], wc[4];
     uint64_t base[3], all[3];
-    dc_bases<3>(counts, base, all);
+    slice_bases<3, true>(counts, BLOCKS, base, all);
     if (blockIdx.x == 0 && threadIdx.x == 0) st[0] = all[0], st[1] = all[1], st[3] = all[2];
     uint64_t grun = base[1], crun = base[2];
-    const dc_slice sl = dc_slice_of(m);
+    const slice sl = slice_of(m);
     for (uint64_t b = sl.lo; b < sl.hi; b += blockDim.x) {
         const uint64_t j = b + threadIdx.x;
         const uint8_t f = j < sl.hi ? flags[j] : 0;
-        const uint64_t gs = dc_tile_slot(f & DC_GHEAD, grun, wg);
-        const uint64_t cs = dc_tile_slot(f & DC_CHEAD, crun, wc);
+        const uint64_t gs = tile_slot(f & DC_GHEAD, grun);
+        const uint64_t cs = tile_slot(f & DC_CHEAD, crun);
         if (!(f & DC_VALID)) continue;
         // position 0 is a head of both kinds: a follower has a head before it
         gslot[j] = (f & DC_GHEAD) ? gs : gs - 1;
@@ -209,7 +127,7 @@ __device__ __forceinline__ uint64_t dc_run_size(const uint64_t* __restrict__ hpo
 }
 
 // rep, class_size and verdict to file order (each may be null); the confirmed classes per slice
-// -> counts[3 * DC_BLOCKS + blockIdx.x]; st[2], [4], [5], [6], [7] by one add per workgroup each.
+// -> counts[3 * BLOCKS + blockIdx.x]; st[2], [4], [5], [6], [7] by one add per workgroup each.
 // Nothing happens once `tie` is up: the full-width pass follows.
 __global__ __launch_bounds__(256) void k_dc_scatter(const uint64_t* __restrict__ perm,
                                                     const uint8_t* __restrict__ flags, uint64_t m,
@@ -219,10 +137,9 @@ __global__ __launch_bounds__(256) void k_dc_scatter(const uint64_t* __restrict__
                                                     const uint64_t* __restrict__ gpos, uint64_t* __restrict__ rep,
                                                     uint64_t* __restrict__ class_size, uint8_t* __restrict__ verdict,
                                                     uint64_t* __restrict__ counts, uint64_t* __restrict__ st) {
-    __shared__ uint64_t ws[4][5];
     if (st[DC_ST_TIE]) return;
     const uint64_t nvalid = st[0], groups = st[1], classes = st[3];
-    const dc_slice sl = dc_slice_of(m);
+    const slice sl = slice_of(m);
     uint64_t v[5] = {0, 0, 0, 0, 0};  // candidate groups, confirmed classes, their files, refuted files, lying groups
     for (uint64_t j = sl.lo + threadIdx.x; j < sl.hi; j += blockDim.x) {
         const uint64_t p = perm[j];
@@ -244,21 +161,12 @@ __global__ __launch_bounds__(256) void k_dc_scatter(const uint64_t* __restrict__
         if ((f & DC_CHEAD) && csize >= 2) v[1]++, v[2] += csize;
         v[3] += vd == SD_CONFIRM_REFUTED;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 5; k++) v[k] += __shfl_xor(v[k], o);
-    }
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 5; k++) ws[threadIdx.x >> 6][k] = v[k];
-    __syncthreads();
+    block_sum(v);
     if (threadIdx.x != 0) return;
-    uint64_t t[5];
-    for (int k = 0; k < 5; k++) t[k] = ws[0][k] + ws[1][k] + ws[2][k] + ws[3][k];
-    counts[3 * DC_BLOCKS + blockIdx.x] = t[1];
+    counts[3 * BLOCKS + blockIdx.x] = v[1];
     const int at[5] = {2, 4, 5, 6, 7};
     for (int k = 0; k < 5; k++)
-        if (t[k]) atomicAdd(reinterpret_cast<unsigned long long*>(st + at[k]), (unsigned long long)t[k]);
+        if (v[k]) atomicAdd(reinterpret_cast<unsigned long long*>(st + at[k]), (unsigned long long)v[k]);
 }
 
 // One row (key, rep, size) per confirmed class in sorted order: ascending key, then ascending
@@ -268,20 +176,19 @@ __global__ __launch_bounds__(256) void k_dc_sets(const uint64_t* __restrict__ ke
                                                  const uint64_t* __restrict__ cslot, const uint64_t* __restrict__ cpos,
                                                  const uint64_t* __restrict__ counts, const uint64_t* __restrict__ st,
                                                  uint64_t* __restrict__ sets, uint64_t capacity) {
-    __shared__ uint32_t wc[4];
     if (st[DC_ST_TIE]) return;
     uint64_t base[1], all[1];
-    dc_bases<1>(counts + 3 * DC_BLOCKS, base, all);
+    slice_bases<1, true>(counts + 3 * BLOCKS, 0, base, all);
     if (all[0] > capacity) return;
     const uint64_t nvalid = st[0], classes = st[3];
     uint64_t run = base[0];
-    const dc_slice sl = dc_slice_of(m);
+    const slice sl = slice_of(m);
     for (uint64_t b = sl.lo; b < sl.hi; b += blockDim.x) {
         const uint64_t j = b + threadIdx.x;
         const uint8_t f = j < sl.hi ? flags[j] : 0;
         uint64_t csize = 0;
         if (f & DC_CHEAD) csize = dc_run_size(cpos, cslot[j], classes, nvalid);
-        const uint64_t slot = dc_tile_slot(csize >= 2, run, wc);
+        const uint64_t slot = tile_slot(csize >= 2, run);
         if (csize < 2) continue;
         const uint64_t p = perm[j];
         sets[3 * slot] = keys[p];
@@ -290,17 +197,8 @@ __global__ __launch_bounds__(256) void k_dc_sets(const uint64_t* __restrict__ ke
     }
 }
 
-size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
-
-size_t dc_sort_bytes(uint64_t m, hipStream_t s) {
-    size_t b = 0;
-    uint64_t* nul = nullptr;
-    if (rocprim::radix_sort_pairs(nullptr, b, nul, nul, nul, nul, (size_t)m, 0, 64, s) != hipSuccess) return 0;
-    return round256(b);
-}
-
 // scratch: a[6][m] u64 (perm, perm2, word / cpos, word2 / gpos, cslot, gslot), flags[m] u8,
-// counts[4 * DC_BLOCKS] u64, then the radix sort's temporary storage
+// counts[4 * BLOCKS] u64, then the radix sort's temporary storage
 struct dc_scratch {
     uint64_t *perm, *perm2, *word, *word2, *cslot, *gslot, *counts;
     uint8_t* flags;
@@ -316,16 +214,9 @@ dc_scratch dc_scratch_at(void* base, uint64_t m) {
     x.flags = p;
     p += round256(m);
     x.counts = reinterpret_cast<uint64_t*>(p);
-    p += round256(4 * DC_BLOCKS * sizeof(uint64_t));
+    p += round256(4 * BLOCKS * sizeof(uint64_t));
     x.tmp = p;
     return x;
-}
-
-uint32_t flat_grid(uint64_t n) {
-    uint64_t g = (n + 255) / 256;
-    if (g < 1) g = 1;
-    if (g > 4096) g = 4096;
-    return (uint32_t)g;
 }
 
 }  // namespace
@@ -333,8 +224,8 @@ uint32_t flat_grid(uint64_t n) {
 namespace sdk {
 
 size_t dedup_confirm_scratch(uint64_t m) {
-    return 256 + round256(6 * m * sizeof(uint64_t)) + round256(m) + round256(4 * DC_BLOCKS * sizeof(uint64_t)) +
-           dc_sort_bytes(m, nullptr) + 256;
+    return 256 + round256(6 * m * sizeof(uint64_t)) + round256(m) + round256(4 * BLOCKS * sizeof(uint64_t)) +
+           sort_pairs_bytes(m, nullptr) + 256;
 }
 
 // One pass, queued on s: state[0..7] = the stats, state[8] = tie (prefix path only; then the
@@ -348,11 +239,11 @@ hipError_t dedup_confirm(const uint64_t* keys, const uint8_t* hash32, const uint
     hipError_t e = hipMemsetAsync(state, 0, DEDUP_CONFIRM_STATE * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
     uint64_t *perm = x.perm, *perm2 = x.perm2;
-    hipLaunchKernelGGL(k_dc_iota, dim3(flat_grid(m)), dim3(256), 0, s, perm, m);
+    hipLaunchKernelGGL(k_iota, dim3(flat_grid(m)), dim3(256), 0, s, perm, m);
     const int prefix_words[] = {0, 4, 5}, full_words[] = {3, 2, 1, 0, 4, 5};
     const int* words = full ? full_words : prefix_words;
     const int nwords = full ? 6 : 3;
-    const size_t temp = dc_sort_bytes(m, s);
+    const size_t temp = sort_pairs_bytes(m, s);
     for (int k = 0; k < nwords; k++) {
         if (words[k] == 5 && !valid) continue;  // every file is valid
         hipLaunchKernelGGL(k_dc_word, dim3(flat_grid(m)), dim3(256), 0, s, keys, hash, valid, perm, m, words[k],
@@ -362,7 +253,7 @@ hipError_t dedup_confirm(const uint64_t* keys, const uint8_t* hash32, const uint
         if (e != hipSuccess) return e;
         std::swap(perm, perm2);
     }
-    const uint32_t g = dc_grid(m);
+    const uint32_t g = sliced_grid(m);
     uint64_t *cpos = x.word, *gpos = x.word2;  // the sort words are done with
     hipLaunchKernelGGL(k_dc_heads, dim3(g), dim3(256), 0, s, keys, hash, valid, perm, m, full ? 0 : 1, x.flags,
                        x.counts, state);

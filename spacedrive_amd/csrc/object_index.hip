@@ -16,14 +16,11 @@
 //
 // Ordered compaction (new heads; an insert's surviving pairs; a removal's survivors and its
 // dropped entries; distinct pairs, ids and groups) without atomics on the data path: a fixed
-// grid in which workgroup b owns the contiguous slice b of the input.  Two kernel skeletons hold
-// the slice and tile arithmetic, and every such pass is a functor of a few lines over one of them:
-//   sliced_flag     a predicate per position -> flags[i] and one count per workgroup
-//   sliced_compact  each workgroup takes the sum of the counts before it, ranks its flags in
-//                   order (ballot / popcount inside a wave, LDS counts across the four waves)
-//                   and hands every position its slot
+// grid in which workgroup b owns the contiguous slice b of the input.  sliced.h holds the slice
+// and tile arithmetic and the two kernel skeletons over it (sliced_flag, sliced_compact); every
+// such pass here is a functor of a few lines over one of them.
 // k_apply_merge, k_group_totals, k_entry_flag, k_object_totals, k_key_links and k_group_stats use
-// the slices in ways of their own and stand alone.
+// the slices in ways of their own and stand alone, on that header's primitives.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -32,130 +29,11 @@
 
 #include "object_index.h"
 #include "sd_internal.h"
+#include "sliced.h"
+
+using namespace sliced;
 
 namespace {
-
-constexpr uint32_t OI_BLOCKS = 1024;  // most workgroups of a sliced pass (= the count slots)
-
-struct oi_slice { uint64_t lo, hi; };
-__device__ __forceinline__ oi_slice oi_slice_of(uint64_t n) {
-    const uint64_t per = ((n + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;  // whole tiles
-    uint64_t lo = (uint64_t)blockIdx.x * per, hi = lo + per;
-    if (lo > n) lo = n;
-    if (hi > n) hi = n;
-    return {lo, hi};
-}
-
-uint32_t grid_for(uint64_t n) {
-    uint64_t g = (n + 255) / 256;
-    if (g < 1) g = 1;
-    if (g > 4096) g = 4096;
-    return (uint32_t)g;
-}
-
-uint32_t sliced_grid(uint64_t n) { return std::min<uint32_t>(grid_for(n), OI_BLOCKS); }
-
-// workgroup total of `mine` (256 lanes) -> counts[blockIdx.x], by lane 0
-__device__ __forceinline__ void block_count(uint32_t mine, uint64_t* __restrict__ counts) {
-    __shared__ uint32_t ws[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = (uint64_t)ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-// sum of counts[0 .. blockIdx.x) for every lane; the last workgroup also writes the total
-__device__ __forceinline__ uint64_t block_base(const uint64_t* __restrict__ counts, uint64_t* __restrict__ total) {
-    __shared__ uint64_t ws[4];
-    __shared__ uint64_t base;
-    uint64_t v = 0;
-    for (uint32_t k = threadIdx.x; k < blockIdx.x; k += blockDim.x) v += counts[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        base = ws[0] + ws[1] + ws[2] + ws[3];
-        if (blockIdx.x + 1 == gridDim.x && total) *total = base + counts[blockIdx.x];
-    }
-    __syncthreads();
-    return base;
-}
-
-// this lane's output slot among the flagged lanes of the tile, in lane order; `run` (the
-// slot of the tile's first flagged lane) advances by the tile's count
-__device__ __forceinline__ uint64_t tile_slot(bool flag, uint64_t& run) {
-    __shared__ uint32_t wcnt[4];
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint64_t bal = __ballot(flag);
-    if (lane == 0) wcnt[w] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint64_t slot = run + __popcll(bal & ((1ull << lane) - 1));
-    for (uint32_t k = 0; k < w; k++) slot += wcnt[k];
-    const uint32_t all = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-    __syncthreads();
-    run += all;
-    return slot;
-}
-
-// The flagging skeleton: workgroup b passes every position i of its slice of [0, n) and n to the
-// functor, stores the answer at flags[i] (unless flags is null: a count-only pass) and leaves
-// its count of true answers at counts[b].  n is *d_n if d_n is set (a count the host never
-// waited for), else the value.  The functor may write side outputs of its own.
-template <class F>
-__global__ __launch_bounds__(256) void sliced_flag(F f, const uint64_t* __restrict__ d_n, uint64_t n,
-                                                   uint8_t* __restrict__ flags, uint64_t* __restrict__ counts) {
-    if (d_n) n = *d_n;
-    const oi_slice sl = oi_slice_of(n);
-    uint32_t mine = 0;
-    for (uint64_t i = sl.lo + threadIdx.x; i < sl.hi; i += blockDim.x) {
-        const bool flag = f(i, n);
-        if (flags) flags[i] = flag ? 1 : 0;
-        mine += flag;
-    }
-    block_count(mine, counts);
-}
-
-// The compaction skeleton over the same slices: slot = the flagged positions before i (counts[]
-// of the flagging pass before this workgroup, tile_slot inside it), which is a flagged
-// position's row of the output, and taken from i an unflagged position's rank among the
-// unflagged.  Whole tiles: every lane of the workgroup makes the same trips (tile_slot has
-// barriers); the lanes past the slice's end are unflagged and emit nothing.  f.flag(i) says
-// whether i is flagged, f.emit(i, flag, slot, n) writes; *total (may be null) takes the count.
-template <class F>
-__global__ __launch_bounds__(256) void sliced_compact(F f, const uint64_t* __restrict__ d_n, uint64_t n,
-                                                      const uint64_t* __restrict__ counts,
-                                                      uint64_t* __restrict__ total) {
-    uint64_t run = block_base(counts, total);
-    if (d_n) n = *d_n;
-    const oi_slice sl = oi_slice_of(n);
-    for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
-        const uint64_t i = base + threadIdx.x;
-        const bool act = i < sl.hi;
-        const bool flag = act && f.flag(i);
-        const uint64_t slot = tile_slot(flag, run);
-        if (act) f.emit(i, flag, slot, n);
-    }
-}
-
-// the flags of a sliced_flag pass, for the compactions that read them
-struct from_flags {
-    const uint8_t* __restrict__ flags;
-    __device__ bool flag(uint64_t i) const { return flags[i] != 0; }
-};
-
-template <class F>
-void launch_flag(uint32_t grid, hipStream_t s, F f, const uint64_t* d_n, uint64_t n, uint8_t* flags,
-                 uint64_t* counts) {
-    hipLaunchKernelGGL(sliced_flag<F>, dim3(grid), dim3(256), 0, s, f, d_n, n, flags, counts);
-}
-
-template <class F>
-void launch_compact(uint32_t grid, hipStream_t s, F f, const uint64_t* d_n, uint64_t n, const uint64_t* counts,
-                    uint64_t* total) {
-    hipLaunchKernelGGL(sliced_compact<F>, dim3(grid), dim3(256), 0, s, f, d_n, n, counts, total);
-}
 
 // the first of a run of equal values in a sorted array: the listed ids by Object, the groups
 // (runs of equal keys) of the index
@@ -219,11 +97,6 @@ struct heads_out {
         existing[i] = 0;  // a head's key is not in the index: bit 0 is clear
     }
 };
-
-__global__ __launch_bounds__(256) void k_iota(uint64_t* __restrict__ p, uint64_t m) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x)
-        p[i] = i;
-}
 
 // an insert's pairs sorted by (key, position): a pair survives if it is its key's first, its
 // key belongs to this shard and the index does not have it
@@ -580,7 +453,7 @@ __global__ __launch_bounds__(256) void k_apply_merge(
         return;
     }
     uint64_t run = block_base(counts, nullptr);
-    const oi_slice sl = oi_slice_of(n);
+    const slice sl = slice_of(n);
     const uint64_t d_rm = *r_total, d_in = *i_total;
     for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
         const uint64_t i = base + threadIdx.x;
@@ -705,7 +578,7 @@ __global__ __launch_bounds__(256) void k_object_totals(const uint64_t* __restric
                                                        uint64_t* __restrict__ tot) {
     __shared__ uint64_t su[LDS ? OI_LDS_IDS : 1];
     __shared__ uint64_t lt[LDS && SUMS ? 2 * OI_LDS_IDS : 1];  // the workgroup's totals per slot
-    __shared__ uint64_t pick, wl[4], we[4];
+    __shared__ uint64_t pick;
     const uint64_t d = *d_total;  // <= the listed count, which chose LDS
     if (LDS) {
         for (uint64_t j = threadIdx.x; j < d && j < OI_LDS_IDS; j += blockDim.x) {
@@ -716,7 +589,7 @@ __global__ __launch_bounds__(256) void k_object_totals(const uint64_t* __restric
     }
     const uint64_t* ids = LDS ? su : u;
     uint64_t* acc = LDS && SUMS ? lt : tot;  // where a lane that changes slots adds what it holds
-    const oi_slice sl = oi_slice_of(n);
+    const slice sl = slice_of(n);
     bool have = false;
     uint64_t cur = 0, sum = 0, cnt = 0;
     for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {  // whole tiles: the same trips for every lane
@@ -752,15 +625,9 @@ __global__ __launch_bounds__(256) void k_object_totals(const uint64_t* __restric
         __syncthreads();
         const uint64_t chosen = pick;
         const bool same = pend && cur == chosen;
-        uint64_t l = same ? sum : 0, e = same ? cnt : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            l += __shfl_xor(l, o);
-            e += __shfl_xor(e, o);
-        }
-        if ((threadIdx.x & 63) == 0) wl[threadIdx.x >> 6] = l, we[threadIdx.x >> 6] = e;
-        __syncthreads();
-        if (threadIdx.x == 0) add_totals(tot, chosen, wl[0] + wl[1] + wl[2] + wl[3], we[0] + we[1] + we[2] + we[3]);
+        uint64_t le[2] = {same ? sum : 0, same ? cnt : 0};
+        block_sum(le);
+        if (threadIdx.x == 0) add_totals(tot, chosen, le[0], le[1]);
         pend = pend && !same;
     }
     if (pend) add_totals(tot, cur, sum, cnt);
@@ -868,7 +735,7 @@ __global__ __launch_bounds__(256) void k_group_totals(const uint64_t* __restrict
                                                       uint64_t* __restrict__ hpos, uint64_t* __restrict__ gl,
                                                       uint64_t* __restrict__ g_total) {
     uint64_t run = block_base(counts, g_total);
-    const oi_slice sl = oi_slice_of(n);
+    const slice sl = slice_of(n);
     const uint32_t lane = threadIdx.x & 63;
     for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
         const uint64_t i = base + threadIdx.x;
@@ -936,7 +803,7 @@ __global__ __launch_bounds__(256) void k_entry_flag(const uint64_t* __restrict__
                                                     const uint8_t* __restrict__ gflags,
                                                     uint8_t* __restrict__ eflags, uint64_t* __restrict__ counts) {
     uint64_t run = block_base(head_counts, nullptr);
-    const oi_slice sl = oi_slice_of(n);
+    const slice sl = slice_of(n);
     uint32_t mine = 0;
     for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
         const uint64_t i = base + threadIdx.x;
@@ -969,45 +836,31 @@ __global__ __launch_bounds__(256) void k_group_stats(const uint64_t* __restrict_
                                                      const uint64_t* __restrict__ gl,
                                                      const uint64_t* __restrict__ g_total, uint64_t n,
                                                      uint64_t* __restrict__ st) {
-    __shared__ uint64_t ws[4][6];
+    __shared__ uint64_t wmax[4];
     const uint64_t groups = *g_total;
-    const oi_slice sl = oi_slice_of(groups);
-    uint64_t v[6] = {0, 0, 0, 0, 0, 0};  // v[k] is st[2 + k]; v[5] = the largest links(k)
+    const slice sl = slice_of(groups);
+    uint64_t v[5] = {0, 0, 0, 0, 0}, big = 0;  // v[k] is st[2 + k]; big = the largest links(k)
     for (uint64_t g = sl.lo + threadIdx.x; g < sl.hi; g += blockDim.x) {
         const uint64_t l = gl[g], o = group_owners(hpos, g, groups, n);
         v[0] += l;
         if (l >= 2) v[1] += 1, v[2] += l;
         if (o >= 2) v[3] += 1, v[4] += o;
-        if (l > v[5]) v[5] = l;
+        if (l > big) big = l;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 5; k++) v[k] += __shfl_xor(v[k], o);
-        const uint64_t other = __shfl_xor(v[5], o);
-        if (other > v[5]) v[5] = other;
+        const uint64_t other = __shfl_xor(big, o);
+        if (other > big) big = other;
     }
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 6; k++) ws[threadIdx.x >> 6][k] = v[k];
-    __syncthreads();
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = big;
+    block_sum(v);  // its first barrier is wmax's too
     if (threadIdx.x != 0) return;
-    for (int k = 0; k < 5; k++) {
-        const uint64_t t = ws[0][k] + ws[1][k] + ws[2][k] + ws[3][k];
-        if (t) atomicAdd(reinterpret_cast<unsigned long long*>(st + 2 + k), (unsigned long long)t);
-    }
-    uint64_t mx = ws[0][5];
-    for (int w = 1; w < 4; w++) mx = ws[w][5] > mx ? ws[w][5] : mx;
-    if (mx)atomicMax(reinterpret_cast<unsigned long long*>(st + 7), (unsigned long long)mx);
+    for (int k = 0; k < 5; k++)
+        if (v[k]) atomicAdd(reinterpret_cast<unsigned long long*>(st + 2 + k), (unsigned long long)v[k]);
+    uint64_t mx = wmax[0];
+    for (int w = 1; w < 4; w++) mx = wmax[w] > mx ? wmax[w] : mx;
+    if (mx) atomicMax(reinterpret_cast<unsigned long long*>(st + 7), (unsigned long long)mx);
     if (blockIdx.x == 0) st[0] = groups, st[1] = n;
-}
-
-size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
-
-size_t insert_sort_bytes(uint64_t m, hipStream_t s) {
-    size_t b = 0;
-    uint64_t* nul = nullptr;
-    if (rocprim::radix_sort_pairs(nullptr, b, nul, nul, nul, nul, (size_t)m, 0, 64, s) != hipSuccess) return 0;
-    return round256(b);
 }
 
 size_t remove_sort_bytes(uint64_t m, hipStream_t s) {
@@ -1028,7 +881,7 @@ struct pair_batch {
 };
 
 size_t pair_batch_bytes(uint64_t m, bool insert) {
-    return round256((insert ? 8 : 5) * m * sizeof(uint64_t)) + round256(2 * m) + 512 + insert_sort_bytes(m, nullptr) +
+    return round256((insert ? 8 : 5) * m * sizeof(uint64_t)) + round256(2 * m) + 512 + sort_pairs_bytes(m, nullptr) +
            256;
 }
 
@@ -1049,7 +902,7 @@ pair_batch pair_batch_at(void* base, uint64_t m, bool insert) {
 // positions of their runs' heads and their count
 hipError_t aggregate_pairs(const pair_batch& b, const uint64_t* in_keys, const uint64_t* in_ids, uint64_t m,
                            uint64_t* counts, hipStream_t s) {
-    size_t tb = insert_sort_bytes(m, s);
+    size_t tb = sort_pairs_bytes(m, s);
     hipError_t e = rocprim::radix_sort_pairs(b.tmp, tb, in_ids, b.t0, in_keys, b.t1, (size_t)m, 0, 64, s);
     if (e != hipSuccess) return e;
     e = rocprim::radix_sort_pairs(b.tmp, tb, b.t1, b.sk, b.t0, b.sv, (size_t)m, 0, 64, s);
@@ -1069,7 +922,7 @@ uint32_t index_slots(uint64_t n) { return sliced_grid(n); }
 hipError_t index_lookup(const oi_view& x, const uint64_t* q, uint64_t m, uint64_t* out, uint8_t* found,
                         hipStream_t s) {
     if (m == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_index_lookup, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, q, m, out,
+    hipLaunchKernelGGL(k_index_lookup, dim3(flat_grid(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, q, m, out,
                        found);
     return hipGetLastError();
 }
@@ -1088,7 +941,7 @@ hipError_t owners_indexed(const oi_view& x, const uint64_t* records, uint64_t m,
 // scratch: sk[m], spos[m], pos[m], nk[m], nv[m] (u64), flags[m] (u8), total (u64), then the
 // radix sort's temporary storage
 size_t index_insert_scratch(uint64_t m) {
-    return round256(5 * m * sizeof(uint64_t) + m) + 256 + insert_sort_bytes(m, nullptr) + 256;
+    return round256(5 * m * sizeof(uint64_t) + m) + 256 + sort_pairs_bytes(m, nullptr) + 256;
 }
 
 hipError_t index_insert_select(const oi_view& x, int nparts, int part, const uint64_t* in_keys,
@@ -1103,8 +956,8 @@ hipError_t index_insert_select(const oi_view& x, int nparts, int part, const uin
     uint8_t* flags = reinterpret_cast<uint8_t*>(nv + m);
     uint64_t* total = reinterpret_cast<uint64_t*>(round256((uintptr_t)(flags + m)));
     void* tmp = reinterpret_cast<uint8_t*>(total) + 256;
-    size_t tb = insert_sort_bytes(m, s);
-    hipLaunchKernelGGL(k_iota, dim3(grid_for(m)), dim3(256), 0, s, pos, m);
+    size_t tb = sort_pairs_bytes(m, s);
+    hipLaunchKernelGGL(k_iota, dim3(flat_grid(m)), dim3(256), 0, s, pos, m);
     // a stable sort by key leaves equal keys in ascending position: (key, position) order
     hipError_t e = rocprim::radix_sort_pairs(tmp, tb, in_keys, sk, pos, spos, (size_t)m, 0, 64, s);
     if (e != hipSuccess) return e;
@@ -1120,7 +973,7 @@ hipError_t index_insert_select(const oi_view& x, int nparts, int part, const uin
 hipError_t index_merge(const oi_view& x, const uint64_t* nk, const uint64_t* nv, uint64_t r, uint64_t* out_keys,
                        uint64_t* out_vals, hipStream_t s) {
     if (x.n + r == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_index_merge, dim3(grid_for(x.n + r)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, x.n, nk,
+    hipLaunchKernelGGL(k_index_merge, dim3(flat_grid(x.n + r)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, x.n, nk,
                        nv, r, out_keys, out_vals);
     return hipGetLastError();
 }
@@ -1138,7 +991,7 @@ hipError_t index_remove_flag_keys(const oi_view& x, const uint64_t* rm_keys, con
     uint8_t* flags = reinterpret_cast<uint8_t*>(scratch);
     hipError_t e = hipMemsetAsync(flags, 0, x.n, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_remove_mark, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, rm_keys,
+    hipLaunchKernelGGL(k_remove_mark, dim3(flat_grid(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, rm_keys,
                        rm_ids, m, flags);
     launch_flag(sliced_grid(x.n), s, marked{flags}, nullptr, x.n, nullptr, counts);
     return hipGetLastError();
@@ -1197,7 +1050,7 @@ hipError_t index_owners_insert_select(const oi_view& x, int nparts, int part, co
 hipError_t index_owners_merge(const oi_view& x, const uint64_t* nk, const uint64_t* nv, const uint64_t* nl, uint64_t r,
                               uint64_t* out_keys, uint64_t* out_vals, uint64_t* out_links, hipStream_t s) {
     if (x.n + r == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_owners_merge, dim3(grid_for(x.n + r)), dim3(256), 0, s, x.keys, x.vals, x.links, x.dir, x.bits,
+    hipLaunchKernelGGL(k_owners_merge, dim3(flat_grid(x.n + r)), dim3(256), 0, s, x.keys, x.vals, x.links, x.dir, x.bits,
                        x.n, nk, nv, nl, r, out_keys, out_vals, out_links);
     return hipGetLastError();
 }
@@ -1205,7 +1058,7 @@ hipError_t index_owners_merge(const oi_view& x, const uint64_t* nk, const uint64
 hipError_t index_owners_add_links(const void* scratch, uint64_t m, const uint64_t* nk, const uint64_t* nv, uint64_t r,
                                   uint64_t* links, hipStream_t s) {
     const pair_batch b = pair_batch_at(const_cast<void*>(scratch), m, true);
-    hipLaunchKernelGGL(k_owners_add_links, dim3(grid_for(m)), dim3(256), 0, s, b.t0, b.t1, b.dcnt, b.drank, b.dstate,
+    hipLaunchKernelGGL(k_owners_add_links, dim3(flat_grid(m)), dim3(256), 0, s, b.t0, b.t1, b.dcnt, b.drank, b.dstate,
                        b.d_total, nk, nv, r, links);
     return hipGetLastError();
 }
@@ -1229,7 +1082,7 @@ hipError_t index_owners_remove_flag_pairs(const oi_view& x, const uint64_t* rm_k
     if (e != hipSuccess) return e;
     e = aggregate_pairs(b, rm_keys, rm_ids, m, counts, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_owners_remove_ask, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, b.t0,
+    hipLaunchKernelGGL(k_owners_remove_ask, dim3(flat_grid(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, b.t0,
                        b.t1, b.dpos, b.d_total, m, asked);
     launch_flag(sliced_grid(x.n), s, links_drop{x.links, asked}, nullptr, x.n, flags, counts);
     return hipGetLastError();
@@ -1238,7 +1091,7 @@ hipError_t index_owners_remove_flag_pairs(const oi_view& x, const uint64_t* rm_k
 hipError_t index_owners_take_links(const oi_view& x, const void* scratch, uint64_t m, uint64_t* links, hipStream_t s) {
     const uint8_t* asked = reinterpret_cast<const uint8_t*>(index_owners_asked(scratch, x.n));
     const pair_batch b = pair_batch_at(const_cast<uint8_t*>(asked) + round256(x.n * sizeof(uint64_t)), m, false);
-    hipLaunchKernelGGL(k_owners_take_links, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, b.t0,
+    hipLaunchKernelGGL(k_owners_take_links, dim3(flat_grid(m)), dim3(256), 0, s, x.keys, x.vals, x.dir, x.bits, b.t0,
                        b.t1, b.dpos, b.d_total, m, links);
     return hipGetLastError();
 }
@@ -1276,7 +1129,7 @@ apply_scratch apply_scratch_at(void* base, uint64_t n, uint64_t m_rm, uint64_t m
     p += round256(n);
     a.leaving = reinterpret_cast<uint64_t*>(p);
     a.entering = a.leaving + sliced_grid(n);
-    p += 2 * OI_BLOCKS * sizeof(uint64_t);
+    p += 2 * BLOCKS * sizeof(uint64_t);
     a.rm = pair_batch_at(p, m_rm, false);
     p += pair_batch_bytes(std::max<uint64_t>(m_rm, 1), false);
     a.in = pair_batch_at(p, m_in, true);
@@ -1287,7 +1140,7 @@ apply_scratch apply_scratch_at(void* base, uint64_t n, uint64_t m_rm, uint64_t m
 }  // namespace
 
 size_t index_apply_scratch(uint64_t n, uint64_t m_rm, uint64_t m_in) {
-    return round256(n) + 2 * OI_BLOCKS * sizeof(uint64_t) + pair_batch_bytes(std::max<uint64_t>(m_rm, 1), false) +
+    return round256(n) + 2 * BLOCKS * sizeof(uint64_t) + pair_batch_bytes(std::max<uint64_t>(m_rm, 1), false) +
            pair_batch_bytes(std::max<uint64_t>(m_in, 1), true) + round256(m_in * sizeof(uint64_t)) + 256;
 }
 
@@ -1313,7 +1166,7 @@ hipError_t index_apply_flag(const oi_view& x, int nparts, int part, const uint64
                                  a.in.dcnt, a.in.drank, a.in.dstate, a.mark},
                 a.in.d_total, 0, nullptr, a.entering);
     if (m_rm)
-        hipLaunchKernelGGL(k_apply_mark_removals, dim3(grid_for(m_rm)), dim3(256), 0, s, x.keys, x.vals, x.links, x.dir,
+        hipLaunchKernelGGL(k_apply_mark_removals, dim3(flat_grid(m_rm)), dim3(256), 0, s, x.keys, x.vals, x.links, x.dir,
                            x.bits, a.rm.t0, a.rm.t1, a.rm.dpos, a.rm.d_total, m_rm, a.in.t0, a.in.t1, a.in.dpos,
                            a.in.d_total, m_in, a.mark);
     launch_flag(sliced_grid(x.n), s, marked{a.mark}, nullptr, x.n, nullptr, a.leaving);
@@ -1323,7 +1176,7 @@ hipError_t index_apply_flag(const oi_view& x, int nparts, int part, const uint64
 hipError_t index_apply_in_place(const oi_view& x, const void* scratch, uint64_t m_rm, uint64_t m_in, uint64_t* links,
                                 hipStream_t s) {
     const apply_scratch a = apply_scratch_at(const_cast<void*>(scratch), x.n, m_rm, m_in);
-    hipLaunchKernelGGL(k_apply_links_in_place, dim3(grid_for(m_rm + m_in)), dim3(256), 0, s, x.keys, x.vals, x.dir,
+    hipLaunchKernelGGL(k_apply_links_in_place, dim3(flat_grid(m_rm + m_in)), dim3(256), 0, s, x.keys, x.vals, x.dir,
                        x.bits, a.rm.t0, a.rm.t1, a.rm.dpos, a.rm.d_total, m_rm, a.in.t0, a.in.t1, a.in.dpos, a.in.dcnt,
                        a.in.drank, a.in.dstate, a.in.d_total, m_in, a.mark, links);
     return hipGetLastError();
@@ -1348,14 +1201,14 @@ hipError_t index_apply_merge(const oi_view& x, const void* scratch, uint64_t m_r
 hipError_t index_links(const oi_view& x, const uint64_t* q_keys, const uint64_t* q_ids, uint64_t m, uint64_t* out,
                        hipStream_t s) {
     if (m == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_index_links, dim3(grid_for(m)), dim3(256), 0, s, x.keys, x.vals, x.links, x.dir, x.bits, q_keys,
+    hipLaunchKernelGGL(k_index_links, dim3(flat_grid(m)), dim3(256), 0, s, x.keys, x.vals, x.links, x.dir, x.bits, q_keys,
                        q_ids, m, out);
     return hipGetLastError();
 }
 
 // ---- by Object, read-only.  scratch: sid[m], spos[m], u[m], pslot[m], tot[2 * m] (u64),
 // flags[m] (u8), the distinct count (u64), the per-slice counts of the two ordered compactions
-// (OI_BLOCKS u64: the calls by Object share no count slot with sd_dedup_owners_indexed, which
+// (BLOCKS u64: the calls by Object share no count slot with sd_dedup_owners_indexed, which
 // uses the index's own), then the radix sort's temporary storage
 namespace {
 struct objects_scratch {
@@ -1388,13 +1241,13 @@ objects_scratch objects_scratch_at(void* base, uint64_t m) {
     b += round256(m);
     q.d_total = reinterpret_cast<uint64_t*>(b);
     q.counts = reinterpret_cast<uint64_t*>(b + 256);
-    q.tmp = b + 256 + OI_BLOCKS * sizeof(uint64_t);
+    q.tmp = b + 256 + BLOCKS * sizeof(uint64_t);
     return q;
 }
 }  // namespace
 
 size_t index_objects_scratch(uint64_t m) {
-    return round256(6 * m * sizeof(uint64_t)) + round256(m) + 256 + OI_BLOCKS * sizeof(uint64_t) + objects_sort_bytes(m) + 256;
+    return round256(6 * m * sizeof(uint64_t)) + round256(m) + 256 + BLOCKS * sizeof(uint64_t) + objects_sort_bytes(m) + 256;
 }
 
 // m > 0.  After it tot[2 * slot], tot[2 * slot + 1] hold links and entries of the distinct ids
@@ -1425,7 +1278,7 @@ hipError_t index_objects_totals(const oi_view& x, const uint64_t* ids, uint64_t 
 hipError_t index_objects_scatter(const void* scratch, uint64_t m, uint64_t* links_out, uint64_t* entries_out,
                                  hipStream_t s) {
     const objects_scratch q = objects_scratch_at(const_cast<void*>(scratch), m);
-    hipLaunchKernelGGL(k_object_scatter, dim3(grid_for(m)), dim3(256), 0, s, q.pslot, q.tot, m, links_out, entries_out);
+    hipLaunchKernelGGL(k_object_scatter, dim3(flat_grid(m)), dim3(256), 0, s, q.pslot, q.tot, m, links_out, entries_out);
     return hipGetLastError();
 }
 
@@ -1456,7 +1309,7 @@ hipError_t index_key_links(const oi_view& x, const uint64_t* q_keys, uint64_t m,
         if (e == hipSuccess && owners_out) e = hipMemsetAsync(owners_out, 0, m * sizeof(uint64_t), s);
         return e;
     }
-    const dim3 g(grid_for(m)), b(256);
+    const dim3 g(flat_grid(m)), b(256);
     if (links_out) hipLaunchKernelGGL((k_key_links<true>), g, b, 0, s, x.keys, x.links, x.dir, x.bits, q_keys, m, links_out, owners_out);
     else hipLaunchKernelGGL((k_key_links<false>), g, b, 0, s, x.keys, x.links, x.dir, x.bits, q_keys, m, links_out, owners_out);
     return hipGetLastError();
@@ -1464,7 +1317,7 @@ hipError_t index_key_links(const oi_view& x, const uint64_t* q_keys, uint64_t m,
 
 // The group calls' scratch for n entries: hpos[n], gl[n] (u64), gflags[n], eflags[n] (u8), the
 // group count and the eight stats (u64, 256 bytes apart), the head counts and the selection
-// counts per slice (OI_BLOCKS u64 each): 18 B per entry and 17 KiB.
+// counts per slice (BLOCKS u64 each): 18 B per entry and 17 KiB.
 namespace {
 struct groups_scratch {
     uint64_t *hpos, *gl, *g_total, *stats, *head_counts, *sel_counts;
@@ -1481,13 +1334,13 @@ groups_scratch groups_scratch_at(void* base, uint64_t n) {
     q.g_total = reinterpret_cast<uint64_t*>(b);
     q.stats = reinterpret_cast<uint64_t*>(b + 256);
     q.head_counts = reinterpret_cast<uint64_t*>(b + 512);
-    q.sel_counts = q.head_counts + OI_BLOCKS;
+    q.sel_counts = q.head_counts + BLOCKS;
     return q;
 }
 }  // namespace
 
 size_t index_groups_scratch(uint64_t n) {
-    return round256(2 * n * sizeof(uint64_t)) + 2 * round256(n) + 512 + 2 * OI_BLOCKS * sizeof(uint64_t);
+    return round256(2 * n * sizeof(uint64_t)) + 2 * round256(n) + 512 + 2 * BLOCKS * sizeof(uint64_t);
 }
 
 // n > 0.  After it hpos[g] and gl[g] hold the head position and links of every group g, and
@@ -1550,7 +1403,7 @@ const uint64_t* index_groups_stats_at(const void* scratch, uint64_t n) {
 
 hipError_t index_build_dir(const uint64_t* keys, uint64_t n, uint32_t bits, uint64_t* dir, hipStream_t s) {
     if (n == 0) return hipMemsetAsync(dir, 0, 2 * sizeof(uint64_t), s);
-    hipLaunchKernelGGL(k_index_dir, dim3(grid_for(n)), dim3(256), 0, s, keys, n, bits, dir);
+    hipLaunchKernelGGL(k_index_dir, dim3(flat_grid(n)), dim3(256), 0, s, keys, n, bits, dir);
     return hipGetLastError();
 }
 

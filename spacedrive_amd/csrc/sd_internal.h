@@ -78,7 +78,9 @@ struct oi_view {
     uint32_t bits;
     const uint64_t* links = nullptr;  // owners mode only: the link count per entry
 };
-constexpr uint32_t OI_COUNT_SLOTS = 1024;  // u64 per-workgroup counts of an ordered compaction
+// u64 per-workgroup counts of an ordered compaction: sliced.h's BLOCKS (a static_assert there; that
+// header is device code, this one is also the host sources')
+constexpr uint32_t OI_COUNT_SLOTS = 1024;
 // the count slots a sliced pass over n positions fills: one per workgroup, at most OI_COUNT_SLOTS
 uint32_t index_slots(uint64_t n);
 hipError_t index_lookup(const oi_view& x, const uint64_t* q, uint64_t m, uint64_t* out, uint8_t* found,

@@ -15,21 +15,14 @@ from __future__ import annotations
 
 import numpy as np
 
+from tests.sliced_cases import BLOCKS, SLICE_COUNTS, TILE, slice_len
+
 U = np.uint64
 M64 = (1 << 64) - 1
-TILE = 256      # dedup_confirm.hip DC_TILE: the positions of a workgroup's tile
-BLOCKS = 1024   # dedup_confirm.hip DC_BLOCKS: most workgroups of a sliced pass
 INVALID, SINGLE, CONFIRMED, REFUTED = 0, 1, 2, 3
 SIZES = (0, 1, 2, 63, 64, 65, 255, 256, 257, 511, 513)
 PAST_GRID = BLOCKS * TILE + 1  # every workgroup's slice holds more than one tile
 MIX = 100_000
-
-
-def slice_len(m: int) -> int:
-    """the positions of one workgroup's slice in a sliced pass over m, as dc_slice_of and dc_grid of
-    dedup_confirm.hip compute it: whole tiles"""
-    grid = min(max((m + TILE - 1) // TILE, 1), BLOCKS)
-    return ((m + grid - 1) // grid + TILE - 1) // TILE * TILE
 
 
 def confirm_model(keys, hashes, valid=None) -> dict:
@@ -121,6 +114,14 @@ def past_grid_case():
     keys[at], hashes[at], valid[at] = U(1) << U(63), rand_hashes(rng, 1)[0], 1
     assert confirm_model(keys[at], hashes[at])["size"].max() == long_run > 2 * slice_len(m)
     return ("past_grid", keys, hashes, valid)
+
+
+def border_case(m: int):
+    """m of SLICE_COUNTS pooled files, with its model and whether it ties as all_cases() gives them:
+    the counts at which the slice arithmetic changes (size_* and past_grid pass through five of
+    them; BLOCKS * TILE, every workgroup exactly one whole tile, only here)"""
+    keys, hashes, valid = pooled(m, 400 + SLICE_COUNTS.index(m), True)
+    return (f"border_{m}", keys, hashes, valid, confirm_model(keys, hashes, valid), has_tie(keys, hashes, valid))
 
 
 def long_class_case():

@@ -24,25 +24,17 @@ import numpy as np
 from tests import object_index_cases as oc
 from tests import object_index_orphans_cases as pc
 from tests import object_index_owners_cases as wc
+from tests.sliced_cases import BLOCKS, TILE, slice_len
 
 U = np.uint64
 M64 = oc.M64
 E = pc.E
-TILE = 256          # object_index.hip: a workgroup's tile
-BLOCKS = 1024       # object_index.hip OI_BLOCKS: most workgroups of a sliced pass
 MIN_OWNERS = (0, 1, 2, wc.RUN, wc.RUN + 1)
 
 
 def min_links_for(largest: int):
     """the thresholds on links(k) for an index whose largest links(k) is `largest`"""
     return (0, 1, 2, 3, largest, min(largest + 1, M64), M64)
-
-
-def slice_len(n: int) -> int:
-    """the entries of one workgroup's slice in a sliced pass over n entries, as oi_slice_of and
-    sliced_grid of object_index.hip compute it: whole tiles"""
-    grid = min(max((n + TILE - 1) // TILE, 1), BLOCKS)
-    return ((n + grid - 1) // grid + TILE - 1) // TILE * TILE
 
 
 class DictDuplicates(pc.DictOrphans):

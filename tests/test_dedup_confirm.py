@@ -17,6 +17,7 @@ from oracle import cas_spec as cs
 from spacedrive_amd import _native, cpu, dedup, library
 from spacedrive_amd._native import SD_ERR_CAPACITY, SdCasError, lib
 from tests import dedup_confirm_cases as dc
+from tests import sliced_cases as sl
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "spacedrive_amd", "csrc")
@@ -56,10 +57,10 @@ def test_random_mix_is_a_prefix_path_case():
     assert ties == {"tie_aba", "tie_byte8", "tie_byte31", "tie_among_others", "order_tail_0001_0100", "order_tail_7f_80"}
 
 
-def parse_grid_constants(path: str) -> dict:
+def parse_grid_constants(path: str, names) -> dict:
     src = open(path).read()
     out = {}
-    for name in ("DC_BLOCKS", "DC_TILE"):
+    for name in names:
         found = re.findall(r"^constexpr\s+uint32_t\s+" + name + r"\s*=\s*(\d+)\s*;", src, re.M)
         assert len(found) == 1, name
         out[name] = int(found[0])
@@ -67,12 +68,21 @@ def parse_grid_constants(path: str) -> dict:
 
 
 def test_grid_constants_match_the_kernels():
-    """The cases' slice arithmetic uses dedup_confirm.hip's constants: a retune of the kernels fails
-    here instead of moving a border out from under the sweep."""
-    got = parse_grid_constants(os.path.join(CSRC, "dedup_confirm.hip"))
-    assert got == {"DC_BLOCKS": dc.BLOCKS, "DC_TILE": dc.TILE}
+    """The cases' slice arithmetic (tests/sliced_cases.py, for the confirm step and the Object index
+    alike) uses sliced.h's constants: a retune of the kernels fails here instead of moving a border
+    out from under the sweeps.  Neither user of the header keeps constants of its own, and the
+    index's count slots are the header's workgroups."""
+    got = parse_grid_constants(os.path.join(CSRC, "sliced.h"), ("BLOCKS", "TILE"))
+    assert got == {"BLOCKS": sl.BLOCKS, "TILE": sl.TILE} and (dc.BLOCKS, dc.TILE) == (sl.BLOCKS, sl.TILE)
+    assert dc.slice_len is sl.slice_len
     assert dc.PAST_GRID == dc.BLOCKS * dc.TILE + 1 and dc.slice_len(dc.PAST_GRID) == 2 * dc.TILE
     assert dc.slice_len(1) == dc.slice_len(dc.BLOCKS * dc.TILE) == dc.TILE
+    assert sl.SLICE_COUNTS == (1, 255, 256, 257, 262144, 262145)
+    assert [sl.slice_len(n) for n in sl.SLICE_COUNTS] == [256] * 5 + [512]
+    for name in ("dedup_confirm.hip", "object_index.hip"):
+        assert not re.search(r"constexpr[^;=]*\b(\w+_)?(BLOCKS|TILE)\s*=", open(os.path.join(CSRC, name)).read()), name
+    slots = parse_grid_constants(os.path.join(CSRC, "sd_internal.h"), ("OI_COUNT_SLOTS",))
+    assert slots == {"OI_COUNT_SLOTS": got["BLOCKS"]}
     src = open(os.path.join(CSRC, "dedup_confirm.hip")).read()
     assert "__launch_bounds__(256)" in src and dc.TILE == 256  # a tile is a workgroup's lanes
 

@@ -96,6 +96,16 @@ def test_every_case_on_both_paths(ctx, cases):
             assert_case(ctx, case, full)
 
 
+@pytest.mark.parametrize("m", dc.SLICE_COUNTS)
+def test_both_paths_at_a_slice_border(ctx, m):
+    """The counts at which a sliced pass's arithmetic changes (tests/sliced_cases.py), as the
+    Object index has them in tests/test_gpu_object_index_slices.py: bit-exact and between guard
+    rows down both paths."""
+    case = dc.border_case(m)
+    for full in (0, 1):
+        assert_case(ctx, case, full)
+
+
 def test_path_counters(ctx, cases):
     """The random mix and the uniform tie run finish on the prefix path; tails A, B, A take the
     full-width path."""

@@ -1,5 +1,6 @@
-"""The slice arithmetic of the Object index's two kernel skeletons (csrc/object_index.hip:
-sliced_flag, sliced_compact) at the entry counts where it changes -- run on an MI355X: -m gpu.
+"""The slice arithmetic of the Object index's sliced passes (csrc/sliced.h: sliced_flag,
+sliced_compact and the primitives under them) at the entry counts where it changes
+(tests/sliced_cases.py) -- run on an MI355X: -m gpu.
 A sliced pass gives each of at most 1024 workgroups a contiguous run of whole 256-entry tiles:
 one entry, the last lane of a tile (255), a whole tile (256), one entry into the second
 workgroup (257), every workgroup one whole tile (262 144), and one entry more, at which a
@@ -16,14 +17,13 @@ pytestmark = pytest.mark.gpu
 
 from tests import object_index_apply_cases as ac  # noqa: E402
 from tests import object_index_owners_cases as wc  # noqa: E402
+from tests.sliced_cases import BLOCKS, SLICE_COUNTS, TILE, grid, slice_len  # noqa: E402
 from tests.test_gpu_object_index_duplicates import DeviceDuplicates  # noqa: E402
 from tests.test_object_index_apply import exports_equal, same  # noqa: E402
 from tests.test_object_index_duplicates import MirrorDuplicates  # noqa: E402
 
 U = np.uint64
 E = ac.E
-TILE, SLOTS = 256, 1024
-SLICE_COUNTS = (1, TILE - 1, TILE, TILE + 1, SLOTS * TILE, SLOTS * TILE + 1)
 
 
 @pytest.fixture(scope="module")
@@ -36,12 +36,10 @@ def ctx():
 
 
 def test_the_counts_are_where_the_slices_change():
-    """a workgroup's slice, as oi_slice_of computes it: whole tiles of ceil(n / workgroups)"""
-    def tiles_per_slice(n):
-        groups = min(max((n + TILE - 1) // TILE, 1), SLOTS)
-        return ((n + groups - 1) // groups + TILE - 1) // TILE
-    assert [tiles_per_slice(n) for n in SLICE_COUNTS] == [1, 1, 1, 1, 1, 2]
-    assert [min((n + TILE - 1) // TILE, SLOTS) for n in SLICE_COUNTS] == [1, 1, 1, 2, SLOTS, SLOTS]
+    """a workgroup's slice, as slice_of computes it: whole tiles of ceil(n / workgroups)"""
+    assert [slice_len(n) // TILE for n in SLICE_COUNTS] == [1, 1, 1, 1, 1, 2]
+    assert all(slice_len(n) % TILE == 0 for n in SLICE_COUNTS)
+    assert [grid(n) for n in SLICE_COUNTS] == [1, 1, 1, 2, BLOCKS, BLOCKS]
 
 
 @pytest.mark.parametrize("n", SLICE_COUNTS)
