@@ -16,10 +16,10 @@ for r in 1 2 3; do
     SD_CAS_LIB=$L timeout -k 10 300 python3 bench.py $ARGS > gpurun_out/$TAG/$v$r.json 2> gpurun_out/$TAG/$v$r.err || exit $?
     python3 -c "
 import json; d=json.loads(open('gpurun_out/$TAG/$v$r.json').read().strip().splitlines()[-1]); k=d['kernels']
-c=d.get('configs', {}); ck=d.get('checksum', {})
-print('$v$r', 'sampled %.3f whole %.3f step %.3f value %.1f M' % (k['sampled_ms'], k['whole_ms'], d['ms_per_step'], d['value']/1e6),
-      ' small %.3f sampled1M %.3f' % (c['small']['kernel_ms'], c['sampled']['kernel_ms']) if c else '',
-      ' sclk %s' % ((d['roofline'].get('clock') or {}).get('sclk_mhz_median')),
-      ' checksum %.1f GB/s' % ck['GBps'] if ck else '', ' parity', d['parity_sample']['mismatches'])"
+g=d.get('legs', {}); ck=g.get('checksum', {}); rf=d['roofline']
+print('$v$r', 'sampled %.3f whole %.3f hash %.3f step %.3f value %.1f M' % (k['sampled_ms'], k['whole_ms'], k['hash_ms'], d['ms_per_step'], d['value']/1e6),
+      ' small %.3f sampled1M %.3f' % (g['configs_small']['kernel_ms'], g['configs_sampled']['kernel_ms']) if 'configs_small' in g else '',
+      ' sclk %s power %s W' % (rf.get('sclk_mhz_median'), rf.get('board_power_w')),
+      ' checksum %.1f GB/s' % ck['GBps'] if ck else '', ' parity mismatches', d['parity']['sample'][1], d['parity']['full'][1])"
   done
 done

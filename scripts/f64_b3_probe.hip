@@ -74,7 +74,7 @@ struct F {
 template <int V>
 __device__ __forceinline__ void compress_v(uint32_t (&cv)[8], const uint32_t (&m)[16], uint32_t cl, uint32_t ch,
                                            uint32_t bl, uint32_t fl) {
-    if (V == 0) sdb3::compress(cv, m, cl, ch, bl, fl);
+    if (V == 0) sdb3::compress<false>(cv, m, cl, ch, bl, fl);  // the G without priority windows
     else F<V>::compress(cv, m, cl, ch, bl, fl);
 }
 

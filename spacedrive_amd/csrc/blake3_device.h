@@ -89,7 +89,91 @@ __device__ __forceinline__ void round_r(uint32_t& s0, uint32_t& s1, uint32_t& s2
     SD_G(s3, s4, s9, s14, m[sigma(R, 14)], m[sigma(R, 15)]);
 }
 
-// cv <- first 8 words of compress(cv, m, counter, block_len, flags)
+// Priority windows over G's class runs.  The compiled G issues as runs of one class: the
+// half-rate set (v_add3, the SDWA xors, v_alignbit) and the full-rate set (v_add_u32,
+// v_xor_b32).  A SIMD's arbiter picks by priority, then age; with every wave at priority 0
+// the oldest wave's full-rate ops take whole issue slots from the other waves' half-rate ops.
+// With windows (W) the half-rate runs issue at s_setprio SD_G_PRIO and the full-rate runs at
+// s_setprio 0, so a wave inside a full-rate run only fills what the half-rate ops of the
+// others leave free.  Registers only (scripts/valu_probe10.hip, profiles/g_prio/probe.txt, 5
+// waves/SIMD): 56.8-57.0 T lane-ops/s against 39.2-39.4 T unsteered; the other way round,
+// priority 1 or 3 over the full-rate runs, 38.5-38.7 T, which is why that is not built.  On the
+// bench step, same box, three runs each: 139.1-139.9 against 110.1-110.6 M files/s
+// (profiles/g_prio/ab.txt).  The four G of a half-round are written in lockstep, since a
+// window has to hold one class run of all four columns, and sched_barrier pins each s_setprio
+// between the runs.  A wave leaves compress at priority 0.
+// The windows pay only where waves share a SIMD: a wave alone on its SIMD just issues the
+// s_setprio on top (one wave per SIMD or fewer: 7-11 % slower, more than one: 10-30 % faster;
+// profiles/g_prio/small_batch.md).  So compress and everything that inlines it take
+// `template <bool W>`, and the launchers pick per launch (cas_kernels.hip, g_windows);
+// SD_G_PRIO = 0 makes them never pick W, which is the G as it was.
+#ifndef SD_G_PRIO
+#define SD_G_PRIO 1
+#endif
+
+template <int P>
+__device__ __forceinline__ void g_prio() {
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(P);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// four independent G (one half-round) step by step with the windows; enters and leaves inside a
+// half-rate run
+__device__ __forceinline__ void g4(uint32_t (&a)[4], uint32_t (&b)[4], uint32_t (&c)[4], uint32_t (&d)[4],
+                                   const uint32_t (&x)[4], const uint32_t (&y)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) a[k] = add3(a[k], b[k], x[k]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) d[k] = xor_rotr16(d[k], a[k]);
+    g_prio<0>();
+#pragma unroll
+    for (int k = 0; k < 4; k++) c[k] = c[k] + d[k];
+#pragma unroll
+    for (int k = 0; k < 4; k++) b[k] = b[k] ^ c[k];
+    g_prio<SD_G_PRIO>();
+#pragma unroll
+    for (int k = 0; k < 4; k++) b[k] = rotr(b[k], 12);
+#pragma unroll
+    for (int k = 0; k < 4; k++) a[k] = add3(a[k], b[k], y[k]);
+    g_prio<0>();
+#pragma unroll
+    for (int k = 0; k < 4; k++) d[k] = d[k] ^ a[k];
+    g_prio<SD_G_PRIO>();
+#pragma unroll
+    for (int k = 0; k < 4; k++) d[k] = rotr(d[k], 8);
+    g_prio<0>();
+#pragma unroll
+    for (int k = 0; k < 4; k++) c[k] = c[k] + d[k];
+#pragma unroll
+    for (int k = 0; k < 4; k++) b[k] = b[k] ^ c[k];
+    g_prio<SD_G_PRIO>();
+#pragma unroll
+    for (int k = 0; k < 4; k++) b[k] = rotr(b[k], 7);
+}
+
+// one round on s[4 * row + column]: the columns, then the diagonals as the rows rotated
+template <int R>
+__device__ __forceinline__ void round_w(uint32_t (&a)[4], uint32_t (&b)[4], uint32_t (&c)[4], uint32_t (&d)[4],
+                                        const uint32_t (&m)[16]) {
+    {
+        const uint32_t x[4] = {m[sigma(R, 0)], m[sigma(R, 2)], m[sigma(R, 4)], m[sigma(R, 6)]};
+        const uint32_t y[4] = {m[sigma(R, 1)], m[sigma(R, 3)], m[sigma(R, 5)], m[sigma(R, 7)]};
+        g4(a, b, c, d, x, y);
+    }
+    {
+        const uint32_t x[4] = {m[sigma(R, 8)], m[sigma(R, 10)], m[sigma(R, 12)], m[sigma(R, 14)]};
+        const uint32_t y[4] = {m[sigma(R, 9)], m[sigma(R, 11)], m[sigma(R, 13)], m[sigma(R, 15)]};
+        uint32_t b1[4] = {b[1], b[2], b[3], b[0]}, c2[4] = {c[2], c[3], c[0], c[1]}, d3[4] = {d[3], d[0], d[1], d[2]};
+        g4(a, b1, c2, d3, x, y);
+        b[1] = b1[0]; b[2] = b1[1]; b[3] = b1[2]; b[0] = b1[3];
+        c[2] = c2[0]; c[3] = c2[1]; c[0] = c2[2]; c[1] = c2[3];
+        d[3] = d3[0]; d[0] = d3[1]; d[1] = d3[2]; d[2] = d3[3];
+    }
+}
+
+// cv <- first 8 words of compress(cv, m, counter, block_len, flags); W: with priority windows
+template <bool W>
 __device__ __forceinline__ void compress(uint32_t (&cv)[8], const uint32_t (&m)[16],
                                          uint32_t ctr_lo, uint32_t ctr_hi, uint32_t block_len,
                                          uint32_t flags) {
@@ -97,6 +181,16 @@ __device__ __forceinline__ void compress(uint32_t (&cv)[8], const uint32_t (&m)[
     uint32_t s4 = cv[4], s5 = cv[5], s6 = cv[6], s7 = cv[7];
     uint32_t s8 = SD_IV0, s9 = SD_IV1, s10 = SD_IV2, s11 = SD_IV3;
     uint32_t s12 = ctr_lo, s13 = ctr_hi, s14 = block_len, s15 = flags;
+    if constexpr (W) {
+        uint32_t a[4] = {s0, s1, s2, s3}, b[4] = {s4, s5, s6, s7}, c[4] = {s8, s9, s10, s11}, d[4] = {s12, s13, s14, s15};
+        g_prio<SD_G_PRIO>();
+        round_w<0>(a, b, c, d, m); round_w<1>(a, b, c, d, m); round_w<2>(a, b, c, d, m); round_w<3>(a, b, c, d, m);
+        round_w<4>(a, b, c, d, m); round_w<5>(a, b, c, d, m); round_w<6>(a, b, c, d, m);
+        g_prio<0>();  // the feed-forward xors are a full-rate run
+#pragma unroll
+        for (int k = 0; k < 4; k++) { cv[k] = a[k] ^ c[k]; cv[4 + k] = b[k] ^ d[k]; }
+        return;
+    }
 #define SD_ROUND(R) round_r<R>(s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15, m)
     SD_ROUND(0); SD_ROUND(1); SD_ROUND(2); SD_ROUND(3); SD_ROUND(4); SD_ROUND(5); SD_ROUND(6);
 #undef SD_ROUND
@@ -110,13 +204,14 @@ __device__ __forceinline__ void set_iv(uint32_t (&cv)[8]) {
 }
 
 // parent node: out <- compress(IV, left || right, 0, 64, PARENT | extra)
+template <bool W>
 __device__ __forceinline__ void parent(uint32_t (&out)[8], const uint32_t (&l)[8],
                                        const uint32_t (&r)[8], uint32_t extra_flags) {
     uint32_t m[16];
 #pragma unroll
     for (int i = 0; i < 8; i++) { m[i] = l[i]; m[8 + i] = r[i]; }
     set_iv(out);
-    compress(out, m, 0u, 0u, BLOCK_LEN, PARENT | extra_flags);
+    compress<W>(out, m, 0u, 0u, BLOCK_LEN, PARENT | extra_flags);
 }
 
 // 64 message bytes -> 16 little-endian words (4x 16-byte loads; ptr 16-B aligned)
@@ -152,6 +247,7 @@ __device__ __forceinline__ void load_block_partial(uint32_t (&m)[16], const uint
 
 // Chaining value of one chunk of `len` bytes (1..1024; 0 only for an empty message),
 // chunk index `counter`.  If is_root, the last block carries ROOT and cv is the hash.
+template <bool W>
 __device__ __forceinline__ void chunk_cv(uint32_t (&cv)[8], const uint8_t* __restrict__ p,
                                          uint32_t len, uint64_t counter, bool is_root) {
     set_iv(cv);
@@ -160,16 +256,17 @@ __device__ __forceinline__ void chunk_cv(uint32_t (&cv)[8], const uint8_t* __res
     uint32_t m[16];
     for (uint32_t b = 0; b + 1 < nblocks; b++) {
         load_block(m, p + 64u * b);
-        compress(cv, m, clo, chi, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
+        compress<W>(cv, m, clo, chi, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
     }
     const uint32_t last = nblocks - 1;
     const uint32_t tail = len - 64u * last;
     if (tail == 64u) load_block(m, p + 64u * last);
     else load_block_partial(m, p + 64u * last, tail);
-    compress(cv, m, clo, chi, tail, (last == 0 ? CHUNK_START : 0u) | CHUNK_END | (is_root ? ROOT : 0u));
+    compress<W>(cv, m, clo, chi, tail, (last == 0 ? CHUNK_START : 0u) | CHUNK_END | (is_root ? ROOT : 0u));
 }
 
 // Full 1 KiB non-root chunk with line-pair loads (see full_chunks_cv)
+template <bool W>
 __device__ __forceinline__ void full_chunk_cv_lp(uint32_t (&cv)[8], const uint8_t* __restrict__ p,
                                                  uint64_t counter) {
     set_iv(cv);
@@ -179,8 +276,8 @@ __device__ __forceinline__ void full_chunk_cv_lp(uint32_t (&cv)[8], const uint8_
     for (uint32_t b = 0; b < 16; b += 2) {
         load_block(ma, p + 64u * b);
         load_block(mb, p + 64u * (b + 1));
-        compress(cv, ma, clo, chi, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
-        compress(cv, mb, clo, chi, BLOCK_LEN, b == 14 ? CHUNK_END : 0u);
+        compress<W>(cv, ma, clo, chi, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
+        compress<W>(cv, mb, clo, chi, BLOCK_LEN, b == 14 ? CHUNK_END : 0u);
     }
 }
 
@@ -190,7 +287,7 @@ __device__ __forceinline__ void full_chunk_cv_lp(uint32_t (&cv)[8], const uint8_
 // compressed, so a line is consumed whole instead of across a compression (with ~7 MB of
 // lines in flight per XCD against a 4 MB L2, half-consumed lines were evicted and fetched
 // again: 1.10x the algorithmic HBM bytes before, 1.00x after).
-template <int U>
+template <int U, bool W>
 __device__ __forceinline__ void full_chunks_cv(uint32_t (&out)[8], const uint8_t* __restrict__ p, uint64_t c0) {
     static_assert(U == 1 || U == 2 || U == 4, "U");
     uint32_t held[2][8];  // level-wise merge stack: at most two pending nodes for U <= 4
@@ -206,8 +303,8 @@ __device__ __forceinline__ void full_chunks_cv(uint32_t (&out)[8], const uint8_t
         for (uint32_t b = 0; b < 16; b += 2) {
             load_block(ma, q + 64u * b);
             load_block(mb, q + 64u * (b + 1));
-            compress(cv, ma, clo, chi, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
-            compress(cv, mb, clo, chi, BLOCK_LEN, b + 1 == 15 ? CHUNK_END : 0u);
+            compress<W>(cv, ma, clo, chi, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
+            compress<W>(cv, mb, clo, chi, BLOCK_LEN, b + 1 == 15 ? CHUNK_END : 0u);
         }
         if (U == 1) {
 #pragma unroll
@@ -216,15 +313,15 @@ __device__ __forceinline__ void full_chunks_cv(uint32_t (&out)[8], const uint8_t
 #pragma unroll
             for (int i = 0; i < 8; i++) held[u >> 1][i] = cv[i];
         } else if (u == 1) {
-            parent(out, held[0], cv, 0u);
+            parent<W>(out, held[0], cv, 0u);
             if (U == 4) {
 #pragma unroll
                 for (int i = 0; i < 8; i++) held[0][i] = out[i];
             }
         } else {  // u == 3
             uint32_t p23[8];
-            parent(p23, held[1], cv, 0u);
-            parent(out, held[0], p23, 0u);
+            parent<W>(p23, held[1], cv, 0u);
+            parent<W>(out, held[0], p23, 0u);
         }
     }
 }

@@ -40,6 +40,7 @@ __device__ __forceinline__ void load_cv(uint32_t (&cv)[8], const uint32_t* src) 
 
 // Level-wise merge of n (1..blockDim) CVs held in lds[0..n) -> lds[0].  ROOT goes on the
 // final parent when `root`.  Every thread of the workgroup must call it.
+template <bool W>
 __device__ void lds_reduce(uint32_t (*lds)[8], uint32_t n, bool root) {
     const uint32_t t = threadIdx.x;
     while (n > 1) {
@@ -51,7 +52,7 @@ __device__ void lds_reduce(uint32_t (*lds)[8], uint32_t n, bool root) {
             uint32_t l[8], r[8];
             load_cv(l, lds[2 * t]);
             load_cv(r, lds[2 * t + 1]);
-            parent(res, l, r, (root && n == 2) ? ROOT : 0u);
+            parent<W>(res, l, r, (root && n == 2) ? ROOT : 0u);
             have = true;
         } else if (carry && t == P) {
             load_cv(res, lds[n - 1]);
@@ -102,9 +103,10 @@ struct CvStack {
         for (int i = 0; i < 8; i++) s[0][i] = c[i];
     }
     // c <- parent(top, c), and the top popped
+    template <bool W>
     __device__ __forceinline__ void merge_top(uint32_t (&c)[8], uint32_t flags) {
         uint32_t r[8];
-        parent(r, s[0], c, flags);
+        parent<W>(r, s[0], c, flags);
 #pragma unroll
         for (int i = 0; i < 8; i++) c[i] = r[i];
 #pragma unroll
@@ -118,10 +120,10 @@ constexpr int ilog2(int x) { return x <= 1 ? 0 : 1 + ilog2(x / 2); }
 
 // CV of U (a power of two) consecutive full non-root chunks c0.. : U = 2 is full_chunks_cv's
 // unrolled pair; larger groups merge each chunk into the stack as it completes.
-template <int U>
+template <int U, bool W>
 __device__ __forceinline__ void group_cv(uint32_t (&out)[8], const uint8_t* __restrict__ p, uint64_t c0) {
     if constexpr (U <= 2) {
-        full_chunks_cv<U>(out, p, c0);
+        full_chunks_cv<U, W>(out, p, c0);
     } else {
         CvStack<ilog2(U)> st;
         uint32_t ma[16], mb[16];
@@ -135,17 +137,17 @@ __device__ __forceinline__ void group_cv(uint32_t (&out)[8], const uint8_t* __re
             for (uint32_t b = 0; b < 16; b += 2) {
                 load_block(ma, q + 64u * b);
                 load_block(mb, q + 64u * (b + 1));
-                compress(out, ma, clo, chi, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
-                compress(out, mb, clo, chi, BLOCK_LEN, b + 1 == 15 ? CHUNK_END : 0u);
+                compress<W>(out, ma, clo, chi, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
+                compress<W>(out, mb, clo, chi, BLOCK_LEN, b + 1 == 15 ? CHUNK_END : 0u);
             }
 #pragma unroll 1
-            for (uint32_t t = u + 1; (t & 1u) == 0; t >>= 1) st.merge_top(out, 0u);
+            for (uint32_t t = u + 1; (t & 1u) == 0; t >>= 1) st.template merge_top<W>(out, 0u);
             if (u + 1 < (uint32_t)U) st.push(out);
         }
     }
 }
 
-template <int U>
+template <int U, bool W>
 __global__ __launch_bounds__(256) void k_cas_sampled_lanes(const uint8_t* __restrict__ staged,
                                                            const uint64_t* __restrict__ soff, uint32_t n,
                                                            uint32_t* __restrict__ rows) {
@@ -154,11 +156,11 @@ __global__ __launch_bounds__(256) void k_cas_sampled_lanes(const uint8_t* __rest
     if (g >= (uint64_t)n * K) return;
     const uint32_t f = (uint32_t)(g / K), j = (uint32_t)(g - (uint64_t)f * K);
     uint32_t cv[8];
-    group_cv<U>(cv, staged + soff[f] + (size_t)j * U * CHUNK_LEN, (uint64_t)j * U);
+    group_cv<U, W>(cv, staged + soff[f] + (size_t)j * U * CHUNK_LEN, (uint64_t)j * U);
     store_cv(rows + ((size_t)j * n + f) * 8, cv);
 }
 
-template <int U>
+template <int U, bool W>
 __global__ __launch_bounds__(256) void k_cas_sampled_merge(const uint8_t* __restrict__ staged,
                                                            const uint64_t* __restrict__ soff,
                                                            const uint32_t* __restrict__ idx, uint32_t n,
@@ -176,15 +178,15 @@ __global__ __launch_bounds__(256) void k_cas_sampled_merge(const uint8_t* __rest
         for (int i = 0; i < 8; i++) cur[i] = nxt[i];
         if (k + 1 < K) load_cv(nxt, rows + ((size_t)(k + 1) * n + f) * 8);  // in flight during the merges
 #pragma unroll 1
-        for (uint32_t t = k + 1; (t & 1u) == 0; t >>= 1) st.merge_top(cur, 0u);
+        for (uint32_t t = k + 1; (t & 1u) == 0; t >>= 1) st.template merge_top<W>(cur, 0u);
         st.push(cur);
     }
     // the tail chunk is the rightmost node; the stack's subtrees fold onto it, ROOT last
-    chunk_cv(cur, staged + soff[f] + (size_t)S_FULL * CHUNK_LEN, SD_SAMPLED_MSG_LEN - S_FULL * CHUNK_LEN, S_FULL,
+    chunk_cv<W>(cur, staged + soff[f] + (size_t)S_FULL * CHUNK_LEN, SD_SAMPLED_MSG_LEN - S_FULL * CHUNK_LEN, S_FULL,
              false);
     constexpr int P = __builtin_popcount(K);  // subtrees on the stack after K nodes
 #pragma unroll 1
-    for (int d = 0; d < P; d++) st.merge_top(cur, d + 1 == P ? ROOT : 0u);
+    for (int d = 0; d < P; d++) st.template merge_top<W>(cur, d + 1 == P ? ROOT : 0u);
     store_cv(out + (size_t)idx[f] * 8, cur);
 }
 
@@ -198,6 +200,7 @@ __global__ __launch_bounds__(256) void k_cas_sampled_merge(const uint8_t* __rest
 // Full 1 KiB non-root chunk, the next line pair in flight while the current one is
 // compressed: latency kernels (one chunk per lane, few waves) that cannot hide the load
 // of each line pair behind other waves.
+template <bool W>
 __device__ __forceinline__ void full_chunk_cv_prefetch(uint32_t (&cv)[8], const uint8_t* __restrict__ q,
                                                        uint32_t counter) {
     set_iv(cv);
@@ -210,8 +213,8 @@ __device__ __forceinline__ void full_chunk_cv_prefetch(uint32_t (&cv)[8], const 
             load_block(na, q + 64u * (b + 2));
             load_block(nb, q + 64u * (b + 3));
         }
-        compress(cv, ma, counter, 0u, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
-        compress(cv, mb, counter, 0u, BLOCK_LEN, b + 1 == 15 ? CHUNK_END : 0u);
+        compress<W>(cv, ma, counter, 0u, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
+        compress<W>(cv, mb, counter, 0u, BLOCK_LEN, b + 1 == 15 ? CHUNK_END : 0u);
 #pragma unroll
         for (int i = 0; i < 16; i++) {
             ma[i] = na[i];
@@ -220,6 +223,7 @@ __device__ __forceinline__ void full_chunk_cv_prefetch(uint32_t (&cv)[8], const 
     }
 }
 
+template <bool W>
 __global__ __launch_bounds__(64) void k_cas_sampled_wave(const uint8_t* __restrict__ staged,
                                                          const uint64_t* __restrict__ soff,
                                                          const uint32_t* __restrict__ idx, uint32_t n,
@@ -229,14 +233,14 @@ __global__ __launch_bounds__(64) void k_cas_sampled_wave(const uint8_t* __restri
     const uint8_t* msg = staged + soff[f];
     uint32_t cv[8];
     if (t < (uint32_t)S_FULL) {
-        full_chunk_cv_prefetch(cv, msg + (size_t)t * CHUNK_LEN, t);
+        full_chunk_cv_prefetch<W>(cv, msg + (size_t)t * CHUNK_LEN, t);
         store_cv(lds[t], cv);
     } else if (t == (uint32_t)S_FULL) {
-        chunk_cv(cv, msg + (size_t)S_FULL * CHUNK_LEN, SD_SAMPLED_MSG_LEN - S_FULL * CHUNK_LEN, S_FULL, false);
+        chunk_cv<W>(cv, msg + (size_t)S_FULL * CHUNK_LEN, SD_SAMPLED_MSG_LEN - S_FULL * CHUNK_LEN, S_FULL, false);
         store_cv(lds[t], cv);
     }
     __syncthreads();
-    lds_reduce(lds, S_FULL + 1, true);
+    lds_reduce<W>(lds, S_FULL + 1, true);
     if (t < 8) out[(size_t)idx[f] * 8 + t] = lds[0][t];
 }
 
@@ -255,12 +259,12 @@ __global__ __launch_bounds__(128) void k_whole_wave(const uint8_t* __restrict__ 
     if (t < C) {
         const uint32_t len = L == 0 ? 0u : (L - t * CHUNK_LEN < CHUNK_LEN ? L - t * CHUNK_LEN : CHUNK_LEN);
         uint32_t cv[8];
-        if (len == CHUNK_LEN && C > 1) full_chunk_cv_prefetch(cv, msg + (size_t)t * CHUNK_LEN, t);
-        else chunk_cv(cv, msg + (size_t)t * CHUNK_LEN, len, t, C == 1);
+        if (len == CHUNK_LEN && C > 1) full_chunk_cv_prefetch<false>(cv, msg + (size_t)t * CHUNK_LEN, t);
+        else chunk_cv<false>(cv, msg + (size_t)t * CHUNK_LEN, len, t, C == 1);
         store_cv(lds[t], cv);
     }
     __syncthreads();
-    lds_reduce(lds, C, C > 1);  // one chunk: its last block already carried ROOT
+    lds_reduce<false>(lds, C, C > 1);  // one chunk: its last block already carried ROOT
     if (t < 8) out[(size_t)r.w * 8 + t] = lds[0][t];
 }
 
@@ -277,6 +281,7 @@ __global__ __launch_bounds__(128) void k_whole_wave(const uint8_t* __restrict__ 
 // branch); the tail path hashes its chunks one after the other without the second message
 // buffer, so the kernel keeps the full path's register budget, and its latency-bound
 // lanes run while the last full-pair waves drain.
+template <bool W>
 __global__ __launch_bounds__(256) void k_whole_items(const uint8_t* __restrict__ staged,
                                                      const uint4* __restrict__ full, uint32_t n_full, uint32_t wf,
                                                      const uint4* __restrict__ tail, uint32_t n_tail,
@@ -287,7 +292,7 @@ __global__ __launch_bounds__(256) void k_whole_items(const uint8_t* __restrict__
         const uint4 it = full[g];
         const uint64_t off = (uint64_t)it.x | ((uint64_t)it.y << 32);
         uint32_t cv[8];
-        full_chunks_cv<2>(cv, staged + off, it.w);
+        full_chunks_cv<2, W>(cv, staged + off, it.w);
         store_cv(cvbuf + (size_t)it.z * 8, cv);
         return;
     }
@@ -299,12 +304,12 @@ __global__ __launch_bounds__(256) void k_whole_items(const uint8_t* __restrict__
     const bool root = (it.w >> 31) != 0u;
     uint32_t cv[8];
     if (glen <= CHUNK_LEN) {
-        chunk_cv(cv, p, glen, c0, root);
+        chunk_cv<W>(cv, p, glen, c0, root);
     } else {
         uint32_t l[8], r[8];
-        chunk_cv(l, p, CHUNK_LEN, c0, false);
-        chunk_cv(r, p + CHUNK_LEN, glen - CHUNK_LEN, c0 + 1, false);
-        parent(cv, l, r, root ? ROOT : 0u);
+        chunk_cv<W>(l, p, CHUNK_LEN, c0, false);
+        chunk_cv<W>(r, p + CHUNK_LEN, glen - CHUNK_LEN, c0 + 1, false);
+        parent<W>(cv, l, r, root ? ROOT : 0u);
     }
     store_cv((root ? out : cvbuf) + (size_t)it.z * 8, cv);
 }
@@ -316,6 +321,7 @@ __global__ __launch_bounds__(256) void k_whole_items(const uint8_t* __restrict__
 // those) cover messages of up to 128 chunks.  (Round 5: every node loaded up front, 4 %
 // faster than merging each into a CV stack as it arrived, profiles/r5/r5w_merge8_trace.md;
 // the stack version is in e9a97a5.)
+template <bool W>
 __global__ __launch_bounds__(256) void k_whole_merge8(const uint4* __restrict__ items, uint32_t n,
                                                       const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
                                                       uint32_t* __restrict__ out) {
@@ -341,7 +347,7 @@ __global__ __launch_bounds__(256) void k_whole_merge8(const uint4* __restrict__ 
         for (int k = 0; k < 4 >> lvl; k++) {
             if ((uint32_t)(2 * k + 1) < cnt) {
                 uint32_t r[8];
-                parent(r, nd[2 * k], nd[2 * k + 1], flags);
+                parent<W>(r, nd[2 * k], nd[2 * k + 1], flags);
 #pragma unroll
                 for (int i = 0; i < 8; i++) nd[k][i] = r[i];
             } else if ((uint32_t)(2 * k) < cnt) {
@@ -392,6 +398,7 @@ constexpr uint32_t CK_TREE_LEVELS = ilog2(CK_BLOCK_LANES);
 static_assert((CK_LANE_CHUNKS & (CK_LANE_CHUNKS - 1)) == 0 && CK_LANE_CHUNKS >= 2 && CK_LANE_CHUNKS <= 16, "lane chunks");
 static_assert(CK_WG_THREADS >= 64 && CK_WG_THREADS <= 1024 && CK_WG_THREADS % 64 == 0, "workgroup size");
 
+template <bool W>
 __global__ __launch_bounds__(CK_WG_THREADS) void k_ck_leaf(
     const uint8_t* __restrict__ data, uint64_t shift, uint32_t blk_base, const ck_file* __restrict__ files,
     const uint2* __restrict__ wg_map, uint32_t n_blocks, uint32_t* __restrict__ cvbuf, uint32_t* __restrict__ out) {
@@ -425,17 +432,17 @@ __global__ __launch_bounds__(CK_WG_THREADS) void k_ck_leaf(
                 const uint64_t ci = blk0 + c0 + j;
                 const uint64_t rem = fi.len - ci * CHUNK_LEN;
                 const uint32_t len = fi.len == 0 ? 0u : (rem < CHUNK_LEN ? (uint32_t)rem : CHUNK_LEN);
-                if (len == CHUNK_LEN && nchunks > 1) full_chunk_cv_lp(cv, p + ci * CHUNK_LEN, ci);
-                else chunk_cv(cv, p + ci * CHUNK_LEN, len, ci, nchunks == 1);
+                if (len == CHUNK_LEN && nchunks > 1) full_chunk_cv_lp<W>(cv, p + ci * CHUNK_LEN, ci);
+                else chunk_cv<W>(cv, p + ci * CHUNK_LEN, len, ci, nchunks == 1);
                 if (j + 1 < nch) {  // an aligned group that ends here merges, then waits on the stack
 #pragma unroll 1
-                    for (uint32_t g = j + 1; (g & 1u) == 0; g >>= 1) st.merge_top(cv, 0u);
+                    for (uint32_t g = j + 1; (g & 1u) == 0; g >>= 1) st.template merge_top<W>(cv, 0u);
                     st.push(cv);
                 } else {  // the lane's last chunk: its aligned merges and the fold, one run of
                           // popcount(nch - 1) merges; ROOT on the last when the file is this lane
                     const uint32_t ops = (uint32_t)__builtin_popcount(nch - 1);
 #pragma unroll 1
-                    for (uint32_t k = ops; k > 0; k--) st.merge_top(cv, (file_is_lane && k == 1) ? ROOT : 0u);
+                    for (uint32_t k = ops; k > 0; k--) st.template merge_top<W>(cv, (file_is_lane && k == 1) ? ROOT : 0u);
                 }
             }
             store_cv(lds[t], cv);
@@ -463,7 +470,7 @@ __global__ __launch_bounds__(CK_WG_THREADS) void k_ck_leaf(
                 uint32_t l8[8], r8[8];
                 load_cv(l8, lds[CK_BLOCK_LANES * b + 2 * j]);
                 load_cv(r8, lds[CK_BLOCK_LANES * b + 2 * j + 1]);
-                parent(res, l8, r8, (s_root[b] && nb == 2) ? ROOT : 0u);
+                parent<W>(res, l8, r8, (s_root[b] && nb == 2) ? ROOT : 0u);
                 have = true;
             } else if (2 * j + 1 == nb) {  // the odd last node
                 load_cv(res, lds[CK_BLOCK_LANES * b + 2 * j]);
@@ -498,7 +505,7 @@ __global__ __launch_bounds__(256) void k_ck_reduce(const uint32_t* __restrict__ 
         store_cv(lds[t], cv);
     }
     __syncthreads();
-    lds_reduce(lds, w.count, w.is_root != 0);
+    lds_reduce<false>(lds, w.count, w.is_root != 0);
     if (t < 8) {
         if (w.is_root) out[(size_t)w.file * 8 + t] = lds[0][t];
         else dst[w.dst_index * 8 + t] = lds[0][t];
@@ -508,6 +515,30 @@ __global__ __launch_bounds__(256) void k_ck_reduce(const uint32_t* __restrict__ 
 // --------------------------------------------------------------------- launchers
 namespace sdk {
 
+// Priority windows (blake3_device.h, SD_G_PRIO) for a launch of `waves` waves?  They steer the
+// arbiter between the waves of one SIMD, so they need more waves than the device has SIMDs;
+// below that a wave only pays for the s_setprio (profiles/g_prio/small_batch.md).  The count is
+// the launch's own: what else runs on the device at the time is not considered.  k_whole_wave
+// (<= 512 workgroups of two waves) and k_ck_reduce (an LDS tree of a few waves) never have them.
+static bool g_windows(uint64_t waves) {
+    static const uint64_t simds = [] {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+            cus = 256;
+        return (uint64_t)cus * 4;
+    }();
+    return SD_G_PRIO != 0 && waves > simds;
+}
+// K<W> on `wgs` workgroups of `threads` lanes, W = g_windows(the launch's waves)
+#define SD_LAUNCH_W(K_TRUE, K_FALSE, wgs, threads, s, ...)                                           \
+    do {                                                                                             \
+        if (g_windows((uint64_t)(wgs) * ((threads) / 64)))                                           \
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(K_TRUE), dim3(wgs), dim3(threads), 0, s, __VA_ARGS__);  \
+        else                                                                                         \
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(K_FALSE), dim3(wgs), dim3(threads), 0, s, __VA_ARGS__); \
+    } while (0)
+
 uint64_t cas_sampled_rows_bytes(uint32_t n) { return (uint64_t)n * S_K * 32; }
 
 // rows >= cas_sampled_rows_bytes(n)
@@ -515,8 +546,9 @@ hipError_t launch_cas_sampled(const uint8_t* staged, const uint64_t* soff, const
                               uint32_t* rows, uint32_t* out, hipStream_t s) {
     if (n == 0) return hipSuccess;
     const uint32_t lanes_wg = (uint32_t)(((uint64_t)n * S_K + 255) / 256), merge_wg = (n + 255) / 256;
-    hipLaunchKernelGGL(k_cas_sampled_lanes<S_U>, dim3(lanes_wg), dim3(256), 0, s, staged, soff, n, rows);
-    hipLaunchKernelGGL(k_cas_sampled_merge<S_U>, dim3(merge_wg), dim3(256), 0, s, staged, soff, idx, n, rows, out);
+    SD_LAUNCH_W((k_cas_sampled_lanes<S_U, true>), (k_cas_sampled_lanes<S_U, false>), lanes_wg, 256, s, staged, soff, n, rows);
+    SD_LAUNCH_W((k_cas_sampled_merge<S_U, true>), (k_cas_sampled_merge<S_U, false>), merge_wg, 256, s, staged, soff, idx, n,
+                rows, out);
     return hipGetLastError();
 }
 
@@ -529,7 +561,7 @@ hipError_t launch_whole_wave(const uint8_t* staged, const uint4* rows, uint32_t 
 hipError_t launch_cas_sampled_wave(const uint8_t* staged, const uint64_t* soff, const uint32_t* idx, uint32_t n,
                                    uint32_t* out, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_cas_sampled_wave, dim3(n), dim3(64), 0, s, staged, soff, idx, n, out);
+    SD_LAUNCH_W(k_cas_sampled_wave<true>, k_cas_sampled_wave<false>, n, 64, s, staged, soff, idx, n, out);
     return hipGetLastError();
 }
 
@@ -538,14 +570,14 @@ hipError_t launch_whole_items(const uint8_t* staged, const uint4* full, uint32_t
                               uint32_t* cvbuf, uint32_t* cv2, uint32_t* out, hipStream_t s) {
     const uint32_t wf = (n_full + 255) / 256, wt = (n_tail + 255) / 256;
     if (wf + wt)
-        hipLaunchKernelGGL(k_whole_items, dim3(wf + wt), dim3(256), 0, s, staged, full, n_full, wf, tail, n_tail,
-                           cvbuf, out);
+        SD_LAUNCH_W(k_whole_items<true>, k_whole_items<false>, wf + wt, 256, s, staged, full, n_full, wf, tail, n_tail,
+                    cvbuf, out);
     if (n_a)
-        hipLaunchKernelGGL(k_whole_merge8, dim3((n_a + 255) / 256), dim3(256), 0, s, merge_a, n_a,
-                           (const uint32_t*)cvbuf, cv2, out);
+        SD_LAUNCH_W(k_whole_merge8<true>, k_whole_merge8<false>, (n_a + 255) / 256, 256, s, merge_a, n_a,
+                    (const uint32_t*)cvbuf, cv2, out);
     if (n_b)
-        hipLaunchKernelGGL(k_whole_merge8, dim3((n_b + 255) / 256), dim3(256), 0, s, merge_b, n_b,
-                           (const uint32_t*)cv2, (uint32_t*)nullptr, out);
+        SD_LAUNCH_W(k_whole_merge8<true>, k_whole_merge8<false>, (n_b + 255) / 256, 256, s, merge_b, n_b,
+                    (const uint32_t*)cv2, (uint32_t*)nullptr, out);
     return hipGetLastError();
 }
 
@@ -558,8 +590,8 @@ hipError_t launch_scatter_hash(const uint32_t* src, const uint32_t* idx, uint32_
 hipError_t launch_ck_leaf(const uint8_t* data, uint64_t shift, uint32_t blk_base, const ck_file* files,
                           const uint2* wg_map, uint32_t n_wg, uint32_t* cvbuf, uint32_t* out, hipStream_t s) {
     if (n_wg == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ck_leaf, dim3((n_wg + CK_WG_BLOCKS - 1) / CK_WG_BLOCKS), dim3(CK_WG_THREADS), 0, s, data, shift,
-                       blk_base, files, wg_map, n_wg, cvbuf, out);
+    SD_LAUNCH_W(k_ck_leaf<true>, k_ck_leaf<false>, (n_wg + CK_WG_BLOCKS - 1) / CK_WG_BLOCKS, CK_WG_THREADS, s, data, shift,
+                blk_base, files, wg_map, n_wg, cvbuf, out);
     return hipGetLastError();
 }
 
@@ -569,5 +601,7 @@ hipError_t launch_ck_reduce(const uint32_t* src, uint32_t* dst, const ck_reduce_
     hipLaunchKernelGGL(k_ck_reduce, dim3(n_wg), dim3(256), 0, s, src, dst, wgs, out);
     return hipGetLastError();
 }
+
+#undef SD_LAUNCH_W
 
 }  // namespace sdk
