@@ -230,6 +230,13 @@ extern "C" {
                                              stream: *mut c_void) -> c_int;
     pub fn sd_object_index_duplicate_stats(ctx: *mut sd_cas_ctx, index: *const sd_object_index, out: *mut u64,
                                            stream: *mut c_void) -> c_int;
+    // merge Objects: "Object from IS Object to" (mod.rs:229-333 gave same-step duplicates an
+    // Object each); every id relabelled once and simultaneously, equal pairs of a key coalesced
+    pub fn sd_object_index_merge_objects(ctx: *mut sd_cas_ctx, index: *mut sd_object_index, d_from: *const u64,
+                                         d_to: *const u64, m: u64, moved: *mut u64, coalesced: *mut u64,
+                                         stream: *mut c_void) -> c_int;
+    pub fn sd_cpu_object_index_merge_objects(index: *mut sd_cpu_object_index, from: *const u64, to: *const u64,
+                                             m: u64, moved: *mut u64, coalesced: *mut u64) -> c_int;
     // a duplicate group is a candidate set (cas.rs:30-58 samples): split by full checksum
     // (hash.rs:10-24) on the device, or over host arrays without one
     pub fn sd_dedup_confirm(ctx: *mut sd_cas_ctx, d_keys: *const u64, d_hash32: *const u8, d_valid: *const u8,

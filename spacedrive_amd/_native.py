@@ -184,6 +184,8 @@ SIGNATURES = [
     ("sd_cpu_object_index_duplicates", I32, [P, U64, U64, P, P, P, P, U64, PU64]),
     ("sd_cpu_object_index_duplicate_entries", I32, [P, U64, U64, P, P, P, U64, PU64]),
     ("sd_cpu_object_index_duplicate_stats", I32, [P, P]),
+    ("sd_object_index_merge_objects", I32, [P, P, P, P, U64, PU64, PU64, P]),
+    ("sd_cpu_object_index_merge_objects", I32, [P, P, P, U64, PU64, PU64]),
     ("sd_dedup_confirm", I32, [P, P, P, P, U64, P, P, P, P, U64, PU64, P, P]),
     ("sd_dedup_confirm_stats", I32, [P, P]),
     ("sd_cpu_dedup_confirm", I32, [P, P, P, U64, P, P, P, P, U64, PU64, P]),

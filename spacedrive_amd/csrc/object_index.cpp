@@ -7,7 +7,8 @@
 // (sd_object_index_apply), and that mode's read-only view by Object, which answers the orphan
 // remover's own query (sd_object_index_object_links, sd_object_index_orphans), and its view by
 // key, the duplicate groups per cas_id (sd_object_index_key_links, _duplicates,
-// _duplicate_entries, _duplicate_stats).  Kernels:
+// _duplicate_entries, _duplicate_stats), and the call that acts on that view's answer
+// (sd_object_index_merge_objects).  Kernels:
 // object_index.hip; layout, lookup,
 // the removal rules and the directory / growth policies: object_index.h,
 // object_index_host.cpp (shared with the sd_cpu_object_index_* mirror).
@@ -440,6 +441,61 @@ int sd_object_index_apply_hex(sd_cas_ctx* ctx, sd_object_index* index, const cha
     uint64_t* p = d.as<uint64_t>();
     return sd_object_index_apply(ctx, index, p, p + m_rm, m_rm, p + 2 * m_rm, p + 2 * m_rm + m_in, m_in, nullptr, 0,
                                  removed, taken, nullptr);
+    SD_GUARD_END
+}
+
+// Object `from` is Object `to` (object_index.h, merge Objects): the map sorted and every entry
+// whose id changes marked (nothing of the index written); the per-slice counts of contradictions
+// and of leaving entries in one copy and one sync -- the only wait before the rewrite; then the
+// ids in place (first mode) or the leaving entries' rows coalesced and ONE merge-compaction into
+// the other buffer triple, the swap and the directory, as apply's.  The count cannot grow, so
+// both triples hold it; the entering pairs are counted on the device and read once the rewrite
+// is queued.
+int sd_object_index_merge_objects(sd_cas_ctx* ctx, sd_object_index* index, const uint64_t* d_from,
+                                  const uint64_t* d_to, uint64_t m, uint64_t* moved, uint64_t* coalesced,
+                                  void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !index || (m && (!d_from || !d_to))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_index(ctx, index);
+    if (moved) *moved = 0;
+    if (coalesced) *coalesced = 0;
+    if (m == 0) return SD_OK;
+    sd_object_index* x = index;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    x->scratch.ensure(sdk::index_relabel_scratch(x->n, m, 0));
+    HIP_CHECK(sdk::index_relabel_flag(x->view(), d_from, d_to, m, x->scratch.p, s));
+    const uint32_t slots_map = sdk::index_slots(m), slots_out = x->n ? sdk::index_slots(x->n) : 0;
+    x->host.ensure(2 * sdk::OI_COUNT_SLOTS * sizeof(uint64_t));
+    HIP_CHECK(hipMemcpyAsync(x->host.p, sdk::index_relabel_counts(x->scratch.p, x->n),
+                             (sdk::OI_COUNT_SLOTS + slots_out) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const uint64_t* c = reinterpret_cast<const uint64_t*>(x->host.p);
+    uint64_t contradictions = 0, r_out = 0;
+    for (uint32_t k = 0; k < slots_map; k++) contradictions += c[k];
+    for (uint32_t k = 0; k < slots_out; k++) r_out += c[sdk::OI_COUNT_SLOTS + k];
+    if (contradictions) throw sd_failure(SD_ERR_INVALID, "merge: one `from` id is sent to two different `to` ids");
+    if (r_out > x->n) throw sd_failure(SD_ERR_INTERNAL, "merge: more leaving entries than entries");
+    if (moved) *moved = r_out;
+    if (r_out == 0) return SD_OK;  // nothing is written
+    if (!x->owners()) {
+        HIP_CHECK(sdk::index_relabel_in_place(x->view(), m, x->scratch.p, x->vals[x->cur].as<uint64_t>(), s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        return SD_OK;
+    }
+    x->scratch.grow_preserve(sdk::index_relabel_scratch(x->n, m, r_out));  // the stream is idle: the marks stay
+    const int to = 1 - x->cur;  // both triples hold `cap` entries since the insert that grew them
+    const uint64_t* d_entered = nullptr;
+    HIP_CHECK(sdk::index_relabel_rewrite(x->view(), m, r_out, x->scratch.p, x->counts.as<uint64_t>(),
+                                         x->keys[to].as<uint64_t>(), x->vals[to].as<uint64_t>(),
+                                         x->links[to].as<uint64_t>(), &d_entered, s));
+    HIP_CHECK(hipMemcpyAsync(x->host.p, d_entered, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const uint64_t r_in = *reinterpret_cast<const uint64_t*>(x->host.p);
+    if (r_in > r_out) throw sd_failure(SD_ERR_INTERNAL, "merge: more entering pairs than leaving entries");
+    if (coalesced) *coalesced = r_out - r_in;
+    swap_in(x, to, x->cap, x->n - r_out + r_in, s);
+    return SD_OK;
     SD_GUARD_END
 }
 

@@ -167,6 +167,33 @@ SD_OI_HD bool oi_qualifies(uint64_t links, uint64_t owners, uint64_t min_links, 
     return links >= (min_links ? min_links : 1) && owners >= (min_owners ? min_owners : 1);
 }
 
+// ---- merge Objects (sd_object_index_merge_objects): same-step duplicates each get an Object
+// (mod.rs:229-333), so one cas_id is split over several; once the host has decided that Object
+// `from` IS Object `to`, the index follows in one call.  The m pairs (from[j], to[j]) -- ids
+// compared unsigned, any u64 legal -- define
+//   phi(v) = to[j] if some from[j] == v, else v
+// applied ONCE and SIMULTANEOUSLY to the ids as they stand before the call: a -> b, b -> c sends
+// a's entries to b and b's to c; a -> b, b -> a is a swap (chains are the host's to resolve).
+// Repeated pairs, from == to and a `from` the index does not hold are no-ops.  One `from` with two
+// different `to` ((a -> a) with (a -> b) is one) is a CONTRADICTION: the call is refused with the
+// index untouched.
+//   owners mode: after(k, w) = the sum, in u64, of links(k, v) over every v with phi(v) = w; an
+//     entry exists iff that sum is >= 1.  Keys never change: entries move inside their key's run,
+//     and entries of one key that now share an id coalesce into one.
+//   first mode:  vals[i] = phi(vals[i]) in place.
+//   moved = the entries, before the call, whose id phi changes; coalesced = the count before less
+//   the count after (0 in the first mode).
+// Both paths sort the map by `from` (sf[m] with its st[m]) and search an entry's id among sf: a
+// lower bound lands on the first row of a run of equal `from`, and without a contradiction every
+// row of the run carries the same `to`.
+SD_OI_HD bool oi_map_contradicts(const uint64_t* sf, const uint64_t* st, uint64_t i) {
+    return i != 0 && sf[i - 1] == sf[i] && st[i - 1] != st[i];
+}
+SD_OI_HD uint64_t oi_relabel(const uint64_t* sf, const uint64_t* st, uint64_t m, uint64_t id) {
+    uint64_t slot;
+    return oi_object_slot(sf, m, id, &slot) ? st[slot] : id;
+}
+
 // ---- policies (object_index_host.cpp; the device path calls the same functions)
 // directory bits for n entries: ~log2(n / 8), 0 for tiny indexes, at most 24
 uint32_t oi_dir_bits(uint64_t n);

@@ -7,7 +7,8 @@
 // merge-compaction; and that mode's read-only view by Object: the link totals of listed ids and
 // the orphans among them, in one pass over the entries; and its read-only view by key: the
 // duplicate groups (the runs of equal keys) with their link and owner totals, selected by
-// thresholds and compacted in order.
+// thresholds and compacted in order; and merge Objects, which relabels the owners by a map and
+// coalesces the pairs that meet, in apply's rewrite.
 //
 // Reference semantics: identifier_job_step joins a step's cas_ids against the Objects the
 // library already has (core/src/object/file_identifier/mod.rs:168-175), links each file to
@@ -19,11 +20,12 @@
 // grid in which workgroup b owns the contiguous slice b of the input.  sliced.h holds the slice
 // and tile arithmetic and the two kernel skeletons over it (sliced_flag, sliced_compact); every
 // such pass here is a functor of a few lines over one of them.
-// k_apply_merge, k_group_totals, k_entry_flag, k_object_totals, k_key_links and k_group_stats use
+// k_apply_merge (apply's and the merge's rewrite), k_group_totals, k_entry_flag, k_object_totals, k_key_links and k_group_stats use
 // the slices in ways of their own and stand alone, on that header's primitives.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
@@ -424,6 +426,19 @@ __global__ __launch_bounds__(256) void k_apply_links_in_place(
     }
 }
 
+// the links afterwards of a staying entry that apply's lists name (mark 2: the insertion list
+// alone, 3: the removal list too)
+struct apply_links {
+    const uint64_t *__restrict__ rk, *__restrict__ rv, *__restrict__ rpos, *__restrict__ r_total;
+    uint64_t m_rm;
+    const uint64_t *__restrict__ ik, *__restrict__ iv, *__restrict__ ipos, *__restrict__ i_total;
+    uint64_t m_in;
+    __device__ uint64_t operator()(uint8_t mk, uint64_t k, uint64_t v, uint64_t l) const {
+        return oi_links_after(l, mk == 3 ? pair_multiplicity(rk, rv, rpos, *r_total, m_rm, k, v) : 0,
+                              pair_multiplicity(ik, iv, ipos, *i_total, m_in, k, v));
+    }
+};
+
 // The one rewrite: k_owners_merge and the owners branch of remove_out in one sliced pass
 // over the entries.  With L(i) the leaving entries before position i (block_base + tile_slot)
 // and E(i) the entering pairs ranked at or before i (a search of nrank[r]):
@@ -433,16 +448,18 @@ __global__ __launch_bounds__(256) void k_apply_links_in_place(
 //                             places it (L inside a tile from LDS); the tile that holds the
 //                             last entry also places the pairs ranked at n
 // n == 0: workgroup 0 copies the entering pairs.
+// A staying entry that a pair names (mark >= 2) takes its links from `after` (apply_links above,
+// merge_links below).  r is *d_r if d_r is set (a count the host never waited for), else the value.
+template <class After>
 __global__ __launch_bounds__(256) void k_apply_merge(
     const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals, const uint64_t* __restrict__ links,
-    uint64_t n, const uint8_t* __restrict__ mark, const uint64_t* __restrict__ counts,
-    const uint64_t* __restrict__ rk, const uint64_t* __restrict__ rv, const uint64_t* __restrict__ rpos,
-    const uint64_t* __restrict__ r_total, uint64_t m_rm, const uint64_t* __restrict__ ik,
-    const uint64_t* __restrict__ iv, const uint64_t* __restrict__ ipos, const uint64_t* __restrict__ i_total,
-    uint64_t m_in, const uint64_t* __restrict__ nk, const uint64_t* __restrict__ nv, const uint64_t* __restrict__ nl,
-    const uint64_t* __restrict__ nrank, uint64_t r, uint64_t* __restrict__ out_keys, uint64_t* __restrict__ out_vals,
-    uint64_t* __restrict__ out_links, uint64_t* __restrict__ rm_out) {
+    uint64_t n, const uint8_t* __restrict__ mark, const uint64_t* __restrict__ counts, After after,
+    const uint64_t* __restrict__ nk, const uint64_t* __restrict__ nv, const uint64_t* __restrict__ nl,
+    const uint64_t* __restrict__ nrank, const uint64_t* __restrict__ d_r, uint64_t r,
+    uint64_t* __restrict__ out_keys, uint64_t* __restrict__ out_vals, uint64_t* __restrict__ out_links,
+    uint64_t* __restrict__ rm_out) {
     __shared__ uint32_t before[257];  // leaving entries of the tile before each lane; [256] = all
+    if (d_r) r = *d_r;
     if (n == 0) {
         if (blockIdx.x == 0)
             for (uint64_t j = threadIdx.x; j < r; j += blockDim.x) {
@@ -454,7 +471,6 @@ __global__ __launch_bounds__(256) void k_apply_merge(
     }
     uint64_t run = block_base(counts, nullptr);
     const slice sl = slice_of(n);
-    const uint64_t d_rm = *r_total, d_in = *i_total;
     for (uint64_t base = sl.lo; base < sl.hi; base += blockDim.x) {
         const uint64_t i = base + threadIdx.x;
         const bool act = i < sl.hi;
@@ -489,14 +505,101 @@ __global__ __launch_bounds__(256) void k_apply_merge(
         }
         const uint64_t at = i - slot + (e_hi > e_lo ? oi_lower_bound(nrank, e_lo, e_hi, i + 1) : e_lo);
         uint64_t l = links[i];
-        if (mk >= 2)
-            l = oi_links_after(l, mk == 3 ? pair_multiplicity(rk, rv, rpos, d_rm, m_rm, k, v) : 0,
-                               pair_multiplicity(ik, iv, ipos, d_in, m_in, k, v));
+        if (mk >= 2) l = after(mk, k, v, l);
         out_keys[at] = k;
         out_vals[at] = v;
         out_links[at] = l;
     }
 }
+
+// ---- merge Objects (object_index.h oi_relabel / oi_map_contradicts; mod.rs:229-333 gives
+// same-step duplicates an Object each): the map sorted by `from`; one pass over its rows counts
+// the contradictions, one sliced pass over the entries marks those whose id phi changes (mark 1,
+// apply's leaving entries).  The host reads both counts in its one wait.  First mode: the marked
+// entries are relabelled in place.  Owners mode: the leaving entries are compacted in order into
+// rows (key, phi(id), links), put into (key, id) order by two stable sorts of their positions,
+// and coalesced: the heads of the runs of equal pairs are compacted as aggregate_pairs does, and a
+// run's links are the difference of two elements of the rows' inclusive scan, so no lane walks a
+// run however many ids of one key go to one.  A coalesced pair that meets an entry that stays adds
+// its sum there (mark 2); one that meets a leaving entry, or none, enters at its rank.  The
+// rewrite is k_apply_merge with merge_links.
+struct map_contradiction {
+    const uint64_t *__restrict__ sf, *__restrict__ st;
+    __device__ bool operator()(uint64_t i, uint64_t) const { return oi_map_contradicts(sf, st, i); }
+};
+
+struct relabelled {
+    const uint64_t *__restrict__ vals, *__restrict__ sf, *__restrict__ st;
+    uint64_t m;
+    __device__ bool operator()(uint64_t i, uint64_t) const {
+        const uint64_t v = vals[i];
+        return oi_relabel(sf, st, m, v) != v;
+    }
+};
+
+// first mode: one entry per key, so the marked entries take phi(id) where they stand
+__global__ __launch_bounds__(256) void k_relabel_in_place(const uint8_t* __restrict__ mark,
+                                                          const uint64_t* __restrict__ sf,
+                                                          const uint64_t* __restrict__ st, uint64_t m, uint64_t n,
+                                                          uint64_t* __restrict__ vals) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        if (mark[i]) vals[i] = oi_relabel(sf, st, m, vals[i]);
+}
+
+struct leaving_rows : from_flags {
+    const uint64_t *__restrict__ keys, *__restrict__ vals, *__restrict__ links, *__restrict__ sf, *__restrict__ st;
+    uint64_t m;
+    uint64_t *__restrict__ rk, *__restrict__ rv, *__restrict__ rl;
+    __device__ void emit(uint64_t i, bool flag, uint64_t slot, uint64_t) const {
+        if (!flag) return;
+        rk[slot] = keys[i];
+        rv[slot] = oi_relabel(sf, st, m, vals[i]);
+        rl[slot] = links[i];
+    }
+};
+
+// out[i] = a[pos[i]] (and outb[i] = b[pos[i]] where b is given): the rows behind sorted positions
+__global__ __launch_bounds__(256) void k_gather_rows(const uint64_t* __restrict__ pos, uint64_t m,
+                                                     const uint64_t* __restrict__ a, uint64_t* __restrict__ out,
+                                                     const uint64_t* __restrict__ b, uint64_t* __restrict__ outb) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t p = pos[i];
+        out[i] = a[p];
+        if (b) outb[i] = b[p];
+    }
+}
+
+// Every coalesced pair (d of them, the pass's bound) takes the links of its run (pre = the
+// inclusive scan of the m rows' links in (key, id) order; u64 sums wrap alike on both sides of the
+// difference), its (key, id) rank in the index and its state: 2 = it meets an entry that stays
+// and marks it 2 (distinct pairs name distinct entries: one reader and one writer per byte), 1 =
+// it enters.  Flags the entering ones.
+struct merged_pair_state {
+    const uint64_t *__restrict__ keys, *__restrict__ vals, *__restrict__ dir;
+    uint32_t bits;
+    const uint64_t *__restrict__ dk, *__restrict__ dv, *__restrict__ dpos, *__restrict__ pre;
+    uint64_t m;
+    uint64_t *__restrict__ dcnt, *__restrict__ drank;
+    uint8_t *__restrict__ dstate, *mark;
+    __device__ bool operator()(uint64_t i, uint64_t d) const {
+        uint64_t at;
+        const bool stays = oi_find_pair(keys, vals, dir, bits, dk[i], dv[i], &at) && mark[at] == 0;
+        const uint64_t lo = dpos[i], hi = i + 1 < d ? dpos[i + 1] : m;
+        dcnt[i] = pre[hi - 1] - (lo ? pre[lo - 1] : 0);
+        drank[i] = at;
+        dstate[i] = stays ? 2 : 1;
+        if (stays) mark[at] = 2;
+        return !stays;
+    }
+};
+
+// the links afterwards of a staying entry that a coalesced pair met (mark 2)
+struct merge_links {
+    const uint64_t *__restrict__ dk, *__restrict__ dv, *__restrict__ dcnt, *__restrict__ d_total;
+    __device__ uint64_t operator()(uint8_t, uint64_t k, uint64_t v, uint64_t l) const {
+        return l + dcnt[oi_lower_bound_pair(dk, dv, 0, *d_total, k, v)];
+    }
+};
 
 // ---- by Object, read-only (owners mode): per-Object link totals and the orphans among listed
 // ids (object_index.h oi_object_slot / oi_unowned; orphan_remover.rs:57-95 asks the DB which
@@ -1191,10 +1294,152 @@ hipError_t index_apply_merge(const oi_view& x, const void* scratch, uint64_t m_r
                        enter_out<true>{a.in.t0, a.in.t1, a.in.dcnt, a.in.drank, a.in.dstate, a.in.sk, a.in.sv, a.in.nl,
                                        a.nrank},
                        a.in.d_total, 0, a.entering, nullptr);
-    hipLaunchKernelGGL(k_apply_merge, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, x.links, x.n, a.mark,
-                       a.leaving, a.rm.t0, a.rm.t1, a.rm.dpos, a.rm.d_total, m_rm, a.in.t0, a.in.t1, a.in.dpos,
-                       a.in.d_total, m_in, a.in.sk, a.in.sv, a.in.nl, a.nrank, r_in, out_keys, out_vals, out_links,
-                       rm_out);
+    const apply_links after{a.rm.t0, a.rm.t1, a.rm.dpos, a.rm.d_total, m_rm,
+                            a.in.t0, a.in.t1, a.in.dpos, a.in.d_total, m_in};
+    hipLaunchKernelGGL(k_apply_merge<apply_links>, dim3(sliced_grid(x.n)), dim3(256), 0, s, x.keys, x.vals, x.links, x.n,
+                       a.mark, a.leaving, after, a.in.sk, a.in.sv, a.in.nl, a.nrank, nullptr, r_in, out_keys, out_vals,
+                       out_links, rm_out);
+    return hipGetLastError();
+}
+
+// ---- merge Objects.  scratch: mark[n] (u8); the per-slice counts of contradictions, of leaving
+// entries and of entering pairs (BLOCKS u64 each; the first two side by side for the host's one
+// copy); the sorted map sf[m], st[m] and its sort's temporary storage.  Behind that, sized once
+// the host knows the leaving entries L: nine u64 arrays of L that the passes hand on to each other
+// (merge_rows below), heads[L] and dstate[L] (u8), the coalesced and the entering count (u64, 256
+// bytes apart), then the temporary storage of the sorts and the scan.
+namespace {
+struct merge_scratch {
+    uint8_t* mark;
+    uint64_t *contra, *leaving, *entering, *sf, *st;
+    void* map_tmp;
+    uint8_t* rows;
+};
+
+size_t merge_flag_bytes(uint64_t n, uint64_t m) {
+    return round256(n) + 3 * BLOCKS * sizeof(uint64_t) + 2 * round256(m * sizeof(uint64_t)) + sort_pairs_bytes(m, nullptr) +
+           256;
+}
+
+merge_scratch merge_scratch_at(void* base, uint64_t n, uint64_t m) {
+    merge_scratch q;
+    uint8_t* p = reinterpret_cast<uint8_t*>(base);
+    q.mark = p;
+    p += round256(n);
+    q.contra = reinterpret_cast<uint64_t*>(p);
+    q.leaving = q.contra + BLOCKS, q.entering = q.contra + 2 * BLOCKS;
+    p += 3 * BLOCKS * sizeof(uint64_t);
+    q.sf = reinterpret_cast<uint64_t*>(p);
+    q.st = reinterpret_cast<uint64_t*>(p + round256(m * sizeof(uint64_t)));
+    q.map_tmp = p + 2 * round256(m * sizeof(uint64_t));
+    q.rows = reinterpret_cast<uint8_t*>(base) + merge_flag_bytes(n, m);
+    return q;
+}
+
+size_t scan_bytes(uint64_t m) {
+    size_t b = 0;
+    uint64_t* nul = nullptr;
+    if (rocprim::inclusive_scan(nullptr, b, nul, nul, (size_t)m, rocprim::plus<uint64_t>(), nullptr) != hipSuccess) return 0;
+    return round256(b);
+}
+
+// The arrays of L rows, by the pass that writes them; a later pass takes over an array whose
+// last reader ran before it:
+//   compaction   rk, rv, rl     the leaving entries' (key, phi(id), links), in entry order
+//   sort by id   p0 -> p1       positions 0 .. L in phi(id) order (the sorted ids go to sk, unread)
+//   sort by key  gk = rk[p1], p1 -> sk, p2     the rows' keys and positions in (key, id) order
+//   gather       sv = rv[p2], sl = rl[p2]; scan sl -> pre
+//   heads        dk, dv, dpos   the coalesced pairs and their runs' first rows (over rk, rv, rl)
+//   state        dcnt, drank    (over p2, sl)
+//   entering     nk, nv, nl, nrank   (over sv, sk, pre; nrank its own)
+struct merge_rows {
+    uint64_t *rk, *rv, *rl, *p0, *p1, *gk, *sk, *p2, *sv, *sl, *pre, *dk, *dv, *dpos, *dcnt, *drank, *nk, *nv, *nl, *nrank;
+    uint64_t *d_total, *r_total;
+    uint8_t *heads, *dstate;
+    void* tmp;
+};
+
+size_t merge_rows_bytes(uint64_t L) {
+    return 9 * round256(L * sizeof(uint64_t)) + round256(2 * L) + 512 +
+           std::max(sort_pairs_bytes(L, nullptr), scan_bytes(L)) + 256;
+}
+
+merge_rows merge_rows_at(uint8_t* base, uint64_t L) {
+    merge_rows r;
+    uint64_t* a[9];
+    for (int k = 0; k < 9; k++) a[k] = reinterpret_cast<uint64_t*>(base + k * round256(L * sizeof(uint64_t)));
+    r.rk = a[0], r.rv = a[1], r.rl = a[2], r.p0 = a[3], r.sk = a[4], r.p1 = a[5], r.p2 = a[6], r.pre = a[7];
+    r.gk = a[3], r.sv = a[3], r.sl = a[5];
+    r.dk = a[0], r.dv = a[1], r.dpos = a[2], r.dcnt = a[6], r.drank = a[5];
+    r.nk = a[3], r.nv = a[4], r.nl = a[7], r.nrank = a[8];
+    uint8_t* p = base + 9 * round256(L * sizeof(uint64_t));
+    r.heads = p, r.dstate = p + L;
+    p += round256(2 * L);
+    r.d_total = reinterpret_cast<uint64_t*>(p), r.r_total = reinterpret_cast<uint64_t*>(p + 256);
+    r.tmp = p + 512;
+    return r;
+}
+}  // namespace
+
+size_t index_relabel_scratch(uint64_t n, uint64_t m, uint64_t leaving) {
+    return merge_flag_bytes(n, m) + (leaving ? merge_rows_bytes(leaving) : 0);
+}
+
+const uint64_t* index_relabel_counts(const void* scratch, uint64_t n) {
+    return reinterpret_cast<const uint64_t*>(reinterpret_cast<const uint8_t*>(scratch) + round256(n));
+}
+
+hipError_t index_relabel_flag(const oi_view& x, const uint64_t* from, const uint64_t* to, uint64_t m, void* scratch,
+                              hipStream_t s) {
+    const merge_scratch q = merge_scratch_at(scratch, x.n, m);
+    size_t tb = sort_pairs_bytes(m, s);
+    hipError_t e = rocprim::radix_sort_pairs(q.map_tmp, tb, from, q.sf, to, q.st, (size_t)m, 0, 64, s);
+    if (e != hipSuccess) return e;
+    launch_flag(sliced_grid(m), s, map_contradiction{q.sf, q.st}, nullptr, m, nullptr, q.contra);
+    if (x.n) launch_flag(sliced_grid(x.n), s, relabelled{x.vals, q.sf, q.st, m}, nullptr, x.n, q.mark, q.leaving);
+    return hipGetLastError();
+}
+
+hipError_t index_relabel_in_place(const oi_view& x, uint64_t m, const void* scratch, uint64_t* vals, hipStream_t s) {
+    const merge_scratch q = merge_scratch_at(const_cast<void*>(scratch), x.n, m);
+    hipLaunchKernelGGL(k_relabel_in_place, dim3(flat_grid(x.n)), dim3(256), 0, s, q.mark, q.sf, q.st, m, x.n, vals);
+    return hipGetLastError();
+}
+
+hipError_t index_relabel_rewrite(const oi_view& x, uint64_t m, uint64_t leaving, void* scratch, uint64_t* counts,
+                                 uint64_t* out_keys, uint64_t* out_vals, uint64_t* out_links, const uint64_t** entered,
+                                 hipStream_t s) {
+    const merge_scratch q = merge_scratch_at(scratch, x.n, m);
+    const uint64_t L = leaving;
+    const merge_rows r = merge_rows_at(q.rows, L);
+    const uint32_t gn = sliced_grid(x.n), gl = sliced_grid(L);
+    const dim3 flat(flat_grid(L)), b(256);
+    launch_compact(gn, s, leaving_rows{{q.mark}, x.keys, x.vals, x.links, q.sf, q.st, m, r.rk, r.rv, r.rl}, nullptr, x.n,
+                   q.leaving, nullptr);
+    // (key, id) order: the positions sorted by phi(id), then, stably, by the key behind them
+    hipLaunchKernelGGL(k_iota, flat, b, 0, s, r.p0, L);
+    size_t tb = sort_pairs_bytes(L, s);
+    hipError_t e = rocprim::radix_sort_pairs(r.tmp, tb, r.rv, r.sk, r.p0, r.p1, (size_t)L, 0, 64, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_gather_rows, flat, b, 0, s, r.p1, L, r.rk, r.gk, nullptr, nullptr);
+    e = rocprim::radix_sort_pairs(r.tmp, tb, r.gk, r.sk, r.p1, r.p2, (size_t)L, 0, 64, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_gather_rows, flat, b, 0, s, r.p2, L, r.rv, r.sv, r.rl, r.sl);
+    size_t sb = scan_bytes(L);
+    e = rocprim::inclusive_scan(r.tmp, sb, r.sl, r.pre, (size_t)L, rocprim::plus<uint64_t>(), s);
+    if (e != hipSuccess) return e;
+    launch_flag(gl, s, pair_head{r.sk, r.sv}, nullptr, L, r.heads, counts);
+    launch_compact(gl, s, pair_out{{r.heads}, r.sk, r.sv, r.dk, r.dv, r.dpos}, nullptr, L, counts, r.d_total);
+    launch_flag(gl, s,
+                merged_pair_state{x.keys, x.vals, x.dir, x.bits, r.dk, r.dv, r.dpos, r.pre, L, r.dcnt, r.drank, r.dstate,
+                                  q.mark},
+                r.d_total, 0, nullptr, q.entering);
+    launch_compact(gl, s, enter_out<true>{r.dk, r.dv, r.dcnt, r.drank, r.dstate, r.nk, r.nv, r.nl, r.nrank}, r.d_total, 0,
+                   q.entering, r.r_total);
+    hipLaunchKernelGGL(k_apply_merge<merge_links>, dim3(gn), b, 0, s, x.keys, x.vals, x.links, x.n, q.mark, q.leaving,
+                       merge_links{r.dk, r.dv, r.dcnt, r.d_total}, r.nk, r.nv, r.nl, r.nrank, r.r_total, 0, out_keys,
+                       out_vals, out_links, nullptr);
+    *entered = r.r_total;
     return hipGetLastError();
 }
 

@@ -9,7 +9,8 @@
 // files change (location/manager/watcher/utils.rs:410-494).  No HIP: built with g++ under
 // the sanitizers too (object_index_selftest.cpp, object_index_remove_selftest.cpp,
 // object_index_owners_selftest.cpp, object_index_apply_selftest.cpp,
-// object_index_orphans_selftest.cpp, object_index_duplicates_selftest.cpp; `make
+// object_index_orphans_selftest.cpp, object_index_duplicates_selftest.cpp,
+// object_index_merge_selftest.cpp; `make sanitize-object-index-merge`, `make
 // sanitize-object-index`, `make sanitize-object-index-remove`, `make
 // sanitize-object-index-owners`, `make sanitize-object-index-apply`, `make
 // sanitize-object-index-orphans`, `make sanitize-object-index-duplicates`).  The owners mode
@@ -424,6 +425,75 @@ int sd_cpu_object_index_apply(sd_cpu_object_index* index, const uint64_t* rm_key
             x->keys2[o] = x->keys[i], x->vals2[o] = x->vals[i], x->links2[o] = after;
             o++;
         }
+    }
+    x->keys.swap(x->keys2);
+    x->vals.swap(x->vals2);
+    x->links.swap(x->links2);
+    x->n = o;
+    build_dir(x);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+// sd_object_index_merge_objects over host arrays (object_index.h, merge Objects): the map sorted
+// by `from` and refused on a contradiction before the index is read; the entries phi changes
+// flagged; their rows (key, phi(id), links) put into (key, id) order and coalesced; a coalesced
+// pair that meets an entry that stays adds its sum there, every other one enters at its rank; one
+// rewrite into the other buffers, as apply's.
+int sd_cpu_object_index_merge_objects(sd_cpu_object_index* index, const uint64_t* from, const uint64_t* to, uint64_t m,
+                                      uint64_t* moved, uint64_t* coalesced) {
+    SD_GUARD_BEGIN
+    if (!index || (m && (!from || !to))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (moved) *moved = 0;
+    if (coalesced) *coalesced = 0;
+    if (m == 0) return SD_OK;
+    sd_cpu_object_index* x = index;
+    std::vector<uint64_t> pos(m), sf(m), st(m);
+    std::iota(pos.begin(), pos.end(), 0);
+    std::sort(pos.begin(), pos.end(), [&](uint64_t a, uint64_t b) { return from[a] < from[b]; });
+    for (uint64_t j = 0; j < m; j++) sf[j] = from[pos[j]], st[j] = to[pos[j]];
+    for (uint64_t j = 0; j < m; j++)
+        if (oi_map_contradicts(sf.data(), st.data(), j))
+            throw sd_failure(SD_ERR_INVALID, "merge: one `from` id is sent to two different `to` ids");
+    std::vector<uint64_t> at_old;  // the positions of the entries whose id phi changes
+    for (uint64_t i = 0; i < x->n; i++)
+        if (oi_relabel(sf.data(), st.data(), m, x->vals[i]) != x->vals[i]) at_old.push_back(i);
+    const uint64_t r_out = at_old.size();
+    if (moved) *moved = r_out;
+    if (r_out == 0) return SD_OK;  // nothing is written
+    if (!x->owners()) {
+        for (uint64_t i : at_old) x->vals[i] = oi_relabel(sf.data(), st.data(), m, x->vals[i]);
+        return SD_OK;
+    }
+    // the leaving entries' rows in (key, phi(id)) order; equal pairs are adjacent and add up
+    std::vector<uint64_t> rv(r_out);
+    for (uint64_t j = 0; j < r_out; j++) rv[j] = oi_relabel(sf.data(), st.data(), m, x->vals[at_old[j]]);
+    std::vector<uint64_t> row(r_out);
+    std::iota(row.begin(), row.end(), 0);
+    std::sort(row.begin(), row.end(), [&](uint64_t a, uint64_t b) {
+        const uint64_t ka = x->keys[at_old[a]], kb = x->keys[at_old[b]];
+        return ka != kb ? ka < kb : rv[a] < rv[b];
+    });
+    std::vector<uint8_t> leaves(x->n, 0);
+    for (uint64_t i : at_old) leaves[i] = 1;
+    std::vector<uint64_t> gain(x->n, 0), nk, nv, nl, nrank;
+    for (uint64_t j = 0; j < r_out;) {
+        const uint64_t k = x->keys[at_old[row[j]]], v = rv[row[j]];
+        uint64_t sum = 0;
+        for (; j < r_out && x->keys[at_old[row[j]]] == k && rv[row[j]] == v; j++) sum += x->links[at_old[row[j]]];
+        uint64_t at;
+        if (oi_find_pair(x->keys.data(), x->vals.data(), x->dir.data(), x->bits, k, v, &at) && !leaves[at]) gain[at] = sum;
+        else nk.push_back(k), nv.push_back(v), nl.push_back(sum), nrank.push_back(at);
+    }
+    const uint64_t r_in = nk.size();
+    if (coalesced) *coalesced = r_out - r_in;
+    uint64_t o = 0, j = 0;  // the count cannot grow: the other buffers hold it
+    for (uint64_t i = 0; i <= x->n; i++) {
+        for (; j < r_in && nrank[j] == i; j++, o++)  // the entering pairs ranked at i go before entry i
+            x->keys2[o] = nk[j], x->vals2[o] = nv[j], x->links2[o] = nl[j];
+        if (i == x->n || leaves[i]) continue;
+        x->keys2[o] = x->keys[i], x->vals2[o] = x->vals[i], x->links2[o] = x->links[i] + gain[i];
+        o++;
     }
     x->keys.swap(x->keys2);
     x->vals.swap(x->vals2);

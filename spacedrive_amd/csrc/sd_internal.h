@@ -166,6 +166,24 @@ hipError_t index_apply_in_place(const oi_view& x, const void* scratch, uint64_t 
 hipError_t index_apply_merge(const oi_view& x, const void* scratch, uint64_t m_rm, uint64_t m_in, uint64_t r_in,
                              uint64_t* out_keys, uint64_t* out_vals, uint64_t* out_links, uint64_t* rm_out,
                              hipStream_t s);
+// merge Objects (object_index.h oi_relabel): relabel the owners by the m pairs (from, to), m > 0.
+// First half: the map sorted in `scratch`, every entry whose id changes marked;
+// index_relabel_counts(scratch, n) then holds the per-slice counts of contradictions
+// (index_slots(m)) and, OI_COUNT_SLOTS further, of leaving entries (index_slots(n); unset when n
+// == 0).  Nothing of the index is written.  The scratch is index_relabel_scratch(n, m, 0) bytes
+// for the first half and, its contents kept, index_relabel_scratch(n, m, leaving) for the rewrite.
+size_t index_relabel_scratch(uint64_t n, uint64_t m, uint64_t leaving);
+const uint64_t* index_relabel_counts(const void* scratch, uint64_t n);
+hipError_t index_relabel_flag(const oi_view& x, const uint64_t* from, const uint64_t* to, uint64_t m, void* scratch,
+                              hipStream_t s);
+// first mode: the marked entries' ids in place, `vals` being the index's own
+hipError_t index_relabel_in_place(const oi_view& x, uint64_t m, const void* scratch, uint64_t* vals, hipStream_t s);
+// owners mode, leaving > 0: the leaving entries' rows coalesced, the staying entries (with the
+// links they gain) and the entering pairs merged into out_* (n - leaving + **entered entries;
+// *entered is a device count); `counts`: OI_COUNT_SLOTS u64 of scratch
+hipError_t index_relabel_rewrite(const oi_view& x, uint64_t m, uint64_t leaving, void* scratch, uint64_t* counts,
+                                 uint64_t* out_keys, uint64_t* out_vals, uint64_t* out_links, const uint64_t** entered,
+                                 hipStream_t s);
 // the link count per (key, id) pair, 0 if absent
 hipError_t index_links(const oi_view& x, const uint64_t* q_keys, const uint64_t* q_ids, uint64_t m, uint64_t* out,
                        hipStream_t s);

@@ -566,6 +566,37 @@ def owners_duplicate_stats_host(keys, vals, links):
                      int(go[o2].sum()), int(gl.max()) if len(gl) else 0], dtype=np.uint64)
 
 
+def merge_map(keys, ids):
+    """The map for merge_objects from the rows of duplicate_entries(0, 2) (key, Object id; any
+    order; the caller may first drop the rows of groups the host did not confirm): Object ids that
+    share any key are one component (a host union-find over the distinct ids), and every id but
+    the component's smallest (unsigned) maps to that smallest id.  -> (from_ids, to_ids) uint64,
+    `from` ascending and distinct; no `to` is a `from`, so the map is chain-free and has no
+    contradiction, and a component of one id adds no row."""
+    keys = np.ascontiguousarray(host_u64(keys)).reshape(-1)
+    ids = np.ascontiguousarray(host_u64(ids)).reshape(-1)
+    assert keys.size == ids.size
+    u, at = np.unique(ids, return_inverse=True)  # ascending: a smaller slot is a smaller id
+    parent = list(range(len(u)))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+    order = np.argsort(keys, kind="stable")
+    sk, sa = keys[order], at.reshape(-1)[order]
+    head = np.flatnonzero(np.r_[True, sk[1:] != sk[:-1]]) if len(sk) else np.zeros(0, np.int64)
+    first = np.repeat(sa[head], np.diff(np.r_[head, len(sk)]))  # the slot of each row's key's first row
+    for a, b in zip(sa.tolist(), first.tolist()):
+        a, b = find(a), find(b)
+        if a != b:
+            parent[max(a, b)] = min(a, b)  # the root is the component's smallest slot
+    root = np.array([find(a) for a in range(len(u))], dtype=np.int64).reshape(-1)
+    moved = root != np.arange(len(u))
+    return u[moved], u[root[moved]]
+
+
 def combine_duplicates(per_shard):
     """The shards' rows of duplicates (or duplicate_entries) -> the library's: per_shard is a list
     of column tuples, one per rank IN RANK ORDER.  sd_dedup_partition's destination is monotone in

@@ -212,7 +212,8 @@ class ObjectIndex:
     (``object_links``, ``orphans``; ``apply(..., orphans=True)``) answers the orphan remover's
     query too: which of these Objects own nothing any more (orphan_remover.rs:57-95).  Its view
     by key (``key_links``, ``duplicates``, ``duplicate_entries``, ``duplicate_stats``) lists the
-    cas_ids that several file_paths have or that are split over several Objects."""
+    cas_ids that several file_paths have or that are split over several Objects, and
+    ``merge_objects`` acts on it: "Object B is Object A" in one call (both modes)."""
 
     def __init__(self, ctx: Context, nparts: int = 1, part: int = 0, owners: bool = False):
         self.ctx, self.nparts, self.part, self.owners_mode = ctx, nparts, part, bool(owners)
@@ -471,6 +472,24 @@ class ObjectIndex:
         check(lib().sd_object_index_duplicate_stats(self.ctx.handle, self.handle, _ptr(out), _stream(stream)))
         return out
 
+    # -------------------------------------------------------------- merge Objects
+    def merge_objects(self, d_from: torch.Tensor, d_to: torch.Tensor, stream=None):
+        """sd_object_index_merge_objects: Object d_from[j] IS Object d_to[j] (mod.rs:229-333 gave
+        same-step duplicates an Object each).  Every id is relabelled once and simultaneously
+        (chains are the caller's to resolve: dedup.merge_map returns a chain-free map); in the
+        owners mode the entries of one key that now share an id coalesce and their links add up,
+        in one rewrite of the index.  -> (moved, coalesced): the entries whose id changed and the
+        drop in the count.  One `from` with two `to` raises SdCasError and changes nothing.
+        ``orphans(d_from)`` afterwards lists the Objects that no longer own anything."""
+        m = int(d_from.numel())
+        for t in (d_from, d_to):
+            assert t.numel() == m and t.dtype == torch.int64 and (m == 0 or (t.is_cuda and t.is_contiguous()))
+        moved, coalesced = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(lib().sd_object_index_merge_objects(self.ctx.handle, self.handle, _ptr(d_from) if m else None,
+                                                  _ptr(d_to) if m else None, m, ctypes.byref(moved),
+                                                  ctypes.byref(coalesced), _stream(stream)))
+        return int(moved.value), int(coalesced.value)
+
     def apply_hex(self, rm_cas_ids, rm_object_ids, in_cas_ids, in_object_ids):
         """apply from the DB's strings -> (entries removed, entries taken)."""
         bufs, ids = [], []
@@ -702,6 +721,16 @@ class HostObjectIndex:
         if orphans:
             return pairs, int(taken.value), self._orphans_of(pairs)
         return pairs, int(taken.value)
+
+    def merge_objects(self, from_ids, to_ids):
+        """sd_cpu_object_index_merge_objects -> (moved, coalesced), as ObjectIndex.merge_objects."""
+        f, t = (np.ascontiguousarray(a, dtype=np.uint64) for a in (from_ids, to_ids))
+        assert f.size == t.size
+        moved, coalesced = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(lib().sd_cpu_object_index_merge_objects(self.handle, _ptr(f) if f.size else None,
+                                                      _ptr(t) if f.size else None, f.size, ctypes.byref(moved),
+                                                      ctypes.byref(coalesced)))
+        return int(moved.value), int(coalesced.value)
 
     def lookup(self, keys):
         k = np.ascontiguousarray(keys, dtype=np.uint64)
