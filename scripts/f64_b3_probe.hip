@@ -36,7 +36,7 @@ struct F {
                                              uint64_t y) {
         if (V == 2) a = fadd(fadd(a, x), b);
         else a = fadd(setlo(a, lo(a) + lo(x)), b);
-        d = setlo(d, sdb3::xor_rotr16(lo(d), lo(a)));
+        d = setlo(d, sdb3::xor_rotr16<sdb3::rotr16_sdwa(false)>(lo(d), lo(a)));  // as compress<false> below
         c = fadd(c, d);
         b = setlo(b, sdb3::rotr(lo(b) ^ lo(c), 12));
         if (V == 2) a = fadd(fadd(a, y), b);

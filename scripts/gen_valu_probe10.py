@@ -22,6 +22,9 @@ over the whole reading, lane-ops/clk/CU from the workgroups' s_memtime spans (as
 prints it: a workgroup's span is shorter than its launch, so compare it between arms only), the shader clock from s_memtime/s_memrealtime inside
 the kernel and from the card's hwmon freq1_input sampled every 20 ms on a host thread while
 the arm runs (as power_probe.py reads it).
+emit() writes the kernels and the host harness for any list of arms; gen_valu_probe11.py uses it
+with its own arms.  With probe11 the harness also samples the board power beside the clock and
+prints blocks/s (profiles/g_prio/probe.txt is from before and has neither column).
 python scripts/gen_valu_probe10.py  (writes the .hip; build line in its header)"""
 import os
 
@@ -96,19 +99,25 @@ def asm_str(lines):
     return "".join(f'"{ln}\\n"' for ln in lines)
 
 
-def main():
+def emit(arms, stem, title, profile, wps=(5, 8)):
+    """writes scripts/<stem>.hip: one kernel per arm and the host harness.  An arm is (name,
+    block, s_setprio before the loop[, asm input operands that the block names %0, %1, ...]);
+    every arm's block has the same number of VALU instructions."""
+    arms = [tuple(a) + ("",) * (4 - len(a)) for a in arms]
     body, pre = [], []
-    for k, (name, lines, p0) in enumerate(ARMS):
-        body.append(f"    if (ARM == {k}) asm volatile({asm_str(lines)} ::: CLOB);")
+    for k, (name, lines, p0, ins) in enumerate(arms):
+        body.append(f"    if (ARM == {k}) asm volatile({asm_str(lines)} :: {ins}: CLOB);")
         if p0:
             pre.append(f"    if (ARM == {k}) __builtin_amdgcn_s_setprio({p0});")
-    nvalu = len(G)
-    names = ",\n    ".join(f'{{"{n}", "{shape(l, p0)}"}}' for n, l, p0 in ARMS)
+    nvalu = len([ln for ln in arms[0][1] if not ln.startswith("s_setprio")])
+    assert all(len([ln for ln in l if not ln.startswith("s_setprio")]) == nvalu for _, l, _, _ in arms)
+    names = ",\n    ".join(f'{{"{n}", "{shape(l, p0)}"}}' for n, l, p0, _ in arms)
+    wps_list = ", ".join(str(w) for w in wps)
     clob = ", ".join(f'"v{i}"' for i in range(8, 36))
     inits = "".join(f"v_mov_b32 v{i}, {i * 2654435761 % 65521}\\n" for i in range(8, 36))
-    src = f'''// GENERATED by scripts/gen_valu_probe10.py -- s_setprio windows over BLAKE3 G's class runs on gfx950
-// Build: hipcc --offload-arch=gfx950 -O3 -w -pthread -o scripts/valu_probe10 scripts/valu_probe10.hip
-// Run:   scripts/valu_probe10 [seconds per reading, default 1.5] > profiles/g_prio/probe.txt
+    src = f'''// GENERATED by scripts/gen_{stem}.py -- {title}
+// Build: hipcc --offload-arch=gfx950 -O3 -w -pthread -o scripts/{stem} scripts/{stem}.hip
+// Run:   scripts/{stem} [seconds per reading, default 1.5] > {profile}
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -135,7 +144,7 @@ struct Arm {{
 }};
 static const Arm kArms[] = {{
     {names}}};
-constexpr int NARMS = {len(ARMS)};
+constexpr int NARMS = {len(arms)};
 
 template <int ARM>
 __global__ __launch_bounds__(256) void k_arm(uint64_t* cyc, uint32_t iters) {{
@@ -211,13 +220,29 @@ static std::string freq_path() {{
     return found;
 }}
 
-static void sample_freq(const std::string& path, const std::atomic<bool>* stop, std::vector<double>* mhz) {{
+// power1_average (or power1_input) beside freq1_input, "" when there is none
+static std::string power_path(const std::string& fpath) {{
+    if (fpath.empty()) return "";
+    const std::string dir = fpath.substr(0, fpath.rfind('/') + 1);
+    for (const char* n : {{"power1_average", "power1_input"}})
+        if (access((dir + n).c_str(), R_OK) == 0) return dir + n;
+    return "";
+}}
+
+static bool read_ll(const std::string& path, long long* v) {{
+    FILE* f = path.empty() ? nullptr : fopen(path.c_str(), "r");
+    if (!f) return false;
+    const bool ok = fscanf(f, "%lld", v) == 1;
+    fclose(f);
+    return ok;
+}}
+
+static void sample_freq(const std::string& path, const std::string& ppath, const std::atomic<bool>* stop,
+                        std::vector<double>* mhz, std::vector<double>* watts) {{
     while (!stop->load()) {{
-        if (FILE* f = fopen(path.c_str(), "r")) {{
-            long long hz = 0;
-            if (fscanf(f, "%lld", &hz) == 1) mhz->push_back((double)hz / 1e6);
-            fclose(f);
-        }}
+        long long v = 0;
+        if (read_ll(path, &v)) mhz->push_back((double)v / 1e6);
+        if (read_ll(ppath, &v)) watts->push_back((double)v / 1e6);  // microwatts
         std::this_thread::sleep_for(std::chrono::milliseconds(20));
     }}
 }}
@@ -229,29 +254,31 @@ int main(int argc, char** argv) {{
     void (*fns[NARMS])(uint64_t*, uint32_t);
     Table<0>::fill(fns);
     const int cus = p.multiProcessorCount;
-    const std::string fpath = freq_path();
+    const std::string fpath = freq_path(), ppath = power_path(fpath);
     printf("# %s, %d CUs; each reading loops one arm for %.1f s; T = VALU lane-ops/s by wall clock (HIP events over "
            "the whole reading); lane/clk/CU and cyc/ins from the median workgroup s_memtime span of the last launch; "
-           "MHz krn = s_memtime/s_memrealtime in the kernel, MHz hw = median hwmon freq1_input over the reading (%s)\\n",
-           p.gcnArchName, cus, secs, fpath.empty() ? "not found" : "sampled every 20 ms");
+           "MHz krn = s_memtime/s_memrealtime in the kernel, MHz hw and W = median hwmon freq1_input and board power over the reading (%s, %s); G blk/s = T / %d, the "
+           "blocks of %d VALU ops per lane, in 1e9/s\\n",
+           p.gcnArchName, cus, secs, fpath.empty() ? "clock not found" : "sampled every 20 ms",
+           ppath.empty() ? "power not found" : "power likewise", NVALU, NVALU);
     for (int k = 0; k < NARMS; k++) {{
         hipFuncAttributes fa;
         HIP_OK(hipFuncGetAttributes(&fa, (const void*)fns[k]));
         printf("# arm %d (%d VGPRs): %s\\n", k, fa.numRegs, kArms[k].shape);
     }}
-    printf("# %-4s %-3s %-3s %-42s %9s %8s %12s %8s %8s %7s\\n", "pass", "wps", "arm", "name", "T lane/s", "vs arm0",
-           "lane/clk/CU", "cyc/ins", "MHz krn", "MHz hw");
+    printf("# %-4s %-3s %-3s %-42s %9s %8s %12s %8s %8s %7s %6s %9s\\n", "pass", "wps", "arm", "name", "T lane/s",
+           "vs arm0", "lane/clk/CU", "cyc/ins", "MHz krn", "MHz hw", "W", "G blk/s");
     const uint32_t iters = (uint32_t)(4096 * 8 / NVALU);
     const double per_wave = (double)iters * REP * NVALU;
     for (int pass = 0; pass < 2; pass++)
-        for (int wps : {{5, 8}}) {{
+        for (int wps : {{{wps_list}}}) {{
             // 256-lane workgroups, one wave per SIMD each; the LDS each asks for (and never touches) lets
             // exactly wps of them share a CU's 160 KiB, so the whole grid is resident at wps waves/SIMD
             const int grid = cus * wps;
             const size_t lds = (size_t)160 * 1024 / wps / 1024 * 1024;
             uint64_t* cyc;
             HIP_OK(hipMalloc(&cyc, (size_t)grid * 16));
-            double T[NARMS], lpc[NARMS], cpi[NARMS], mk[NARMS], mh[NARMS];
+            double T[NARMS], lpc[NARMS], cpi[NARMS], mk[NARMS], mh[NARMS], pw[NARMS];
             for (int j = 0; j < NARMS; j++) {{
                 const int k = (j + 2 * pass) % NARMS;  // second pass: rotated order
                 hipEvent_t e0, e1;
@@ -259,10 +286,10 @@ int main(int argc, char** argv) {{
                 HIP_OK(hipEventCreate(&e1));
                 for (int w = 0; w < 20; w++) hipLaunchKernelGGL(fns[k], dim3(grid), dim3(256), lds, 0, cyc, iters);
                 HIP_OK(hipDeviceSynchronize());
-                std::vector<double> hz;
+                std::vector<double> hz, watts;
                 std::atomic<bool> stop(false);
                 std::thread th;
-                if (!fpath.empty()) th = std::thread(sample_freq, fpath, &stop, &hz);
+                if (!fpath.empty()) th = std::thread(sample_freq, fpath, ppath, &stop, &hz, &watts);
                 long launches = 0;
                 const auto c0 = std::chrono::steady_clock::now();
                 HIP_OK(hipEventRecord(e0));
@@ -287,24 +314,31 @@ int main(int argc, char** argv) {{
                 std::sort(c.begin(), c.end());
                 std::sort(mhz.begin(), mhz.end());
                 std::sort(hz.begin(), hz.end());
+                std::sort(watts.begin(), watts.end());
                 T[k] = (double)launches * grid * 256.0 * per_wave / (ms * 1e-3) / 1e12;
                 lpc[k] = per_wave * 64.0 * 4 * wps / c[grid / 2];
                 cpi[k] = c[grid / 2] / (wps * per_wave);
                 mk[k] = mhz[grid / 2];
                 mh[k] = hz.empty() ? 0.0 : hz[hz.size() / 2];
+                pw[k] = watts.empty() ? 0.0 : watts[watts.size() / 2];
                 HIP_OK(hipEventDestroy(e0));
                 HIP_OK(hipEventDestroy(e1));
             }}
             for (int k = 0; k < NARMS; k++)
-                printf("  %-4d %-3d %-3d %-42s %9.2f %+7.2f%% %12.1f %8.2f %8.0f %7.0f\\n", pass, wps, k, kArms[k].name,
-                       T[k], 100.0 * (T[k] / T[0] - 1.0), lpc[k], cpi[k], mk[k], mh[k]);
+                printf("  %-4d %-3d %-3d %-42s %9.2f %+7.2f%% %12.1f %8.2f %8.0f %7.0f %6.0f %9.1f\\n", pass, wps, k,
+                       kArms[k].name, T[k], 100.0 * (T[k] / T[0] - 1.0), lpc[k], cpi[k], mk[k], mh[k], pw[k],
+                       T[k] * 1e3 / NVALU);
             fflush(stdout);
             HIP_OK(hipFree(cyc));
         }}
     return 0;
 }}
 '''
-    open(os.path.join(HERE, "valu_probe10.hip"), "w").write(src)
+    open(os.path.join(HERE, stem + ".hip"), "w").write(src)
+
+
+def main():
+    emit(ARMS, "valu_probe10", "s_setprio windows over BLAKE3 G's class runs on gfx950", "profiles/g_prio/probe.txt")
 
 
 if __name__ == "__main__":

@@ -37,26 +37,39 @@ __device__ __forceinline__ uint32_t rotr(uint32_t x, uint32_t n) {
 constexpr int PERM[16] = {2, 6, 3, 10, 7, 0, 4, 13, 1, 11, 12, 5, 9, 14, 15, 8};
 constexpr int sigma(int r, int i) { return r == 0 ? i : sigma(r - 1, PERM[i]); }
 
-// rotr(d ^ a, 16) as two VOP2-SDWA xors that write the two 16-bit halves crosswise:
-// both are 2-source ops, where xor + v_alignbit pays one 3-source op (half issue rate on
-// gfx950).  scripts/valu_probe7.hip at 8 waves/SIMD: 39.51 vs 38.49 T lane-ops/s for the G
-// mix (profiles/r3/r3c_valu_probe7.txt; first seen with archive/scripts/valu_probe4.hip,
-// profiles/r2/r2z4_valu_probe4.txt).  Not volatile: the compiler
-// still schedules it; the early-clobber output keeps d and a readable by the second xor.
-#ifndef SD_ROTR16_SDWA
-#define SD_ROTR16_SDWA 1
-#endif
-__device__ __forceinline__ uint32_t xor_rotr16(uint32_t d, uint32_t a) {
-#if SD_ROTR16_SDWA
-    uint32_t t;
-    asm("v_xor_b32_sdwa %0, %1, %2 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1\n\t"
-        "v_xor_b32_sdwa %0, %1, %2 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 src1_sel:WORD_0"
-        : "=&v"(t)
-        : "v"(d), "v"(a));
-    return t;
+// rotr(d ^ a, 16) has two forms, and which is faster depends on how G issues:
+//   SDWA    two VOP2-SDWA xors that write the two 16-bit halves crosswise: 2 half-rate ops (H)
+//   plain   v_xor_b32 + v_alignbit_b32: 1 full-rate op (F) + 1 H
+// Unsteered, every op pays its slot and a half-round (4 G) costs about the weighted sum, so the
+// SDWA pair wins: 39.51 vs 38.49 T lane-ops/s for the G mix (scripts/valu_probe7.hip, 8
+// waves/SIMD, profiles/r3/r3c_valu_probe7.txt).  Under the priority windows below the F ops issue
+// into what the other waves' H ops leave free, and a half-round costs about max(4 H, 2 (H + F))
+// cycles per wave: only H counts until the issue port binds.  SDWA makes H = 28, F = 20 (bound
+// 112), plain H = 24, F = 24 with the same 48 ops (bound 96).  Registers only
+// (scripts/valu_probe11.hip, profiles/g_rotr16/probe.txt): plain 61.8 / 66.1 / 68.6 T against
+// SDWA 56.8 / 58.7 / 60.5 T at 5 / 6 / 8 waves/SIMD with the windows, 38.5-39.0 T without them.
+// So the form follows the instantiation: plain with the windows, SDWA without
+// (rotr16_sdwa(W), the default of compress's second parameter).  k_cas_sampled_wave names SDWA
+// for both (cas_kernels.hip).  -DSD_ROTR16_SDWA=0 or 1 forces one form everywhere (A/B builds).
+// The SDWA asm is not volatile: the compiler still schedules it; the early-clobber output keeps
+// d and a readable by the second xor.
+#ifdef SD_ROTR16_SDWA
+constexpr bool rotr16_sdwa(bool) { return SD_ROTR16_SDWA != 0; }
 #else
-    return rotr(d ^ a, 16);
+constexpr bool rotr16_sdwa(bool windows) { return !windows; }
 #endif
+template <bool SDWA>
+__device__ __forceinline__ uint32_t xor_rotr16(uint32_t d, uint32_t a) {
+    if constexpr (SDWA) {
+        uint32_t t;
+        asm("v_xor_b32_sdwa %0, %1, %2 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1\n\t"
+            "v_xor_b32_sdwa %0, %1, %2 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 src1_sel:WORD_0"
+            : "=&v"(t)
+            : "v"(d), "v"(a));
+        return t;
+    } else {
+        return rotr(d ^ a, 16);
+    }
 }
 
 // a + b + m: one v_add3_u32 (3 sources, half issue rate).  Two 2-source adds issue faster
@@ -68,12 +81,12 @@ __device__ __forceinline__ uint32_t add3(uint32_t a, uint32_t b, uint32_t m) { r
 __device__ __forceinline__ uint32_t xor_rotr8(uint32_t d, uint32_t a) { return rotr(d ^ a, 8); }
 
 #define SD_G(a, b, c, d, x, y)              \
-    a = add3(a, b, (x)); d = xor_rotr16(d, a); \
+    a = add3(a, b, (x)); d = xor_rotr16<SDWA16>(d, a); \
     c = c + d;           b = rotr(b ^ c, 12); \
     a = add3(a, b, (y)); d = xor_rotr8(d, a); \
     c = c + d;           b = rotr(b ^ c, 7);
 
-template <int R>
+template <int R, bool SDWA16>
 __device__ __forceinline__ void round_r(uint32_t& s0, uint32_t& s1, uint32_t& s2, uint32_t& s3,
                                         uint32_t& s4, uint32_t& s5, uint32_t& s6, uint32_t& s7,
                                         uint32_t& s8, uint32_t& s9, uint32_t& s10, uint32_t& s11,
@@ -90,18 +103,22 @@ __device__ __forceinline__ void round_r(uint32_t& s0, uint32_t& s1, uint32_t& s2
 }
 
 // Priority windows over G's class runs.  The compiled G issues as runs of one class: the
-// half-rate set (v_add3, the SDWA xors, v_alignbit) and the full-rate set (v_add_u32,
+// half-rate set H (v_add3, v_alignbit, the SDWA xors) and the full-rate set F (v_add_u32,
 // v_xor_b32).  A SIMD's arbiter picks by priority, then age; with every wave at priority 0
-// the oldest wave's full-rate ops take whole issue slots from the other waves' half-rate ops.
-// With windows (W) the half-rate runs issue at s_setprio SD_G_PRIO and the full-rate runs at
-// s_setprio 0, so a wave inside a full-rate run only fills what the half-rate ops of the
-// others leave free.  Registers only (scripts/valu_probe10.hip, profiles/g_prio/probe.txt, 5
-// waves/SIMD): 56.8-57.0 T lane-ops/s against 39.2-39.4 T unsteered; the other way round,
-// priority 1 or 3 over the full-rate runs, 38.5-38.7 T, which is why that is not built.  On the
-// bench step, same box, three runs each: 139.1-139.9 against 110.1-110.6 M files/s
-// (profiles/g_prio/ab.txt).  The four G of a half-round are written in lockstep, since a
+// the oldest wave's F ops take whole issue slots from the other waves' H ops.  With windows (W)
+// the H runs issue at s_setprio SD_G_PRIO and the F runs at s_setprio 0, so a wave inside an F
+// run only fills what the H ops of the others leave free, and a half-round costs about
+// max(4 H, 2 (H + F)) cycles per wave instead of a weighted sum.  Registers only
+// (scripts/valu_probe10.hip, profiles/g_prio/probe.txt, 5 waves/SIMD, SDWA rotr16): 56.8-57.0 T
+// lane-ops/s against 39.2-39.4 T unsteered; the other way round, priority 1 or 3 over the F
+// runs, 38.5-38.7 T, which is why that is not built.  On the bench step, same box, three runs
+// each: 139.1-139.9 against 110.1-110.6 M files/s (profiles/g_prio/ab.txt); with rotr16 in its
+// plain form on top, H8 F4 H4 F8 H8 F4 H4 F8 per half-round, 142.1-142.3 against 136.5-136.7
+// (profiles/g_rotr16/ab.txt).  The four G of a half-round are written in lockstep, since a
 // window has to hold one class run of all four columns, and sched_barrier pins each s_setprio
-// between the runs.  A wave leaves compress at priority 0.
+// between the runs.  The plain rotr16's xor run is a window of its own at priority 0: left at
+// priority 1 between the add3 and the alignbit runs it keeps 1-2 % of the 9-13 % (probe11 arm 2).
+// A wave leaves compress at priority 0.
 // The windows pay only where waves share a SIMD: a wave alone on its SIMD just issues the
 // s_setprio on top (one wave per SIMD or fewer: 7-11 % slower, more than one: 10-30 % faster;
 // profiles/g_prio/small_batch.md).  So compress and everything that inlines it take
@@ -119,13 +136,23 @@ __device__ __forceinline__ void g_prio() {
 }
 
 // four independent G (one half-round) step by step with the windows; enters and leaves inside a
-// half-rate run
+// half-rate run.  SDWA16: the form of rotr16 (above)
+template <bool SDWA16>
 __device__ __forceinline__ void g4(uint32_t (&a)[4], uint32_t (&b)[4], uint32_t (&c)[4], uint32_t (&d)[4],
                                    const uint32_t (&x)[4], const uint32_t (&y)[4]) {
 #pragma unroll
     for (int k = 0; k < 4; k++) a[k] = add3(a[k], b[k], x[k]);
+    if constexpr (SDWA16) {
 #pragma unroll
-    for (int k = 0; k < 4; k++) d[k] = xor_rotr16(d[k], a[k]);
+        for (int k = 0; k < 4; k++) d[k] = xor_rotr16<true>(d[k], a[k]);
+    } else {
+        g_prio<0>();  // the xor run: a full-rate window of its own
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] = d[k] ^ a[k];
+        g_prio<SD_G_PRIO>();
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] = rotr(d[k], 16);
+    }
     g_prio<0>();
 #pragma unroll
     for (int k = 0; k < 4; k++) c[k] = c[k] + d[k];
@@ -153,19 +180,19 @@ __device__ __forceinline__ void g4(uint32_t (&a)[4], uint32_t (&b)[4], uint32_t 
 }
 
 // one round on s[4 * row + column]: the columns, then the diagonals as the rows rotated
-template <int R>
+template <int R, bool SDWA16>
 __device__ __forceinline__ void round_w(uint32_t (&a)[4], uint32_t (&b)[4], uint32_t (&c)[4], uint32_t (&d)[4],
                                         const uint32_t (&m)[16]) {
     {
         const uint32_t x[4] = {m[sigma(R, 0)], m[sigma(R, 2)], m[sigma(R, 4)], m[sigma(R, 6)]};
         const uint32_t y[4] = {m[sigma(R, 1)], m[sigma(R, 3)], m[sigma(R, 5)], m[sigma(R, 7)]};
-        g4(a, b, c, d, x, y);
+        g4<SDWA16>(a, b, c, d, x, y);
     }
     {
         const uint32_t x[4] = {m[sigma(R, 8)], m[sigma(R, 10)], m[sigma(R, 12)], m[sigma(R, 14)]};
         const uint32_t y[4] = {m[sigma(R, 9)], m[sigma(R, 11)], m[sigma(R, 13)], m[sigma(R, 15)]};
         uint32_t b1[4] = {b[1], b[2], b[3], b[0]}, c2[4] = {c[2], c[3], c[0], c[1]}, d3[4] = {d[3], d[0], d[1], d[2]};
-        g4(a, b1, c2, d3, x, y);
+        g4<SDWA16>(a, b1, c2, d3, x, y);
         b[1] = b1[0]; b[2] = b1[1]; b[3] = b1[2]; b[0] = b1[3];
         c[2] = c2[0]; c[3] = c2[1]; c[0] = c2[2]; c[1] = c2[3];
         d[3] = d3[0]; d[0] = d3[1]; d[1] = d3[2]; d[2] = d3[3];
@@ -173,7 +200,7 @@ __device__ __forceinline__ void round_w(uint32_t (&a)[4], uint32_t (&b)[4], uint
 }
 
 // cv <- first 8 words of compress(cv, m, counter, block_len, flags); W: with priority windows
-template <bool W>
+template <bool W, bool SDWA16 = rotr16_sdwa(W)>
 __device__ __forceinline__ void compress(uint32_t (&cv)[8], const uint32_t (&m)[16],
                                          uint32_t ctr_lo, uint32_t ctr_hi, uint32_t block_len,
                                          uint32_t flags) {
@@ -184,14 +211,15 @@ __device__ __forceinline__ void compress(uint32_t (&cv)[8], const uint32_t (&m)[
     if constexpr (W) {
         uint32_t a[4] = {s0, s1, s2, s3}, b[4] = {s4, s5, s6, s7}, c[4] = {s8, s9, s10, s11}, d[4] = {s12, s13, s14, s15};
         g_prio<SD_G_PRIO>();
-        round_w<0>(a, b, c, d, m); round_w<1>(a, b, c, d, m); round_w<2>(a, b, c, d, m); round_w<3>(a, b, c, d, m);
-        round_w<4>(a, b, c, d, m); round_w<5>(a, b, c, d, m); round_w<6>(a, b, c, d, m);
+        round_w<0, SDWA16>(a, b, c, d, m); round_w<1, SDWA16>(a, b, c, d, m); round_w<2, SDWA16>(a, b, c, d, m);
+        round_w<3, SDWA16>(a, b, c, d, m); round_w<4, SDWA16>(a, b, c, d, m); round_w<5, SDWA16>(a, b, c, d, m);
+        round_w<6, SDWA16>(a, b, c, d, m);
         g_prio<0>();  // the feed-forward xors are a full-rate run
 #pragma unroll
         for (int k = 0; k < 4; k++) { cv[k] = a[k] ^ c[k]; cv[4 + k] = b[k] ^ d[k]; }
         return;
     }
-#define SD_ROUND(R) round_r<R>(s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15, m)
+#define SD_ROUND(R) round_r<R, SDWA16>(s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15, m)
     SD_ROUND(0); SD_ROUND(1); SD_ROUND(2); SD_ROUND(3); SD_ROUND(4); SD_ROUND(5); SD_ROUND(6);
 #undef SD_ROUND
     cv[0] = s0 ^ s8;  cv[1] = s1 ^ s9;  cv[2] = s2 ^ s10; cv[3] = s3 ^ s11;
@@ -204,14 +232,14 @@ __device__ __forceinline__ void set_iv(uint32_t (&cv)[8]) {
 }
 
 // parent node: out <- compress(IV, left || right, 0, 64, PARENT | extra)
-template <bool W>
+template <bool W, bool SDWA16 = rotr16_sdwa(W)>
 __device__ __forceinline__ void parent(uint32_t (&out)[8], const uint32_t (&l)[8],
                                        const uint32_t (&r)[8], uint32_t extra_flags) {
     uint32_t m[16];
 #pragma unroll
     for (int i = 0; i < 8; i++) { m[i] = l[i]; m[8 + i] = r[i]; }
     set_iv(out);
-    compress<W>(out, m, 0u, 0u, BLOCK_LEN, PARENT | extra_flags);
+    compress<W, SDWA16>(out, m, 0u, 0u, BLOCK_LEN, PARENT | extra_flags);
 }
 
 // 64 message bytes -> 16 little-endian words (4x 16-byte loads; ptr 16-B aligned)
@@ -247,7 +275,7 @@ __device__ __forceinline__ void load_block_partial(uint32_t (&m)[16], const uint
 
 // Chaining value of one chunk of `len` bytes (1..1024; 0 only for an empty message),
 // chunk index `counter`.  If is_root, the last block carries ROOT and cv is the hash.
-template <bool W>
+template <bool W, bool SDWA16 = rotr16_sdwa(W)>
 __device__ __forceinline__ void chunk_cv(uint32_t (&cv)[8], const uint8_t* __restrict__ p,
                                          uint32_t len, uint64_t counter, bool is_root) {
     set_iv(cv);
@@ -256,13 +284,13 @@ __device__ __forceinline__ void chunk_cv(uint32_t (&cv)[8], const uint8_t* __res
     uint32_t m[16];
     for (uint32_t b = 0; b + 1 < nblocks; b++) {
         load_block(m, p + 64u * b);
-        compress<W>(cv, m, clo, chi, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
+        compress<W, SDWA16>(cv, m, clo, chi, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
     }
     const uint32_t last = nblocks - 1;
     const uint32_t tail = len - 64u * last;
     if (tail == 64u) load_block(m, p + 64u * last);
     else load_block_partial(m, p + 64u * last, tail);
-    compress<W>(cv, m, clo, chi, tail, (last == 0 ? CHUNK_START : 0u) | CHUNK_END | (is_root ? ROOT : 0u));
+    compress<W, SDWA16>(cv, m, clo, chi, tail, (last == 0 ? CHUNK_START : 0u) | CHUNK_END | (is_root ? ROOT : 0u));
 }
 
 // Full 1 KiB non-root chunk with line-pair loads (see full_chunks_cv)

@@ -40,7 +40,7 @@ __device__ __forceinline__ void load_cv(uint32_t (&cv)[8], const uint32_t* src) 
 
 // Level-wise merge of n (1..blockDim) CVs held in lds[0..n) -> lds[0].  ROOT goes on the
 // final parent when `root`.  Every thread of the workgroup must call it.
-template <bool W>
+template <bool W, bool SDWA16 = rotr16_sdwa(W)>
 __device__ void lds_reduce(uint32_t (*lds)[8], uint32_t n, bool root) {
     const uint32_t t = threadIdx.x;
     while (n > 1) {
@@ -52,7 +52,7 @@ __device__ void lds_reduce(uint32_t (*lds)[8], uint32_t n, bool root) {
             uint32_t l[8], r[8];
             load_cv(l, lds[2 * t]);
             load_cv(r, lds[2 * t + 1]);
-            parent<W>(res, l, r, (root && n == 2) ? ROOT : 0u);
+            parent<W, SDWA16>(res, l, r, (root && n == 2) ? ROOT : 0u);
             have = true;
         } else if (carry && t == P) {
             load_cv(res, lds[n - 1]);
@@ -120,8 +120,15 @@ constexpr int ilog2(int x) { return x <= 1 ? 0 : 1 + ilog2(x / 2); }
 
 // CV of U (a power of two) consecutive full non-root chunks c0.. : U = 2 is full_chunks_cv's
 // unrolled pair; larger groups merge each chunk into the stack as it completes.
+// c0 is a chunk index of a sampled message (< 57) and 32 bits wide: as a uint64_t it and c0 + u
+// each held a second register through the loops, and with the windows the lanes kernel took 81
+// VGPRs, one over the 80 at which a sixth wave shares the SIMD.  Now 79 and 6 waves/SIMD, no
+// scratch, no instruction added (profiles/g_rotr16/resource_usage.md; registers only, 5 -> 6
+// waves is 61.8 -> 66.1 T lane-ops/s, profiles/g_rotr16/probe.txt).
 template <int U, bool W>
-__device__ __forceinline__ void group_cv(uint32_t (&out)[8], const uint8_t* __restrict__ p, uint64_t c0) {
+__device__ __forceinline__ void group_cv(uint32_t (&out)[8], const uint8_t* __restrict__ p, uint32_t c0) {
+    // sampled messages only: a caller with chunk indices of long messages needs full_chunks_cv's 64-bit counter
+    static_assert((long long)S_FULL + 1 < (1ll << 32), "group_cv counts a sampled message's chunks in 32 bits");
     if constexpr (U <= 2) {
         full_chunks_cv<U, W>(out, p, c0);
     } else {
@@ -129,8 +136,7 @@ __device__ __forceinline__ void group_cv(uint32_t (&out)[8], const uint8_t* __re
         uint32_t ma[16], mb[16];
 #pragma unroll 1
         for (uint32_t u = 0; u < (uint32_t)U; u++) {
-            const uint64_t ctr = c0 + u;
-            const uint32_t clo = (uint32_t)ctr, chi = (uint32_t)(ctr >> 32);
+            const uint32_t clo = c0 + u, chi = 0u;
             const uint8_t* q = p + (size_t)u * CHUNK_LEN;
             set_iv(out);
 #pragma unroll 1
@@ -156,7 +162,7 @@ __global__ __launch_bounds__(256) void k_cas_sampled_lanes(const uint8_t* __rest
     if (g >= (uint64_t)n * K) return;
     const uint32_t f = (uint32_t)(g / K), j = (uint32_t)(g - (uint64_t)f * K);
     uint32_t cv[8];
-    group_cv<U, W>(cv, staged + soff[f] + (size_t)j * U * CHUNK_LEN, (uint64_t)j * U);
+    group_cv<U, W>(cv, staged + soff[f] + (size_t)j * U * CHUNK_LEN, j * U);
     store_cv(rows + ((size_t)j * n + f) * 8, cv);
 }
 
@@ -200,7 +206,7 @@ __global__ __launch_bounds__(256) void k_cas_sampled_merge(const uint8_t* __rest
 // Full 1 KiB non-root chunk, the next line pair in flight while the current one is
 // compressed: latency kernels (one chunk per lane, few waves) that cannot hide the load
 // of each line pair behind other waves.
-template <bool W>
+template <bool W, bool SDWA16 = rotr16_sdwa(W)>
 __device__ __forceinline__ void full_chunk_cv_prefetch(uint32_t (&cv)[8], const uint8_t* __restrict__ q,
                                                        uint32_t counter) {
     set_iv(cv);
@@ -213,8 +219,8 @@ __device__ __forceinline__ void full_chunk_cv_prefetch(uint32_t (&cv)[8], const 
             load_block(na, q + 64u * (b + 2));
             load_block(nb, q + 64u * (b + 3));
         }
-        compress<W>(cv, ma, counter, 0u, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
-        compress<W>(cv, mb, counter, 0u, BLOCK_LEN, b + 1 == 15 ? CHUNK_END : 0u);
+        compress<W, SDWA16>(cv, ma, counter, 0u, BLOCK_LEN, b == 0 ? CHUNK_START : 0u);
+        compress<W, SDWA16>(cv, mb, counter, 0u, BLOCK_LEN, b + 1 == 15 ? CHUNK_END : 0u);
 #pragma unroll
         for (int i = 0; i < 16; i++) {
             ma[i] = na[i];
@@ -223,24 +229,28 @@ __device__ __forceinline__ void full_chunk_cv_prefetch(uint32_t (&cv)[8], const 
     }
 }
 
+// With or without the windows this kernel keeps rotr16 as the SDWA pair: its prefetching chunk loop
+// is unrolled whole, and with xor + alignbit under the windows the compiler lets it grow from 91 to
+// 179 VGPRs (2 waves/SIMD), or spills when held to 5 waves (profiles/g_rotr16/resource_usage.md).
 template <bool W>
 __global__ __launch_bounds__(64) void k_cas_sampled_wave(const uint8_t* __restrict__ staged,
                                                          const uint64_t* __restrict__ soff,
                                                          const uint32_t* __restrict__ idx, uint32_t n,
                                                          uint32_t* __restrict__ out) {
+    constexpr bool S16 = rotr16_sdwa(false);
     __shared__ __attribute__((aligned(16))) uint32_t lds[64][8];
     const uint32_t f = blockIdx.x, t = threadIdx.x;
     const uint8_t* msg = staged + soff[f];
     uint32_t cv[8];
     if (t < (uint32_t)S_FULL) {
-        full_chunk_cv_prefetch<W>(cv, msg + (size_t)t * CHUNK_LEN, t);
+        full_chunk_cv_prefetch<W, S16>(cv, msg + (size_t)t * CHUNK_LEN, t);
         store_cv(lds[t], cv);
     } else if (t == (uint32_t)S_FULL) {
-        chunk_cv<W>(cv, msg + (size_t)S_FULL * CHUNK_LEN, SD_SAMPLED_MSG_LEN - S_FULL * CHUNK_LEN, S_FULL, false);
+        chunk_cv<W, S16>(cv, msg + (size_t)S_FULL * CHUNK_LEN, SD_SAMPLED_MSG_LEN - S_FULL * CHUNK_LEN, S_FULL, false);
         store_cv(lds[t], cv);
     }
     __syncthreads();
-    lds_reduce<W>(lds, S_FULL + 1, true);
+    lds_reduce<W, S16>(lds, S_FULL + 1, true);
     if (t < 8) out[(size_t)idx[f] * 8 + t] = lds[0][t];
 }
 
@@ -308,6 +318,13 @@ __global__ __launch_bounds__(256) void k_whole_items(const uint8_t* __restrict__
     } else {
         uint32_t l[8], r[8];
         chunk_cv<W>(l, p, CHUNK_LEN, c0, false);
+        // Hold l here (the empty asm emits nothing).  With rotr16 in its plain form no op of G is an
+        // asm, and the compiler sank the whole last compression of l out of its windows, past r, to
+        // parent() where l is first read.
+        if constexpr (W) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) asm volatile("" : "+v"(l[k]));
+        }
         chunk_cv<W>(r, p + CHUNK_LEN, glen - CHUNK_LEN, c0 + 1, false);
         parent<W>(cv, l, r, root ? ROOT : 0u);
     }
