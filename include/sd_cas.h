@@ -955,6 +955,74 @@ int sd_cpu_split_leaves(const uint8_t* slice, uint64_t total_len, int nranks, in
                         int nthreads);
 int sd_cpu_split_root(const uint8_t* cvs, uint64_t total_len, uint8_t* out_hash32);
 
+/* ---------------------------------------------------------------- checksum trees */
+/* WHERE a file stopped matching its checksum (validator_job.rs:138-141 "we can also compare old
+ * and new checksums here"; spaceblock's 128 KiB blocks, p2p/src/spaceblock/block_size.rs:20-23):
+ * the file's BLAKE3 tree cut at block granularity, stored beside the checksum.
+ *   block size  B = 2^block_log2 bytes, SD_TREE_BLOCK_LOG2_MIN <= block_log2 <= _MAX (128 KiB ..
+ *               1 MiB); any other value is SD_ERR_INVALID
+ *   blocks      nb = max(1, ceil(len / B)); block j = bytes [jB, min((j+1)B, len))
+ *   node N_j    32 bytes (8 little-endian words): the BLAKE3 chaining value of the subtree over
+ *               block j's chunks, chunk counters from j*B/1024, ROOT not set; inside the block
+ *               pairs merge level by level with the odd node carried up (BLAKE3's own tree); the
+ *               trailing partial block the same over the chunks it has
+ *   nb == 1     N_0 is the file's root hash itself (ROOT set), as slot 0 of sd_split_*; an empty
+ *               file has one node, the hash of the empty message
+ *   level       N_0 .. N_{nb-1}; its root is N_0 if nb == 1, else the level-wise pairwise merge
+ *               of the nodes, the odd node carried up, ROOT on the last parent -- file_checksum's
+ *               32 bytes, bit for bit
+ *   position    a full block's node, unless nb == 1, does not depend on the file's length
+ *   batch       file i's level starts at node node_base[i]; node_base is the exclusive prefix sum
+ *               of nb, node_base[n] the total
+ * The ranges are those of sd_checksum_batch_create (host arrays, 16-byte aligned starts, the
+ * buffer readable to the next 64-byte boundary).  d_nodes / d_expected are 16-byte aligned.
+ * Only the device-resident batch has levels; the streamed and from-files routes do not. */
+#define SD_TREE_BLOCK_LOG2_MIN 17
+#define SD_TREE_BLOCK_LOG2_MAX 20
+typedef struct sd_checksum_tree sd_checksum_tree;
+/* nb of a file of len bytes.  GPU-free. */
+int sd_checksum_tree_nodes(uint64_t len, uint32_t block_log2, uint64_t* n_nodes);
+int sd_checksum_tree_create(sd_cas_ctx* ctx, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                            uint32_t block_log2, sd_checksum_tree** out);
+void sd_checksum_tree_destroy(sd_checksum_tree* tree);
+/* node_base[0 .. n] (host) */
+int sd_checksum_tree_layout(const sd_checksum_tree* tree, uint64_t* node_base);
+/* [0] files, [1] total bytes, [2] BLAKE3 compressions (those of sd_checksum_batch: the nodes cost
+ * none), [3] nodes */
+int sd_checksum_tree_stats(const sd_checksum_tree* tree, uint64_t out[4]);
+/* One pass over the data: every file's level -> d_nodes (node_base[n] * 32 B) and its root ->
+ * d_hash32 (n * 32 B), the bytes sd_checksum_batch_run writes for the same ranges.  Asynchronous
+ * on `stream`; one run of a tree at a time (it owns its scratch). */
+int sd_checksum_tree_run(sd_cas_ctx* ctx, const sd_checksum_tree* tree, const uint8_t* d_data, uint8_t* d_nodes,
+                         uint8_t* d_hash32, void* stream);
+/* Roots from levels alone, no file bytes: does a level I was sent belong to the checksum I trust?
+ * Asynchronous on `stream`. */
+int sd_checksum_tree_roots(sd_cas_ctx* ctx, const sd_checksum_tree* tree, const uint8_t* d_nodes, uint8_t* d_hash32,
+                           void* stream);
+/* Hashes d_data's blocks and compares each node with d_expected (same layout, 32 bytes per node).
+ *   d_bad (node_base[n] bytes, may be NULL): 1 where block's node differs, else 0
+ *   d_rows_out (2 x u64 per row, may be NULL): one row (file, block) per differing block,
+ *     ascending; *count (host, may be NULL) = the rows.  If d_rows_out is given and capacity <
+ *     *count: SD_ERR_CAPACITY with *count = the requirement and no row written; d_bad and stats are
+ *     complete then too.  With d_rows_out NULL the call only counts.
+ *   stats[4] (host, may be NULL): [0] files, [1] blocks compared, [2] blocks that differ, [3] files
+ *     with at least one differing block
+ * Runs on `stream` and syncs it; the level it computes lives in the context's pooled slot
+ * (grow-only, 33 bytes per node and 33 per file: no allocation in a call that fits). */
+int sd_checksum_tree_verify(sd_cas_ctx* ctx, const sd_checksum_tree* tree, const uint8_t* d_data,
+                            const uint8_t* d_expected, uint8_t* d_bad, uint64_t* d_rows_out, uint64_t capacity,
+                            uint64_t* count, uint64_t stats[4], void* stream);
+/* The same over host memory on host cores, without a context or a device, with the device calls'
+ * rules (a start that is not 16-byte aligned is SD_ERR_INVALID here too: one batch description
+ * serves both).  nodes is laid out as node_base says (sd_checksum_tree_nodes per file). */
+int sd_cpu_checksum_tree(const uint8_t* data, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                         uint32_t block_log2, uint8_t* nodes, uint8_t* hash32, int nthreads);
+int sd_cpu_checksum_tree_roots(const uint8_t* nodes, const uint64_t* lens, size_t n, uint32_t block_log2,
+                               uint8_t* hash32);
+int sd_cpu_checksum_tree_verify(const uint8_t* data, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                                uint32_t block_log2, const uint8_t* expected, uint8_t* bad, uint64_t* rows_out,
+                                uint64_t capacity, uint64_t* count, uint64_t stats[4], int nthreads);
+
 /* ---------------------------------------------------------------- synthetic data */
 /* Device generator of SURVEY.md §8(d) (seed 0x5D5DCA51D, splitmix64 counter stream),
  * for benchmarks and parity tests: writes the exact cas message of each synthetic file

@@ -50,6 +50,10 @@ pub struct sd_object_index {
 pub struct sd_cpu_object_index {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct sd_checksum_tree {
+    _p: [u8; 0],
+}
 
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -71,6 +75,9 @@ pub const SD_FILE_SHORT_READ: i32 = 3;
 pub const SD_FILE_CHANGED: i32 = 4;
 pub const SD_COMM_ID_BYTES: usize = 128;
 pub const SD_OBJECT_INDEX_OWNERS: c_int = 1;
+// checksum trees: block_log2 of the level (128 KiB .. 1 MiB)
+pub const SD_TREE_BLOCK_LOG2_MIN: u32 = 17;
+pub const SD_TREE_BLOCK_LOG2_MAX: u32 = 20;
 // sd_dedup_confirm's verdict per file
 pub const SD_CONFIRM_INVALID: u8 = 0;
 pub const SD_CONFIRM_SINGLE: u8 = 1;
@@ -247,6 +254,29 @@ extern "C" {
     pub fn sd_cpu_dedup_confirm(keys: *const u64, hash32: *const u8, valid: *const u8, m: u64, rep: *mut u64,
                                 class_size: *mut u64, verdict: *mut u8, sets_out: *mut u64, capacity: u64,
                                 n_sets: *mut u64, stats: *mut u64) -> c_int;
+    // checksum trees: a file's level (one 32-byte node per 2^block_log2 bytes) beside its checksum,
+    // the roots from levels alone, and a verify that names the (file, block) rows that differ
+    // (validator_job.rs:138-141; spaceblock's 128 KiB blocks, block_size.rs:20-23)
+    pub fn sd_checksum_tree_nodes(len: u64, block_log2: u32, n_nodes: *mut u64) -> c_int;
+    pub fn sd_checksum_tree_create(ctx: *mut sd_cas_ctx, offsets: *const u64, lens: *const u64, n: usize,
+                                   block_log2: u32, out: *mut *mut sd_checksum_tree) -> c_int;
+    pub fn sd_checksum_tree_destroy(tree: *mut sd_checksum_tree);
+    pub fn sd_checksum_tree_layout(tree: *const sd_checksum_tree, node_base: *mut u64) -> c_int;
+    pub fn sd_checksum_tree_stats(tree: *const sd_checksum_tree, out: *mut u64) -> c_int;
+    pub fn sd_checksum_tree_run(ctx: *mut sd_cas_ctx, tree: *const sd_checksum_tree, d_data: *const u8,
+                                d_nodes: *mut u8, d_hash32: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn sd_checksum_tree_roots(ctx: *mut sd_cas_ctx, tree: *const sd_checksum_tree, d_nodes: *const u8,
+                                  d_hash32: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn sd_checksum_tree_verify(ctx: *mut sd_cas_ctx, tree: *const sd_checksum_tree, d_data: *const u8,
+                                   d_expected: *const u8, d_bad: *mut u8, d_rows_out: *mut u64, capacity: u64,
+                                   count: *mut u64, stats: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_cpu_checksum_tree(data: *const u8, offsets: *const u64, lens: *const u64, n: usize, block_log2: u32,
+                                nodes: *mut u8, hash32: *mut u8, nthreads: c_int) -> c_int;
+    pub fn sd_cpu_checksum_tree_roots(nodes: *const u8, lens: *const u64, n: usize, block_log2: u32,
+                                      hash32: *mut u8) -> c_int;
+    pub fn sd_cpu_checksum_tree_verify(data: *const u8, offsets: *const u64, lens: *const u64, n: usize,
+                                       block_log2: u32, expected: *const u8, bad: *mut u8, rows_out: *mut u64,
+                                       capacity: u64, count: *mut u64, stats: *mut u64, nthreads: c_int) -> c_int;
     // device buffers for callers that hold their lists on the host (sd_memcpy syncs `stream`)
     pub fn sd_device_malloc(ctx: *mut sd_cas_ctx, bytes: u64, out: *mut *mut c_void) -> c_int;
     pub fn sd_device_free(ctx: *mut sd_cas_ctx, p: *mut c_void);

@@ -189,7 +189,19 @@ SIGNATURES = [
     ("sd_dedup_confirm", I32, [P, P, P, P, U64, P, P, P, P, U64, PU64, P, P]),
     ("sd_dedup_confirm_stats", I32, [P, P]),
     ("sd_cpu_dedup_confirm", I32, [P, P, P, U64, P, P, P, P, U64, PU64, P]),
+    ("sd_checksum_tree_nodes", I32, [U64, U32, PU64]),
+    ("sd_checksum_tree_create", I32, [P, P, P, SZ, U32, ctypes.POINTER(P)]),
+    ("sd_checksum_tree_destroy", None, [P]),
+    ("sd_checksum_tree_layout", I32, [P, P]),
+    ("sd_checksum_tree_stats", I32, [P, P]),
+    ("sd_checksum_tree_run", I32, [P, P, P, P, P, P]),
+    ("sd_checksum_tree_roots", I32, [P, P, P, P, P]),
+    ("sd_checksum_tree_verify", I32, [P, P, P, P, P, P, U64, PU64, P, P]),
+    ("sd_cpu_checksum_tree", I32, [P, P, P, SZ, U32, P, P, I32]),
+    ("sd_cpu_checksum_tree_roots", I32, [P, P, SZ, U32, P]),
+    ("sd_cpu_checksum_tree_verify", I32, [P, P, P, SZ, U32, P, P, P, U64, PU64, P, I32]),
 ]
+SD_TREE_BLOCK_LOG2_MIN, SD_TREE_BLOCK_LOG2_MAX = 17, 20
 SD_CONFIRM_INVALID, SD_CONFIRM_SINGLE, SD_CONFIRM_CONFIRMED, SD_CONFIRM_REFUTED = 0, 1, 2, 3
 SD_OBJECT_INDEX_OWNERS = 1
 

@@ -127,6 +127,83 @@ def confirm(keys, hash32, valid=None, capacity: Optional[int] = None, want_sets:
     return rep[:m], size[:m], verdict[:m], sets[:int(n_sets.value) if want_sets else 0], stats
 
 
+def tree_nodes(length: int, block_log2: int = 17) -> int:
+    """sd_checksum_tree_nodes: the blocks (= nodes) of a file of `length` bytes."""
+    v = ctypes.c_uint64(0)
+    check(lib().sd_checksum_tree_nodes(int(length), int(block_log2), ctypes.byref(v)))
+    return int(v.value)
+
+
+def tree_node_base(lens, block_log2: int = 17) -> np.ndarray:
+    """node_base uint64 [n + 1] of a batch: the exclusive prefix sum of the files' node counts."""
+    tree_nodes(0, block_log2)  # refuses a block size outside 128 KiB .. 1 MiB
+    ls = np.ascontiguousarray(lens, dtype=np.uint64)
+    nb = np.maximum((ls + np.uint64((1 << block_log2) - 1)) >> np.uint64(block_log2), np.uint64(1))
+    return np.concatenate([np.zeros(1, np.uint64), np.cumsum(nb, dtype=np.uint64)])
+
+
+def checksum_tree(data, offsets, lens, block_log2: int = 17, nthreads: int = THREADS):
+    """sd_cpu_checksum_tree: (nodes uint8 [node_base[n], 32], roots uint8 [n, 32], node_base) of n
+    byte ranges of a host buffer (starts 16-byte aligned): every file's level at 2^block_log2
+    bytes and its file_checksum (hash.rs:10-24)."""
+    from .cas import _host_ranges
+    keep, addr, offs, ls = _host_ranges(data, offsets, lens)
+    n = len(ls)
+    base = tree_node_base(ls, block_log2)
+    nodes, roots = np.zeros((max(int(base[n]), 1), 32), np.uint8), np.zeros((max(n, 1), 32), np.uint8)
+    check(lib().sd_cpu_checksum_tree(addr, offs.ctypes.data, ls.ctypes.data, n, int(block_log2), nodes.ctypes.data,
+                                     roots.ctypes.data, nthreads))
+    return nodes[:int(base[n])], roots[:n], base
+
+
+def checksum_tree_roots(nodes, lens, block_log2: int = 17) -> np.ndarray:
+    """sd_cpu_checksum_tree_roots: roots uint8 [n, 32] from the levels alone."""
+    ls = np.ascontiguousarray(lens, dtype=np.uint64)
+    n = len(ls)
+    nd = np.ascontiguousarray(nodes, dtype=np.uint8).reshape(-1)
+    if nd.size != 32 * int(tree_node_base(ls, block_log2)[n]):
+        raise ValueError("nodes is not node_base[n] x 32 bytes")
+    roots = np.zeros((max(n, 1), 32), np.uint8)
+    check(lib().sd_cpu_checksum_tree_roots(nd.ctypes.data if nd.size else None, ls.ctypes.data, n, int(block_log2),
+                                           roots.ctypes.data))
+    return roots[:n]
+
+
+def checksum_tree_verify(data, offsets, lens, expected, block_log2: int = 17, capacity: Optional[int] = None,
+                         want_rows: bool = True, want_flags: bool = False, nthreads: int = THREADS):
+    """sd_cpu_checksum_tree_verify: the blocks of n byte ranges whose node differs from `expected`
+    (uint8 [node_base[n], 32]).  Returns (rows uint64 [count, 2] of (file, block) ascending, stats
+    uint64 [4]: files, blocks compared, blocks that differ, files with a differing block) and, with
+    want_flags, the 0/1 byte per node as a third value.  `capacity` (default: every block) short of
+    the rows raises SdCasError (SD_ERR_CAPACITY) with ``.needed`` and writes no row;
+    want_rows=False only counts (rows comes back empty)."""
+    from ._native import SdCasError
+    from .cas import _host_ranges
+    keep, addr, offs, ls = _host_ranges(data, offsets, lens)
+    n = len(ls)
+    total = int(tree_node_base(ls, block_log2)[n])
+    exp = np.ascontiguousarray(expected, dtype=np.uint8).reshape(-1)
+    if exp.size != 32 * total:
+        raise ValueError("expected is not node_base[n] x 32 bytes")
+    cap = total if capacity is None else int(capacity)
+    rows = np.zeros((max(cap, 1), 2), np.uint64)
+    bad = np.zeros(max(total, 1), np.uint8)
+    count = ctypes.c_uint64(0)
+    stats = np.zeros(4, np.uint64)
+    rc = lib().sd_cpu_checksum_tree_verify(addr, offs.ctypes.data, ls.ctypes.data, n, int(block_log2),
+                                           exp.ctypes.data if n else None, bad.ctypes.data if want_flags else None,
+                                           rows.ctypes.data if want_rows else None, cap, ctypes.byref(count),
+                                           stats.ctypes.data, nthreads)
+    try:
+        check(rc)
+    except SdCasError as e:
+        e.needed = int(count.value)
+        e.stats = stats
+        raise
+    out = (rows[:int(count.value) if want_rows else 0], stats)
+    return out + (bad[:total],) if want_flags else out
+
+
 def blake3(data: bytes) -> bytes:
     """Full 32-byte BLAKE3 of a host buffer (sd_cpu_checksums of one range)."""
     buf = np.frombuffer(bytes(data) + bytes(64), np.uint8)

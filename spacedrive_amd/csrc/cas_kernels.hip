@@ -13,6 +13,8 @@
 //                   blocks per workgroup, 4 consecutive chunks per lane merged in-lane, each
 //                   block's 256 lane CVs merged in LDS (both trees packed into the lowest
 //                   lanes); then 256-way LDS reductions over the block CVs.
+//   k_ck_leaf_tree  k_ck_leaf's body, also storing the LDS tree's level at 128 KiB .. 1 MiB
+//                   granularity: the checksum trees (checksum_tree.hip).
 //
 // Tree shape: every merge is the level-wise pairwise merge with the odd node carried up
 // unchanged, over power-of-two aligned groups.  It is the BLAKE3 tree (left subtree =
@@ -415,21 +417,31 @@ constexpr uint32_t CK_TREE_LEVELS = ilog2(CK_BLOCK_LANES);
 static_assert((CK_LANE_CHUNKS & (CK_LANE_CHUNKS - 1)) == 0 && CK_LANE_CHUNKS >= 2 && CK_LANE_CHUNKS <= 16, "lane chunks");
 static_assert(CK_WG_THREADS >= 64 && CK_WG_THREADS <= 1024 && CK_WG_THREADS % 64 == 0, "workgroup size");
 
-template <bool W>
-__global__ __launch_bounds__(CK_WG_THREADS) void k_ck_leaf(
+// The leaf's body, shared by k_ck_leaf and k_ck_leaf_tree.
+// T (k_ck_leaf_tree, the checksum tree's level at 2^k-byte granularity, 17 <= k <= 20): the
+// LDS tree after iteration L holds the CVs of aligned 2^(13+L)-byte groups, so after iteration
+// node_level = k - 13 the first ceil(block bytes / 2^k) slots of a leaf block are its nodes; the
+// lanes that just computed them also store them to nodes[node_base[file] + blk 2^(20-k) + j].
+// A file of one node has its root there (ROOT went on in the lane or at the nb == 2 merge below
+// that level and is only carried since); a longer file's nodes are plain CVs.
+template <bool W, bool T>
+__device__ __forceinline__ void ck_leaf_body(
     const uint8_t* __restrict__ data, uint64_t shift, uint32_t blk_base, const ck_file* __restrict__ files,
-    const uint2* __restrict__ wg_map, uint32_t n_blocks, uint32_t* __restrict__ cvbuf, uint32_t* __restrict__ out) {
+    const uint2* __restrict__ wg_map, uint32_t n_blocks, uint32_t* __restrict__ cvbuf, uint32_t* __restrict__ out,
+    const uint64_t* __restrict__ node_base, uint32_t node_level, uint32_t* __restrict__ nodes) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[CK_WG_THREADS][8];
     __shared__ uint32_t s_lanes[CK_WG_BLOCKS], s_root[CK_WG_BLOCKS];
     __shared__ uint64_t s_dst[CK_WG_BLOCKS];  // output row: file (root) or CV slot, | 1 << 63 for out
+    __shared__ uint64_t s_node[CK_WG_BLOCKS];  // T: the block's first node
     const uint32_t t = threadIdx.x, wv = t / CK_BLOCK_LANES, lane = t % CK_BLOCK_LANES;
     const uint32_t bi = blockIdx.x * CK_WG_BLOCKS + wv;  // this lane's block entry
     uint32_t lanes_b = 0, root_b = 0;
-    uint64_t dst_b = 0;
+    uint64_t dst_b = 0, node_b = 0;
     if (bi < n_blocks) {
         const uint2 wm = wg_map[bi];  // (file, block)
         const uint32_t blk = wm.y + blk_base;
         const ck_file fi = files[wm.x];
+        if constexpr (T) node_b = node_base[wm.x] + ((uint64_t)blk << (CK_TREE_LEVELS - 1 - node_level));
         const uint64_t nchunks = fi.len == 0 ? 1 : (fi.len + CHUNK_LEN - 1) / CHUNK_LEN;
         const uint64_t blk0 = (uint64_t)blk * CK_BLOCK_CHUNKS;
         const uint32_t blk_chunks = (uint32_t)(nchunks - blk0 < CK_BLOCK_CHUNKS ? nchunks - blk0 : CK_BLOCK_CHUNKS);
@@ -469,6 +481,7 @@ __global__ __launch_bounds__(CK_WG_THREADS) void k_ck_leaf(
         s_lanes[wv] = lanes_b;
         s_root[wv] = root_b;
         s_dst[wv] = dst_b;
+        if constexpr (T) s_node[wv] = node_b;
     }
     __syncthreads();
     // the blocks' trees, level-wise with the odd node carried up (CK_BLOCK_LANES -> 1); block
@@ -497,6 +510,12 @@ __global__ __launch_bounds__(CK_WG_THREADS) void k_ck_leaf(
         }
         __syncthreads();
         if (have) store_cv(lds[to], res);
+        if constexpr (T) {
+            if (have && L == node_level) {  // to = CK_BLOCK_LANES b + j: node j of leaf block b
+                const uint32_t b = to / CK_BLOCK_LANES;
+                store_cv(nodes + (s_node[b] + (to - CK_BLOCK_LANES * b)) * 8, res);
+            }
+        }
         __syncthreads();
     }
     if (t < 8 * CK_WG_BLOCKS) {
@@ -507,6 +526,23 @@ __global__ __launch_bounds__(CK_WG_THREADS) void k_ck_leaf(
             else cvbuf[d * 8 + w] = lds[CK_BLOCK_LANES * b][w];
         }
     }
+}
+
+template <bool W>
+__global__ __launch_bounds__(CK_WG_THREADS) void k_ck_leaf(
+    const uint8_t* __restrict__ data, uint64_t shift, uint32_t blk_base, const ck_file* __restrict__ files,
+    const uint2* __restrict__ wg_map, uint32_t n_blocks, uint32_t* __restrict__ cvbuf, uint32_t* __restrict__ out) {
+    ck_leaf_body<W, false>(data, shift, blk_base, files, wg_map, n_blocks, cvbuf, out, nullptr, 0, nullptr);
+}
+
+// the same pass that also leaves the level at 2^(13 + node_level)-byte granularity in `nodes`
+// (16-byte aligned, as cvbuf)
+template <bool W>
+__global__ __launch_bounds__(CK_WG_THREADS) void k_ck_leaf_tree(
+    const uint8_t* __restrict__ data, const ck_file* __restrict__ files, const uint2* __restrict__ wg_map,
+    uint32_t n_blocks, uint32_t* __restrict__ cvbuf, uint32_t* __restrict__ out,
+    const uint64_t* __restrict__ node_base, uint32_t node_level, uint32_t* __restrict__ nodes) {
+    ck_leaf_body<W, true>(data, 0, 0, files, wg_map, n_blocks, cvbuf, out, node_base, node_level, nodes);
 }
 
 // Reduce: workgroup = up to 256 consecutive CVs of one message's level; writes one CV to
@@ -609,6 +645,19 @@ hipError_t launch_ck_leaf(const uint8_t* data, uint64_t shift, uint32_t blk_base
     if (n_wg == 0) return hipSuccess;
     SD_LAUNCH_W(k_ck_leaf<true>, k_ck_leaf<false>, (n_wg + CK_WG_BLOCKS - 1) / CK_WG_BLOCKS, CK_WG_THREADS, s, data, shift,
                 blk_base, files, wg_map, n_wg, cvbuf, out);
+    return hipGetLastError();
+}
+
+// block_log2 in [SD_TREE_BLOCK_LOG2_MIN, SD_TREE_BLOCK_LOG2_MAX] (the caller checked)
+hipError_t launch_ck_leaf_tree(const uint8_t* data, const ck_file* files, const uint2* wg_map, uint32_t n_wg,
+                               uint32_t* cvbuf, uint32_t* out, const uint64_t* node_base, uint32_t block_log2,
+                               uint32_t* nodes, hipStream_t s) {
+    static_assert(CK_BLOCK_CHUNKS * CHUNK_LEN == (1u << SD_TREE_BLOCK_LOG2_MAX), "the leaf block is the largest tree block");
+    if (n_wg == 0) return hipSuccess;
+    const uint32_t lane_log2 = SD_TREE_BLOCK_LOG2_MAX - CK_TREE_LEVELS;  // bytes of a lane, log2
+    if (block_log2 <= lane_log2 || block_log2 > SD_TREE_BLOCK_LOG2_MAX) return hipErrorInvalidValue;
+    SD_LAUNCH_W(k_ck_leaf_tree<true>, k_ck_leaf_tree<false>, (n_wg + CK_WG_BLOCKS - 1) / CK_WG_BLOCKS, CK_WG_THREADS, s,
+                data, files, wg_map, n_wg, cvbuf, out, node_base, block_log2 - lane_log2 - 1, nodes);
     return hipGetLastError();
 }
 

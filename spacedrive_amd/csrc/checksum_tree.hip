@@ -1,0 +1,258 @@
+// checksum_tree.hip -- the checksum trees of the C ABI (include/sd_cas.h): every file's BLAKE3
+// tree cut at block granularity beside its root, the roots from levels alone, and a verify that
+// names the blocks that differ.
+//
+// Reference: validator_job.rs:138-141 ("we can also compare old and new checksums here"),
+// p2p/src/spaceblock/block.rs:6,10 (a block to resend needs a checksum) and block_size.rs:20-23
+// (128 KiB blocks); file_checksum is validation/hash.rs:10-24.
+//
+// No BLAKE3 of its own: the level is what k_ck_leaf's LDS tree holds on its way to the 1 MiB CV
+// (k_ck_leaf_tree, cas_kernels.hip), and a level's root is k_ck_reduce run with the level as its
+// level 0 (plan_reduce_passes takes any count per file).  Here: the plan, the copy of one-node
+// files' roots, and the verify's compare / compact on sliced.h's two skeletons.
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <vector>
+
+#include "sd_api_impl.h"
+#include "sliced.h"
+
+using namespace sliced;
+using namespace sdi;
+
+namespace {
+
+// the file of node i: the last f with node_base[f] <= i (node_base ascends strictly, i < node_base[n])
+__device__ __forceinline__ uint64_t tree_file_of(const uint64_t* __restrict__ node_base, uint64_t n, uint64_t i) {
+    uint64_t lo = 0, hi = n;  // node_base[lo] <= i < node_base[hi]
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (node_base[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// a file of one node: the node is its root
+__global__ __launch_bounds__(256) void k_tree_single_roots(const uint64_t* __restrict__ node_base, uint64_t n,
+                                                           const uint32_t* __restrict__ nodes,
+                                                           uint32_t* __restrict__ out) {
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < 8 * n; g += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = g >> 3, b = node_base[i];
+        if (node_base[i + 1] - b == 1) out[g] = nodes[8 * b + (g & 7u)];
+    }
+}
+
+// node i differs from the expected one; its file is marked (the same value from every writer)
+struct tree_differs {
+    const uint4* __restrict__ got;
+    const uint4* __restrict__ want;
+    const uint64_t* __restrict__ node_base;
+    uint64_t n_files;
+    uint8_t* __restrict__ file_bad;
+    __device__ bool operator()(uint64_t i, uint64_t) const {
+        const uint4 a0 = got[2 * i], a1 = got[2 * i + 1], b0 = want[2 * i], b1 = want[2 * i + 1];
+        const bool d = a0.x != b0.x || a0.y != b0.y || a0.z != b0.z || a0.w != b0.w || a1.x != b1.x || a1.y != b1.y ||
+                       a1.z != b1.z || a1.w != b1.w;
+        if (d) file_bad[tree_file_of(node_base, n_files, i)] = 1;
+        return d;
+    }
+};
+
+struct tree_file_marked {
+    const uint8_t* __restrict__ file_bad;
+    __device__ bool operator()(uint64_t i, uint64_t) const { return file_bad[i] != 0; }
+};
+
+// one row (file, block) per flagged node, in order
+struct tree_rows : from_flags {
+    const uint64_t* __restrict__ node_base;
+    uint64_t n_files;
+    uint64_t* __restrict__ rows;
+    __device__ void emit(uint64_t i, bool flag, uint64_t slot, uint64_t) const {
+        if (!flag) return;
+        const uint64_t f = tree_file_of(node_base, n_files, i);
+        rows[2 * slot] = f;
+        rows[2 * slot + 1] = i - node_base[f];
+    }
+};
+
+// the verify's scratch in a pooled slot: the level, the roots the leaf pass writes anyway, the
+// flags when the caller wants none, the files' marks, two rows of per-workgroup counts
+struct verify_scratch {
+    uint8_t *nodes, *roots, *flags, *file_bad;
+    uint64_t* counts;
+    static size_t bytes(uint64_t total, uint64_t n) {
+        return 256 + round256(32 * total) + round256(32 * n) + round256(total) + round256(n) +
+               round256(2 * BLOCKS * sizeof(uint64_t));
+    }
+    verify_scratch(void* base, uint64_t total, uint64_t n) {
+        uint8_t* p = reinterpret_cast<uint8_t*>(((uintptr_t)base + 255) & ~uintptr_t(255));
+        nodes = p, p += round256(32 * total);
+        roots = p, p += round256(32 * n);
+        flags = p, p += round256(total);
+        file_bad = p, p += round256(n);
+        counts = reinterpret_cast<uint64_t*>(p);
+    }
+};
+
+void plan_tree(sd_checksum_tree* t, const uint64_t* offsets, const uint64_t* lens, size_t n, uint32_t block_log2) {
+    plan_tree_layout(lens, n, block_log2, t->node_base);  // refuses a bad block_log2 before anything is allocated
+    plan_checksum_batch(&t->ck, offsets, lens, n, nullptr);
+    t->block_log2 = block_log2;
+    std::vector<uint64_t> level_n(n), base(t->node_base.begin(), t->node_base.end() - 1);
+    for (size_t i = 0; i < n; i++) level_n[i] = t->node_base[i + 1] - t->node_base[i];
+    t->roots.lvl_cap[0] = t->roots.lvl_cap[1] = 0;
+    plan_reduce_passes(t->roots, std::move(level_n), std::move(base));
+    t->tab.begin();
+    t->o_base = t->tab.add(t->node_base);
+    t->o_pass.clear();
+    for (const auto& ps : t->roots.passes) t->o_pass.push_back(t->tab.add(ps));
+    t->tab.upload(nullptr);
+    t->lvl[0].ensure(t->roots.lvl_cap[0] * 32);
+    t->lvl[1].ensure(t->roots.lvl_cap[1] * 32);
+}
+
+// leaf pass with the level -> nodes; roots of files of at most 1 MiB -> out, longer files' 1 MiB CVs
+// -> the batch's level 0
+void run_tree_leaf(const sd_checksum_tree* t, const uint8_t* d_data, uint8_t* nodes, uint8_t* out, hipStream_t s) {
+    HIP_CHECK(sdk::launch_ck_leaf_tree(d_data, t->ck.d_files(), t->ck.d_map(), (uint32_t)t->ck.plan.wg_map.size(),
+                                       t->ck.lvl[0].as<uint32_t>(), reinterpret_cast<uint32_t*>(out), t->d_base(),
+                                       t->block_log2, reinterpret_cast<uint32_t*>(nodes), s));
+}
+
+void check_aligned16(const void* p, const char* what) {
+    if (reinterpret_cast<uintptr_t>(p) % 16) throw sd_failure(SD_ERR_INVALID, std::string(what) + " must be 16-byte aligned");
+}
+
+}  // namespace
+
+extern "C" {
+
+int sd_checksum_tree_create(sd_cas_ctx* ctx, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                            uint32_t block_log2, sd_checksum_tree** out) {
+    SD_GUARD_BEGIN
+    if (!ctx || !out || (n && (!offsets || !lens))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    ctx->bind();
+    auto t = std::make_unique<sd_checksum_tree>();
+    plan_tree(t.get(), offsets, lens, n, block_log2);
+    *out = t.release();
+    return SD_OK;
+    SD_GUARD_END
+}
+
+void sd_checksum_tree_destroy(sd_checksum_tree* t) {
+    try {
+        delete t;
+    } catch (...) {
+    }
+}
+
+int sd_checksum_tree_layout(const sd_checksum_tree* t, uint64_t* node_base) {
+    SD_GUARD_BEGIN
+    if (!t || !node_base) throw sd_failure(SD_ERR_INVALID, "null argument");
+    std::copy(t->node_base.begin(), t->node_base.end(), node_base);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_stats(const sd_checksum_tree* t, uint64_t out[4]) {
+    SD_GUARD_BEGIN
+    if (!t || !out) throw sd_failure(SD_ERR_INVALID, "null argument");
+    out[0] = t->ck.n; out[1] = t->ck.plan.total_bytes; out[2] = t->ck.plan.compressions; out[3] = t->total();
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_run(sd_cas_ctx* ctx, const sd_checksum_tree* t, const uint8_t* d_data, uint8_t* d_nodes,
+                         uint8_t* d_hash32, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !t || (t->ck.n && (!d_data || !d_nodes || !d_hash32))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_aligned16(d_nodes, "d_nodes");
+    if (t->ck.n == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    run_tree_leaf(t, d_data, d_nodes, d_hash32, s);
+    run_checksum_reduce(&t->ck, reinterpret_cast<uint32_t*>(d_hash32), s);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_roots(sd_cas_ctx* ctx, const sd_checksum_tree* t, const uint8_t* d_nodes, uint8_t* d_hash32,
+                           void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !t || (t->ck.n && (!d_nodes || !d_hash32))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_aligned16(d_nodes, "d_nodes");
+    const uint64_t n = t->ck.n;
+    if (n == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    uint32_t* out = reinterpret_cast<uint32_t*>(d_hash32);
+    hipLaunchKernelGGL(k_tree_single_roots, dim3(flat_grid(8 * n)), dim3(256), 0, s, t->d_base(), n,
+                       reinterpret_cast<const uint32_t*>(d_nodes), out);
+    HIP_CHECK(hipGetLastError());
+    for (size_t k = 0; k < t->roots.passes.size(); k++) {
+        const uint32_t* src = k == 0 ? reinterpret_cast<const uint32_t*>(d_nodes) : t->lvl[k & 1].as<uint32_t>();
+        HIP_CHECK(sdk::launch_ck_reduce(src, t->lvl[1 - (k & 1)].as<uint32_t>(), t->d_pass(k),
+                                        (uint32_t)t->roots.passes[k].size(), out, s));
+    }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_verify(sd_cas_ctx* ctx, const sd_checksum_tree* t, const uint8_t* d_data,
+                            const uint8_t* d_expected, uint8_t* d_bad, uint64_t* d_rows_out, uint64_t capacity,
+                            uint64_t* count, uint64_t stats[4], void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !t || (t->ck.n && (!d_data || !d_expected))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_aligned16(d_expected, "d_expected");
+    if (count) *count = 0;
+    if (stats) memset(stats, 0, 4 * sizeof(uint64_t));
+    const uint64_t n = t->ck.n, total = t->total();
+    if (n == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    auto slot = ctx->acquire();
+    struct Rel {
+        sd_cas_ctx* c;
+        std::unique_ptr<Slot>* s;
+        ~Rel() { c->release(std::move(*s)); }
+    } rel{ctx, &slot};
+    slot->staged.ensure(verify_scratch::bytes(total, n));
+    slot->host_hashes.ensure(2 * BLOCKS * sizeof(uint64_t));
+    const verify_scratch x(slot->staged.p, total, n);
+    run_tree_leaf(t, d_data, x.nodes, x.roots, s);
+    HIP_CHECK(hipMemsetAsync(x.file_bad, 0, n, s));
+    uint8_t* flags = d_bad ? d_bad : x.flags;
+    const uint32_t g_nodes = sliced_grid(total), g_files = sliced_grid(n);
+    launch_flag(g_nodes, s,
+                tree_differs{reinterpret_cast<const uint4*>(x.nodes), reinterpret_cast<const uint4*>(d_expected),
+                             t->d_base(), n, x.file_bad},
+                nullptr, total, flags, x.counts);
+    launch_flag(g_files, s, tree_file_marked{x.file_bad}, nullptr, n, nullptr, x.counts + BLOCKS);
+    HIP_CHECK(hipGetLastError());
+    const uint64_t* h = reinterpret_cast<const uint64_t*>(slot->host_hashes.p);
+    HIP_CHECK(hipMemcpyAsync(slot->host_hashes.p, x.counts, 2 * BLOCKS * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    uint64_t bad_blocks = 0, bad_files = 0;
+    for (uint32_t b = 0; b < g_nodes; b++) bad_blocks += h[b];
+    for (uint32_t b = 0; b < g_files; b++) bad_files += h[BLOCKS + b];
+    if (bad_blocks > total || bad_files > n || bad_files > bad_blocks)
+        throw sd_failure(SD_ERR_INTERNAL, "verify: inconsistent totals");
+    if (count) *count = bad_blocks;
+    if (stats) stats[0] = n, stats[1] = total, stats[2] = bad_blocks, stats[3] = bad_files;
+    if (!d_rows_out) return SD_OK;
+    if (capacity < bad_blocks)
+        throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of differing blocks");
+    if (bad_blocks == 0) return SD_OK;
+    tree_rows rows{{flags}, t->d_base(), n, d_rows_out};
+    launch_compact(g_nodes, s, rows, nullptr, total, x.counts, nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+}  // extern "C"

@@ -1,0 +1,354 @@
+// checksum_tree_selftest.cpp -- sd_cpu_checksum_tree, _roots and _verify (checksum_tree_host.cpp)
+// against a byte-at-a-time model of the node definitions (include/sd_cas.h, checksum trees): a
+// scalar BLAKE3 of its own that absorbs one byte per step, compresses a block when the next byte
+// arrives, and builds every node and every root by the level-wise rule, sharing nothing with
+// cpu_blake3.cpp.  Small sizes around the chunk, the lane (4 KiB) and the block boundaries at each
+// block size, in one batch with an odd start; the position rule; the flips of a verify with the
+// capacity rule over pre-filled buffers and every NULL output; the refusals; an empty batch; and
+// concurrent calls.  A program of its own: built plain for the CPU suite (`make
+// checksum-tree-selftest`, tests/test_checksum_tree.py) and under ASan + UBSan and TSan (`make
+// sanitize-checksum-tree`, logs in profiles/checksum_tree/).
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <array>
+#include <thread>
+#include <vector>
+
+#include "sd_host.h"
+
+static int g_fail = 0;
+#define CHECK(cond)                                                       \
+    do {                                                                  \
+        if (!(cond)) {                                                    \
+            printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);        \
+            g_fail++;                                                     \
+        }                                                                 \
+    } while (0)
+
+typedef std::vector<uint8_t> bytes;
+typedef std::array<uint32_t, 8> cv_t;
+
+// ---------------------------------------------------------------- the model's BLAKE3
+static const uint32_t M_IV[8] = {0x6A09E667u, 0xBB67AE85u, 0x3C6EF372u, 0xA54FF53Au,
+                                 0x510E527Fu, 0x9B05688Cu, 0x1F83D9ABu, 0x5BE0CD19u};
+static const int M_PERM[16] = {2, 6, 3, 10, 7, 0, 4, 13, 1, 11, 12, 5, 9, 14, 15, 8};
+enum { M_START = 1, M_END = 2, M_PARENT = 4, M_ROOT = 8 };
+
+static uint32_t m_rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
+static void m_g(uint32_t* s, int a, int b, int c, int d, uint32_t x, uint32_t y) {
+    s[a] = s[a] + s[b] + x, s[d] = m_rotr(s[d] ^ s[a], 16);
+    s[c] = s[c] + s[d], s[b] = m_rotr(s[b] ^ s[c], 12);
+    s[a] = s[a] + s[b] + y, s[d] = m_rotr(s[d] ^ s[a], 8);
+    s[c] = s[c] + s[d], s[b] = m_rotr(s[b] ^ s[c], 7);
+}
+static cv_t m_compress(const cv_t& cv, const uint8_t block[64], uint64_t counter, uint32_t len, uint32_t flags) {
+    uint32_t m[16], s[16];
+    for (int i = 0; i < 16; i++)
+        m[i] = (uint32_t)block[4 * i] | (uint32_t)block[4 * i + 1] << 8 | (uint32_t)block[4 * i + 2] << 16 |
+               (uint32_t)block[4 * i + 3] << 24;
+    for (int i = 0; i < 8; i++) s[i] = cv[i];
+    for (int i = 0; i < 4; i++) s[8 + i] = M_IV[i];
+    s[12] = (uint32_t)counter, s[13] = (uint32_t)(counter >> 32), s[14] = len, s[15] = flags;
+    for (int r = 0; r < 7; r++) {
+        m_g(s, 0, 4, 8, 12, m[0], m[1]), m_g(s, 1, 5, 9, 13, m[2], m[3]);
+        m_g(s, 2, 6, 10, 14, m[4], m[5]), m_g(s, 3, 7, 11, 15, m[6], m[7]);
+        m_g(s, 0, 5, 10, 15, m[8], m[9]), m_g(s, 1, 6, 11, 12, m[10], m[11]);
+        m_g(s, 2, 7, 8, 13, m[12], m[13]), m_g(s, 3, 4, 9, 14, m[14], m[15]);
+        uint32_t p[16];
+        for (int i = 0; i < 16; i++) p[i] = m[M_PERM[i]];
+        memcpy(m, p, sizeof m);
+    }
+    cv_t out;
+    for (int i = 0; i < 8; i++) out[i] = s[i] ^ s[i + 8];
+    return out;
+}
+
+// one chunk, a byte at a time: a full block is compressed when the byte after it arrives
+static cv_t m_chunk(const uint8_t* p, size_t n, uint64_t counter, bool root) {
+    cv_t cv;
+    memcpy(cv.data(), M_IV, 32);
+    uint8_t block[64] = {0};
+    uint32_t fill = 0, blocks = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (fill == 64) {
+            cv = m_compress(cv, block, counter, 64, blocks == 0 ? M_START : 0);
+            blocks++, fill = 0;
+            memset(block, 0, 64);
+        }
+        block[fill++] = p[i];
+    }
+    return m_compress(cv, block, counter, fill, (blocks == 0 ? M_START : 0) | M_END | (root ? M_ROOT : 0));
+}
+static cv_t m_parent(const cv_t& l, const cv_t& r, bool root) {
+    uint8_t block[64];
+    for (int i = 0; i < 8; i++)
+        for (int b = 0; b < 4; b++) block[4 * i + b] = (uint8_t)(l[i] >> (8 * b)), block[32 + 4 * i + b] = (uint8_t)(r[i] >> (8 * b));
+    cv_t iv;
+    memcpy(iv.data(), M_IV, 32);
+    return m_compress(iv, block, 0, 64, M_PARENT | (root ? M_ROOT : 0));
+}
+// level-wise pairwise merge, the odd node carried up, ROOT (if asked) on the last parent
+static cv_t m_merge(std::vector<cv_t> lvl, bool root) {
+    while (lvl.size() > 1) {
+        const bool last = lvl.size() == 2;
+        std::vector<cv_t> nxt;
+        for (size_t i = 0; i + 1 < lvl.size(); i += 2) nxt.push_back(m_parent(lvl[i], lvl[i + 1], root && last));
+        if (lvl.size() & 1) nxt.push_back(lvl.back());
+        lvl.swap(nxt);
+    }
+    return lvl[0];
+}
+// the subtree over chunks of [p, p + n), counters from chunk0; root: the whole message
+static cv_t m_subtree(const uint8_t* p, size_t n, uint64_t chunk0, bool root) {
+    if (n <= 1024) return m_chunk(p, n, chunk0, root);
+    std::vector<cv_t> cvs;
+    for (size_t at = 0; at < n; at += 1024) cvs.push_back(m_chunk(p + at, std::min<size_t>(1024, n - at), chunk0 + at / 1024, false));
+    return m_merge(cvs, root);
+}
+static void m_put(const cv_t& cv, uint8_t* out) {
+    for (int i = 0; i < 8; i++)
+        for (int b = 0; b < 4; b++) out[4 * i + b] = (uint8_t)(cv[i] >> (8 * b));
+}
+static cv_t m_get(const uint8_t* in) {
+    cv_t cv;
+    for (int i = 0; i < 8; i++)
+        cv[i] = (uint32_t)in[4 * i] | (uint32_t)in[4 * i + 1] << 8 | (uint32_t)in[4 * i + 2] << 16 | (uint32_t)in[4 * i + 3] << 24;
+    return cv;
+}
+
+// ---------------------------------------------------------------- batches
+static uint64_t mix(uint64_t seed, uint64_t i) {  // splitmix64
+    uint64_t z = seed + (i + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+struct batch_t {
+    uint32_t k = 17;
+    std::vector<uint64_t> offs, lens, base;
+    bytes data;
+    size_t n() const { return lens.size(); }
+    uint64_t total() const { return base.back(); }
+    void build(uint32_t k_, const std::vector<uint64_t>& ls, uint64_t seed) {
+        k = k_;
+        lens = ls;
+        offs.clear();
+        base.assign(1, 0);
+        uint64_t cur = 0;
+        for (size_t i = 0; i < ls.size(); i++) {
+            if (i == 3) cur += 16;  // a 16-byte aligned start that is on no 128-byte line
+            offs.push_back(cur);
+            cur = (cur + ls[i] + 127) / 128 * 128;
+            base.push_back(base.back() + std::max<uint64_t>(1, (ls[i] + (1ull << k) - 1) >> k));
+        }
+        data.resize(cur + 64);
+        for (size_t i = 0; i < data.size(); i += 8) {
+            const uint64_t v = mix(seed, i);
+            memcpy(data.data() + i, &v, std::min<size_t>(8, data.size() - i));
+        }
+    }
+};
+
+struct answer_t {
+    bytes nodes, roots;
+};
+
+static answer_t model(const batch_t& b) {
+    answer_t a;
+    a.nodes.resize(32 * b.total());
+    a.roots.resize(32 * b.n());
+    const uint64_t B = 1ull << b.k;
+    for (size_t i = 0; i < b.n(); i++) {
+        const uint8_t* p = b.data.data() + b.offs[i];
+        const uint64_t nb = b.base[i + 1] - b.base[i];
+        if (nb == 1) {
+            m_put(m_subtree(p, b.lens[i], 0, true), a.nodes.data() + 32 * b.base[i]);
+            memcpy(a.roots.data() + 32 * i, a.nodes.data() + 32 * b.base[i], 32);
+            continue;
+        }
+        std::vector<cv_t> lvl;
+        for (uint64_t j = 0; j < nb; j++) {
+            lvl.push_back(m_subtree(p + j * B, std::min<uint64_t>(B, b.lens[i] - j * B), j * B / 1024, false));
+            m_put(lvl.back(), a.nodes.data() + 32 * (b.base[i] + j));
+        }
+        m_put(m_merge(lvl, true), a.roots.data() + 32 * i);
+    }
+    return a;
+}
+
+static answer_t run(const batch_t& b, int nthreads) {
+    answer_t a;
+    a.nodes.assign(32 * b.total() + 32, 0xA5);  // one guard row each
+    a.roots.assign(32 * b.n() + 32, 0xA5);
+    CHECK(sd_cpu_checksum_tree(b.data.data(), b.offs.data(), b.lens.data(), b.n(), b.k, a.nodes.data(), a.roots.data(),
+                               nthreads) == SD_OK);
+    CHECK(std::all_of(a.nodes.end() - 32, a.nodes.end(), [](uint8_t x) { return x == 0xA5; }));
+    CHECK(std::all_of(a.roots.end() - 32, a.roots.end(), [](uint8_t x) { return x == 0xA5; }));
+    a.nodes.resize(32 * b.total());
+    a.roots.resize(32 * b.n());
+    return a;
+}
+
+static std::vector<uint64_t> small_sizes(uint32_t k) {
+    const uint64_t B = 1ull << k;
+    std::vector<uint64_t> ls = {0, 1, 63, 64, 65, 1023, 1024, 1025, 4096, 4097, B - 1, B, B + 1};
+    if (k == 17) {
+        const uint64_t more[] = {2 * B - 1, 2 * B + 1, 3 * B + 5000, 8 * B + 1, 9 * B + 1024};  // past one 1 MiB block too
+        ls.insert(ls.end(), more, more + 5);
+    }
+    return ls;
+}
+
+static void test_levels_and_roots() {
+    for (uint32_t k = SD_TREE_BLOCK_LOG2_MIN; k <= SD_TREE_BLOCK_LOG2_MAX; k++) {
+        batch_t b;
+        b.build(k, small_sizes(k), 100 + k);
+        const answer_t want = model(b);
+        for (int nthreads : {1, 4}) {
+            const answer_t got = run(b, nthreads);
+            CHECK(got.nodes == want.nodes);
+            CHECK(got.roots == want.roots);
+        }
+        // the roots are file_checksum's, and come from the level alone
+        for (size_t i = 0; i < b.n(); i++) {
+            uint8_t h[32];
+            cpu_blake3(b.data.data() + b.offs[i], b.lens[i], h);
+            CHECK(memcmp(h, want.roots.data() + 32 * i, 32) == 0);
+        }
+        bytes roots(32 * b.n(), 0);
+        CHECK(sd_cpu_checksum_tree_roots(want.nodes.data(), b.lens.data(), b.n(), k, roots.data()) == SD_OK);
+        CHECK(roots == want.roots);
+        for (size_t i = 0; i < b.n(); i++) {
+            uint64_t nb = 0;
+            CHECK(sd_checksum_tree_nodes(b.lens[i], k, &nb) == SD_OK && nb == b.base[i + 1] - b.base[i]);
+        }
+    }
+}
+
+static void test_position_rule() {  // a full block's node does not depend on the file's length
+    const uint32_t k = 17;
+    const uint64_t B = 1ull << k;
+    batch_t a, c;
+    a.build(k, {3 * B + 5000}, 7);
+    c.build(k, {3 * B + 5000 - B - 7}, 7);  // the same bytes, shorter
+    const answer_t x = run(a, 2), y = run(c, 2);
+    CHECK(memcmp(x.nodes.data(), y.nodes.data(), 2 * 32) == 0);       // blocks 0 and 1: full in both
+    CHECK(memcmp(x.nodes.data() + 64, y.nodes.data() + 64, 32) != 0);  // block 2: partial in the shorter
+    CHECK(m_get(x.nodes.data()) == m_subtree(a.data.data(), B, 0, false));
+}
+
+static void test_verify() {
+    const uint32_t k = 17;
+    const uint64_t B = 1ull << k;
+    batch_t b;
+    b.build(k, {4097, 3 * B + 5000, 0, 2 * B + 1, B, 700}, 9);
+    const answer_t want = model(b);
+    const uint64_t total = b.total();
+    uint64_t count = 99, stats[4];
+    bytes bad(total + 1, 0xA5);
+    std::vector<uint64_t> rows(2 * total + 2, 0xA5A5);
+    // a clean batch
+    CHECK(sd_cpu_checksum_tree_verify(b.data.data(), b.offs.data(), b.lens.data(), b.n(), k, want.nodes.data(), bad.data(),
+                                      rows.data(), total, &count, stats, 3) == SD_OK);
+    CHECK(count == 0 && stats[0] == b.n() && stats[1] == total && stats[2] == 0 && stats[3] == 0);
+    CHECK(std::all_of(bad.begin(), bad.end() - 1, [](uint8_t x) { return x == 0; }) && bad[total] == 0xA5);
+    CHECK(std::all_of(rows.begin(), rows.end(), [](uint64_t x) { return x == 0xA5A5; }));
+    // the first byte of a middle block, the last byte of a file, a byte of a partial last block, a
+    // byte of a one-block file
+    batch_t f = b;
+    f.data[f.offs[1] + B] ^= 1, f.data[f.offs[3] + 2 * B] ^= 1, f.data[f.offs[1] + 3 * B + 4000] ^= 1, f.data[f.offs[0] + 100] ^= 1;
+    const std::vector<uint64_t> want_rows = {0, 0, 1, 1, 1, 3, 3, 2};
+    bytes want_bad(total, 0);
+    for (size_t r = 0; r < want_rows.size(); r += 2) want_bad[b.base[want_rows[r]] + want_rows[r + 1]] = 1;
+    for (int mask = 0; mask < 4; mask++) {  // bad and rows each NULL in turn
+        std::fill(bad.begin(), bad.end(), 0xA5);
+        std::fill(rows.begin(), rows.end(), 0xA5A5);
+        count = 99;
+        CHECK(sd_cpu_checksum_tree_verify(f.data.data(), f.offs.data(), f.lens.data(), f.n(), k, want.nodes.data(),
+                                          mask & 1 ? bad.data() : nullptr, mask & 2 ? rows.data() : nullptr, 4, &count,
+                                          mask == 3 ? stats : nullptr, 1 + mask) == SD_OK);
+        CHECK(count == 4);
+        if (mask & 1) CHECK(memcmp(bad.data(), want_bad.data(), total) == 0 && bad[total] == 0xA5);
+        if (mask & 2) CHECK(std::equal(want_rows.begin(), want_rows.end(), rows.begin()) && rows[8] == 0xA5A5);
+    }
+    CHECK(stats[0] == b.n() && stats[1] == total && stats[2] == 4 && stats[3] == 3);
+    // a capacity one short: the requirement, the flags and stats complete, no row written
+    std::fill(bad.begin(), bad.end(), 0xA5);
+    std::fill(rows.begin(), rows.end(), 0xA5A5);
+    count = 0;
+    memset(stats, 0, sizeof stats);
+    CHECK(sd_cpu_checksum_tree_verify(f.data.data(), f.offs.data(), f.lens.data(), f.n(), k, want.nodes.data(), bad.data(),
+                                      rows.data(), 3, &count, stats, 2) == SD_ERR_CAPACITY);
+    CHECK(count == 4 && stats[2] == 4 && stats[3] == 3 && memcmp(bad.data(), want_bad.data(), total) == 0);
+    CHECK(std::all_of(rows.begin(), rows.end(), [](uint64_t x) { return x == 0xA5A5; }));
+    // count and stats may be NULL
+    CHECK(sd_cpu_checksum_tree_verify(f.data.data(), f.offs.data(), f.lens.data(), f.n(), k, want.nodes.data(), nullptr,
+                                      nullptr, 0, nullptr, nullptr, 1) == SD_OK);
+}
+
+static void test_refusals_and_empty() {
+    batch_t b;
+    b.build(17, {100, 5000}, 3);
+    bytes nodes(64, 0xA5), roots(64, 0xA5);
+    uint64_t nb = 7, count = 0;
+    for (uint32_t k : {0u, 16u, 21u, 64u, ~0u}) {
+        CHECK(sd_checksum_tree_nodes(1, k, &nb) == SD_ERR_INVALID && nb == 7);
+        CHECK(sd_cpu_checksum_tree(b.data.data(), b.offs.data(), b.lens.data(), 2, k, nodes.data(), roots.data(), 1) == SD_ERR_INVALID);
+        CHECK(sd_cpu_checksum_tree_roots(nodes.data(), b.lens.data(), 2, k, roots.data()) == SD_ERR_INVALID);
+        CHECK(sd_cpu_checksum_tree_verify(b.data.data(), b.offs.data(), b.lens.data(), 2, k, nodes.data(), nullptr, nullptr, 0,
+                                          &count, nullptr, 1) == SD_ERR_INVALID);
+    }
+    CHECK(sd_checksum_tree_nodes(1, 17, nullptr) == SD_ERR_INVALID);
+    const uint64_t odd[2] = {0, 136};
+    CHECK(sd_cpu_checksum_tree(b.data.data(), odd, b.lens.data(), 2, 17, nodes.data(), roots.data(), 1) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree_verify(b.data.data(), odd, b.lens.data(), 2, 17, nodes.data(), nullptr, nullptr, 0, &count,
+                                      nullptr, 1) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree(nullptr, b.offs.data(), b.lens.data(), 2, 17, nodes.data(), roots.data(), 1) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree(b.data.data(), nullptr, b.lens.data(), 2, 17, nodes.data(), roots.data(), 1) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree(b.data.data(), b.offs.data(), nullptr, 2, 17, nodes.data(), roots.data(), 1) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree(b.data.data(), b.offs.data(), b.lens.data(), 2, 17, nullptr, roots.data(), 1) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree(b.data.data(), b.offs.data(), b.lens.data(), 2, 17, nodes.data(), nullptr, 1) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree_verify(b.data.data(), b.offs.data(), b.lens.data(), 2, 17, nullptr, nullptr, nullptr, 0, &count,
+                                      nullptr, 1) == SD_ERR_INVALID);
+    CHECK(std::all_of(nodes.begin(), nodes.end(), [](uint8_t x) { return x == 0xA5; }));
+    CHECK(std::all_of(roots.begin(), roots.end(), [](uint8_t x) { return x == 0xA5; }));
+    // an empty batch
+    uint64_t stats[4] = {9, 9, 9, 9};
+    count = 9;
+    CHECK(sd_cpu_checksum_tree(nullptr, nullptr, nullptr, 0, 17, nullptr, nullptr, 1) == SD_OK);
+    CHECK(sd_cpu_checksum_tree_roots(nullptr, nullptr, 0, 17, nullptr) == SD_OK);
+    CHECK(sd_cpu_checksum_tree_verify(nullptr, nullptr, nullptr, 0, 17, nullptr, nullptr, nullptr, 0, &count, stats, 1) == SD_OK);
+    CHECK(count == 0 && stats[0] == 0 && stats[1] == 0 && stats[2] == 0 && stats[3] == 0);
+}
+
+static void test_concurrent_calls() {  // the calls hold no shared state beyond the thread pools
+    batch_t b;
+    b.build(17, small_sizes(17), 21);
+    const answer_t want = model(b);
+    std::vector<std::thread> ts;
+    std::vector<int> ok(4, 0);
+    for (int t = 0; t < 4; t++)
+        ts.emplace_back([&, t] {
+            const answer_t got = run(b, 1 + t);
+            ok[t] = got.nodes == want.nodes && got.roots == want.roots;
+        });
+    for (auto& t : ts) t.join();
+    CHECK(ok == std::vector<int>(4, 1));
+}
+
+int main() {
+    test_levels_and_roots();
+    test_position_rule();
+    test_verify();
+    test_refusals_and_empty();
+    test_concurrent_calls();
+    if (g_fail) {
+        printf("checksum_tree_selftest: %d failure(s)\n", g_fail);
+        return 1;
+    }
+    printf("checksum_tree_selftest: ok\n");
+    return 0;
+}

@@ -675,6 +675,8 @@ int sd_cpu_cas_id_path(const char* path, uint64_t size, char* out_hex17, int32_t
 
 }  // extern "C"
 
+void cpu_parallel_for(size_t n, int nthreads, const std::function<void(size_t)>& fn) { parallel_for(n, nthreads, fn); }
+
 void cpu_block_cvs(const uint8_t* msg, uint64_t total_len, uint64_t b0, uint64_t b1, uint8_t* cvs, int nthreads) {
     parallel_for(b1 - b0, nthreads, [&](size_t k) {
         const uint64_t b = b0 + k;

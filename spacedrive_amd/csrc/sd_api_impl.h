@@ -149,6 +149,22 @@ struct sd_checksum_batch {
     const ck_reduce_wg* d_pass(size_t k) const { return tab.at<ck_reduce_wg>(o_pass[k]); }
 };
 
+// a checksum batch that also leaves every file's level at 2^block_log2-byte granularity
+// (include/sd_cas.h, checksum trees; checksum_tree.hip)
+struct sd_checksum_tree {
+    uint32_t block_log2 = 0;
+    sd_checksum_batch ck;             // the leaf tables and the reduce over 1 MiB CVs: _run's roots
+    std::vector<uint64_t> node_base;  // n + 1
+    CkPlan roots;                     // reduce passes whose level 0 is the level itself: _roots
+    sdi::Tables tab;                  // node_base, then one table per pass of `roots`
+    size_t o_base = 0;
+    std::vector<size_t> o_pass;
+    sdi::DevBuf lvl[2];               // _roots' levels above the caller's (pass k writes lvl[1 - (k & 1)])
+    uint64_t total() const { return node_base.empty() ? 0 : node_base.back(); }
+    const uint64_t* d_base() const { return tab.at<uint64_t>(o_base); }
+    const ck_reduce_wg* d_pass(size_t k) const { return tab.at<ck_reduce_wg>(o_pass[k]); }
+};
+
 // one file over the ranks of a communicator (include/sd_cas.h, sd_split_range)
 struct sd_split_checksum {
     SplitPlan sp;

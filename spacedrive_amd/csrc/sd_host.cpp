@@ -673,6 +673,12 @@ void plan_checksum(CkPlan& p, const uint64_t* offsets, const uint64_t* lens, siz
     }
     p.lvl_cap[0] = cv0;
     p.lvl_cap[1] = 0;
+    plan_reduce_passes(p, std::move(level_n), std::move(base));
+}
+
+void plan_reduce_passes(CkPlan& p, std::vector<uint64_t> level_n, std::vector<uint64_t> base) {
+    const size_t n = level_n.size();
+    p.passes.clear();
     int src = 0;
     for (;;) {
         std::vector<ck_reduce_wg> wgs;

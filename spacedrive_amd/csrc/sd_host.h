@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -221,6 +222,19 @@ struct CkPlan {
     uint64_t total_bytes = 0, compressions = 0, blocks = 0;
 };
 void plan_checksum(CkPlan& p, const uint64_t* offsets, const uint64_t* lens, size_t n);
+// The reduce passes alone -> p.passes and p.lvl_cap (raised, never lowered): message i has
+// level_n[i] CVs from slot base[i] of the level-0 buffer, whatever bytes a CV covers (1 MiB
+// leaf blocks for plan_checksum, the blocks of a checksum tree's level for its roots).
+void plan_reduce_passes(CkPlan& p, std::vector<uint64_t> level_n, std::vector<uint64_t> base);
+
+// ------------------------------------------------------------------ checksum trees
+// nb of include/sd_cas.h's checksum trees; block_log2 already checked
+inline uint64_t tree_nodes(uint64_t len, uint32_t block_log2) {
+    return len == 0 ? 1 : ((len - 1) >> block_log2) + 1;
+}
+// node_base[0 .. n] of a batch; throws SD_ERR_INVALID on a block_log2 outside
+// [SD_TREE_BLOCK_LOG2_MIN, SD_TREE_BLOCK_LOG2_MAX]
+void plan_tree_layout(const uint64_t* lens, size_t n, uint32_t block_log2, std::vector<uint64_t>& node_base);
 
 // ------------------------------------------------------------------ fingerprints
 // k_cas_gather (gather.hip) builds each file's cas message from its resident bytes.  Its
@@ -449,6 +463,9 @@ void cpu_root_from_cvs(const uint8_t* cvs, uint64_t nb, uint8_t out[32]);
 // the (non-root) chaining values of 1 MiB blocks [b0, b1) of a message of total_len >= 2
 // blocks, on nthreads threads: block b's 32 bytes at cvs + 32 * b
 void cpu_block_cvs(const uint8_t* msg, uint64_t total_len, uint64_t b0, uint64_t b1, uint8_t* cvs, int nthreads);
+// fn(i) for i in [0, n) on up to nthreads threads of the CPU path's persistent pools (the
+// caller's included; capped by the host budget)
+void cpu_parallel_for(size_t n, int nthreads, const std::function<void(size_t)>& fn);
 // sd_checksums' co-hashing: the index of the range of >= min_len bytes
 // nearest the byte where the GPU (gpu_gbps, from the front) and host_threads host threads
 // (thread_gbps each, from the back) are predicted to meet; the first of equally near ones;

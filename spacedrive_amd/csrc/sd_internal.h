@@ -33,6 +33,11 @@ hipError_t launch_whole_items(const uint8_t* staged, const uint4* full, uint32_t
 hipError_t launch_scatter_hash(const uint32_t* src, const uint32_t* idx, uint32_t n, uint32_t* out, hipStream_t s);
 hipError_t launch_ck_leaf(const uint8_t* data, uint64_t shift, uint32_t blk_base, const ck_file* files,
                           const uint2* wg_map, uint32_t n_wg, uint32_t* cvbuf, uint32_t* out, hipStream_t s);
+// launch_ck_leaf over whole resident messages that also stores every message's level at
+// 2^block_log2-byte granularity (17..20): message i's nodes from nodes[8 * node_base[i]], 16-byte aligned
+hipError_t launch_ck_leaf_tree(const uint8_t* data, const ck_file* files, const uint2* wg_map, uint32_t n_wg,
+                               uint32_t* cvbuf, uint32_t* out, const uint64_t* node_base, uint32_t block_log2,
+                               uint32_t* nodes, hipStream_t s);
 hipError_t launch_ck_reduce(const uint32_t* src, uint32_t* dst, const ck_reduce_wg* wgs, uint32_t n_wg,
                             uint32_t* out, hipStream_t s);
 hipError_t launch_synth_stage_cas(const uint64_t* sizes, const uint64_t* cids, const uint32_t* twins,

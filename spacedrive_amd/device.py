@@ -84,6 +84,9 @@ class Context:
     def fingerprint_batch(self, offsets, lens) -> "FingerprintBatch":
         return FingerprintBatch(self, offsets, lens)
 
+    def checksum_tree(self, offsets, lens, block_log2: int = 17) -> "ChecksumTree":
+        return ChecksumTree(self, offsets, lens, block_log2)
+
     # -------------------------------------------------------------- files -> device hashes
     def hashes_files(self, paths, sizes, d_hash32, d_valid=None, nthreads: int = 16) -> np.ndarray:
         """sd_cas_hashes_files: generate_cas_id's messages of these files hashed into
@@ -909,6 +912,89 @@ class ChecksumBatch:
     def close(self) -> None:
         if self.handle:
             lib().sd_checksum_batch_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ChecksumTree:
+    """Prepared checksum-tree batch (sd_checksum_tree) over byte ranges of one buffer: every
+    file's level at 2^block_log2 bytes (128 KiB .. 1 MiB) beside its checksum.  File i's nodes are
+    rows node_base[i] .. node_base[i + 1] of the [total_nodes, 32] level buffer."""
+
+    def __init__(self, ctx: Context, offsets, lens, block_log2: int = 17):
+        self.ctx = ctx
+        self.block_log2 = int(block_log2)
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self.lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        h = ctypes.c_void_p()
+        check(lib().sd_checksum_tree_create(ctx.handle, _ptr(self.offsets), _ptr(self.lens), len(self.lens),
+                                            self.block_log2, ctypes.byref(h)))
+        self.handle = h
+        st = np.zeros(4, np.uint64)
+        check(lib().sd_checksum_tree_stats(h, _ptr(st)))
+        self.n, self.total_bytes, self.compressions, self.total_nodes = (int(v) for v in st)
+        self.node_base = np.zeros(self.n + 1, np.uint64)
+        check(lib().sd_checksum_tree_layout(h, _ptr(self.node_base)))
+
+    def run(self, d_data: torch.Tensor, d_nodes: torch.Tensor, d_hash32: torch.Tensor, stream=None) -> None:
+        """one pass over the data: the levels -> d_nodes, the roots -> d_hash32"""
+        assert d_nodes.numel() >= 32 * self.total_nodes and d_hash32.numel() >= 32 * self.n
+        check(lib().sd_checksum_tree_run(self.ctx.handle, self.handle, _ptr(d_data), _ptr(d_nodes), _ptr(d_hash32),
+                                         _stream(stream)))
+
+    def roots(self, d_nodes: torch.Tensor, d_hash32: torch.Tensor, stream=None) -> None:
+        """the roots from the levels alone -> d_hash32"""
+        assert d_nodes.numel() >= 32 * self.total_nodes and d_hash32.numel() >= 32 * self.n
+        check(lib().sd_checksum_tree_roots(self.ctx.handle, self.handle, _ptr(d_nodes), _ptr(d_hash32),
+                                           _stream(stream)))
+
+    def verify(self, d_data: torch.Tensor, d_expected: torch.Tensor, d_bad: Optional[torch.Tensor] = None,
+               d_rows_out: Optional[torch.Tensor] = None, capacity: Optional[int] = None, want_rows: bool = True,
+               stream=None):
+        """sd_checksum_tree_verify: hashes d_data's blocks and compares them with d_expected (a level
+        buffer).  Returns (rows int64 [count, 2] of (file, block) ascending, stats uint64 [4]: files,
+        blocks compared, blocks that differ, files with a differing block), and d_bad (uint8
+        [total_nodes], written when given) as a third value.  Without d_rows_out the rows go to a
+        tensor with room for every block; with it and a short `capacity` the call
+        raises SdCasError (SD_ERR_CAPACITY, ``.needed`` rows, ``.stats``) and writes no row.
+        want_rows=False only counts (rows comes back empty)."""
+        assert d_expected.numel() >= 32 * self.total_nodes and (d_bad is None or d_bad.numel() >= self.total_nodes)
+        st = _stream(stream)
+        count = ctypes.c_uint64(0)
+        stats = np.zeros(4, np.uint64)
+
+        def call(rows, cap):
+            rc = lib().sd_checksum_tree_verify(self.ctx.handle, self.handle, _ptr(d_data), _ptr(d_expected), _ptr(d_bad),
+                                               _ptr(rows), cap, ctypes.byref(count), _ptr(stats), st)
+            try:
+                check(rc)
+            except SdCasError as e:
+                e.needed = int(count.value)
+                e.stats = stats
+                raise
+
+        dev = torch.device("cuda", self.ctx.device)
+        if not want_rows:
+            call(None, 0)
+            rows = torch.empty((0, 2), dtype=torch.int64, device=dev)
+        elif d_rows_out is None:  # room for every block: 16 B per >= 128 KiB of data, and one pass
+            rows = torch.empty((max(self.total_nodes, 1), 2), dtype=torch.int64, device=dev)
+            call(rows, self.total_nodes)
+            rows = rows[:int(count.value)]
+        else:
+            assert d_rows_out.dtype == torch.int64 and d_rows_out.is_cuda and d_rows_out.is_contiguous()
+            call(d_rows_out, d_rows_out.numel() // 2 if capacity is None else int(capacity))
+            rows = d_rows_out.reshape(-1)[:2 * int(count.value)].reshape(-1, 2)
+        return (rows, stats) if d_bad is None else (rows, stats, d_bad)
+
+    def close(self) -> None:
+        if self.handle:
+            lib().sd_checksum_tree_destroy(self.handle)
             self.handle = None
 
     def __del__(self):  # pragma: no cover
