@@ -56,6 +56,8 @@ def lib():
         L.sdo_checksum_mt.restype = I
         L.sdo_simd_level.argtypes = [I]
         L.sdo_simd_level.restype = I
+        L.sdo_subtree_simd.argtypes = [P, U64, U64, I, P, I, P]
+        L.sdo_subtree_simd.restype = None
         _lib = L
     return _lib
 
@@ -149,6 +151,19 @@ def checksum_mt(data: np.ndarray, size: int, nthreads: int = 8, simd: int = -1) 
 
 def simd_level(requested: int = -1) -> int:
     return lib().sdo_simd_level(requested)
+
+
+def subtree_cv(data, chunk0: int, simd: int = -1) -> bytes:
+    """The non-root CV of the subtree over `data` (bytes or a uint8 array: an aligned power-of-two
+    group of chunks, or the last group of a message) whose first chunk has the 64-bit counter
+    `chunk0`.  simd as cas_ids_staged: 0 scalar compressions, -1 the best SIMD available."""
+    d = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data,
+                             dtype=np.uint8).reshape(-1)
+    out = ctypes.create_string_buffer(32)
+    scratch = np.empty(32 * max(1, -(-d.size // 1024)), np.uint8)
+    lvl = 0 if simd == 0 else lib().sdo_simd_level(simd)
+    lib().sdo_subtree_simd(_p(d) if d.size else None, d.size, int(chunk0), 0, out, lvl, _p(scratch))
+    return out.raw
 
 
 def checksums_simd(data: np.ndarray, offsets, lens, nthreads: int = 1, simd: int = -1) -> np.ndarray:

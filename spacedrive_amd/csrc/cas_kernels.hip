@@ -138,6 +138,8 @@ __device__ __forceinline__ void group_cv(uint32_t (&out)[8], const uint8_t* __re
         uint32_t ma[16], mb[16];
 #pragma unroll 1
         for (uint32_t u = 0; u < (uint32_t)U; u++) {
+            // chi = 0 holds for sampled messages only; the 64-bit counter of the long-message path is held by
+            // tests/test_gpu_high_counter.py (test_split_leaves_past_2_32)
             const uint32_t clo = c0 + u, chi = 0u;
             const uint8_t* q = p + (size_t)u * CHUNK_LEN;
             set_iv(out);
@@ -458,6 +460,8 @@ __device__ __forceinline__ void ck_leaf_body(
             uint32_t cv[8];
 #pragma unroll 1
             for (uint32_t j = 0; j < nch; j++) {
+                // 64 bits: the chunk counter passes 2^32 at 4 TiB of a message, and both words reach compress
+                // (tests/test_gpu_high_counter.py::test_split_leaves_past_2_32 fails on a narrower one)
                 const uint64_t ci = blk0 + c0 + j;
                 const uint64_t rem = fi.len - ci * CHUNK_LEN;
                 const uint32_t len = fi.len == 0 ? 0u : (rem < CHUNK_LEN ? (uint32_t)rem : CHUNK_LEN);

@@ -69,6 +69,23 @@ def pattern_reader(o: int, n: int) -> bytes:
     return bytes((o + k) % 251 for k in range(n))
 
 
+def high_counter() -> dict:
+    """The two full 1 MiB blocks either side of the chunk counter's 2^32 (tests/high_counter_cases.py):
+    blocks B0 = 2^22 - 1 and B0 + 1 of synthetic content 4242, their spec CVs with the true counter
+    and, as the control, with the counter masked to 32 bits (equal for B0, different for B0 + 1).
+    Pure Python takes seconds per block, so they are recorded here and not recomputed per test."""
+    from tests import high_counter_cases as hc
+    blocks = []
+    for b in (hc.B0, hc.B0 + 1):
+        data = cs.synth_bytes(hc.CID, 0, b * hc.MIB, hc.MIB)
+        chunk0 = b * (hc.MIB // hc.CHUNK)
+        blocks.append({"block": b, "chunk0": chunk0, "cv": hc.spec_block_cv(data, chunk0).hex(),
+                       "cv_counter_mod_2_32": hc.spec_block_cv(data, chunk0, 0xFFFFFFFF).hex()})
+    assert blocks[0]["cv"] == blocks[0]["cv_counter_mod_2_32"] and blocks[1]["cv"] != blocks[1]["cv_counter_mod_2_32"]
+    return {"content_id": hc.CID, "twin": 0, "offset": hc.B0 * hc.MIB, "block_bytes": hc.MIB, "ranks": hc.R,
+            "rank": hc.RANK, "blocks": blocks}
+
+
 def main() -> None:
     pat = lambda n: pattern_reader(0, n)  # noqa: E731
     blake = {}
@@ -106,6 +123,7 @@ def main() -> None:
                            "files": cas_synth, "synth_prefix40": synth_prefix},
         "checksum_pattern.json": {"pattern": "byte i = i % 251", "checksum": checks_pattern},
         "checksum_synth.json": {"files": checks_synth},
+        "high_counter.json": high_counter(),
     }
     for name, obj in out.items():
         with open(os.path.join(HERE, name), "w") as f:

@@ -1738,7 +1738,7 @@ def test_split_checksum_ranks_on_one_gpu(ctx, oracle_native):
     """One file over R ranks (sd_split_checksum_leaves / _root), the ranks emulated on one
     device: each rank's leaves read only its own slice (a view at its byte range) and write
     only its own CV slots, so one shared CV buffer stands for the gathered one.  Bit-exact
-    vs the oracle's BLAKE3 of the whole file, up to 4 GiB + 12345 (block CVs past 2^32)."""
+    vs the oracle's BLAKE3 of the whole file, up to 4 GiB + 12345 (byte offsets past 2^32)."""
     from spacedrive_amd.device import SplitChecksum
     MiB = 1 << 20
     cases = [(0, (1, 2)), (1, (1, 3)), (MiB, (1, 2)), (MiB + 1, (1, 2, 3)), (5 * MiB + 3, (1, 2, 4, 7)),
