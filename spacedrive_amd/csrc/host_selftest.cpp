@@ -5,10 +5,11 @@
 // plan_checksum), the stager with generate_cas_id's read semantics (stage_one, cas.rs:
 // 23-62), the sequential and parallel message readers (MsgSource, hash.rs:14-20), the
 // stager thread pool (StagePool, incl. the context's grow-while-in-use pattern), the CPU
-// path (CpuHasher, sd_cpu_*), and the latency-path coalescer with both of its routes.  The
-// coalescer's GPU batch calls are stubbed here with the CPU path (no device in this
-// build); everything else is the library's own code.  Prints "host_selftest: ok" or the
-// failed checks and exits non-zero.
+// path (CpuHasher, sd_cpu_*), the claim protocols of the calls the GPU and host threads share
+// (EndClaims, BlockQueue, plan_range_window, LearnedRoute), and the latency-path coalescer
+// with both of its routes.  The coalescer's GPU batch calls are stubbed here with the CPU
+// path (no device in this build); everything else is the library's own code.  Prints
+// "host_selftest: ok" or the failed checks and exits non-zero.
 #include <dirent.h>
 #include <sched.h>
 #include <fcntl.h>
@@ -1018,6 +1019,419 @@ void test_split_routes() {
     // the co-hash cap scales with the budget
     CHECK(checksum_cohash_cap(16) == 13 && checksum_cohash_cap(8) == 6 && checksum_cohash_cap(4) == 3);
     CHECK(checksum_cohash_cap(2) == 1 && checksum_cohash_cap(1) == 0 && checksum_cohash_cap(32) == 26);
+    // LearnedRoute: the same rule behind a lock, dropped when the generation moves
+    using clk = std::chrono::steady_clock;
+    LearnedRoute lr;
+    for (int want : {0, 0, 1, 1}) {  // a warm-up and a counted call each; about 1 and 2 GB/s
+        const int r = lr.begin(8);
+        CHECK(r == want);
+        lr.record(r, r ? 2000000000ull : 1000000000ull, clk::now() - std::chrono::seconds(1));
+    }
+    CHECK(lr.begin(0) == 1);
+    SplitRoutes snap = lr.snapshot();
+    CHECK(snap.n[0] == 1 && snap.n[1] == 1 && snap.rate[1] > snap.rate[0] && snap.rate[0] > 0.5);
+    CHECK(sd_cas_set_tuning("checksum_hybrid_threads", keep + 1) == SD_OK);
+    CHECK(lr.begin(8) == 0);  // learns afresh
+    snap = lr.snapshot();
+    CHECK(snap.n[0] == 0 && snap.n[1] == 0 && snap.seen[0] == 0 && snap.calls == 0);
+    CHECK(sd_cas_set_tuning("checksum_hybrid_threads", keep) == SD_OK);
+    std::vector<std::thread> th;
+    for (int t = 0; t < 4; t++)
+        th.emplace_back([&lr, t] {
+            for (int k = 0; k < 200; k++) {
+                const int r = lr.begin(8);
+                lr.record(r, 1000000 * (uint64_t)(t + r + 1), clk::now() - std::chrono::milliseconds(1));
+                (void)lr.snapshot();
+            }
+        });
+    for (auto& x : th) x.join();
+    snap = lr.snapshot();
+    CHECK(snap.seen[0] + snap.seen[1] == 800 && snap.calls == 798);
+}
+
+// ---- the claim protocols (sd_host.h): every item and block to exactly one side, under threads
+struct Marks {  // who claimed what: hits per index, and the side (1 front, 2 back) that did
+    std::vector<std::atomic<int>> hits, side;
+    explicit Marks(size_t n) : hits(n), side(n) {}
+    void mark(size_t a, size_t b, int s) {
+        for (size_t q = a; q < b; q++) {
+            hits[q]++;
+            side[q] = s;
+        }
+    }
+    // each once, the front's a prefix and the back's the suffix that meets it
+    bool split_once() const {
+        size_t q = 0;
+        while (q < hits.size() && side[q] == 1) q++;
+        for (size_t k = q; k < hits.size(); k++)
+            if (side[k] != 2) return false;
+        for (auto& h : hits)
+            if (h != 1) return false;
+        return true;
+    }
+    bool none_twice() const {
+        for (auto& h : hits)
+            if (h > 1) return false;
+        return true;
+    }
+};
+
+void test_end_claims_plain() {
+    for (size_t n : {0, 1, 2, 255, 256, 257, 8192})
+        for (int nback : {1, 3, 15}) {
+            EndClaims c(n);
+            Marks m(n);
+            // the back threads start behind a gate that opens after the front's first window;
+            // the front then waits for the back's first claim (or for all of them to find
+            // nothing), so for a large n both sides are claiming while they approach each other
+            std::atomic<bool> go{false};
+            std::atomic<int> back_claims{0}, back_ended{0};
+            std::vector<std::thread> backs;
+            for (int t = 0; t < nback; t++)
+                backs.emplace_back([&] {
+                    while (!go) std::this_thread::yield();
+                    for (size_t a, b; c.back_claim(256, a, b, [](size_t, size_t) { return true; });) {
+                        CHECK(b - a <= 256 && a < b);
+                        m.mark(a, b, 2);
+                        back_claims++;
+                        std::this_thread::yield();
+                    }
+                    back_ended++;
+                });
+            std::mt19937 rng((unsigned)(n * 31 + nback));
+            size_t front_items = 0;
+            for (size_t gi = 0;;) {  // windows of seeded sizes, as sd_cas_ids grows them
+                const size_t want = 1 + rng() % 300;
+                const size_t gj = c.front_claim(gi, [&](size_t q) { return q - gi < want; });
+                go = true;
+                if (gj == gi) break;
+                m.mark(gi, gj, 1);
+                front_items += gj - gi;
+                gi = gj;
+                while (back_claims == 0 && back_ended < nback) std::this_thread::yield();
+                std::this_thread::yield();
+            }
+            for (auto& t : backs) t.join();
+            CHECK(m.split_once());
+            if (n == 8192) CHECK(front_items > 0 && back_claims > 0);  // (a first window is 300 items at most)
+        }
+    // where they meet, in one thread: the back's chunk ends at the front's claims
+    EndClaims c(10);
+    size_t a = 0, b = 0;
+    CHECK(c.front_claim(0, [](size_t q) { return q < 4; }) == 4);
+    CHECK(c.back_claim(256, a, b, [](size_t, size_t) { return true; }) && a == 4 && b == 10);
+    CHECK(!c.back_claim(256, a, b, [](size_t, size_t) { return true; }) && !c.front_claim(4));
+}
+
+// The skip rule and the shared item's hand-over, in one thread: the back takes everything
+// after the shared item, all its blocks, then an item before it; the front finds item 3
+// taken, skips to the shared item, gets no block and no wait.
+void test_end_claims_skip() {
+    const auto all = [](size_t, size_t) { return true; };
+    EndClaims c(9, 4, 100);
+    size_t b0 = 0, b1 = 0;
+    uint64_t u0 = 0, u1 = 100, w0 = 0, w1 = 0;
+    CHECK(!c.back_blocks(64, u0, u1));  // items after the shared one are unclaimed
+    CHECK(c.back_claim(SIZE_MAX, b0, b1, all) && b0 == 5 && b1 == 9);  // never the shared item
+    for (uint64_t top = 100; top > 0; top = u0) {
+        CHECK(c.back_blocks(64, u0, u1) && u1 == top && u0 == (top > 64 ? top - 64 : 0));
+        EndClaims::BlocksDone done{c};
+    }
+    CHECK(!c.back_blocks(64, u0, u1));
+    CHECK(c.back_claim(1, b0, b1, all) && b0 == 3 && b1 == 4);
+    CHECK(c.front_claim(0) && c.front_claim(1) && c.front_claim(2) && !c.front_claim(3));
+    CHECK(c.front_skip(3) == 4 && c.front_claim(4));
+    CHECK(!c.front_blocks(256, w0, w1) && c.wait_back_blocks() == 0);
+    CHECK(c.front_skip(4) == EndClaims::NONE && !c.front_claim(5) && !c.back_claim(1, b0, b1, all));
+}
+
+// The front loop of sd_checksums over an EndClaims with a shared item, recording into m
+// (items) and mb (the shared item's blocks); stops where the claims stop it.  Returns how often
+// it reached the shared item.
+int drive_front(EndClaims& c, size_t n, size_t sh, Marks& m, Marks& mb, const std::atomic<bool>* stopped = nullptr) {
+    int visits = 0;
+    for (size_t i = 0; i < n;) {
+        const bool was_stopped = stopped && stopped->load();
+        if (!c.front_claim(i)) {
+            if ((i = c.front_skip(i)) == EndClaims::NONE) break;
+            continue;
+        }
+        CHECK(!was_stopped);
+        if (i == sh) {
+            visits++;
+            uint64_t sf = 0;
+            for (;;) {
+                const bool s = stopped && stopped->load();
+                uint64_t w0, w1;
+                if (!c.front_blocks(256, w0, w1)) break;
+                CHECK(!s && w0 == sf && w1 > w0 && w1 - w0 <= 256);
+                mb.mark(w0, w1, 1);
+                sf = w1;
+            }
+            const uint64_t sb = c.wait_back_blocks();
+            if (!stopped) CHECK(sf == sb);  // the two sides met
+            CHECK(sf <= sb);
+        } else {
+            m.mark(i, i + 1, 1);
+            std::this_thread::yield();
+        }
+        i++;
+    }
+    return visits;
+}
+
+// The back side as sd_checksums' host thread: the shared item's blocks 64 at a time, else
+// items (seeded group sizes).  `after_claim(k)` runs after its k-th claim.
+void drive_back(EndClaims& c, size_t sh, Marks& m, Marks& mb, unsigned seed, std::atomic<int>& open,
+                const std::function<void(int)>& after_claim, const std::atomic<bool>* stopped = nullptr) {
+    std::mt19937 rng(seed);
+    for (int k = 0;; k++) {
+        const bool was_stopped = stopped && stopped->load();
+        uint64_t u0, u1;
+        size_t b0, b1;
+        if (c.back_blocks(64, u0, u1)) {
+            EndClaims::BlocksDone done{c};
+            open++;
+            CHECK(!was_stopped && u1 > u0 && u1 - u0 <= 64);
+            // granted only once every item after the shared one is claimed (this thread, the
+            // only one at the back, has marked them)
+            for (size_t q = sh + 1; q < m.hits.size(); q++) CHECK(m.hits[q] == 1);
+            mb.mark(u0, u1, 2);
+            open--;  // before the done-marker
+        } else if (c.back_claim(SIZE_MAX, b0, b1, [&](size_t, size_t) { return rng() % 3 != 0; })) {
+            CHECK(!was_stopped && b1 > b0 && !(b0 <= sh && sh < b1));
+            m.mark(b0, b1, 2);
+        } else {
+            return;
+        }
+        after_claim(k);
+    }
+}
+
+void test_end_claims_shared() {
+    const size_t n = 9;
+    for (size_t sh : {(size_t)0, n / 2, n - 1})
+        for (uint64_t nb : {2, 31, 32, 33, 64, 65, 256, 1025}) {
+            EndClaims c(n, sh, nb);
+            Marks m(n), mb(nb);
+            std::atomic<int> open{0};
+            // for odd nb the front starts after the back's first claim, for even nb at once
+            std::atomic<bool> back_began{nb % 2 == 0};
+            std::thread back([&] {
+                drive_back(c, sh, m, mb, (unsigned)(nb + sh), open, [&](int) { back_began = true; });
+                back_began = true;
+            });
+            while (!back_began) std::this_thread::yield();
+            CHECK(drive_front(c, n, sh, m, mb) == 1);  // the shared item reached once, skipped to if need be
+            CHECK(open == 0);  // wait_back_blocks came back after every done-marker
+            back.join();
+            for (size_t q = 0; q < n; q++) CHECK(m.hits[q] == (q == sh ? 0 : 1));  // the shared item is nobody's whole
+            CHECK(mb.split_once());  // its blocks: each once, the front's [0, sf), the back's [sb, nb), sf == sb
+        }
+    // wait_back_blocks does not pass a back claim that is still open
+    EndClaims c(1, 0, 128);
+    uint64_t u0 = 0, u1 = 0, w0 = 0, w1 = 0;
+    CHECK(c.back_blocks(64, u0, u1) && u0 == 64 && u1 == 128);
+    std::unique_ptr<EndClaims::BlocksDone> held(new EndClaims::BlocksDone{c});
+    CHECK(c.front_claim(0));
+    while (c.front_blocks(256, w0, w1)) {
+    }
+    CHECK(w1 == 64 && !c.back_blocks(64, u0, u1));
+    std::atomic<bool> passed{false};
+    std::thread waiter([&] {
+        CHECK(c.wait_back_blocks() == 64);
+        passed = true;
+    });
+    std::this_thread::sleep_for(std::chrono::milliseconds(20));
+    CHECK(!passed);
+    held.reset();  // the done-marker runs
+    waiter.join();
+    CHECK(passed);
+}
+
+void test_end_claims_stops() {
+    const size_t n = 64;
+    for (size_t sh : {EndClaims::NONE, (size_t)20})
+        for (unsigned seed : {1u, 2u, 3u}) {
+            const uint64_t nb = sh == EndClaims::NONE ? 0 : 300;
+            const int at = (int)(std::mt19937(seed)() % 6);
+            std::atomic<int> open{0};
+            {  // stop_back mid-run: the back gets nothing more, the front everything not yet claimed
+                EndClaims c(n, sh, nb);
+                Marks m(n), mb(nb);
+                // taken after the back's at-th claim, of the twenty or so it would make alone;
+                // the front starts then
+                std::atomic<bool> stopped{false}, back_done{false};
+                std::thread back([&] {
+                    drive_back(c, sh, m, mb, seed, open, [&](int k) {
+                        if (k != at) return;
+                        c.stop_back();
+                        stopped = true;
+                        uint64_t u0, u1;
+                        size_t b0, b1;
+                        CHECK(!c.back_blocks(64, u0, u1));
+                        CHECK(!c.back_claim(SIZE_MAX, b0, b1, [](size_t, size_t) { return true; }));
+                    }, &stopped);
+                    back_done = true;
+                });
+                while (!stopped && !back_done) std::this_thread::yield();
+                CHECK(stopped);
+                size_t back_items = 0, back_blocks = 0;  // what the back holds at the stop
+                for (auto& h : m.hits) back_items += h;
+                for (auto& h : mb.hits) back_blocks += h;
+                CHECK(back_items + back_blocks > 0 && back_items < n - 1);
+                CHECK(drive_front(c, n, sh, m, mb) == (sh == EndClaims::NONE ? 0 : 1));
+                back.join();
+                for (size_t q = 0; q < n; q++) CHECK(m.hits[q] == (q == sh ? 0 : 1));
+                CHECK(nb == 0 || mb.split_once());  // the front's blocks reach up to where the back stood
+            }
+            {  // stop_front after the back's at-th claim: no front claim succeeds from then on
+                EndClaims c(n, sh, nb);
+                Marks m(n), mb(nb);
+                std::atomic<bool> stopped{false}, started{false};
+                std::thread back([&] {
+                    drive_back(c, sh, m, mb, seed, open, [&](int k) {
+                        started = true;
+                        if (k != at) return;
+                        c.stop_front();
+                        stopped = true;
+                    });
+                    started = true;
+                });
+                while (!started) std::this_thread::yield();
+                drive_front(c, n, sh, m, mb, &stopped);
+                back.join();
+                if (stopped) CHECK(!c.front_claim(0) && c.front_skip(0) == EndClaims::NONE);
+                CHECK(m.none_twice() && mb.none_twice());
+            }
+        }
+}
+
+void test_block_queue() {
+    const std::vector<std::vector<uint64_t>> sets{{1}, {2, 1, 33}, {32, 32, 32}, {1000, 7}};
+    for (const auto& counts : sets)
+        for (int threads : {1, 4, 16}) {
+            std::vector<uint64_t> fb(counts.size() + 1, 0);
+            for (size_t q = 0; q < counts.size(); q++) fb[q + 1] = fb[q] + counts[q];
+            BlockQueue bq(fb, threads);
+            std::mutex mu;  // the caller's lock, as split_checksums_blocks' slot lock: ask and claim are one step
+            Marks m(fb.back());
+            std::vector<std::thread> th;
+            for (int t = 0; t < threads; t++)
+                th.emplace_back([&, t] {
+                    size_t q;
+                    uint64_t b0, b1;
+                    // half of the threads ask as a GPU slot does, half for one block (one thread: in turn)
+                    for (int k = 0;; k++) {
+                        {
+                            std::lock_guard<std::mutex> g(mu);
+                            const uint64_t left = bq.left();
+                            const bool gpu = (threads == 1 ? k : t) % 2 == 0;
+                            if (gpu) CHECK(bq.gpu_run() == std::max<uint64_t>(4, std::min<uint64_t>(32, left / (2 * threads))));
+                            if (!bq.claim(gpu ? bq.gpu_run() : 1, q, b0, b1)) break;
+                            CHECK(bq.left() == left - (b1 - b0));
+                        }
+                        CHECK(q < counts.size() && b0 < b1 && b1 <= counts[q] && b1 - b0 <= BlockQueue::GPU_RUN);
+                        m.mark(fb[q] + b0, fb[q] + b1, 1);
+                    }
+                });
+            for (auto& x : th) x.join();
+            CHECK(m.split_once() && bq.left() == 0);
+        }
+}
+
+// plan_range_window over [0, limit) of a range list (the claim refuses from `limit` on), as
+// sd_checksums' loop calls it; ranges too long for a window are the streamed route's
+void check_range_windows(const std::vector<uint64_t>& offs, const std::vector<uint64_t>& lens, uint64_t W,
+                         size_t limit) {
+    const size_t n = offs.size();
+    std::vector<int> taken(n, 0);
+    RangeWindow w;
+    for (size_t i = 0; i < limit;) {
+        if (lens[i] + 128 > W) {
+            taken[i++]++;
+            continue;
+        }
+        const size_t j = plan_range_window(offs.data(), lens.data(), i, n, W, [&](size_t q) { return q < limit; }, w);
+        CHECK(j > i && j <= limit && w.offs.size() == j - i && w.lens.size() == j - i && !w.runs.empty());
+        if (j <= i) return;
+        uint64_t dev_hi = 0, run_end = 0;  // run_end: the current run's host end before this range
+        std::vector<size_t> run_of(j - i, SIZE_MAX);
+        for (size_t t = 0, ri = 0; t < j - i; t++) {
+            const uint64_t o = offs[i + t], L = lens[i + t], d = w.offs[t];
+            taken[i + t]++;
+            CHECK(w.lens[t] == L);
+            // its run: the current one, or the next if this range opens it
+            const bool opens = t == 0 || (ri + 1 < w.runs.size() && w.runs[ri + 1].host_lo == o && w.runs[ri + 1].dev_lo == d);
+            if (t && opens) ri++;
+            const RangeWindow::Run& r = w.runs[ri];
+            run_of[t] = ri;
+            CHECK(o >= r.host_lo && o + L <= r.host_end && d - r.dev_lo == o - r.host_lo);  // device distance = host distance
+            // a leaf block or more that starts at or after its run's end (so it could have
+            // opened a run) lies on a 128-B device line, whether it opened one or not
+            if (L >= SD_CK_BLOCK && (opens || o >= run_end)) CHECK(d % 128 == 0);
+            run_end = opens ? o + L : std::max(run_end, o + L);
+            dev_hi = std::max(dev_hi, sd_align_up(d + L, 64));
+        }
+        CHECK(dev_hi <= W || j - i == 1);
+        CHECK(run_of.back() + 1 == w.runs.size());
+        for (size_t ri = 0; ri < w.runs.size(); ri++) {  // no copied page that no range of the run touches
+            const RangeWindow::Run& r = w.runs[ri];
+            const uint64_t p0 = r.host_lo / 4096;
+            std::vector<bool> touched((r.host_end + 4095) / 4096 - p0, false);
+            for (size_t t = 0; t < j - i; t++)
+                if (run_of[t] == ri && lens[i + t])
+                    for (uint64_t p = offs[i + t] / 4096; p <= (offs[i + t] + lens[i + t] - 1) / 4096; p++)
+                        touched[p - p0] = true;
+            for (size_t p = 0; p < touched.size(); p++)
+                CHECK(touched[p] || (p0 + p) * 4096 < r.host_lo || (p0 + p + 1) * 4096 > r.host_end);
+        }
+        i = j;
+    }
+    for (size_t q = 0; q < n; q++) CHECK(taken[q] == (q < limit ? 1 : 0));
+}
+
+void test_range_windows() {
+    const uint64_t MiB = 1 << 20, page = 4096;
+    std::vector<std::pair<std::vector<uint64_t>, std::vector<uint64_t>>> layouts;
+    {  // every layout a caller may use: 16-byte starts, gaps of 0-128 bytes, a range again, one before the last
+        std::mt19937 rng(355);
+        std::vector<uint64_t> offs, lens;
+        uint64_t off = 16;
+        for (uint64_t L : {MiB + 16, (uint64_t)7, 3 * MiB + 5, 2 * MiB, (uint64_t)100, 5 * MiB + 1, 64 * MiB + 48,
+                           (uint64_t)1025, 130 * MiB + 3, 90 * MiB + 16, 2 * MiB + 1}) {
+            offs.push_back(off);
+            lens.push_back(L);
+            off = (off + L + 16 * (rng() % 9) + 15) / 16 * 16;
+        }
+        for (auto ol : {std::make_pair(offs[2], lens[2]), std::make_pair(offs[1], lens[1]),
+                        std::make_pair((uint64_t)48, 4 * MiB + 9)}) {
+            offs.push_back(ol.first);
+            lens.push_back(ol.second);
+        }
+        layouts.emplace_back(offs, lens);
+    }
+    // ranges that end at a guard page: the buffer starts so that the last one ends on a page boundary
+    using V = std::vector<uint64_t>;
+    for (const V& lens : {V{3, 1000, 4096 + 16}, V{300 * MiB + 16}, V{5, MiB + 16, 3 * MiB + 7, 2 * MiB + 16}}) {
+        std::vector<uint64_t> offs;
+        uint64_t off = 0;
+        for (uint64_t L : lens) {
+            off = (off + 15) / 16 * 16;
+            offs.push_back(off);
+            off += L;
+        }
+        const uint64_t start = (off + page - 1) / page * page - off;
+        for (auto& o : offs) o += start;
+        layouts.emplace_back(offs, lens);
+    }
+    // ranges on both sides of an unreadable page (page 3)
+    layouts.emplace_back(std::vector<uint64_t>{2 * page + 16, 2 * page + 1024, 3 * page - 48, 4 * page, 4 * page + 80,
+                                               5 * page + 16},
+                         std::vector<uint64_t>{100, 2000, 48, 64, 1000, page - 32});
+    for (const auto& l : layouts)
+        for (uint64_t W : {256 * MiB, 8 * MiB, MiB + page, 2 * page})
+            for (size_t limit : {l.first.size(), l.first.size() / 2}) check_range_windows(l.first, l.second, W, limit);
 }
 
 int main() {
@@ -1037,7 +1451,16 @@ int main() {
     test_coalescer();
     test_exchange_plan();
     test_shared_range_pick();
+    const int failed_before = g_fail;
     test_split_routes();
+    test_end_claims_plain();
+    test_end_claims_skip();
+    test_end_claims_shared();
+    test_end_claims_stops();
+    test_block_queue();
+    test_range_windows();
+    printf("claim protocols (LearnedRoute, EndClaims plain / shared / stops, BlockQueue, plan_range_window): %s\n",
+           g_fail == failed_before ? "ok" : "FAILED");
     test_comm_group();
     test_private_fd_tables();
     test_hip_thread_rule();

@@ -291,13 +291,10 @@ struct sd_cas_ctx {
     std::atomic<uint64_t> fp_h2d_bytes{0}, fp_gathered{0}, fp_large{0};
     // sd_dedup_confirm: calls that finished on the prefix path, calls that took the full-width path
     std::atomic<uint64_t> confirm_calls_prefix{0}, confirm_calls_full{0};
-    std::mutex split_mu;
-    SplitRoutes split_routes;  // sd_file_checksums: the split or the CPU path, learned (sd_host.h)
-    uint64_t split_routes_gen = 0;  // split_route_tuning_gen() the rates were learned under
+    LearnedRoute split_route;  // sd_file_checksums: the split or the CPU path, learned (sd_host.h)
     // sd_checksums' co-hashed calls: the GPU + host threads, or the CPU path alone, learned
-    // the same way (route 0 = co-hash, 1 = CPU path; under split_mu)
-    SplitRoutes cohash_routes;
-    uint64_t cohash_routes_gen = 0;
+    // the same way (route 0 = co-hash, 1 = CPU path)
+    LearnedRoute cohash_route;
     std::mutex pool_mu;
     // Reader threads.  stage_pool: tasks that open and close their own files (the cas
     // stager, checksum packs), on private fd tables (stage_pool.h); io_pool: parallel preads

@@ -409,28 +409,15 @@ int sd_cas_ids(sd_cas_ctx* ctx, const uint8_t* staged, uint64_t staged_bytes, co
     // already in host memory, so feeding the GPU costs the host almost nothing (DMA), and the
     // call is bound by PCIe; h host threads hash files from the END of the list on the CPU
     // path meanwhile, claiming chunks of files, while the windows for the GPU are claimed
-    // from the front -- under one lock, so the two meet wherever their rates put them.
+    // from the front -- under one lock (EndClaims), so the two meet wherever their rates put them.
     // (never more host threads than the process's host budget, less one for this thread)
     const int cohash = std::max(0, std::min({64, tuning_get(SD_TUNE_HOST_COHASH_THREADS), host_cpu_budget() - 1}));
     constexpr size_t COHASH_MIN = 8192, COHASH_CHUNK = 256;
-    std::mutex claim_mu;
-    size_t back = live.size();  // live[back, end) is claimed by the host threads
-    size_t front = 0;           // live[0, front) is claimed by the GPU windows
+    EndClaims claims(live.size());  // over live[]: the back is the host threads', the front the GPU windows'
     std::atomic<uint64_t> host_files{0};
     std::vector<std::thread> hosts;
-    struct Join {
-        std::vector<std::thread>& t;
-        std::mutex& mu;
-        size_t& back;
-        ~Join() {  // on an exception below: stop claiming, then wait
-            {
-                std::lock_guard<std::mutex> g(mu);
-                back = 0;
-            }
-            for (auto& x : t)
-                if (x.joinable()) x.join();
-        }
-    } join_hosts{hosts, claim_mu, back};  // declared after everything the threads touch
+    // on an exception below: stop claiming, then wait; declared after everything the threads touch
+    EndClaims::StopBack join_hosts{claims, hosts};
     // while co-hashing, the GPU claims 128 MiB windows (~2 ms of PCIe each), so a mid-size
     // call is not taken whole by its first window before the host threads have started
     uint64_t window = WINDOW;
@@ -439,15 +426,7 @@ int sd_cas_ids(sd_cas_ctx* ctx, const uint8_t* staged, uint64_t staged_bytes, co
         for (int t = 0; t < cohash; t++)
             hosts.emplace_back([&] {
                 library_thread_place();  // the device's NUMA node (sd_host.h)
-                for (;;) {
-                    size_t a, b;
-                    {
-                        std::lock_guard<std::mutex> g(claim_mu);
-                        if (back <= front) return;
-                        b = back;
-                        a = b - std::min(COHASH_CHUNK, b - front);
-                        back = a;
-                    }
+                for (size_t a, b; claims.back_claim(COHASH_CHUNK, a, b, [](size_t, size_t) { return true; });) {
                     // 64 files at a time, their chunks packed across the SIMD lanes together
                     for (size_t q0 = a; q0 < b; q0 += 64) {
                         const size_t k = std::min<size_t>(64, b - q0);
@@ -474,20 +453,15 @@ int sd_cas_ids(sd_cas_ctx* ctx, const uint8_t* staged, uint64_t staged_bytes, co
     for (int w = 0;; w ^= 1) {
         harvest(w);  // frees slot w (its previous window is done)
         uint64_t lo = UINT64_MAX, hi = 0;
-        size_t gj = gi;
-        {
-            std::lock_guard<std::mutex> g(claim_mu);
-            while (gj < back) {
-                const sd_extent& e = extents[live[gj]];
-                const uint64_t nlo = std::min(lo, e.msg_offset);
-                const uint64_t nhi = std::max(hi, align_up(e.msg_offset + e.msg_len, SD_STAGE_PAD));
-                if (gj > gi && nhi - nlo > window) break;
-                lo = nlo;
-                hi = nhi;
-                gj++;
-            }
-            front = gj;
-        }
+        const size_t gj = claims.front_claim(gi, [&](size_t q) {
+            const sd_extent& e = extents[live[q]];
+            const uint64_t nlo = std::min(lo, e.msg_offset);
+            const uint64_t nhi = std::max(hi, align_up(e.msg_offset + e.msg_len, SD_STAGE_PAD));
+            if (q > gi && nhi - nlo > window) return false;
+            lo = nlo;
+            hi = nhi;
+            return true;
+        });
         if (gj == gi) break;  // the host threads hold the rest
         if (hi > staged_bytes) throw sd_failure(SD_ERR_INVALID, "extent beyond staged_bytes");
         ext.clear();
@@ -591,15 +565,17 @@ int sd_file_checksums_bytes(sd_cas_ctx* ctx, uint64_t out[2]) {
     SD_GUARD_END
 }
 
-int sd_file_checksums_learned(sd_cas_ctx* ctx, double out[4]) {
-    SD_GUARD_BEGIN
-    if (!ctx || !out) throw sd_failure(SD_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> g(ctx->split_mu);
-    const SplitRoutes& r = ctx->split_routes;
+static void learned_out(const SplitRoutes& r, double out[4]) {
     out[0] = r.rate[0];
     out[1] = r.rate[1];
     out[2] = (double)r.n[0];
     out[3] = (double)r.n[1];
+}
+
+int sd_file_checksums_learned(sd_cas_ctx* ctx, double out[4]) {
+    SD_GUARD_BEGIN
+    if (!ctx || !out) throw sd_failure(SD_ERR_INVALID, "null argument");
+    learned_out(ctx->split_route.snapshot(), out);
     return SD_OK;
     SD_GUARD_END
 }
@@ -607,12 +583,7 @@ int sd_file_checksums_learned(sd_cas_ctx* ctx, double out[4]) {
 int sd_checksums_learned(sd_cas_ctx* ctx, double out[4]) {
     SD_GUARD_BEGIN
     if (!ctx || !out) throw sd_failure(SD_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> g(ctx->split_mu);
-    const SplitRoutes& r = ctx->cohash_routes;
-    out[0] = r.rate[0];
-    out[1] = r.rate[1];
-    out[2] = (double)r.n[0];
-    out[3] = (double)r.n[1];
+    learned_out(ctx->cohash_route.snapshot(), out);
     return SD_OK;
     SD_GUARD_END
 }

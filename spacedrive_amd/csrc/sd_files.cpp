@@ -750,7 +750,6 @@ void split_checksums_blocks(sd_cas_ctx* ctx, const char* const* paths, char* out
                             int threads, int gpu_slots, const std::vector<size_t>& big,
                             const std::vector<size_t>& rest, const std::vector<uint64_t>& hint) {
     ctx->bind();
-    constexpr uint64_t GPU_RUN = 32;  // blocks per GPU claim while plenty is left
     const size_t nf = big.size();
     // one plan over every large file: file q's blocks are CV slots [fb[q], fb[q+1]) and its
     // message bytes sit at the virtual offset fb[q] MiB, so a window holding its blocks
@@ -805,8 +804,8 @@ void split_checksums_blocks(sd_cas_ctx* ctx, const char* const* paths, char* out
     h_cv.ensure(nb_total * 32);
     for (auto& x : sl.g) {
         x.s = ctx->acquire();
-        x.s->window.ensure(GPU_RUN * SD_CK_BLOCK + 128);
-        x.s->staged.ensure(GPU_RUN * SD_CK_BLOCK + 128);
+        x.s->window.ensure(BlockQueue::GPU_RUN * SD_CK_BLOCK + 128);
+        x.s->staged.ensure(BlockQueue::GPU_RUN * SD_CK_BLOCK + 128);
         HIP_CHECK(hipEventCreateWithFlags(&x.copied, hipEventDisableTiming));
     }
     // a slot's run is done when the stream reaches this host function: it clears `busy`,
@@ -815,27 +814,20 @@ void split_checksums_blocks(sd_cas_ctx* ctx, const char* const* paths, char* out
     const hipHostFn_t slot_done = [](void* p) { static_cast<std::atomic<uint32_t>*>(p)->store(0, std::memory_order_release); };
 
     std::mutex mu, copy_mu;
-    size_t cf = 0;  // claim cursor: file cf, its block cb
-    uint64_t cb = 0, left = nb_total;
+    BlockQueue blocks(fb, threads);
     std::atomic<size_t> small_next{0};
     std::vector<uint8_t> failed(nf, 0);  // a short read: hashed again with the read loop
     std::atomic<uint64_t> gpu_bytes{0}, cpu_bytes{0};
     std::atomic<bool> stop{false};
     int err_rc = SD_OK;
     std::string err_msg;
-    // [b0, b1) of file q, at most `want` blocks (under mu)
-    auto claim = [&](uint64_t want, size_t& q, uint64_t& b0, uint64_t& b1) -> bool {
-        while (cf < nf && cb >= fb[cf + 1] - fb[cf]) {
-            cf++;
-            cb = 0;
+    auto fail = [&](int rc, const char* msg) {  // the first failure is the call's; every thread stops
+        std::lock_guard<std::mutex> g(mu);
+        if (err_rc == SD_OK) {
+            err_rc = rc;
+            err_msg = msg;
         }
-        if (cf >= nf) return false;
-        q = cf;
-        b0 = cb;
-        b1 = std::min(fb[cf + 1] - fb[cf], cb + want);
-        cb = b1;
-        left -= b1 - b0;
-        return true;
+        stop.store(true);
     };
     auto worker = [&](size_t) {
         int fd = -1;               // this thread's descriptor of file fd_q, kept across its claims
@@ -856,12 +848,10 @@ void split_checksums_blocks(sd_cas_ctx* ctx, const char* const* paths, char* out
                 uint64_t b0 = 0, b1 = 0;
                 {
                     std::lock_guard<std::mutex> g(mu);
-                    if (left > 0)
+                    if (blocks.left() > 0)
                         for (int j = 0; j < (int)sl.g.size() && k < 0; j++)
                             if (!sl.g[j].filling && sl.g[j].busy.load(std::memory_order_acquire) == 0) k = j;
-                    // the GPU's runs shrink towards the end, so its last ones finish with the host's
-                    if (k >= 0 && claim(std::max<uint64_t>(4, std::min<uint64_t>(GPU_RUN, left / (2 * (uint64_t)threads))),
-                                        q, b0, b1)) {
+                    if (k >= 0 && blocks.claim(blocks.gpu_run(), q, b0, b1)) {
                         sl.g[k].filling = true;
                         sl.g[k].busy.store(1, std::memory_order_relaxed);
                     } else {
@@ -907,7 +897,7 @@ void split_checksums_blocks(sd_cas_ctx* ctx, const char* const* paths, char* out
                 }
                 {
                     std::lock_guard<std::mutex> g(mu);
-                    if (!claim(1, q, b0, b1)) break;
+                    if (!blocks.claim(1, q, b0, b1)) break;
                     if (failed[q]) continue;
                 }
                 const int f = file(q);
@@ -919,19 +909,9 @@ void split_checksums_blocks(sd_cas_ctx* ctx, const char* const* paths, char* out
                 cpu_bytes.fetch_add(std::min(SD_CK_BLOCK, files[q].len - b0 * SD_CK_BLOCK), std::memory_order_relaxed);
             }
         } catch (const sd_failure& e) {
-            std::lock_guard<std::mutex> g(mu);
-            if (err_rc == SD_OK) {
-                err_rc = e.rc;
-                err_msg = e.what();
-            }
-            stop.store(true);
+            fail(e.rc, e.what());
         } catch (...) {
-            std::lock_guard<std::mutex> g(mu);
-            if (err_rc == SD_OK) {
-                err_rc = SD_ERR_NOMEM;
-                err_msg = "host allocation failed in a split sd_file_checksums call";
-            }
-            stop.store(true);
+            fail(SD_ERR_NOMEM, "host allocation failed in a split sd_file_checksums call");
         }
         if (fd >= 0) close(fd);
     };
@@ -962,6 +942,298 @@ void split_checksums_blocks(sd_cas_ctx* ctx, const char* const* paths, char* out
             status[i] = cpu_checksum_file(paths[i], out_hex65 + 65 * i);
         }
     }
+}
+
+// Round 4's split ("checksum_split_blocks" 0): the GPU route on `hyb` reader threads and the
+// CPU path on the rest on a second host thread, whole large files to whichever is free next
+// (one shared cursor over `big`, largest first).
+void split_checksums_files(sd_cas_ctx* ctx, const char* const* paths, char* out_hex65, int32_t* status, int threads,
+                           int hyb, const std::vector<size_t>& big, const std::vector<size_t>& rest,
+                           const std::vector<uint64_t>& hint, const std::vector<uint8_t>& regular) {
+    {
+        // the GPU route's two windows exist before the two sides race for files (the context
+        // hands the same slots out again below): growing them, 256 MiB of pinned memory each,
+        // took longer than the CPU half needs for a whole small call, which then ran on
+        // threads - hyb threads alone
+        ctx->bind();
+        SlotPair warm(ctx);
+        Streamer::prepare(warm);
+    }
+    std::atomic<size_t> cursor{0};
+    auto next_big = [&]() -> size_t {
+        const size_t k = cursor.fetch_add(1, std::memory_order_relaxed);
+        return k < big.size() ? big[k] : SIZE_MAX;
+    };
+    const int cpu_threads = threads - hyb;
+    int cpu_rc = SD_OK;
+    std::string cpu_err;
+    std::thread cpu([&] {
+        library_thread_place();  // the device's NUMA node (sd_host.h)
+        // one CPU-path call over files `idx`, `bytes` in all; false stops both routes
+        auto cpu_call = [&](const std::vector<size_t>& idx, uint64_t bytes) {
+            ctx->checksum_bytes_cpu_split.fetch_add(bytes, std::memory_order_relaxed);
+            std::vector<const char*> p(idx.size());
+            std::vector<char> hex(idx.size() * 65);
+            std::vector<int32_t> st(idx.size());
+            for (size_t q = 0; q < idx.size(); q++) p[q] = paths[idx[q]];
+            cpu_rc = sd_cpu_file_checksums(p.data(), idx.size(), hex.data(), st.data(), cpu_threads);
+            if (cpu_rc != SD_OK) {
+                cpu_err = sd_cas_last_error();
+                cursor.store(big.size());  // stop the GPU route at its next file
+                return false;
+            }
+            for (size_t q = 0; q < idx.size(); q++) {
+                status[idx[q]] = st[q];
+                memcpy(out_hex65 + 65 * idx[q], hex.data() + 65 * q, 65);
+            }
+            return true;
+        };
+        try {
+            if (!rest.empty()) {  // the small and non-regular files: one CPU-path call
+                uint64_t rest_bytes = 0;
+                for (size_t i : rest) rest_bytes += hint[i];
+                if (!cpu_call(rest, rest_bytes)) return;
+            }
+            // then large files, as they come.  The CPU path hashes a file's 1 MiB blocks on
+            // all its threads and idles them at the file's last blocks, so it claims files
+            // until it holds about 16 MiB per thread (the large ones come first, singly; the
+            // smaller tail of the list a few at a time)
+            const uint64_t group_bytes = (uint64_t)cpu_threads << 24;
+            for (std::vector<size_t> grp;; grp.clear()) {
+                uint64_t bytes = 0;
+                for (size_t i; bytes < group_bytes && (i = next_big()) != SIZE_MAX;) {
+                    grp.push_back(i);
+                    bytes += hint[i];
+                }
+                if (grp.empty() || !cpu_call(grp, bytes)) return;
+            }
+        } catch (...) {  // an allocation here: nothing may escape a thread
+            cpu_rc = SD_ERR_NOMEM;
+            cpu_err = "host allocation failed in the CPU half of a split sd_file_checksums call";
+            cursor.store(big.size());
+        }
+    });
+    try {
+        gpu_file_checksums(ctx, paths, out_hex65, status, hyb, hint, regular, [&]() -> size_t {
+            const size_t i = next_big();
+            if (i != SIZE_MAX) ctx->checksum_bytes_gpu.fetch_add(hint[i], std::memory_order_relaxed);
+            return i;
+        });
+    } catch (...) {
+        cursor.store(big.size());  // the CPU thread takes no further file
+        cpu.join();
+        throw;
+    }
+    cpu.join();
+    if (cpu_rc != SD_OK) throw sd_failure(cpu_rc, cpu_err);
+}
+
+// ------------------------------------------------------- sd_checksums (ranges of host memory)
+struct HostRanges {  // a call's arguments
+    const uint8_t* data;
+    const uint64_t *offsets, *lens;
+    size_t n;
+    char* out_hex65;
+};
+
+// The call's two slots.  Copies on one queue (copy_stream), kernels on the two slots' streams,
+// joined by events: copied[k] = slot k's window has landed; used[k] = slot k's kernels no
+// longer read it.
+struct RangePipe {
+    struct Event {
+        hipEvent_t e = nullptr;
+        ~Event() {
+            if (e) (void)hipEventDestroy(e);
+        }
+    };
+    SlotPair slots;
+    sd_checksum_batch big;  // the plan of a range hashed by itself (shared or streamed)
+    hipStream_t cs;
+    Event copied[2], used[2];
+    bool used_set[2] = {false, false};
+    int cur = 0;
+    struct Pending {  // a packed window's ranges [i0, i1), their hashes on the way home
+        size_t i0 = 0, i1 = 0;
+        bool busy = false;
+    } pend[2];
+    const HostRanges r;
+
+    RangePipe(sd_cas_ctx* ctx, const HostRanges& ranges) : slots(ctx), cs(slots.copy_stream()), r(ranges) {
+        Streamer::prepare(slots);
+        for (int k = 0; k < 2; k++) {
+            HIP_CHECK(hipEventCreateWithFlags(&copied[k].e, hipEventDisableTiming));
+            HIP_CHECK(hipEventCreateWithFlags(&used[k].e, hipEventDisableTiming | hipEventBlockingSync));
+        }
+    }
+    void harvest(int k) {
+        if (!pend[k].busy) return;
+        slots[k].sync();
+        const uint8_t* h = slots[k].host_hashes.u8();
+        for (size_t i = pend[k].i0; i < pend[k].i1; i++) to_hex(h + 32 * (i - pend[k].i0), 32, r.out_hex65 + 65 * i);
+        pend[k].busy = false;
+    }
+    // H2D of `bytes` from `src` to byte `dst` of slot k's device window, after its previous
+    // kernels (first piece of a window) / before its next kernels (last piece)
+    void copy_in(int k, const uint8_t* src, uint64_t bytes, uint64_t dst = 0, bool first = true, bool last = true) {
+        if (first && used_set[k]) HIP_CHECK(hipStreamWaitEvent(cs, used[k].e, 0));
+        HIP_CHECK(hipMemcpyAsync(slots[k].staged.as<uint8_t>() + dst, src, bytes, hipMemcpyHostToDevice, cs));
+        if (!last) return;
+        HIP_CHECK(hipEventRecord(copied[k].e, cs));
+        HIP_CHECK(hipStreamWaitEvent(slots[k].stream, copied[k].e, 0));
+    }
+    void done_with(int k) {
+        HIP_CHECK(hipEventRecord(used[k].e, slots[k].stream));
+        used_set[k] = true;
+    }
+    // one range of L bytes by itself: its plan, for leaf_window and finish_big
+    void plan_big(uint64_t L) {
+        harvest(0);
+        harvest(1);
+        const uint64_t off0 = 0;
+        plan_checksum_batch(&big, &off0, &L, 1, nullptr);
+    }
+    // that range's bytes [pos, pos + here) from `src` through the next slot: the leaf CVs of
+    // its blocks [wg0, wg1)
+    void leaf_window(const uint8_t* src, uint64_t pos, uint64_t here, uint64_t wg0, uint64_t wg1) {
+        const int k = cur;
+        cur ^= 1;
+        copy_in(k, src + pos, here);
+        HIP_CHECK(sdk::launch_ck_leaf(slots[k].staged.as<uint8_t>(), pos, 0, big.d_files(), big.d_map() + wg0,
+                                      (uint32_t)(wg1 - wg0), big.lvl[0].as<uint32_t>(),
+                                      slots[k].hashes.as<uint32_t>(), slots[k].stream));
+        done_with(k);
+    }
+    // that range's root from its block CVs -- the host's, blocks [hb0, nb) of a shared range,
+    // first go beside the GPU's -- as hex
+    void finish_big(char* hex65, const uint8_t* host_cvs = nullptr, uint64_t hb0 = 0, uint64_t nb = 0) {
+        slots.sync_all();
+        Slot& sl = slots[0];
+        if (hb0 < nb)
+            HIP_CHECK(hipMemcpyAsync(big.lvl[0].as<uint8_t>() + 32 * hb0, host_cvs + 32 * hb0, 32 * (nb - hb0),
+                                     hipMemcpyHostToDevice, sl.stream));
+        run_checksum_reduce(&big, sl.hashes.as<uint32_t>(), sl.stream);
+        HIP_CHECK(hipMemcpyAsync(sl.host_hashes.p, sl.hashes.p, 32, hipMemcpyDeviceToHost, sl.stream));
+        sl.sync();
+        to_hex(sl.host_hashes.u8(), 32, hex65);
+    }
+
+    // The shared range i: windows of its blocks from the front until they meet the host's, then
+    // the reduce passes over both sides' block CVs.
+    void hash_shared_range(EndClaims& claims, size_t i, const std::vector<uint8_t>& host_cvs) {
+        const uint64_t L = r.lens[i];
+        plan_big(L);
+        for (uint64_t w0, w1;;) {
+            // claim at the device's pace, not the enqueue rate (the copies are async from
+            // pinned memory): slot cur's previous window must have been hashed first, so
+            // at most two windows are the GPU's ahead of the host's claims
+            if (used_set[cur]) HIP_CHECK(hipEventSynchronize(used[cur].e));
+            if (!claims.front_blocks(Streamer::BPW, w0, w1)) break;
+            const uint64_t pos = w0 * SD_CK_BLOCK;
+            leaf_window(r.data + r.offsets[i], pos, std::min(w1 * SD_CK_BLOCK, L) - pos, w0, w1);
+        }
+        const uint64_t hb0 = claims.wait_back_blocks();  // the host's claims are hashed
+        finish_big(r.out_hex65 + 65 * i, host_cvs.data(), hb0, (L + SD_CK_BLOCK - 1) / SD_CK_BLOCK);
+    }
+
+    // One large range i (more than a window), streamed window by window.
+    void hash_streamed_range(size_t i) {
+        const uint64_t L = r.lens[i];
+        plan_big(L);
+        const uint64_t nb = big.plan.wg_map.size();
+        for (uint64_t pos = 0; pos < L; pos += Streamer::W) {
+            // exactly the range's bytes: the kernels mask past a message's end, so nothing past
+            // it is read from `data`
+            const uint64_t wg0 = pos / SD_CK_BLOCK;
+            leaf_window(r.data + r.offsets[i], pos, std::min<uint64_t>(Streamer::W, L - pos), wg0,
+                        std::min<uint64_t>(nb, wg0 + Streamer::BPW));
+        }
+        finish_big(r.out_hex65 + 65 * i);
+    }
+
+    // The next packed window: consecutive ranges from i on whose device layout fits W
+    // (plan_range_window, sd_host.h), one H2D per run, hashed as one batch.  Returns the first
+    // range not taken.
+    size_t hash_packed_window(EndClaims& claims, size_t i, RangeWindow& w) {
+        const size_t j = plan_range_window(r.offsets, r.lens, i, r.n, Streamer::W,
+                                           [&](size_t q) { return claims.front_claim(q); }, w);
+        const int k = cur;
+        cur ^= 1;
+        harvest(k);
+        Slot& sl = slots[k];
+        plan_checksum_batch(&sl.ck, w.offs.data(), w.lens.data(), j - i, sl.stream);
+        sl.hashes.ensure((j - i) * 32);
+        sl.host_hashes.ensure((j - i) * 32);
+        for (size_t q = 0; q < w.runs.size(); q++)  // not past a run's last range: `data` may end there
+            copy_in(k, r.data + w.runs[q].host_lo, w.runs[q].host_end - w.runs[q].host_lo, w.runs[q].dev_lo, q == 0,
+                    q + 1 == w.runs.size());
+        run_checksum_batch(&sl.ck, sl.staged.as<uint8_t>(), sl.hashes.as<uint8_t>(), sl.stream);
+        done_with(k);
+        HIP_CHECK(hipMemcpyAsync(sl.host_hashes.p, sl.hashes.p, (j - i) * 32, hipMemcpyDeviceToHost, sl.stream));
+        pend[k] = Pending{i, j, true};
+        return j;
+    }
+};
+
+struct CoHost {  // what the co-hashing host thread leaves behind
+    int rc = SD_OK;
+    std::string err;
+    std::atomic<uint64_t> bytes{0};  // bytes it hashed (sd_checksums_stats)
+    std::vector<uint8_t> cvs;        // its block CVs of the shared range, 32 B at 32 * block
+};
+
+// sd_checksums' host thread: claims from the END -- the shared range's blocks, 64 at a time,
+// once every range after it is claimed; else one large range, or consecutive small ones up to
+// 64 MiB -- and hashes them with `threads` pool threads on the CPU path (a range of 8 MiB or
+// more block-parallel: its 1 MiB blocks' chaining values on all threads, then the root).
+void cohash_ranges(EndClaims& claims, const HostRanges& r, size_t shared, int threads, CoHost& host) {
+    constexpr uint64_t HOST_UNIT = 64;  // blocks per claim
+    library_thread_place();  // the device's NUMA node (sd_host.h)
+    try {
+        std::vector<uint8_t> h32, cvs;
+        for (;;) {
+            uint64_t u0, u1;
+            if (claims.back_blocks(HOST_UNIT, u0, u1)) {
+                EndClaims::BlocksDone done{claims};
+                cpu_block_cvs(r.data + r.offsets[shared], r.lens[shared], u0, u1, host.cvs.data(), threads);
+                host.bytes.fetch_add(std::min(u1 * SD_CK_BLOCK, r.lens[shared]) - u0 * SD_CK_BLOCK,
+                                     std::memory_order_relaxed);
+                continue;
+            }
+            // (the host reaches ranges before the shared one only once its blocks are gone)
+            size_t b0, b1;
+            uint64_t sum = 0;  // bytes of the ranges taken so far, [j + 1, end)
+            if (!claims.back_claim(SIZE_MAX, b0, b1, [&](size_t j, size_t end) {
+                    if (j + 2 == end) sum = r.lens[j + 1];  // only the last range is taken yet
+                    if (r.lens[j + 1] >= SD_CPU_SPLIT_MIN || r.lens[j] >= SD_CPU_SPLIT_MIN ||
+                        sum + r.lens[j] > (64ull << 20))
+                        return false;
+                    sum += r.lens[j];
+                    return true;
+                }))
+                return;
+            h32.resize((b1 - b0) * 32);
+            if (b1 - b0 == 1 && r.lens[b0] >= SD_CPU_SPLIT_MIN) {  // one large range, block-parallel
+                uint64_t o = 0, l = 0, cvb = 0;
+                check_rc(sd_split_range(r.lens[b0], 1, 0, &o, &l, &cvb));
+                cvs.resize(cvb);
+                check_rc(sd_cpu_split_leaves(r.data + r.offsets[b0], r.lens[b0], 1, 0, cvs.data(), threads));
+                check_rc(sd_cpu_split_root(cvs.data(), r.lens[b0], h32.data()));
+            } else {
+                check_rc(sd_cpu_checksums(r.data, r.offsets + b0, r.lens + b0, b1 - b0, h32.data(), threads));
+            }
+            for (size_t q = b0; q < b1; q++) {
+                to_hex(h32.data() + 32 * (q - b0), 32, r.out_hex65 + 65 * q);
+                host.bytes.fetch_add(r.lens[q], std::memory_order_relaxed);
+            }
+        }
+    } catch (const sd_failure& e) {
+        host.rc = e.rc;
+        host.err = e.what();
+    } catch (...) {
+        host.rc = SD_ERR_NOMEM;
+        host.err = "host allocation failed in a co-hashed sd_checksums call";
+    }
+    claims.stop_front();  // the GPU loop takes nothing further from here on: stop it
 }
 
 }  // namespace
@@ -1020,123 +1292,22 @@ int sd_file_checksums(sd_cas_ctx* ctx, const char* const* paths, size_t n, char*
             // ("checksum_split_adapt" k > 0: each route once, then the faster by its recent
             // GB/s, the other every k-th call; sd_host.h split_route_choose)
             const int adapt = std::max(0, tuning_get(SD_TUNE_CHECKSUM_SPLIT_ADAPT));
-            int route = 0;
-            if (adapt) {
-                std::lock_guard<std::mutex> g(ctx->split_mu);
-                // what either route's rate depends on: a change of it starts the learning again
-                const uint64_t gen = split_route_tuning_gen();
-                if (ctx->split_routes_gen != gen) {
-                    ctx->split_routes = SplitRoutes{};
-                    ctx->split_routes_gen = gen;
-                }
-                route = split_route_choose(ctx->split_routes, (uint32_t)adapt);
-            }
+            const int route = adapt ? ctx->split_route.begin((uint32_t)adapt) : 0;
             uint64_t call_bytes = 0;
             for (size_t q = 0; q < n; q++) call_bytes += hint[q];
-            auto learn = [&](int r) {
-                if (!adapt) return;
-                const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                std::lock_guard<std::mutex> g(ctx->split_mu);
-                split_route_record(ctx->split_routes, r, (double)call_bytes / std::max(s, 1e-9) / 1e9);
-            };
             if (route == 1) {
                 ctx->checksum_calls_cpu.fetch_add(1, std::memory_order_relaxed);
                 const int rc = sd_cpu_file_checksums(paths, n, out_hex65, status, threads);
-                if (rc == SD_OK) learn(1);
+                if (rc == SD_OK && adapt) ctx->split_route.record(1, call_bytes, t0);
                 return rc;
             }
             ctx->checksum_calls_hybrid.fetch_add(1, std::memory_order_relaxed);
             std::stable_sort(big.begin(), big.end(), [&](size_t a, size_t b) { return hint[a] > hint[b]; });
-            if (tuning_get(SD_TUNE_CHECKSUM_SPLIT_BLOCKS) != 0) {
+            if (tuning_get(SD_TUNE_CHECKSUM_SPLIT_BLOCKS) != 0)
                 split_checksums_blocks(ctx, paths, out_hex65, status, threads, hyb, big, rest, hint);
-                learn(0);
-                return SD_OK;
-            }
-            std::atomic<size_t> cursor{0};
-            auto next_big = [&]() -> size_t {
-                const size_t k = cursor.fetch_add(1, std::memory_order_relaxed);
-                return k < big.size() ? big[k] : SIZE_MAX;
-            };
-            const int cpu_threads = threads - hyb;
-            int cpu_rc = SD_OK;
-            std::string cpu_err;
-            std::thread cpu([&] {
-              library_thread_place();  // the device's NUMA node (sd_host.h)
-              try {
-                if (!rest.empty()) {  // the small and non-regular files: one CPU-path call
-                    std::vector<const char*> p(rest.size());
-                    std::vector<char> hex(rest.size() * 65);
-                    std::vector<int32_t> st(rest.size());
-                    uint64_t rest_bytes = 0;
-                    for (size_t q = 0; q < rest.size(); q++) {
-                        p[q] = paths[rest[q]];
-                        rest_bytes += hint[rest[q]];
-                    }
-                    ctx->checksum_bytes_cpu_split.fetch_add(rest_bytes, std::memory_order_relaxed);
-                    cpu_rc = sd_cpu_file_checksums(p.data(), rest.size(), hex.data(), st.data(), cpu_threads);
-                    if (cpu_rc != SD_OK) {
-                        cpu_err = sd_cas_last_error();
-                        cursor.store(big.size());  // stop the GPU route at its next file
-                        return;
-                    }
-                    for (size_t q = 0; q < rest.size(); q++) {
-                        status[rest[q]] = st[q];
-                        memcpy(out_hex65 + 65 * rest[q], hex.data() + 65 * q, 65);
-                    }
-                }
-                // then large files, as they come.  The CPU path hashes a file's 1 MiB blocks on
-                // all its threads and idles them at the file's last blocks, so it claims files
-                // until it holds about 16 MiB per thread (the large ones come first, singly; the
-                // smaller tail of the list a few at a time)
-                const uint64_t group_bytes = (uint64_t)cpu_threads << 24;
-                std::vector<size_t> grp;
-                std::vector<const char*> gp;
-                std::vector<char> ghex;
-                std::vector<int32_t> gst;
-                for (;;) {
-                    grp.clear();
-                    uint64_t bytes = 0;
-                    for (size_t i; bytes < group_bytes && (i = next_big()) != SIZE_MAX;) {
-                        grp.push_back(i);
-                        bytes += hint[i];
-                    }
-                    if (grp.empty()) break;
-                    ctx->checksum_bytes_cpu_split.fetch_add(bytes, std::memory_order_relaxed);
-                    gp.resize(grp.size());
-                    ghex.resize(grp.size() * 65);
-                    gst.resize(grp.size());
-                    for (size_t q = 0; q < grp.size(); q++) gp[q] = paths[grp[q]];
-                    cpu_rc = sd_cpu_file_checksums(gp.data(), grp.size(), ghex.data(), gst.data(), cpu_threads);
-                    if (cpu_rc != SD_OK) {
-                        cpu_err = sd_cas_last_error();
-                        cursor.store(big.size());
-                        return;
-                    }
-                    for (size_t q = 0; q < grp.size(); q++) {
-                        status[grp[q]] = gst[q];
-                        memcpy(out_hex65 + 65 * grp[q], ghex.data() + 65 * q, 65);
-                    }
-                }
-              } catch (...) {  // an allocation here: nothing may escape a thread
-                cpu_rc = SD_ERR_NOMEM;
-                cpu_err = "host allocation failed in the CPU half of a split sd_file_checksums call";
-                cursor.store(big.size());
-              }
-            });
-            try {
-                gpu_file_checksums(ctx, paths, out_hex65, status, hyb, hint, regular, [&]() -> size_t {
-                    const size_t i = next_big();
-                    if (i != SIZE_MAX) ctx->checksum_bytes_gpu.fetch_add(hint[i], std::memory_order_relaxed);
-                    return i;
-                });
-            } catch (...) {
-                cursor.store(big.size());  // the CPU thread takes no further file
-                cpu.join();
-                throw;
-            }
-            cpu.join();
-            if (cpu_rc != SD_OK) throw sd_failure(cpu_rc, cpu_err);
-            learn(0);
+            else
+                split_checksums_files(ctx, paths, out_hex65, status, threads, hyb, big, rest, hint, regular);
+            if (adapt) ctx->split_route.record(0, call_bytes, t0);
             return SD_OK;
         }
     }
@@ -1172,95 +1343,27 @@ int sd_checksums(sd_cas_ctx* ctx, const uint8_t* data, const uint64_t* offsets, 
     // reaches 98 % of its two halves' sum on one host (13 threads + PCIe) and lost to 16
     // threads alone on a host whose CPU path read 127 GB/s (0.95x, profiles/r6/r6f_*), so no
     // fixed choice is right everywhere.  Calls are timed from here, either route.
-    const int cohash_cap = std::max(0, std::min({64, tuning_get(SD_TUNE_HOST_COHASH_THREADS),
-                                                 checksum_cohash_cap(host_cpu_budget())}));
-    uint64_t call_bytes = 0;
-    for (size_t q = 0; q < n; q++) call_bytes += lens[q];
+    const int cohash = std::max(0, std::min({64, tuning_get(SD_TUNE_HOST_COHASH_THREADS),
+                                             checksum_cohash_cap(host_cpu_budget())}));
+    uint64_t all_bytes = 0;
+    for (size_t q = 0; q < n; q++) all_bytes += lens[q];
+    const bool co = cohash > 0 && n && all_bytes >= (1ull << 30);
     const int adapt = std::max(0, tuning_get(SD_TUNE_CHECKSUM_SPLIT_ADAPT));
-    const bool learn_route = adapt > 0 && cohash_cap > 0 && n && call_bytes >= (1ull << 30);
+    const bool learn_route = adapt > 0 && co;
     const auto t_call = std::chrono::steady_clock::now();
-    auto learn = [&](int route) {
-        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count();
-        std::lock_guard<std::mutex> g(ctx->split_mu);
-        split_route_record(ctx->cohash_routes, route, (double)call_bytes / std::max(sec, 1e-9) / 1e9);
-    };
-    if (learn_route) {
-        int route;
-        {
-            std::lock_guard<std::mutex> g(ctx->split_mu);
-            const uint64_t gen = split_route_tuning_gen();
-            if (ctx->cohash_routes_gen != gen) {
-                ctx->cohash_routes = SplitRoutes{};
-                ctx->cohash_routes_gen = gen;
-            }
-            route = split_route_choose(ctx->cohash_routes, (uint32_t)adapt);
-        }
-        if (route == 1) {  // the CPU path alone, on the host budget's threads
-            std::vector<uint8_t> h32(32 * n);
-            check_rc(sd_cpu_checksums(data, offsets, lens, n, h32.data(), host_cpu_budget()));
-            for (size_t q = 0; q < n; q++) to_hex(h32.data() + 32 * q, 32, out_hex65 + 65 * q);
-            ctx->checksums_host_bytes.fetch_add(call_bytes, std::memory_order_relaxed);
-            learn(1);
-            return SD_OK;
-        }
+    if (learn_route && ctx->cohash_route.begin((uint32_t)adapt) == 1) {  // the CPU path alone, on the budget's threads
+        std::vector<uint8_t> h32(32 * n);
+        check_rc(sd_cpu_checksums(data, offsets, lens, n, h32.data(), host_cpu_budget()));
+        for (size_t q = 0; q < n; q++) to_hex(h32.data() + 32 * q, 32, out_hex65 + 65 * q);
+        ctx->checksums_host_bytes.fetch_add(all_bytes, std::memory_order_relaxed);
+        ctx->cohash_route.record(1, all_bytes, t_call);
+        return SD_OK;
     }
-    constexpr uint64_t W = Streamer::W;
-    SlotPair slots(ctx);
-    Streamer::prepare(slots);
-    sd_checksum_batch big;
-    struct Pending {
-        size_t i0 = 0, i1 = 0;
-        bool busy = false;
-    } pend[2];
-    auto harvest = [&](int k) {
-        if (!pend[k].busy) return;
-        slots[k].sync();
-        const uint8_t* h = slots[k].host_hashes.u8();
-        for (size_t i = pend[k].i0; i < pend[k].i1; i++) to_hex(h + 32 * (i - pend[k].i0), 32, out_hex65 + 65 * i);
-        pend[k].busy = false;
-    };
-    // copies on one queue (copy_stream), kernels on the two slots' streams, joined by events:
-    // copied[k] = slot k's window has landed; used[k] = slot k's kernels no longer read it
-    hipStream_t cs = slots.copy_stream();
-    hipEvent_t copied[2] = {nullptr, nullptr}, used[2] = {nullptr, nullptr};
-    bool used_set[2] = {false, false};
-    struct Events {
-        hipEvent_t* e[2];
-        ~Events() {
-            for (auto* p : e)
-                for (int k = 0; k < 2; k++)
-                    if (p[k]) (void)hipEventDestroy(p[k]);
-        }
-    } ev_guard{{copied, used}};
-    for (int k = 0; k < 2; k++) {
-        HIP_CHECK(hipEventCreateWithFlags(&copied[k], hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&used[k], hipEventDisableTiming | hipEventBlockingSync));
-    }
-    // H2D of `bytes` from `src` to byte `dst` of slot k's device window, after its previous
-    // kernels (first piece of a window) / before its next kernels (last piece)
-    auto copy_in = [&](int k, const uint8_t* src, uint64_t bytes, uint64_t dst = 0, bool first = true,
-                       bool last = true) {
-        if (first && used_set[k]) HIP_CHECK(hipStreamWaitEvent(cs, used[k], 0));
-        HIP_CHECK(hipMemcpyAsync(slots[k].staged.as<uint8_t>() + dst, src, bytes, hipMemcpyHostToDevice, cs));
-        if (!last) return;
-        HIP_CHECK(hipEventRecord(copied[k], cs));
-        HIP_CHECK(hipStreamWaitEvent(slots[k].stream, copied[k], 0));
-    };
-    auto done_with = [&](int k) {
-        HIP_CHECK(hipEventRecord(used[k], slots[k].stream));
-        used_set[k] = true;
-    };
-    int cur = 0;
-    std::vector<uint64_t> offs, ls;
-    struct RunT {  // a piece of a window copied with one H2D
-        uint64_t host_lo, host_end, dev_lo;
-    };
-    std::vector<RunT> runs;
+    RangePipe pipe(ctx, HostRanges{data, offsets, lens, n, out_hex65});
     // Co-hashing (as sd_cas_ids, "host_cohash_threads" h > 0, calls of >= 1 GiB): one host
-    // thread claims ranges from the END -- one large range, or consecutive small ones up to
-    // 64 MiB -- and hashes them with h pool threads on the CPU path (a range of 8 MiB or
-    // more block-parallel: its 1 MiB blocks' chaining values on all threads, then the root),
-    // while the loop below claims its windows and streamed ranges from the front.
+    // thread (cohash_ranges) claims ranges from the END and hashes them with h pool threads
+    // on the CPU path, while the loop below claims its windows and streamed ranges from the
+    // front (EndClaims, sd_host.h).
     // One range of >= 256 MiB is shared at block granularity instead of claimed whole, so the
     // two sides finish together (a whole claim leaves the other side idle for up to one
     // range's time; a call of one huge range would go to whichever side claims it first):
@@ -1279,280 +1382,42 @@ int sd_checksums(sd_cas_ctx* ctx, const uint8_t* data, const uint64_t* offsets, 
     // budget (an absolute 3 left one thread of a 4-CPU budget): 8 -> 6, 4 -> 3,
     // 2 -> 1 (checksum_cohash_cap, sd_host.h).  sd_cas_ids keeps budget - 1: there 15
     // measured best (4.86 vs 4.51 M files/s at 13, r5h_cohash_cas.json).
-    const int cohash = cohash_cap;
-    const uint64_t all_bytes = call_bytes;
-    std::mutex claim_mu;
-    size_t back = n, front = 0;  // [back, n) claimed by the host, [0, front) by the GPU loop
-    constexpr uint64_t SHARED_MIN = 256ull << 20, HOST_UNIT = 64;  // bytes; blocks per host claim
+    constexpr uint64_t SHARED_MIN = 256ull << 20;
     // the meet prediction's rates: the H2D copy bounds the GPU side, ~5.5 GB/s a host thread
     // (BLAKE3 with AVX-512, profiles/r4/r4j_shared_range_probe.json); only the split point
     // depends on them, never a result
     constexpr double GPU_GBPS = 55.0, HOST_THREAD_GBPS = 5.5;
-    struct SharedRange {
-        size_t idx = SIZE_MAX;  // the range (one per call)
-        uint64_t nb = 0, sf = 0, sb = 0;  // its blocks: [0, sf) the GPU's, [sb, nb) the host's
-        int inflight = 0;      // host claims being hashed
-        std::vector<uint8_t> cvs;  // the host's block CVs, 32 B at 32 * block
-        std::condition_variable cv;
-    } sh;
-    int host_rc = SD_OK;
-    std::string host_err;
-    std::atomic<uint64_t> host_bytes{0};  // bytes the host threads hashed (sd_checksums_stats)
-    std::thread host;
-    struct JoinHost {
-        std::thread& t;
-        std::mutex& mu;
-        size_t& back;
-        SharedRange& sh;
-        ~JoinHost() {
-            {
-                std::lock_guard<std::mutex> g(mu);
-                back = 0;
-                sh.sb = sh.sf;  // the host takes no further block
-            }
-            if (t.joinable()) t.join();
-        }
-    } join_host{host, claim_mu, back, sh};
-    if (cohash > 0 && n && all_bytes >= (1ull << 30)) {
-        sh.idx = shared_range_pick(lens, n, SHARED_MIN, cohash, GPU_GBPS, HOST_THREAD_GBPS);
-        if (sh.idx != SIZE_MAX) {
-            sh.nb = (lens[sh.idx] + SD_CK_BLOCK - 1) / SD_CK_BLOCK;
-            sh.sf = 0;
-            sh.sb = sh.nb;
-            sh.cvs.resize(sh.nb * 32);
-        }
-        host = std::thread([&] {
-            library_thread_place();  // the device's NUMA node (sd_host.h)
-            try {
-                std::vector<uint8_t> h32, cvs;
-                for (;;) {
-                    size_t b0, b1;
-                    uint64_t u0 = 0, u1 = 0;  // a claim of the shared range's blocks
-                    {
-                        std::lock_guard<std::mutex> g(claim_mu);
-                        // the shared range's blocks once every range after it is claimed
-                        if (sh.idx != SIZE_MAX && back <= sh.idx + 1 && sh.sb > sh.sf) {
-                            u1 = sh.sb;
-                            u0 = std::max(sh.sf, u1 > HOST_UNIT ? u1 - HOST_UNIT : 0);
-                            sh.sb = u0;
-                            sh.inflight++;
-                        }
-                    }
-                    if (u1 > u0) {
-                        struct Done {  // on every exit, so the GPU loop's wait ends
-                            SharedRange& s;
-                            std::mutex& mu;
-                            ~Done() {
-                                {
-                                    std::lock_guard<std::mutex> g(mu);
-                                    s.inflight--;
-                                }
-                                s.cv.notify_all();
-                            }
-                        } done{sh, claim_mu};
-                        cpu_block_cvs(data + offsets[sh.idx], lens[sh.idx], u0, u1, sh.cvs.data(), cohash);
-                        host_bytes.fetch_add(std::min(u1 * SD_CK_BLOCK, lens[sh.idx]) - u0 * SD_CK_BLOCK,
-                                             std::memory_order_relaxed);
-                        continue;
-                    }
-                    {
-                        std::lock_guard<std::mutex> g(claim_mu);
-                        if (back <= front) return;
-                        b1 = back;
-                        if (b1 - 1 == sh.idx) {  // the shared range: its blocks only, above
-                            back = sh.idx;
-                            continue;
-                        }
-                        // (the host reaches ranges before `sh` only once its blocks are gone)
-                        b0 = b1 - 1;
-                        uint64_t sum = lens[b0];
-                        while (b0 > front && lens[b0] < SD_CPU_SPLIT_MIN && lens[b0 - 1] < SD_CPU_SPLIT_MIN &&
-                               sum + lens[b0 - 1] <= (64ull << 20)) {
-                            b0--;
-                            sum += lens[b0];
-                        }
-                        back = b0;
-                    }
-                    h32.resize((b1 - b0) * 32);
-                    if (b1 - b0 == 1 && lens[b0] >= SD_CPU_SPLIT_MIN) {  // one large range, block-parallel
-                        uint64_t o = 0, l = 0, cvb = 0;
-                        check_rc(sd_split_range(lens[b0], 1, 0, &o, &l, &cvb));
-                        cvs.resize(cvb);
-                        check_rc(sd_cpu_split_leaves(data + offsets[b0], lens[b0], 1, 0, cvs.data(), cohash));
-                        check_rc(sd_cpu_split_root(cvs.data(), lens[b0], h32.data()));
-                    } else {
-                        check_rc(sd_cpu_checksums(data, offsets + b0, lens + b0, b1 - b0, h32.data(), cohash));
-                    }
-                    for (size_t q = b0; q < b1; q++) {
-                        to_hex(h32.data() + 32 * (q - b0), 32, out_hex65 + 65 * q);
-                        host_bytes.fetch_add(lens[q], std::memory_order_relaxed);
-                    }
-                }
-            } catch (const sd_failure& e) {
-                host_rc = e.rc;
-                host_err = e.what();
-            } catch (...) {
-                host_rc = SD_ERR_NOMEM;
-                host_err = "host allocation failed in a co-hashed sd_checksums call";
-            }
-            std::lock_guard<std::mutex> g(claim_mu);
-            back = front;  // the GPU loop takes nothing further from here on: stop it
-        });
-    }
-    // the GPU loop's claims: range i is the GPU's if no host thread took it
-    auto claim = [&](size_t i) -> bool {
-        std::lock_guard<std::mutex> g(claim_mu);
-        if (i >= back && i != sh.idx) return false;
-        front = std::max(front, i + 1);
-        return true;
-    };
+    const size_t sh = co ? shared_range_pick(lens, n, SHARED_MIN, cohash, GPU_GBPS, HOST_THREAD_GBPS) : EndClaims::NONE;
+    const uint64_t sh_blocks = sh == EndClaims::NONE ? 0 : (lens[sh] + SD_CK_BLOCK - 1) / SD_CK_BLOCK;
+    EndClaims claims(n, sh, sh_blocks);
+    CoHost host;
+    host.cvs.resize(sh_blocks * 32);
+    std::vector<std::thread> host_thread;
+    // on an exception below: the host takes nothing further, then wait; declared after
+    // everything the thread touches
+    EndClaims::StopBack join_host{claims, host_thread};
+    if (co) host_thread.emplace_back([&] { cohash_ranges(claims, pipe.r, sh, cohash, host); });
+    RangeWindow win;
     for (size_t i = 0; i < n;) {
-        if (!claim(i)) {
+        if (!claims.front_claim(i)) {
             // the host took range i and everything after it -- except the shared range,
             // which may lie beyond ranges the host claimed whole after sharing it
-            size_t s;
-            {
-                std::lock_guard<std::mutex> g(claim_mu);
-                s = sh.idx;
-            }
-            if (s != SIZE_MAX && s > i) {
-                i = s;
-                continue;
-            }
-            break;
+            if ((i = claims.front_skip(i)) == EndClaims::NONE) break;
+        } else if (i == sh) {
+            pipe.hash_shared_range(claims, i++, host.cvs);
+        } else if (lens[i] + 128 > Streamer::W) {
+            pipe.hash_streamed_range(i++);
+        } else {
+            i = pipe.hash_packed_window(claims, i, win);
         }
-        if (i == sh.idx) {  // the shared range: windows of blocks from the front until the host's
-            harvest(0);
-            harvest(1);
-            const uint64_t off0 = 0, L = lens[i];
-            plan_checksum_batch(&big, &off0, &L, 1, nullptr);
-            constexpr uint64_t BPW = W / SD_CK_BLOCK;
-            for (;;) {
-                uint64_t w0, w1;
-                // claim at the device's pace, not the enqueue rate (the copies are async from
-                // pinned memory): slot cur's previous window must have been hashed first, so
-                // at most two windows are the GPU's ahead of the host's claims
-                if (used_set[cur]) HIP_CHECK(hipEventSynchronize(used[cur]));
-                {
-                    std::lock_guard<std::mutex> g(claim_mu);
-                    if (sh.sf >= sh.sb) break;
-                    // windows shrink to a third of what is left (>= 32 blocks), so the
-                    // GPU's last windows in flight are short when the two sides meet
-                    w0 = sh.sf;
-                    w1 = std::min(sh.sb, w0 + std::min<uint64_t>(BPW, std::max<uint64_t>(32, (sh.sb - w0) / 3)));
-                    sh.sf = w1;
-                }
-                const int k = cur;
-                cur ^= 1;
-                const uint64_t pos = w0 * SD_CK_BLOCK, here = std::min(w1 * SD_CK_BLOCK, L) - pos;
-                copy_in(k, data + offsets[i] + pos, here);
-                HIP_CHECK(sdk::launch_ck_leaf(slots[k].staged.as<uint8_t>(), pos, 0, big.d_files(),
-                                              big.d_map() + w0, (uint32_t)(w1 - w0), big.lvl[0].as<uint32_t>(),
-                                              slots[k].hashes.as<uint32_t>(), slots[k].stream));
-                done_with(k);
-            }
-            uint64_t hb0;
-            {
-                std::unique_lock<std::mutex> lk(claim_mu);
-                sh.cv.wait(lk, [&] { return sh.inflight == 0; });  // the host's claims are hashed
-                hb0 = sh.sb;
-            }
-            slots.sync_all();
-            Slot& sl = slots[0];
-            if (hb0 < sh.nb)  // the host's block CVs beside the GPU's, then the reduce passes
-                HIP_CHECK(hipMemcpyAsync(big.lvl[0].as<uint8_t>() + 32 * hb0, sh.cvs.data() + 32 * hb0,
-                                         32 * (sh.nb - hb0), hipMemcpyHostToDevice, sl.stream));
-            run_checksum_reduce(&big, sl.hashes.as<uint32_t>(), sl.stream);
-            HIP_CHECK(hipMemcpyAsync(sl.host_hashes.p, sl.hashes.p, 32, hipMemcpyDeviceToHost, sl.stream));
-            sl.sync();
-            to_hex(sl.host_hashes.u8(), 32, out_hex65 + 65 * i);
-            i++;
-            continue;
-        }
-        if (lens[i] + 128 > W) {  // one large range, streamed
-            harvest(0);
-            harvest(1);
-            const uint64_t off0 = 0, L = lens[i];
-            plan_checksum_batch(&big, &off0, &L, 1, nullptr);
-            const uint64_t nb = big.plan.wg_map.size();
-            for (uint64_t pos = 0; pos < L; pos += W) {
-                const int k = cur;
-                cur ^= 1;
-                const uint64_t here = std::min<uint64_t>(W, L - pos);
-                copy_in(k, data + offsets[i] + pos, here);  // exactly the range's bytes: the
-                // kernels mask past a message's end, so nothing past it is read from `data`
-                const uint32_t wg0 = (uint32_t)(pos / SD_CK_BLOCK);
-                const uint32_t wg1 = (uint32_t)std::min<uint64_t>(nb, wg0 + W / SD_CK_BLOCK);
-                HIP_CHECK(sdk::launch_ck_leaf(slots[k].staged.as<uint8_t>(), pos, 0, big.d_files(),
-                                              big.d_map() + wg0, wg1 - wg0, big.lvl[0].as<uint32_t>(),
-                                              slots[k].hashes.as<uint32_t>(), slots[k].stream));
-                done_with(k);
-            }
-            slots.sync_all();
-            Slot& sl = slots[0];
-            run_checksum_reduce(&big, sl.hashes.as<uint32_t>(), sl.stream);
-            HIP_CHECK(hipMemcpyAsync(sl.host_hashes.p, sl.hashes.p, 32, hipMemcpyDeviceToHost, sl.stream));
-            sl.sync();
-            to_hex(sl.host_hashes.u8(), 32, out_hex65 + 65 * i);
-            i++;
-            continue;
-        }
-        // the next window: consecutive ranges whose device layout fits W.  Ranges keep their
-        // host-relative offsets, so a run of them is one H2D, except that
-        //  * a gap that holds a whole page no range touches opens a new run (the copy of a
-        //    run reads its gaps: only pages that hold range bytes may be read, since the
-        //    caller's buffer can have unmapped holes between ranges);
-        //  * a range of a leaf block or more that would start mid-line on the device opens a
-        //    new run at the next 128-B line (a mid-line start costs k_ck_leaf 5%, DESIGN.md
-        //    §3.2b).
-        // Only ascending, non-overlapping ranges open runs.
-        runs.clear();
-        offs.clear();
-        ls.clear();
-        uint64_t dev_hi = 0;  // the device layout's padded end
-        size_t j = i;
-        while (j < n && lens[j] + 128 <= W && (j == i || claim(j))) {
-            const uint64_t o = offsets[j], L = lens[j];
-            const RunT* r = runs.empty() ? nullptr : &runs.back();
-            const bool misaligned = r && (r->dev_lo + (o - r->host_lo)) % SD_STAGE_ALIGN != 0;
-            const bool page_gap = r && o >= r->host_end && align_up(r->host_end, 4096) + 4096 <= o;
-            const bool open = !r || page_gap || (o >= r->host_end && L >= SD_CK_BLOCK && misaligned);
-            if (r && !open && o < r->host_lo) break;  // before its run: the next window takes it
-            const uint64_t dev_lo = open ? (r ? align_up(dev_hi, SD_STAGE_ALIGN) : 0) : r->dev_lo;
-            const uint64_t host_lo = open ? o : r->host_lo;
-            const uint64_t d = dev_lo + (o - host_lo);
-            const uint64_t nhi = std::max(dev_hi, align_up(d + L, 64));
-            if (j > i && nhi > W) break;  // (a range claimed here and not taken: see below)
-            if (open) runs.push_back(RunT{o, o + L, dev_lo});
-            else runs.back().host_end = std::max(runs.back().host_end, o + L);
-            offs.push_back(d);
-            ls.push_back(L);
-            dev_hi = nhi;
-            j++;
-        }
-        const int k = cur;
-        cur ^= 1;
-        harvest(k);
-        Slot& sl = slots[k];
-        plan_checksum_batch(&sl.ck, offs.data(), ls.data(), j - i, sl.stream);
-        sl.hashes.ensure((j - i) * 32);
-        sl.host_hashes.ensure((j - i) * 32);
-        for (size_t q = 0; q < runs.size(); q++)  // not past a run's last range: `data` may end there
-            copy_in(k, data + runs[q].host_lo, runs[q].host_end - runs[q].host_lo, runs[q].dev_lo, q == 0,
-                    q + 1 == runs.size());
-        run_checksum_batch(&sl.ck, sl.staged.as<uint8_t>(), sl.hashes.as<uint8_t>(), sl.stream);
-        done_with(k);
-        HIP_CHECK(hipMemcpyAsync(sl.host_hashes.p, sl.hashes.p, (j - i) * 32, hipMemcpyDeviceToHost, sl.stream));
-        pend[k] = Pending{i, j, true};
-        i = j;
     }
-    harvest(0);
-    harvest(1);
-    if (host.joinable()) host.join();
-    if (host_rc != SD_OK) throw sd_failure(host_rc, host_err);
-    ctx->checksums_host_bytes.fetch_add(host_bytes.load(), std::memory_order_relaxed);
-    ctx->checksums_gpu_bytes.fetch_add(all_bytes - std::min(all_bytes, host_bytes.load()), std::memory_order_relaxed);
-    if (learn_route) learn(0);
+    pipe.harvest(0);
+    pipe.harvest(1);
+    for (auto& t : host_thread) t.join();
+    if (host.rc != SD_OK) throw sd_failure(host.rc, host.err);
+    ctx->checksums_host_bytes.fetch_add(host.bytes.load(), std::memory_order_relaxed);
+    ctx->checksums_gpu_bytes.fetch_add(all_bytes - std::min(all_bytes, host.bytes.load()), std::memory_order_relaxed);
+    if (learn_route) ctx->cohash_route.record(0, all_bytes, t_call);
     return SD_OK;
     SD_GUARD_END
 }

@@ -390,6 +390,79 @@ void split_route_record(SplitRoutes& s, int route, double gbps) {
     s.calls++;
 }
 
+int LearnedRoute::begin(uint32_t explore_every) {
+    std::lock_guard<std::mutex> g(mu_);
+    // what either route's rate depends on: a change of it starts the learning again
+    const uint64_t gen = split_route_tuning_gen();
+    if (gen_ != gen) {
+        r_ = SplitRoutes{};
+        gen_ = gen;
+    }
+    return split_route_choose(r_, explore_every);
+}
+
+void LearnedRoute::record(int route, uint64_t bytes, std::chrono::steady_clock::time_point t0) {
+    const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::lock_guard<std::mutex> g(mu_);
+    split_route_record(r_, route, (double)bytes / std::max(s, 1e-9) / 1e9);
+}
+
+SplitRoutes LearnedRoute::snapshot() {
+    std::lock_guard<std::mutex> g(mu_);
+    return r_;
+}
+
+bool BlockQueue::claim(uint64_t want, size_t& q, uint64_t& b0, uint64_t& b1) {
+    const size_t nf = fb_.size() - 1;
+    while (cf_ < nf && cb_ >= fb_[cf_ + 1] - fb_[cf_]) {
+        cf_++;
+        cb_ = 0;
+    }
+    if (cf_ >= nf) return false;
+    q = cf_;
+    b0 = cb_;
+    b1 = std::min(fb_[cf_ + 1] - fb_[cf_], cb_ + want);
+    cb_ = b1;
+    left_ -= b1 - b0;
+    return true;
+}
+
+// Ranges keep their host-relative offsets, so a run of them is one H2D, except that
+//  * a gap that holds a whole page no range touches opens a new run (the copy of a run reads
+//    its gaps: only pages that hold range bytes may be read, since the caller's buffer can
+//    have unmapped holes between ranges);
+//  * a range of a leaf block or more that would start mid-line on the device opens a new run
+//    at the next 128-B line (a mid-line start costs k_ck_leaf 5%).
+// Only ascending, non-overlapping ranges open runs.
+size_t plan_range_window(const uint64_t* offsets, const uint64_t* lens, size_t i, size_t n, uint64_t W,
+                         const std::function<bool(size_t)>& claim, RangeWindow& w) {
+    w.runs.clear();
+    w.offs.clear();
+    w.lens.clear();
+    uint64_t dev_hi = 0;  // the device layout's padded end
+    size_t j = i;
+    while (j < n && lens[j] + 128 <= W && (j == i || claim(j))) {
+        const uint64_t o = offsets[j], L = lens[j];
+        const RangeWindow::Run* r = w.runs.empty() ? nullptr : &w.runs.back();
+        const bool misaligned = r && (r->dev_lo + (o - r->host_lo)) % SD_STAGE_ALIGN != 0;
+        const bool page_gap = r && o >= r->host_end && sd_align_up(r->host_end, 4096) + 4096 <= o;
+        const bool open = !r || page_gap || (o >= r->host_end && L >= SD_CK_BLOCK && misaligned);
+        if (r && !open && o < r->host_lo) break;  // before its run: the next window takes it
+        const uint64_t dev_lo = open ? (r ? sd_align_up(dev_hi, SD_STAGE_ALIGN) : 0) : r->dev_lo;
+        const uint64_t host_lo = open ? o : r->host_lo;
+        const uint64_t d = dev_lo + (o - host_lo);
+        const uint64_t nhi = std::max(dev_hi, sd_align_up(d + L, 64));
+        if (j > i && nhi > W) break;  // (claimed here and not taken: the next window opens with it)
+        if (open) w.runs.push_back(RangeWindow::Run{o, o + L, dev_lo});
+        else w.runs.back().host_end = std::max(w.runs.back().host_end, o + L);
+        w.offs.push_back(d);
+        w.lens.push_back(L);
+        dev_hi = nhi;
+        j++;
+    }
+    return j;
+}
+
 int tuning_get(int key) { return (key >= 0 && key < SD_TUNE_NKEYS) ? g_tune[key].load(std::memory_order_relaxed) : 0; }
 
 SplitPlan split_plan(uint64_t total, int nranks, int rank) {

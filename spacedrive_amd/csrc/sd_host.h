@@ -15,6 +15,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/sd_cas.h"
@@ -504,4 +505,169 @@ uint64_t split_route_tuning_gen();
 // co-hashing threads of a sd_checksums call under a host budget of b: b less 3/16 of it, at
 // least one less (16 -> 13, 8 -> 6, 4 -> 3, 2 -> 1, 1 -> 0)
 inline int checksum_cohash_cap(int b) { return b <= 1 ? 0 : b - std::max(1, (3 * b + 8) / 16); }
+
+// ------------------------------------------------------------------ claim protocols
+// Who hashes what in a call that the GPU and host threads share.  Host-only state machines:
+// host_selftest.cpp drives each with threads under ASan + UBSan and TSan.
+
+// A context's SplitRoutes with the tuning generation they were learned under.
+class LearnedRoute {
+public:
+    // this call's route; a change of split_route_tuning_gen() starts the learning again
+    int begin(uint32_t explore_every);
+    // the call took `route` for `bytes` bytes and started at t0
+    void record(int route, uint64_t bytes, std::chrono::steady_clock::time_point t0);
+    SplitRoutes snapshot();
+
+private:
+    std::mutex mu_;
+    SplitRoutes r_;
+    uint64_t gen_ = 0;
+};
+
+// n items claimed from both ends: [0, front) by the front side (the GPU loop), [back, n) by
+// the back side (host threads), until the two meet.  One item may be `shared`: neither side
+// claims it whole; the front side takes its blocks [0, sf) on reaching it, the back side
+// [sb, nb) once every item after it is claimed, and a back block claim stays in flight until
+// its done-marker runs.
+class EndClaims {
+public:
+    static constexpr size_t NONE = SIZE_MAX;
+    explicit EndClaims(size_t n, size_t shared = NONE, uint64_t shared_blocks = 0)
+        : back_(n), shared_(shared), sb_(shared == NONE ? 0 : shared_blocks) {}
+
+    // The back side takes items [b0, b1): the last unclaimed one, then further ones, at most
+    // max_items in all, while more(j, b1) holds for the next one, j ([j + 1, b1) being taken
+    // so far).  False when nothing is left for it.
+    template <class More>
+    bool back_claim(size_t max_items, size_t& b0, size_t& b1, More more) {
+        std::lock_guard<std::mutex> g(mu_);
+        if (!back_open_) return false;
+        if (back_ > front_ && back_ - 1 == shared_) back_ = shared_;  // its blocks only: back_blocks
+        if (back_ <= front_) return false;
+        b1 = back_;
+        b0 = b1 - 1;
+        while (b0 > front_ && b1 - b0 < max_items && b0 - 1 != shared_ && more(b0 - 1, b1)) b0--;
+        back_ = b0;
+        return true;
+    }
+    // The front side takes items from `from` on while the back side has not claimed them (the
+    // shared item it never has) and take(i) accepts them; the first index not taken.
+    template <class Take>
+    size_t front_claim(size_t from, Take take) {
+        std::lock_guard<std::mutex> g(mu_);
+        size_t i = from;
+        while (front_open_ && (i < back_ || i == shared_) && take(i)) i++;
+        front_ = std::max(front_, i);
+        return i;
+    }
+    bool front_claim(size_t i) {
+        return front_claim(i, [i](size_t q) { return q == i; }) > i;
+    }
+    // after a failed front_claim(i): the shared item if it lies ahead (the back side may have
+    // claimed whole items on both sides of it), else NONE
+    size_t front_skip(size_t i) {
+        std::lock_guard<std::mutex> g(mu_);
+        return front_open_ && shared_ != NONE && shared_ > i ? shared_ : NONE;
+    }
+    // The shared item's blocks [w0, w1) for the front side: at most `max`, shrinking to a
+    // third of what is left (>= 32 blocks), so the GPU's last windows in flight are short
+    // when the two sides meet.
+    bool front_blocks(uint64_t max, uint64_t& w0, uint64_t& w1) {
+        std::lock_guard<std::mutex> g(mu_);
+        if (!front_open_ || sf_ >= sb_) return false;
+        w0 = sf_;
+        w1 = std::min(sb_, w0 + std::min<uint64_t>(max, std::max<uint64_t>(32, (sb_ - w0) / 3)));
+        sf_ = w1;
+        return true;
+    }
+    // Its blocks [u0, u1) for the back side, `unit` at a time, once every item after the
+    // shared one is claimed.  Each claim is in flight until its BlocksDone goes.
+    bool back_blocks(uint64_t unit, uint64_t& u0, uint64_t& u1) {
+        std::lock_guard<std::mutex> g(mu_);
+        if (!back_open_ || sb_ <= sf_ || back_ > shared_ + 1) return false;
+        u1 = sb_;
+        u0 = std::max(sf_, u1 > unit ? u1 - unit : 0);
+        sb_ = u0;
+        inflight_++;
+        return true;
+    }
+    struct BlocksDone {  // a back block claim's done-marker: on every exit, so wait_back_blocks ends
+        EndClaims& c;
+        ~BlocksDone() {
+            {
+                std::lock_guard<std::mutex> g(c.mu_);
+                c.inflight_--;
+            }
+            c.cv_.notify_all();
+        }
+    };
+    // waits until no back block claim is in flight; the back side's first block
+    uint64_t wait_back_blocks() {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return inflight_ == 0; });
+        return sb_;
+    }
+    // the back side takes nothing further (what it holds stays its own)
+    void stop_back() {
+        std::lock_guard<std::mutex> g(mu_);
+        back_open_ = false;
+    }
+    // the front side takes nothing further
+    void stop_front() {
+        std::lock_guard<std::mutex> g(mu_);
+        front_open_ = false;
+    }
+    struct StopBack {  // a caller's guard: declared after everything the back side's threads touch
+        EndClaims& c;
+        std::vector<std::thread>& t;
+        ~StopBack() {
+            c.stop_back();
+            for (auto& x : t)
+                if (x.joinable()) x.join();
+        }
+    };
+
+private:
+    std::mutex mu_;
+    std::condition_variable cv_;
+    size_t front_ = 0, back_;
+    const size_t shared_;
+    uint64_t sf_ = 0, sb_;
+    int inflight_ = 0;
+    bool front_open_ = true, back_open_ = true;
+};
+
+// sd_file_checksums' block split: the 1 MiB blocks of every large file as one queue in file
+// order, file q's being [fb[q], fb[q + 1]) of all.  A claim never spans two files.  It has no
+// lock of its own: split_checksums_blocks asks and claims under its slot lock, as one step.
+class BlockQueue {
+public:
+    static constexpr uint64_t GPU_RUN = 32;  // blocks per GPU claim while plenty is left
+    BlockQueue(const std::vector<uint64_t>& fb, int threads) : fb_(fb), threads_(threads), left_(fb.back()) {}
+    uint64_t left() const { return left_; }
+    // blocks [b0, b1) of file q, at most `want`
+    bool claim(uint64_t want, size_t& q, uint64_t& b0, uint64_t& b1);
+    // what a GPU slot asks for: its runs shrink towards the end, so its last ones finish with the host's
+    uint64_t gpu_run() const { return std::max<uint64_t>(4, std::min<uint64_t>(GPU_RUN, left_ / (2 * (uint64_t)threads_))); }
+
+private:
+    const std::vector<uint64_t>& fb_;
+    const int threads_;
+    size_t cf_ = 0;  // the cursor: file cf_, its block cb_
+    uint64_t cb_ = 0, left_;
+};
+
+// One packed window of sd_checksums: ranges i.. whose device layout fits W bytes.
+struct RangeWindow {
+    struct Run {  // a piece of the window copied with one H2D
+        uint64_t host_lo, host_end, dev_lo;
+    };
+    std::vector<Run> runs;
+    std::vector<uint64_t> offs, lens;  // the taken ranges' device offsets and lengths
+};
+// Fills `w` from range i on and returns the first index not taken.  Range i is the caller's
+// already; each further one is taken only if claim(j) grants it.
+size_t plan_range_window(const uint64_t* offsets, const uint64_t* lens, size_t i, size_t n, uint64_t W,
+                         const std::function<bool(size_t)>& claim, RangeWindow& w);
 void hex_lower(const uint8_t* h, int nbytes, char* out);
