@@ -1023,6 +1023,66 @@ int sd_cpu_checksum_tree_verify(const uint8_t* data, const uint64_t* offsets, co
                                 uint32_t block_log2, const uint8_t* expected, uint8_t* bad, uint64_t* rows_out,
                                 uint64_t capacity, uint64_t* count, uint64_t stats[4], int nthreads);
 
+/* Listed blocks: the nodes of SOME blocks of SOME files, from bytes that sit anywhere in a buffer
+ * -- a spaceblock Block {offset, size, data} as it arrives (p2p/src/spaceblock/block.rs:5-11), the
+ * blocks a sender resent after a scrub, the blocks a write in place touched.  Only the listed bytes
+ * are hashed.
+ *   lens          the files' current lengths (host, n_files); nb and node_base as above
+ *   rows          m x (file f, block j), 2 x u64 each (host): f < n_files, j < nb(f); any order,
+ *                 not every file, repeats allowed (but see _update)
+ *   data_offsets  m (host): row r's bytes -- block j of file f, lens[f] == 0 ? 0 : min(B, lens[f] -
+ *                 jB) of them -- start at d_data + data_offsets[r]; sd_checksum_batch_create's rule
+ *                 (16-byte aligned starts, the buffer readable to the next 64-byte boundary; what
+ *                 lies after a block's last byte is not assumed zero)
+ *   node          row r's node is N_j of file f exactly: the root hash when nb(f) == 1 (the empty
+ *                 file too), else the plain chaining value with chunk counters from j*B/1024 (64
+ *                 bits) -- a 1-byte trailing block or a one-chunk block at a counter > 0 has no ROOT
+ * Anything else is SD_ERR_INVALID at create, before any allocation.  m == 0 is valid, and every call
+ * on such a list does nothing and returns SD_OK.  d_nodes_out / d_expected / d_nodes are 16-byte
+ * aligned. */
+typedef struct sd_checksum_tree_blocks sd_checksum_tree_blocks;
+int sd_checksum_tree_blocks_create(sd_cas_ctx* ctx, const uint64_t* lens, size_t n_files, uint32_t block_log2,
+                                   const uint64_t* rows, const uint64_t* data_offsets, size_t m,
+                                   sd_checksum_tree_blocks** out);
+void sd_checksum_tree_blocks_destroy(sd_checksum_tree_blocks* blocks);
+/* [0] files, [1] rows, [2] bytes hashed, [3] BLAKE3 compressions */
+int sd_checksum_tree_blocks_stats(const sd_checksum_tree_blocks* blocks, uint64_t out[4]);
+/* Row r's node -> d_nodes_out[32 r] (m x 32 B, list order).  Asynchronous on `stream`. */
+int sd_checksum_tree_blocks_run(sd_cas_ctx* ctx, const sd_checksum_tree_blocks* blocks, const uint8_t* d_data,
+                                uint8_t* d_nodes_out, void* stream);
+/* Row r's node against d_expected[32 (node_base[f] + j)] (d_expected: the batch's whole level
+ * layout, node_base[n_files] x 32 B; only the listed nodes are read).
+ *   d_bad (m bytes, may be NULL): 1 where row r's node differs, else 0
+ *   d_rows_out (2 x u64 per row, may be NULL): (file, block) of the differing rows in LIST order, a
+ *     repeated row once per repeat; *count, capacity and SD_ERR_CAPACITY as sd_checksum_tree_verify
+ *   stats[4] (host, may be NULL): [0] files, [1] rows compared, [2] rows that differ, [3] files with
+ *     at least one differing row
+ * Runs on `stream` and syncs it; the nodes it computes live in the context's pooled slot (grow-only,
+ * 33 bytes per row and 1 per file). */
+int sd_checksum_tree_blocks_verify(sd_cas_ctx* ctx, const sd_checksum_tree_blocks* blocks, const uint8_t* d_data,
+                                   const uint8_t* d_expected, uint8_t* d_bad, uint64_t* d_rows_out,
+                                   uint64_t capacity, uint64_t* count, uint64_t stats[4], void* stream);
+/* Row r's node -> d_nodes[32 (node_base[f] + j)] (d_nodes: the whole level layout, patched in place;
+ * every node not listed stays bit for bit), then on the same stream every file's root from the
+ * patched level -> d_hash32 (n_files x 32 B), the bytes sd_checksum_tree_roots would write.  A list
+ * with a repeated (file, block) is SD_ERR_INVALID here (two writers of one node), nothing written.
+ * Asynchronous on `stream`; one update of a list at a time (the first plans the roots' reduce and
+ * the list owns its scratch). */
+int sd_checksum_tree_blocks_update(sd_cas_ctx* ctx, sd_checksum_tree_blocks* blocks, const uint8_t* d_data,
+                                   uint8_t* d_nodes, uint8_t* d_hash32, void* stream);
+/* The same over host memory on host cores (host pointers; the list's arrays passed again in place
+ * of a handle), with the device calls' rules. */
+int sd_cpu_checksum_tree_blocks(const uint8_t* data, const uint64_t* lens, size_t n_files, uint32_t block_log2,
+                                const uint64_t* rows, const uint64_t* data_offsets, size_t m, uint8_t* nodes_out,
+                                int nthreads);
+int sd_cpu_checksum_tree_blocks_verify(const uint8_t* data, const uint64_t* lens, size_t n_files,
+                                       uint32_t block_log2, const uint64_t* rows, const uint64_t* data_offsets,
+                                       size_t m, const uint8_t* expected, uint8_t* bad, uint64_t* rows_out,
+                                       uint64_t capacity, uint64_t* count, uint64_t stats[4], int nthreads);
+int sd_cpu_checksum_tree_blocks_update(const uint8_t* data, const uint64_t* lens, size_t n_files,
+                                       uint32_t block_log2, const uint64_t* rows, const uint64_t* data_offsets,
+                                       size_t m, uint8_t* nodes, uint8_t* hash32, int nthreads);
+
 /* ---------------------------------------------------------------- synthetic data */
 /* Device generator of SURVEY.md §8(d) (seed 0x5D5DCA51D, splitmix64 counter stream),
  * for benchmarks and parity tests: writes the exact cas message of each synthetic file

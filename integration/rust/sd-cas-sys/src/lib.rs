@@ -54,6 +54,10 @@ pub struct sd_cpu_object_index {
 pub struct sd_checksum_tree {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct sd_checksum_tree_blocks {
+    _p: [u8; 0],
+}
 
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -277,6 +281,31 @@ extern "C" {
     pub fn sd_cpu_checksum_tree_verify(data: *const u8, offsets: *const u64, lens: *const u64, n: usize,
                                        block_log2: u32, expected: *const u8, bad: *mut u8, rows_out: *mut u64,
                                        capacity: u64, count: *mut u64, stats: *mut u64, nthreads: c_int) -> c_int;
+    // listed blocks: rows = m x (file, block), data_offsets = where each row's bytes sit
+    pub fn sd_checksum_tree_blocks_create(ctx: *mut sd_cas_ctx, lens: *const u64, n_files: usize, block_log2: u32,
+                                          rows: *const u64, data_offsets: *const u64, m: usize,
+                                          out: *mut *mut sd_checksum_tree_blocks) -> c_int;
+    pub fn sd_checksum_tree_blocks_destroy(blocks: *mut sd_checksum_tree_blocks);
+    pub fn sd_checksum_tree_blocks_stats(blocks: *const sd_checksum_tree_blocks, out: *mut u64) -> c_int;
+    pub fn sd_checksum_tree_blocks_run(ctx: *mut sd_cas_ctx, blocks: *const sd_checksum_tree_blocks,
+                                       d_data: *const u8, d_nodes_out: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn sd_checksum_tree_blocks_verify(ctx: *mut sd_cas_ctx, blocks: *const sd_checksum_tree_blocks,
+                                          d_data: *const u8, d_expected: *const u8, d_bad: *mut u8,
+                                          d_rows_out: *mut u64, capacity: u64, count: *mut u64, stats: *mut u64,
+                                          stream: *mut c_void) -> c_int;
+    pub fn sd_checksum_tree_blocks_update(ctx: *mut sd_cas_ctx, blocks: *mut sd_checksum_tree_blocks,
+                                          d_data: *const u8, d_nodes: *mut u8, d_hash32: *mut u8,
+                                          stream: *mut c_void) -> c_int;
+    pub fn sd_cpu_checksum_tree_blocks(data: *const u8, lens: *const u64, n_files: usize, block_log2: u32,
+                                       rows: *const u64, data_offsets: *const u64, m: usize, nodes_out: *mut u8,
+                                       nthreads: c_int) -> c_int;
+    pub fn sd_cpu_checksum_tree_blocks_verify(data: *const u8, lens: *const u64, n_files: usize, block_log2: u32,
+                                              rows: *const u64, data_offsets: *const u64, m: usize,
+                                              expected: *const u8, bad: *mut u8, rows_out: *mut u64, capacity: u64,
+                                              count: *mut u64, stats: *mut u64, nthreads: c_int) -> c_int;
+    pub fn sd_cpu_checksum_tree_blocks_update(data: *const u8, lens: *const u64, n_files: usize, block_log2: u32,
+                                              rows: *const u64, data_offsets: *const u64, m: usize, nodes: *mut u8,
+                                              hash32: *mut u8, nthreads: c_int) -> c_int;
     // device buffers for callers that hold their lists on the host (sd_memcpy syncs `stream`)
     pub fn sd_device_malloc(ctx: *mut sd_cas_ctx, bytes: u64, out: *mut *mut c_void) -> c_int;
     pub fn sd_device_free(ctx: *mut sd_cas_ctx, p: *mut c_void);

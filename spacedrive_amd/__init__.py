@@ -16,11 +16,11 @@ from .cas import (FileMetadata, UnexpectedEofError, cas_ids_files_stats, cas_ids
                   coalescer_stats, file_checksum,
                   file_checksums, file_checksums_bytes, file_checksums_learned, file_checksums_stats, fingerprints,
                   fingerprints_stats, generate_cas_id, generate_cas_ids, get_tuning, set_tuning)
-from .device import (CasBatch, ChecksumBatch, ChecksumTree, Context, FingerprintBatch, HostObjectIndex, ObjectIndex, SplitChecksum,  # noqa: F401
+from .device import (CasBatch, ChecksumBatch, ChecksumTree, ChecksumTreeBlocks, Context, FingerprintBatch, HostObjectIndex, ObjectIndex, SplitChecksum,  # noqa: F401
                      default_context, stage_plan)
 
 __all__ = ["generate_cas_id", "generate_cas_ids", "file_checksum", "file_checksums", "FileMetadata",
            "UnexpectedEofError", "Context", "CasBatch", "ChecksumBatch", "default_context", "stage_plan",
            "SdCasError", "cas_ids_files_stats", "cas_ids_host_stats", "checksums_host_stats", "file_checksums_stats", "file_checksums_learned", "checksums_learned", "coalescer_stats",
            "set_tuning", "get_tuning", "host_cpu_budget", "rccl_info", "fingerprints", "fingerprints_stats", "FingerprintBatch",
-           "ObjectIndex", "HostObjectIndex", "cpu", "ChecksumTree", "tree"]
+           "ObjectIndex", "HostObjectIndex", "cpu", "ChecksumTree", "ChecksumTreeBlocks", "tree"]

@@ -200,6 +200,15 @@ SIGNATURES = [
     ("sd_cpu_checksum_tree", I32, [P, P, P, SZ, U32, P, P, I32]),
     ("sd_cpu_checksum_tree_roots", I32, [P, P, SZ, U32, P]),
     ("sd_cpu_checksum_tree_verify", I32, [P, P, P, SZ, U32, P, P, P, U64, PU64, P, I32]),
+    ("sd_checksum_tree_blocks_create", I32, [P, P, SZ, U32, P, P, SZ, ctypes.POINTER(P)]),
+    ("sd_checksum_tree_blocks_destroy", None, [P]),
+    ("sd_checksum_tree_blocks_stats", I32, [P, P]),
+    ("sd_checksum_tree_blocks_run", I32, [P, P, P, P, P]),
+    ("sd_checksum_tree_blocks_verify", I32, [P, P, P, P, P, P, U64, PU64, P, P]),
+    ("sd_checksum_tree_blocks_update", I32, [P, P, P, P, P, P]),
+    ("sd_cpu_checksum_tree_blocks", I32, [P, P, SZ, U32, P, P, SZ, P, I32]),
+    ("sd_cpu_checksum_tree_blocks_verify", I32, [P, P, SZ, U32, P, P, SZ, P, P, P, U64, PU64, P, I32]),
+    ("sd_cpu_checksum_tree_blocks_update", I32, [P, P, SZ, U32, P, P, SZ, P, P, I32]),
 ]
 SD_TREE_BLOCK_LOG2_MIN, SD_TREE_BLOCK_LOG2_MAX = 17, 20
 SD_CONFIRM_INVALID, SD_CONFIRM_SINGLE, SD_CONFIRM_CONFIRMED, SD_CONFIRM_REFUTED = 0, 1, 2, 3

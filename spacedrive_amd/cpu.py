@@ -204,6 +204,96 @@ def checksum_tree_verify(data, offsets, lens, expected, block_log2: int = 17, ca
     return out + (bad[:total],) if want_flags else out
 
 
+def _block_list(lens, rows, data_offsets, block_log2: int):
+    """(lens u64 [n_files], rows u64 [m, 2], data_offsets u64 [m], the rows' byte counts or None when
+    a row names no block -- the library refuses such a list before it reads anything)"""
+    ls = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+    rw = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2)
+    offs = np.ascontiguousarray(data_offsets, dtype=np.uint64).reshape(-1)
+    if len(offs) != len(rw):
+        raise ValueError("rows and data_offsets differ in length")
+    sizes = None
+    if len(rw) and 10 <= int(block_log2) <= 40 and int(rw[:, 0].max()) < len(ls):
+        B = 1 << int(block_log2)
+        sizes = [max(0, min(B, int(ls[int(f)]) - int(j) * B)) for f, j in rw]
+    return ls, rw, offs, sizes
+
+
+def _block_data(data, offs, sizes):
+    from .cas import _host_ranges
+    if sizes is None:
+        sizes = np.zeros(len(offs), np.uint64)
+    keep, addr, _, _ = _host_ranges(data, offs, np.array(sizes, np.uint64))
+    return keep, addr
+
+
+def checksum_tree_blocks(data, lens, rows, data_offsets, block_log2: int = 17, nthreads: int = THREADS) -> np.ndarray:
+    """sd_cpu_checksum_tree_blocks: the nodes uint8 [m, 32], in list order, of the listed blocks --
+    row r = (file, block) of files of lengths `lens`, its bytes at data[data_offsets[r]:] (starts
+    16-byte aligned).  Only the listed bytes are hashed."""
+    ls, rw, offs, sizes = _block_list(lens, rows, data_offsets, block_log2)
+    keep, addr = _block_data(data, offs, sizes)
+    m = len(rw)
+    out = np.zeros((max(m, 1), 32), np.uint8)
+    check(lib().sd_cpu_checksum_tree_blocks(addr, ls.ctypes.data, len(ls), int(block_log2), rw.ctypes.data,
+                                            offs.ctypes.data, m, out.ctypes.data, nthreads))
+    return out[:m]
+
+
+def checksum_tree_blocks_verify(data, lens, rows, data_offsets, expected, block_log2: int = 17,
+                                capacity: Optional[int] = None, want_rows: bool = True, want_flags: bool = False,
+                                nthreads: int = THREADS):
+    """sd_cpu_checksum_tree_blocks_verify: the listed blocks whose node differs from its node of
+    `expected` (the batch's whole level, uint8 [node_base[n_files], 32]).  Returns (rows uint64
+    [count, 2] of (file, block) in list order, stats uint64 [4]: files, rows compared, rows that
+    differ, files with a differing row) and, with want_flags, the 0/1 byte per row as a third
+    value.  `capacity` (default: every row) short of the rows raises SdCasError (SD_ERR_CAPACITY)
+    with ``.needed`` and writes no row; want_rows=False only counts."""
+    from ._native import SdCasError
+    ls, rw, offs, sizes = _block_list(lens, rows, data_offsets, block_log2)
+    keep, addr = _block_data(data, offs, sizes)
+    m = len(rw)
+    exp = np.ascontiguousarray(expected, dtype=np.uint8).reshape(-1)
+    if sizes is not None and exp.size != 32 * int(tree_node_base(ls, block_log2)[len(ls)]):
+        raise ValueError("expected is not node_base[n_files] x 32 bytes")
+    cap = m if capacity is None else int(capacity)
+    out_rows = np.zeros((max(cap, 1), 2), np.uint64)
+    bad = np.zeros(max(m, 1), np.uint8)
+    count = ctypes.c_uint64(0)
+    stats = np.zeros(4, np.uint64)
+    rc = lib().sd_cpu_checksum_tree_blocks_verify(addr, ls.ctypes.data, len(ls), int(block_log2), rw.ctypes.data,
+                                                  offs.ctypes.data, m, exp.ctypes.data if exp.size else None,
+                                                  bad.ctypes.data if want_flags else None,
+                                                  out_rows.ctypes.data if want_rows else None, cap, ctypes.byref(count),
+                                                  stats.ctypes.data, nthreads)
+    try:
+        check(rc)
+    except SdCasError as e:
+        e.needed = int(count.value)
+        e.stats = stats
+        raise
+    out = (out_rows[:int(count.value) if want_rows else 0], stats)
+    return out + (bad[:m],) if want_flags else out
+
+
+def checksum_tree_blocks_update(data, lens, rows, data_offsets, nodes, block_log2: int = 17,
+                                nthreads: int = THREADS):
+    """sd_cpu_checksum_tree_blocks_update: (the patched level uint8 [node_base[n_files], 32], roots
+    uint8 [n_files, 32]) -- a copy of `nodes` with the listed blocks' nodes replaced by those of the
+    bytes given, every other node as it was, and every file's root from it.  A (file, block) listed
+    twice raises SdCasError (SD_ERR_INVALID)."""
+    ls, rw, offs, sizes = _block_list(lens, rows, data_offsets, block_log2)
+    keep, addr = _block_data(data, offs, sizes)
+    nd = np.array(nodes, dtype=np.uint8).reshape(-1, 32)  # a copy: patched in place
+    if sizes is not None and len(nd) != int(tree_node_base(ls, block_log2)[len(ls)]):
+        raise ValueError("nodes is not node_base[n_files] x 32 bytes")
+    roots = np.zeros((max(len(ls), 1), 32), np.uint8)
+    check(lib().sd_cpu_checksum_tree_blocks_update(addr, ls.ctypes.data, len(ls), int(block_log2), rw.ctypes.data,
+                                                   offs.ctypes.data, len(rw), nd.ctypes.data if nd.size else None,
+                                                   roots.ctypes.data, nthreads))
+    return nd, roots[:len(ls)]
+
+
 def blake3(data: bytes) -> bytes:
     """Full 32-byte BLAKE3 of a host buffer (sd_cpu_checksums of one range)."""
     buf = np.frombuffer(bytes(data) + bytes(64), np.uint8)

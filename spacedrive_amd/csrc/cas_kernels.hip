@@ -15,6 +15,8 @@
 //                   lanes); then 256-way LDS reductions over the block CVs.
 //   k_ck_leaf_tree  k_ck_leaf's body, also storing the LDS tree's level at 128 KiB .. 1 MiB
 //                   granularity: the checksum trees (checksum_tree.hip).
+//   k_ck_blocks     the nodes of listed blocks of at most 128 KiB .. 1 MiB that sit anywhere in a
+//                   buffer: the leaf's lanes, 16 .. 2 items per workgroup, one item table.
 //
 // Tree shape: every merge is the level-wise pairwise merge with the odd node carried up
 // unchanged, over power-of-two aligned groups.  It is the BLAKE3 tree (left subtree =
@@ -549,6 +551,113 @@ __global__ __launch_bounds__(CK_WG_THREADS) void k_ck_leaf_tree(
     ck_leaf_body<W, true>(data, 0, 0, files, wg_map, n_blocks, cvbuf, out, node_base, node_level, nodes);
 }
 
+// Listed blocks (include/sd_cas.h; checksum_tree.hip): the node of item bi = ck_block_item
+// {src, chunk0, len, root, dst} -- at most 2^k bytes (17 <= k <= 20) that sit anywhere in `data`,
+// chunk counters from chunk0 (64 bits), ROOT only when the item's file has one node.  No file
+// table and no block map: the item is all a workgroup reads.  An item takes 2^il_log2 = 2^(k-12)
+// lanes of CK_LANE_CHUNKS chunks, the leaf's in-lane path, and the workgroup's CK_WG_THREADS lanes
+// hold 512 >> il_log2 items (16 at k = 17 down to 2 at k = 20, the leaf's own shape) whose LDS
+// trees of il_log2 levels are packed into the lowest lanes level by level, as the leaf packs its
+// two.  ROOT, when the item asks: inside the lane for <= CK_LANE_CHUNKS chunks, else on the
+// item's last parent; an item of a longer file never has it (a 1-byte trailing block, a one-chunk
+// block at a counter > 0 are plain CVs).  The lane that holds an item's top after the last level
+// stores it from registers (two 16-byte stores): to row bi of `nodes` (list order), or, `scatter`,
+// to row item.dst (the level layout).
+template <bool W>
+__global__ __launch_bounds__(CK_WG_THREADS) void k_ck_blocks(const uint8_t* __restrict__ data,
+                                                             const ck_block_item* __restrict__ items,
+                                                             uint32_t n_items, uint32_t il_log2, uint32_t scatter,
+                                                             uint32_t* __restrict__ nodes) {
+    constexpr uint32_t MAX_ITEMS = CK_WG_THREADS >> 5;  // il_log2 >= 5
+    __shared__ __attribute__((aligned(16))) uint32_t lds[CK_WG_THREADS][8];
+    __shared__ uint32_t s_lanes[MAX_ITEMS], s_root[MAX_ITEMS];
+    __shared__ uint64_t s_dst[MAX_ITEMS];
+    const uint32_t t = threadIdx.x, wi = t >> il_log2, lane = t & ((1u << il_log2) - 1);
+    const uint32_t per_wg = CK_WG_THREADS >> il_log2;
+    const uint32_t bi = blockIdx.x * per_wg + wi;  // this lane's item
+    uint32_t lanes_b = 0, root_b = 0;
+    uint64_t dst_b = 0;
+    if (bi < n_items) {
+        const uint4* q = reinterpret_cast<const uint4*>(items + bi);
+        const uint4 a = q[0], b = q[1];
+        const uint64_t src = (uint64_t)a.x | ((uint64_t)a.y << 32), chunk0 = (uint64_t)a.z | ((uint64_t)a.w << 32);
+        const uint32_t ilen = b.x;
+        const bool root = b.y != 0u;
+        dst_b = scatter ? ((uint64_t)b.z | ((uint64_t)b.w << 32)) : (uint64_t)bi;
+        const uint32_t nchunks = ilen == 0 ? 1u : (ilen + CHUNK_LEN - 1) / CHUNK_LEN;
+        const bool item_is_lane = nchunks <= CK_LANE_CHUNKS;  // the whole item inside lane 0
+        lanes_b = (nchunks + CK_LANE_CHUNKS - 1) / CK_LANE_CHUNKS;
+        root_b = root && !item_is_lane;
+        const uint32_t c0 = lane * CK_LANE_CHUNKS;
+        if (c0 < nchunks) {
+            const uint32_t nch = nchunks - c0 < CK_LANE_CHUNKS ? nchunks - c0 : CK_LANE_CHUNKS;
+            const uint8_t* p = data + src;
+            CvStack<ilog2(CK_LANE_CHUNKS)> st;  // after chunk j it holds popcount(j + 1) subtrees
+            uint32_t cv[8];
+#pragma unroll 1
+            for (uint32_t j = 0; j < nch; j++) {
+                const uint32_t ci = c0 + j;  // the chunk inside the item; its counter is 64 bits wide
+                const uint32_t rem = ilen - ci * CHUNK_LEN;
+                const uint32_t len = ilen == 0 ? 0u : (rem < CHUNK_LEN ? rem : CHUNK_LEN);
+                const bool root_chunk = root && nchunks == 1;
+                if (len == CHUNK_LEN && !root_chunk) full_chunk_cv_lp<W>(cv, p + (size_t)ci * CHUNK_LEN, chunk0 + ci);
+                else chunk_cv<W>(cv, p + (size_t)ci * CHUNK_LEN, len, chunk0 + ci, root_chunk);
+                if (j + 1 < nch) {  // an aligned group that ends here merges, then waits on the stack
+#pragma unroll 1
+                    for (uint32_t g = j + 1; (g & 1u) == 0; g >>= 1) st.template merge_top<W>(cv, 0u);
+                    st.push(cv);
+                } else {  // the lane's last chunk: ROOT on the last merge when the file is this lane
+                    const uint32_t ops = (uint32_t)__builtin_popcount(nch - 1);
+#pragma unroll 1
+                    for (uint32_t k = ops; k > 0; k--)
+                        st.template merge_top<W>(cv, (root && item_is_lane && k == 1) ? ROOT : 0u);
+                }
+            }
+            store_cv(lds[t], cv);
+        }
+    }
+    if (lane == 0) {
+        s_lanes[wi] = lanes_b;
+        s_root[wi] = root_b;
+        s_dst[wi] = dst_b;
+    }
+    __syncthreads();
+    // the items' trees, level-wise with the odd node carried up (2^il_log2 -> 1); item b's level-L
+    // nodes at lds[(b << il_log2) .. + n_b(L)); the last level's result leaves from registers
+#pragma unroll 1
+    for (uint32_t L = 0; L < il_log2; L++) {
+        const uint32_t p_log2 = il_log2 - 1 - L;  // parent slots per item at this level, log2
+        uint32_t res[8];
+        bool have = false;
+        uint32_t to = 0, b = 0;
+        if (t < (per_wg << p_log2)) {
+            b = t >> p_log2;
+            const uint32_t j = t & ((1u << p_log2) - 1);
+            uint32_t nb = s_lanes[b];
+            for (uint32_t l = 0; l < L; l++) nb = (nb + 1) >> 1;
+            const uint32_t at = (b << il_log2) + 2 * j;
+            if (2 * j + 1 < nb) {
+                uint32_t l8[8], r8[8];
+                load_cv(l8, lds[at]);
+                load_cv(r8, lds[at + 1]);
+                parent<W>(res, l8, r8, (s_root[b] && nb == 2) ? ROOT : 0u);
+                have = true;
+            } else if (2 * j + 1 == nb) {  // the odd last node
+                load_cv(res, lds[at]);
+                have = true;
+            }
+            to = (b << il_log2) + j;
+        }
+        if (L + 1 == il_log2) {  // one slot per item: its node
+            if (have) store_cv(nodes + s_dst[b] * 8, res);
+            break;
+        }
+        __syncthreads();
+        if (have) store_cv(lds[to], res);
+        __syncthreads();
+    }
+}
+
 // Reduce: workgroup = up to 256 consecutive CVs of one message's level; writes one CV to
 // the next level, or the root hash when the level fits one group.
 __global__ __launch_bounds__(256) void k_ck_reduce(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
@@ -662,6 +771,19 @@ hipError_t launch_ck_leaf_tree(const uint8_t* data, const ck_file* files, const 
     if (block_log2 <= lane_log2 || block_log2 > SD_TREE_BLOCK_LOG2_MAX) return hipErrorInvalidValue;
     SD_LAUNCH_W(k_ck_leaf_tree<true>, k_ck_leaf_tree<false>, (n_wg + CK_WG_BLOCKS - 1) / CK_WG_BLOCKS, CK_WG_THREADS, s,
                 data, files, wg_map, n_wg, cvbuf, out, node_base, block_log2 - lane_log2 - 1, nodes);
+    return hipGetLastError();
+}
+
+// block_log2 in [SD_TREE_BLOCK_LOG2_MIN, SD_TREE_BLOCK_LOG2_MAX] (the caller checked)
+hipError_t launch_ck_blocks(const uint8_t* data, const ck_block_item* items, uint32_t n_items, uint32_t block_log2,
+                            bool scatter, uint32_t* nodes, hipStream_t s) {
+    if (n_items == 0) return hipSuccess;
+    const uint32_t lane_log2 = SD_TREE_BLOCK_LOG2_MAX - CK_TREE_LEVELS;  // bytes of a lane, log2
+    if (block_log2 < lane_log2 + 5 || block_log2 > SD_TREE_BLOCK_LOG2_MAX) return hipErrorInvalidValue;
+    const uint32_t il_log2 = block_log2 - lane_log2, per_wg = CK_WG_THREADS >> il_log2;
+    if (per_wg == 0) return hipErrorInvalidValue;
+    SD_LAUNCH_W(k_ck_blocks<true>, k_ck_blocks<false>, (n_items + per_wg - 1) / per_wg, CK_WG_THREADS, s, data, items,
+                n_items, il_log2, scatter ? 1u : 0u, nodes);
     return hipGetLastError();
 }
 

@@ -9,7 +9,10 @@
 // No BLAKE3 of its own: the level is what k_ck_leaf's LDS tree holds on its way to the 1 MiB CV
 // (k_ck_leaf_tree, cas_kernels.hip), and a level's root is k_ck_reduce run with the level as its
 // level 0 (plan_reduce_passes takes any count per file).  Here: the plan, the copy of one-node
-// files' roots, and the verify's compare / compact on sliced.h's two skeletons.
+// files' roots, and the verify's compare / compact on sliced.h's two skeletons.  The listed blocks
+// (sd_checksum_tree_blocks_*) are k_ck_blocks over an item table planned on the host
+// (plan_tree_blocks): its nodes in list order (_run, and _verify's scratch, compared and compacted
+// by the same two skeletons) or scattered into a level that the same reduce then roots (_update).
 #include <hip/hip_runtime.h>
 
 #include <memory>
@@ -97,6 +100,70 @@ struct verify_scratch {
     }
 };
 
+// listed blocks: row i's node (list order) differs from the expected level's node at the item's
+// slot; its file is marked
+struct blocks_differ {
+    const uint4* __restrict__ got;
+    const uint4* __restrict__ want;
+    const ck_block_item* __restrict__ items;
+    const uint64_t* __restrict__ list;
+    uint8_t* __restrict__ file_bad;
+    __device__ bool operator()(uint64_t i, uint64_t) const {
+        const uint64_t q = items[i].dst;
+        const uint4 a0 = got[2 * i], a1 = got[2 * i + 1], b0 = want[2 * q], b1 = want[2 * q + 1];
+        const bool d = a0.x != b0.x || a0.y != b0.y || a0.z != b0.z || a0.w != b0.w || a1.x != b1.x || a1.y != b1.y ||
+                       a1.z != b1.z || a1.w != b1.w;
+        if (d) file_bad[list[2 * i]] = 1;
+        return d;
+    }
+};
+
+// the list's row (file, block) per flagged row, in list order
+struct blocks_rows : from_flags {
+    const uint64_t* __restrict__ list;
+    uint64_t* __restrict__ rows;
+    __device__ void emit(uint64_t i, bool flag, uint64_t slot, uint64_t) const {
+        if (!flag) return;
+        rows[2 * slot] = list[2 * i];
+        rows[2 * slot + 1] = list[2 * i + 1];
+    }
+};
+
+// the list verify's scratch in a pooled slot: the rows' nodes, the flags when the caller wants
+// none, the files' marks, two rows of per-workgroup counts
+struct blocks_scratch {
+    uint8_t *nodes, *flags, *file_bad;
+    uint64_t* counts;
+    static size_t bytes(uint64_t m, uint64_t n) {
+        return 256 + round256(32 * m) + round256(m) + round256(n) + round256(2 * BLOCKS * sizeof(uint64_t));
+    }
+    blocks_scratch(void* base, uint64_t m, uint64_t n) {
+        uint8_t* p = reinterpret_cast<uint8_t*>(((uintptr_t)base + 255) & ~uintptr_t(255));
+        nodes = p, p += round256(32 * m);
+        flags = p, p += round256(m);
+        file_bad = p, p += round256(n);
+        counts = reinterpret_cast<uint64_t*>(p);
+    }
+};
+
+// _update's roots: the reduce passes over the whole level layout, as plan_tree's
+void plan_blocks_roots(sd_checksum_tree_blocks* b) {
+    const size_t n = b->n_files;
+    const std::vector<uint64_t>& nb = b->plan.node_base;
+    std::vector<uint64_t> level_n(n), base(nb.begin(), nb.end() - 1);
+    for (size_t i = 0; i < n; i++) level_n[i] = nb[i + 1] - nb[i];
+    b->roots.lvl_cap[0] = b->roots.lvl_cap[1] = 0;
+    plan_reduce_passes(b->roots, std::move(level_n), std::move(base));
+    b->rtab.begin();
+    b->o_base = b->rtab.add(nb);
+    b->o_pass.clear();
+    for (const auto& ps : b->roots.passes) b->o_pass.push_back(b->rtab.add(ps));
+    b->rtab.upload(nullptr);
+    b->lvl[0].ensure(b->roots.lvl_cap[0] * 32);
+    b->lvl[1].ensure(b->roots.lvl_cap[1] * 32);
+    b->roots_planned = true;
+}
+
 void plan_tree(sd_checksum_tree* t, const uint64_t* offsets, const uint64_t* lens, size_t n, uint32_t block_log2) {
     plan_tree_layout(lens, n, block_log2, t->node_base);  // refuses a bad block_log2 before anything is allocated
     plan_checksum_batch(&t->ck, offsets, lens, n, nullptr);
@@ -120,6 +187,21 @@ void run_tree_leaf(const sd_checksum_tree* t, const uint8_t* d_data, uint8_t* no
     HIP_CHECK(sdk::launch_ck_leaf_tree(d_data, t->ck.d_files(), t->ck.d_map(), (uint32_t)t->ck.plan.wg_map.size(),
                                        t->ck.lvl[0].as<uint32_t>(), reinterpret_cast<uint32_t*>(out), t->d_base(),
                                        t->block_log2, reinterpret_cast<uint32_t*>(nodes), s));
+}
+
+// every file's root from a level buffer: the one-node files' copied, the others' reduced with the
+// level as the reduce's level 0 (T: a tree or a block list, which plan the same passes)
+template <class T>
+void run_level_roots(const T* t, uint64_t n, const uint8_t* d_nodes, uint8_t* d_hash32, hipStream_t s) {
+    uint32_t* out = reinterpret_cast<uint32_t*>(d_hash32);
+    hipLaunchKernelGGL(k_tree_single_roots, dim3(flat_grid(8 * n)), dim3(256), 0, s, t->d_base(), n,
+                       reinterpret_cast<const uint32_t*>(d_nodes), out);
+    HIP_CHECK(hipGetLastError());
+    for (size_t k = 0; k < t->roots.passes.size(); k++) {
+        const uint32_t* src = k == 0 ? reinterpret_cast<const uint32_t*>(d_nodes) : t->lvl[k & 1].template as<uint32_t>();
+        HIP_CHECK(sdk::launch_ck_reduce(src, t->lvl[1 - (k & 1)].template as<uint32_t>(), t->d_pass(k),
+                                        (uint32_t)t->roots.passes[k].size(), out, s));
+    }
 }
 
 void check_aligned16(const void* p, const char* what) {
@@ -189,15 +271,7 @@ int sd_checksum_tree_roots(sd_cas_ctx* ctx, const sd_checksum_tree* t, const uin
     if (n == 0) return SD_OK;
     ctx->bind();
     hipStream_t s = ctx->pick(stream);
-    uint32_t* out = reinterpret_cast<uint32_t*>(d_hash32);
-    hipLaunchKernelGGL(k_tree_single_roots, dim3(flat_grid(8 * n)), dim3(256), 0, s, t->d_base(), n,
-                       reinterpret_cast<const uint32_t*>(d_nodes), out);
-    HIP_CHECK(hipGetLastError());
-    for (size_t k = 0; k < t->roots.passes.size(); k++) {
-        const uint32_t* src = k == 0 ? reinterpret_cast<const uint32_t*>(d_nodes) : t->lvl[k & 1].as<uint32_t>();
-        HIP_CHECK(sdk::launch_ck_reduce(src, t->lvl[1 - (k & 1)].as<uint32_t>(), t->d_pass(k),
-                                        (uint32_t)t->roots.passes[k].size(), out, s));
-    }
+    run_level_roots(t, n, d_nodes, d_hash32, s);
     return SD_OK;
     SD_GUARD_END
 }
@@ -251,6 +325,129 @@ int sd_checksum_tree_verify(sd_cas_ctx* ctx, const sd_checksum_tree* t, const ui
     launch_compact(g_nodes, s, rows, nullptr, total, x.counts, nullptr);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(s));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_blocks_create(sd_cas_ctx* ctx, const uint64_t* lens, size_t n_files, uint32_t block_log2,
+                                   const uint64_t* rows, const uint64_t* data_offsets, size_t m,
+                                   sd_checksum_tree_blocks** out) {
+    SD_GUARD_BEGIN
+    if (!ctx || !out || (n_files && !lens) || (m && (!rows || !data_offsets)))
+        throw sd_failure(SD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (n_files >= (1ull << 31) || m >= (1ull << 32)) throw sd_failure(SD_ERR_INVALID, "list too large");
+    auto b = std::make_unique<sd_checksum_tree_blocks>();
+    plan_tree_blocks(b->plan, lens, n_files, block_log2, rows, data_offsets, m);  // refuses before any allocation
+    b->block_log2 = block_log2;
+    b->n_files = n_files;
+    b->rows.assign(rows, rows + 2 * m);
+    if (m) {
+        ctx->bind();
+        b->tab.begin();
+        b->o_items = b->tab.add(b->plan.items);
+        b->o_rows = b->tab.add(b->rows);
+        b->tab.upload(nullptr);
+    }
+    *out = b.release();
+    return SD_OK;
+    SD_GUARD_END
+}
+
+void sd_checksum_tree_blocks_destroy(sd_checksum_tree_blocks* b) {
+    try {
+        delete b;
+    } catch (...) {
+    }
+}
+
+int sd_checksum_tree_blocks_stats(const sd_checksum_tree_blocks* b, uint64_t out[4]) {
+    SD_GUARD_BEGIN
+    if (!b || !out) throw sd_failure(SD_ERR_INVALID, "null argument");
+    out[0] = b->n_files; out[1] = b->m(); out[2] = b->plan.bytes; out[3] = b->plan.compressions;
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_blocks_run(sd_cas_ctx* ctx, const sd_checksum_tree_blocks* b, const uint8_t* d_data,
+                                uint8_t* d_nodes_out, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !b || (b->m() && (!d_data || !d_nodes_out))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_aligned16(d_nodes_out, "d_nodes_out");
+    if (b->m() == 0) return SD_OK;
+    ctx->bind();
+    HIP_CHECK(sdk::launch_ck_blocks(d_data, b->d_items(), (uint32_t)b->m(), b->block_log2, false,
+                                    reinterpret_cast<uint32_t*>(d_nodes_out), ctx->pick(stream)));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_blocks_verify(sd_cas_ctx* ctx, const sd_checksum_tree_blocks* b, const uint8_t* d_data,
+                                   const uint8_t* d_expected, uint8_t* d_bad, uint64_t* d_rows_out,
+                                   uint64_t capacity, uint64_t* count, uint64_t stats[4], void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !b || (b->m() && (!d_data || !d_expected))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_aligned16(d_expected, "d_expected");
+    if (count) *count = 0;
+    if (stats) memset(stats, 0, 4 * sizeof(uint64_t));
+    const uint64_t n = b->n_files, m = b->m();
+    if (m == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    auto slot = ctx->acquire();
+    struct Rel {
+        sd_cas_ctx* c;
+        std::unique_ptr<Slot>* s;
+        ~Rel() { c->release(std::move(*s)); }
+    } rel{ctx, &slot};
+    slot->staged.ensure(blocks_scratch::bytes(m, n));
+    slot->host_hashes.ensure(2 * BLOCKS * sizeof(uint64_t));
+    const blocks_scratch x(slot->staged.p, m, n);
+    HIP_CHECK(sdk::launch_ck_blocks(d_data, b->d_items(), (uint32_t)m, b->block_log2, false,
+                                    reinterpret_cast<uint32_t*>(x.nodes), s));
+    HIP_CHECK(hipMemsetAsync(x.file_bad, 0, n, s));
+    uint8_t* flags = d_bad ? d_bad : x.flags;
+    const uint32_t g_rows = sliced_grid(m), g_files = sliced_grid(n);
+    launch_flag(g_rows, s,
+                blocks_differ{reinterpret_cast<const uint4*>(x.nodes), reinterpret_cast<const uint4*>(d_expected),
+                              b->d_items(), b->d_rows(), x.file_bad},
+                nullptr, m, flags, x.counts);
+    launch_flag(g_files, s, tree_file_marked{x.file_bad}, nullptr, n, nullptr, x.counts + BLOCKS);
+    HIP_CHECK(hipGetLastError());
+    const uint64_t* h = reinterpret_cast<const uint64_t*>(slot->host_hashes.p);
+    HIP_CHECK(hipMemcpyAsync(slot->host_hashes.p, x.counts, 2 * BLOCKS * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    uint64_t bad_rows = 0, bad_files = 0;
+    for (uint32_t g = 0; g < g_rows; g++) bad_rows += h[g];
+    for (uint32_t g = 0; g < g_files; g++) bad_files += h[BLOCKS + g];
+    if (bad_rows > m || bad_files > n || bad_files > bad_rows)
+        throw sd_failure(SD_ERR_INTERNAL, "verify: inconsistent totals");
+    if (count) *count = bad_rows;
+    if (stats) stats[0] = n, stats[1] = m, stats[2] = bad_rows, stats[3] = bad_files;
+    if (!d_rows_out) return SD_OK;
+    if (capacity < bad_rows) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of differing rows");
+    if (bad_rows == 0) return SD_OK;
+    blocks_rows rows{{flags}, b->d_rows(), d_rows_out};
+    launch_compact(g_rows, s, rows, nullptr, m, x.counts, nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_blocks_update(sd_cas_ctx* ctx, sd_checksum_tree_blocks* b, const uint8_t* d_data,
+                                   uint8_t* d_nodes, uint8_t* d_hash32, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !b || (b->m() && (!d_data || !d_nodes || !d_hash32))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_aligned16(d_nodes, "d_nodes");
+    if (b->plan.repeats) throw sd_failure(SD_ERR_INVALID, "a (file, block) is listed twice: two writers of one node");
+    if (b->m() == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    if (!b->roots_planned) plan_blocks_roots(b);
+    HIP_CHECK(sdk::launch_ck_blocks(d_data, b->d_items(), (uint32_t)b->m(), b->block_log2, true,
+                                    reinterpret_cast<uint32_t*>(d_nodes), s));
+    run_level_roots(b, b->n_files, d_nodes, d_hash32, s);
     return SD_OK;
     SD_GUARD_END
 }

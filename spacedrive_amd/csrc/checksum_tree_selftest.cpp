@@ -5,7 +5,9 @@
 // cpu_blake3.cpp.  Small sizes around the chunk, the lane (4 KiB) and the block boundaries at each
 // block size, in one batch with an odd start; the position rule; the flips of a verify with the
 // capacity rule over pre-filled buffers and every NULL output; the refusals; an empty batch; and
-// concurrent calls.  A program of its own: built plain for the CPU suite (`make
+// concurrent calls.  The listed blocks (sd_cpu_checksum_tree_blocks, _verify, _update) against the
+// same model: every block of those batches in a scrambled order from scattered places over 0xA5, a
+// block at chunk counter 2^32, a repeated and an omitted row, the patched level.  A program of its own: built plain for the CPU suite (`make
 // checksum-tree-selftest`, tests/test_checksum_tree.py) and under ASan + UBSan and TSan (`make
 // sanitize-checksum-tree`, logs in profiles/checksum_tree/).
 #include <stdio.h>
@@ -339,7 +341,193 @@ static void test_concurrent_calls() {  // the calls hold no shared state beyond 
     CHECK(ok == std::vector<int>(4, 1));
 }
 
+// ---------------------------------------------------------------- listed blocks
+// rows (file, block) of a batch's files, their bytes copied to scattered, 16-byte aligned places of
+// a buffer of their own whose every other byte is 0xA5
+struct list_t {
+    std::vector<uint64_t> rows, offs;
+    bytes data;
+    size_t m() const { return offs.size(); }
+    void add(const batch_t& b, uint64_t f, uint64_t j) {
+        const uint64_t B = 1ull << b.k, len = b.lens[f] == 0 ? 0 : std::min<uint64_t>(B, b.lens[f] - j * B);
+        const uint64_t at = (data.size() + 127) / 128 * 128 + (m() % 3 == 1 ? 16 : 0);
+        data.resize(at + len + 64, 0xA5);
+        memcpy(data.data() + at, b.data.data() + b.offs[f] + j * B, len);
+        rows.push_back(f), rows.push_back(j), offs.push_back(at);
+    }
+    // every block of every file, in an order scrambled by `seed`
+    void every(const batch_t& b, uint64_t seed) {
+        std::vector<std::pair<uint64_t, std::pair<uint64_t, uint64_t>>> order;
+        for (size_t i = 0; i < b.n(); i++)
+            for (uint64_t j = 0; j < b.base[i + 1] - b.base[i]; j++) order.push_back({mix(seed, order.size()), {i, j}});
+        std::sort(order.begin(), order.end());
+        for (const auto& o : order) add(b, o.second.first, o.second.second);
+    }
+};
+
+static bytes run_blocks(const batch_t& b, const list_t& l, int nthreads) {
+    bytes out(32 * l.m() + 32, 0xA5);  // one guard row
+    CHECK(sd_cpu_checksum_tree_blocks(l.data.data(), b.lens.data(), b.n(), b.k, l.rows.data(), l.offs.data(), l.m(),
+                                      out.data(), nthreads) == SD_OK);
+    CHECK(std::all_of(out.end() - 32, out.end(), [](uint8_t x) { return x == 0xA5; }));
+    out.resize(32 * l.m());
+    return out;
+}
+
+static void test_blocks() {
+    for (uint32_t k = SD_TREE_BLOCK_LOG2_MIN; k <= SD_TREE_BLOCK_LOG2_MAX; k++) {
+        batch_t b;
+        b.build(k, small_sizes(k), 300 + k);
+        const answer_t want = model(b);
+        list_t l;
+        l.every(b, 17 + k);
+        CHECK(l.m() == b.total());
+        for (int nthreads : {1, 4}) {
+            const bytes got = run_blocks(b, l, nthreads);
+            for (size_t r = 0; r < l.m(); r++)
+                CHECK(memcmp(got.data() + 32 * r, want.nodes.data() + 32 * (b.base[l.rows[2 * r]] + l.rows[2 * r + 1]), 32) == 0);
+        }
+        // a block at chunk counter exactly 2^32 of a file of 4 TiB: only its bytes are resident
+        batch_t h;
+        h.build(k, {4097}, 5);
+        const uint64_t hl[1] = {(1ull << 42) + 4097}, hr[2] = {0, 1ull << (42 - k)}, ho[1] = {0};
+        uint8_t node[32];
+        CHECK(sd_cpu_checksum_tree_blocks(h.data.data(), hl, 1, k, hr, ho, 1, node, 1) == SD_OK);
+        CHECK(m_get(node) == m_subtree(h.data.data(), 4097, 1ull << 32, false));
+        CHECK(!(m_get(node) == m_subtree(h.data.data(), 4097, 0, false)));
+    }
+}
+
+static void test_blocks_verify_and_update() {
+    const uint32_t k = 17;
+    const uint64_t B = 1ull << k;
+    batch_t b;
+    b.build(k, {4097, 3 * B + 5000, 0, 2 * B + 1, B, 700}, 9);
+    const answer_t want = model(b);
+    // flips: the first byte of a middle block, the last byte of a partial last block, a byte of a
+    // one-block file, and a byte of a block the list omits
+    batch_t f = b;
+    f.data[f.offs[1] + B] ^= 1, f.data[f.offs[3] + 2 * B] ^= 1, f.data[f.offs[0] + 100] ^= 1, f.data[f.offs[1] + 2 * B + 9] ^= 1;
+    list_t l;  // (1, 2) is not listed; (1, 1) is listed twice
+    for (const auto& r : std::vector<std::pair<uint64_t, uint64_t>>{{3, 2}, {1, 0}, {1, 1}, {2, 0}, {5, 0}, {0, 0}, {1, 3}, {3, 0}, {1, 1}, {4, 0}})
+        l.add(f, r.first, r.second);
+    const std::vector<uint64_t> want_rows = {3, 2, 1, 1, 0, 0, 1, 1};
+    const bytes want_bad = {1, 0, 1, 0, 0, 1, 0, 0, 1, 0};
+    const size_t m = l.m();
+    uint64_t count = 99, stats[4];
+    bytes bad(m + 1, 0xA5);
+    std::vector<uint64_t> rows(2 * m + 2, 0xA5A5);
+    for (int mask = 0; mask < 4; mask++) {  // bad and rows each NULL in turn
+        std::fill(bad.begin(), bad.end(), 0xA5);
+        std::fill(rows.begin(), rows.end(), 0xA5A5);
+        count = 99;
+        CHECK(sd_cpu_checksum_tree_blocks_verify(l.data.data(), f.lens.data(), f.n(), k, l.rows.data(), l.offs.data(), m,
+                                                 want.nodes.data(), mask & 1 ? bad.data() : nullptr,
+                                                 mask & 2 ? rows.data() : nullptr, 4, &count, mask == 3 ? stats : nullptr,
+                                                 1 + mask) == SD_OK);
+        CHECK(count == 4);
+        if (mask & 1) CHECK(memcmp(bad.data(), want_bad.data(), m) == 0 && bad[m] == 0xA5);
+        if (mask & 2) CHECK(std::equal(want_rows.begin(), want_rows.end(), rows.begin()) && rows[8] == 0xA5A5);
+    }
+    CHECK(stats[0] == b.n() && stats[1] == m && stats[2] == 4 && stats[3] == 3);
+    // a capacity one short: the requirement, the flags and stats complete, no row written
+    std::fill(bad.begin(), bad.end(), 0xA5);
+    std::fill(rows.begin(), rows.end(), 0xA5A5);
+    count = 0;
+    memset(stats, 0, sizeof stats);
+    CHECK(sd_cpu_checksum_tree_blocks_verify(l.data.data(), f.lens.data(), f.n(), k, l.rows.data(), l.offs.data(), m,
+                                             want.nodes.data(), bad.data(), rows.data(), 3, &count, stats, 2) == SD_ERR_CAPACITY);
+    CHECK(count == 4 && stats[2] == 4 && stats[3] == 3 && memcmp(bad.data(), want_bad.data(), m) == 0);
+    CHECK(std::all_of(rows.begin(), rows.end(), [](uint64_t x) { return x == 0xA5A5; }));
+    // update: the repeated row is refused and nothing is written; without it the listed nodes are
+    // the flipped data's, the unlisted ones stay, the roots follow the patched level
+    bytes nodes = want.nodes, roots(32 * b.n() + 32, 0xA5);
+    CHECK(sd_cpu_checksum_tree_blocks_update(l.data.data(), f.lens.data(), f.n(), k, l.rows.data(), l.offs.data(), m,
+                                             nodes.data(), roots.data(), 2) == SD_ERR_INVALID);
+    CHECK(nodes == want.nodes && std::all_of(roots.begin(), roots.end(), [](uint8_t x) { return x == 0xA5; }));
+    list_t u;
+    for (const auto& r : std::vector<std::pair<uint64_t, uint64_t>>{{3, 2}, {1, 1}, {0, 0}, {4, 0}}) u.add(f, r.first, r.second);
+    CHECK(sd_cpu_checksum_tree_blocks_update(u.data.data(), f.lens.data(), f.n(), k, u.rows.data(), u.offs.data(), u.m(),
+                                             nodes.data(), roots.data(), 2) == SD_OK);
+    batch_t g = b;  // the bytes the patched level stands for: the listed flips only
+    g.data[g.offs[1] + B] ^= 1, g.data[g.offs[3] + 2 * B] ^= 1, g.data[g.offs[0] + 100] ^= 1;
+    const answer_t after = model(g);
+    CHECK(nodes == after.nodes);
+    CHECK(memcmp(roots.data(), after.roots.data(), 32 * b.n()) == 0);
+    CHECK(std::all_of(roots.end() - 32, roots.end(), [](uint8_t x) { return x == 0xA5; }));
+}
+
+static void test_blocks_refusals_and_empty() {
+    const uint64_t B = 1ull << 17;
+    batch_t b;
+    b.build(17, {100, B + 1}, 3);
+    list_t l;
+    l.add(b, 0, 0), l.add(b, 1, 1);
+    bytes out(64, 0xA5), nodes(96, 0xA5), roots(64, 0xA5);
+    uint64_t count = 0;
+    auto blocks = [&](const uint8_t* d, const uint64_t* ls, uint32_t k, const uint64_t* rw, const uint64_t* of, uint8_t* o) {
+        return sd_cpu_checksum_tree_blocks(d, ls, 2, k, rw, of, 2, o, 1);
+    };
+    for (uint32_t k : {0u, 16u, 21u, 64u, ~0u}) {
+        CHECK(blocks(l.data.data(), b.lens.data(), k, l.rows.data(), l.offs.data(), out.data()) == SD_ERR_INVALID);
+        CHECK(sd_cpu_checksum_tree_blocks_verify(l.data.data(), b.lens.data(), 2, k, l.rows.data(), l.offs.data(), 2, nodes.data(),
+                                                 nullptr, nullptr, 0, &count, nullptr, 1) == SD_ERR_INVALID);
+        CHECK(sd_cpu_checksum_tree_blocks_update(l.data.data(), b.lens.data(), 2, k, l.rows.data(), l.offs.data(), 2, nodes.data(),
+                                                 roots.data(), 1) == SD_ERR_INVALID);
+    }
+    const uint64_t no_file[4] = {2, 0, 1, 1}, no_block[4] = {0, 1, 1, 1}, past[4] = {0, 0, 1, 2}, odd[2] = {0, l.offs[1] + 8};
+    CHECK(blocks(l.data.data(), b.lens.data(), 17, no_file, l.offs.data(), out.data()) == SD_ERR_INVALID);
+    CHECK(blocks(l.data.data(), b.lens.data(), 17, no_block, l.offs.data(), out.data()) == SD_ERR_INVALID);
+    CHECK(blocks(l.data.data(), b.lens.data(), 17, past, l.offs.data(), out.data()) == SD_ERR_INVALID);
+    CHECK(blocks(l.data.data(), b.lens.data(), 17, l.rows.data(), odd, out.data()) == SD_ERR_INVALID);
+    CHECK(blocks(nullptr, b.lens.data(), 17, l.rows.data(), l.offs.data(), out.data()) == SD_ERR_INVALID);
+    CHECK(blocks(l.data.data(), nullptr, 17, l.rows.data(), l.offs.data(), out.data()) == SD_ERR_INVALID);
+    CHECK(blocks(l.data.data(), b.lens.data(), 17, nullptr, l.offs.data(), out.data()) == SD_ERR_INVALID);
+    CHECK(blocks(l.data.data(), b.lens.data(), 17, l.rows.data(), nullptr, out.data()) == SD_ERR_INVALID);
+    CHECK(blocks(l.data.data(), b.lens.data(), 17, l.rows.data(), l.offs.data(), nullptr) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree_blocks_verify(l.data.data(), b.lens.data(), 2, 17, l.rows.data(), l.offs.data(), 2, nullptr, nullptr,
+                                             nullptr, 0, &count, nullptr, 1) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree_blocks_update(l.data.data(), b.lens.data(), 2, 17, l.rows.data(), l.offs.data(), 2, nullptr,
+                                             roots.data(), 1) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree_blocks_update(l.data.data(), b.lens.data(), 2, 17, l.rows.data(), l.offs.data(), 2, nodes.data(),
+                                             nullptr, 1) == SD_ERR_INVALID);
+    for (const bytes* x : {&out, &nodes, &roots}) CHECK(std::all_of(x->begin(), x->end(), [](uint8_t v) { return v == 0xA5; }));
+    // an empty list: every call does nothing
+    uint64_t stats[4] = {9, 9, 9, 9};
+    count = 9;
+    CHECK(sd_cpu_checksum_tree_blocks(nullptr, b.lens.data(), 2, 17, nullptr, nullptr, 0, nullptr, 1) == SD_OK);
+    CHECK(sd_cpu_checksum_tree_blocks_verify(nullptr, b.lens.data(), 2, 17, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, &count,
+                                             stats, 1) == SD_OK);
+    CHECK(count == 0 && stats[0] == 0 && stats[1] == 0 && stats[2] == 0 && stats[3] == 0);
+    CHECK(sd_cpu_checksum_tree_blocks_update(nullptr, b.lens.data(), 2, 17, nullptr, nullptr, 0, nullptr, nullptr, 1) == SD_OK);
+    CHECK(sd_cpu_checksum_tree_blocks(nullptr, nullptr, 0, 17, nullptr, nullptr, 0, nullptr, 1) == SD_OK);
+}
+
+static void test_blocks_concurrent_calls() {
+    batch_t b;
+    b.build(17, small_sizes(17), 23);
+    const answer_t want = model(b);
+    list_t l;
+    l.every(b, 4);
+    std::vector<std::thread> ts;
+    std::vector<int> ok(4, 0);
+    for (int t = 0; t < 4; t++)
+        ts.emplace_back([&, t] {
+            const bytes got = run_blocks(b, l, 1 + t);
+            int good = 1;
+            for (size_t r = 0; r < l.m(); r++)
+                good &= memcmp(got.data() + 32 * r, want.nodes.data() + 32 * (b.base[l.rows[2 * r]] + l.rows[2 * r + 1]), 32) == 0;
+            ok[t] = good;
+        });
+    for (auto& t : ts) t.join();
+    CHECK(ok == std::vector<int>(4, 1));
+}
+
 int main() {
+    test_blocks();
+    test_blocks_verify_and_update();
+    test_blocks_refusals_and_empty();
+    test_blocks_concurrent_calls();
     test_levels_and_roots();
     test_position_rule();
     test_verify();

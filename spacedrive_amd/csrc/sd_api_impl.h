@@ -165,6 +165,29 @@ struct sd_checksum_tree {
     const ck_reduce_wg* d_pass(size_t k) const { return tab.at<ck_reduce_wg>(o_pass[k]); }
 };
 
+// listed blocks of a batch of files (include/sd_cas.h, listed blocks; checksum_tree.hip)
+struct sd_checksum_tree_blocks {
+    uint32_t block_log2 = 0;
+    size_t n_files = 0;
+    TreeBlocksPlan plan;         // node_base, the items, whether a (file, block) repeats
+    std::vector<uint64_t> rows;  // m x (file, block): what _verify reports
+    sdi::Tables tab;             // the items, then the rows: one upload
+    size_t o_items = 0, o_rows = 0;
+    // _update's roots, planned by the first _update: node_base and the reduce passes over the level
+    bool roots_planned = false;
+    CkPlan roots;
+    sdi::Tables rtab;
+    size_t o_base = 0;
+    std::vector<size_t> o_pass;
+    sdi::DevBuf lvl[2];
+    size_t m() const { return plan.items.size(); }
+    uint64_t total() const { return plan.node_base.back(); }
+    const ck_block_item* d_items() const { return tab.at<ck_block_item>(o_items); }
+    const uint64_t* d_rows() const { return tab.at<uint64_t>(o_rows); }
+    const uint64_t* d_base() const { return rtab.at<uint64_t>(o_base); }
+    const ck_reduce_wg* d_pass(size_t k) const { return rtab.at<ck_reduce_wg>(o_pass[k]); }
+};
+
 // one file over the ranks of a communicator (include/sd_cas.h, sd_split_range)
 struct sd_split_checksum {
     SplitPlan sp;

@@ -236,6 +236,26 @@ inline uint64_t tree_nodes(uint64_t len, uint32_t block_log2) {
 // node_base[0 .. n] of a batch; throws SD_ERR_INVALID on a block_log2 outside
 // [SD_TREE_BLOCK_LOG2_MIN, SD_TREE_BLOCK_LOG2_MAX]
 void plan_tree_layout(const uint64_t* lens, size_t n, uint32_t block_log2, std::vector<uint64_t>& node_base);
+// one listed block (include/sd_cas.h, listed blocks; k_ck_blocks, cas_kernels.hip): 32 bytes
+struct ck_block_item {
+    uint64_t src;     // byte offset of the block's bytes in the data buffer
+    uint64_t chunk0;  // counter of its first chunk: j * B / 1024
+    uint32_t len;     // its bytes, 0 .. B (0: the empty file)
+    uint32_t root;    // its file has one node: ROOT on its last compression
+    uint64_t dst;     // its slot in the batch's level layout: node_base[f] + j
+};
+static_assert(sizeof(ck_block_item) == 32, "two 16-byte loads per item");
+// A block list checked and planned: node_base[0 .. n_files], one item per row, whether a (file,
+// block) repeats, the bytes and compressions of its items.  Throws SD_ERR_INVALID on a block_log2
+// out of range, a file or block past the end, a start that is not 16-byte aligned.
+struct TreeBlocksPlan {
+    std::vector<uint64_t> node_base;
+    std::vector<ck_block_item> items;
+    bool repeats = false;
+    uint64_t bytes = 0, compressions = 0;
+};
+void plan_tree_blocks(TreeBlocksPlan& p, const uint64_t* lens, size_t n_files, uint32_t block_log2,
+                      const uint64_t* rows, const uint64_t* data_offsets, size_t m);
 
 // ------------------------------------------------------------------ fingerprints
 // k_cas_gather (gather.hip) builds each file's cas message from its resident bytes.  Its

@@ -38,6 +38,10 @@ hipError_t launch_ck_leaf(const uint8_t* data, uint64_t shift, uint32_t blk_base
 hipError_t launch_ck_leaf_tree(const uint8_t* data, const ck_file* files, const uint2* wg_map, uint32_t n_wg,
                                uint32_t* cvbuf, uint32_t* out, const uint64_t* node_base, uint32_t block_log2,
                                uint32_t* nodes, hipStream_t s);
+// the nodes of n_items listed blocks of at most 2^block_log2 bytes (17..20): item i's node to
+// nodes[8 * i], or (scatter) to nodes[8 * items[i].dst]; nodes 16-byte aligned
+hipError_t launch_ck_blocks(const uint8_t* data, const ck_block_item* items, uint32_t n_items, uint32_t block_log2,
+                            bool scatter, uint32_t* nodes, hipStream_t s);
 hipError_t launch_ck_reduce(const uint32_t* src, uint32_t* dst, const ck_reduce_wg* wgs, uint32_t n_wg,
                             uint32_t* out, hipStream_t s);
 hipError_t launch_synth_stage_cas(const uint64_t* sizes, const uint64_t* cids, const uint32_t* twins,

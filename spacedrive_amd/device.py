@@ -87,6 +87,9 @@ class Context:
     def checksum_tree(self, offsets, lens, block_log2: int = 17) -> "ChecksumTree":
         return ChecksumTree(self, offsets, lens, block_log2)
 
+    def checksum_tree_blocks(self, lens, rows, data_offsets, block_log2: int = 17) -> "ChecksumTreeBlocks":
+        return ChecksumTreeBlocks(self, lens, rows, data_offsets, block_log2)
+
     # -------------------------------------------------------------- files -> device hashes
     def hashes_files(self, paths, sizes, d_hash32, d_valid=None, nthreads: int = 16) -> np.ndarray:
         """sd_cas_hashes_files: generate_cas_id's messages of these files hashed into
@@ -995,6 +998,94 @@ class ChecksumTree:
     def close(self) -> None:
         if self.handle:
             lib().sd_checksum_tree_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ChecksumTreeBlocks:
+    """A list of blocks (sd_checksum_tree_blocks) of files of lengths `lens`: row r = (file, block),
+    its bytes at d_data[data_offsets[r]:] wherever they sit (16-byte aligned starts).  Only the
+    listed bytes are hashed.  The levels are laid out as ChecksumTree's: file i's nodes are rows
+    node_base[i] .. node_base[i + 1]."""
+
+    def __init__(self, ctx: Context, lens, rows, data_offsets, block_log2: int = 17):
+        from .cpu import tree_node_base
+        self.ctx = ctx
+        self.block_log2 = int(block_log2)
+        self.lens = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+        self.rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2)
+        self.data_offsets = np.ascontiguousarray(data_offsets, dtype=np.uint64).reshape(-1)
+        if len(self.rows) != len(self.data_offsets):
+            raise ValueError("rows and data_offsets differ in length")
+        h = ctypes.c_void_p()
+        check(lib().sd_checksum_tree_blocks_create(ctx.handle, _ptr(self.lens), len(self.lens), self.block_log2,
+                                                   _ptr(self.rows), _ptr(self.data_offsets), len(self.rows),
+                                                   ctypes.byref(h)))
+        self.handle = h
+        st = np.zeros(4, np.uint64)
+        check(lib().sd_checksum_tree_blocks_stats(h, _ptr(st)))
+        self.n, self.m, self.bytes_hashed, self.compressions = (int(v) for v in st)
+        self.node_base = tree_node_base(self.lens, self.block_log2)
+        self.total_nodes = int(self.node_base[self.n])
+
+    def run(self, d_data: torch.Tensor, d_nodes_out: torch.Tensor, stream=None) -> None:
+        """row r's node -> d_nodes_out[32 r], list order"""
+        assert d_nodes_out.numel() >= 32 * self.m
+        check(lib().sd_checksum_tree_blocks_run(self.ctx.handle, self.handle, _ptr(d_data), _ptr(d_nodes_out),
+                                                _stream(stream)))
+
+    def verify(self, d_data: torch.Tensor, d_expected: torch.Tensor, d_bad: Optional[torch.Tensor] = None,
+               d_rows_out: Optional[torch.Tensor] = None, capacity: Optional[int] = None, want_rows: bool = True,
+               stream=None):
+        """sd_checksum_tree_blocks_verify: hashes the listed blocks and compares each with its node of
+        d_expected (the whole level buffer).  Returns (rows int64 [count, 2] of (file, block) in list
+        order, stats uint64 [4]: files, rows compared, rows that differ, files with a differing row),
+        and d_bad (uint8 [m], written when given) as a third value.  Rows, capacity and want_rows as
+        ChecksumTree.verify."""
+        assert d_expected.numel() >= 32 * self.total_nodes and (d_bad is None or d_bad.numel() >= self.m)
+        st = _stream(stream)
+        count = ctypes.c_uint64(0)
+        stats = np.zeros(4, np.uint64)
+
+        def call(rows, cap):
+            rc = lib().sd_checksum_tree_blocks_verify(self.ctx.handle, self.handle, _ptr(d_data), _ptr(d_expected),
+                                                      _ptr(d_bad), _ptr(rows), cap, ctypes.byref(count), _ptr(stats), st)
+            try:
+                check(rc)
+            except SdCasError as e:
+                e.needed = int(count.value)
+                e.stats = stats
+                raise
+
+        dev = torch.device("cuda", self.ctx.device)
+        if not want_rows:
+            call(None, 0)
+            rows = torch.empty((0, 2), dtype=torch.int64, device=dev)
+        elif d_rows_out is None:
+            rows = torch.empty((max(self.m, 1), 2), dtype=torch.int64, device=dev)
+            call(rows, self.m)
+            rows = rows[:int(count.value)]
+        else:
+            assert d_rows_out.dtype == torch.int64 and d_rows_out.is_cuda and d_rows_out.is_contiguous()
+            call(d_rows_out, d_rows_out.numel() // 2 if capacity is None else int(capacity))
+            rows = d_rows_out.reshape(-1)[:2 * int(count.value)].reshape(-1, 2)
+        return (rows, stats) if d_bad is None else (rows, stats, d_bad)
+
+    def update(self, d_data: torch.Tensor, d_nodes: torch.Tensor, d_hash32: torch.Tensor, stream=None) -> None:
+        """the listed blocks' nodes -> their slots of d_nodes (the whole level buffer, patched in
+        place), then every file's root from the patched level -> d_hash32"""
+        assert d_nodes.numel() >= 32 * self.total_nodes and d_hash32.numel() >= 32 * self.n
+        check(lib().sd_checksum_tree_blocks_update(self.ctx.handle, self.handle, _ptr(d_data), _ptr(d_nodes),
+                                                   _ptr(d_hash32), _stream(stream)))
+
+    def close(self) -> None:
+        if self.handle:
+            lib().sd_checksum_tree_blocks_destroy(self.handle)
             self.handle = None
 
     def __del__(self):  # pragma: no cover

@@ -6,6 +6,10 @@ blocks, p2p/src/spaceblock/block_size.rs:20-23).
 Files are read as file_checksum reads them (validation/hash.rs:10-24: 1 MiB reads until a short
 one) and hashed by the library's CPU path, the route it prefers for files in the page cache
 (DESIGN.md §4.1).  For files already resident on the device: ``Context.checksum_tree``.
+
+verify_blocks_file and update_file take a list of blocks and read only those (os.pread): blocks as
+they arrive, the blocks a sender resent, the blocks a write in place touched; blocks_to_rehash
+lists the ones an append or a truncation costs.  On the device: ``Context.checksum_tree_blocks``.
 """
 from __future__ import annotations
 
@@ -50,6 +54,83 @@ def verify_file(path: Union[str, os.PathLike], length: int, nodes, block_log2: i
         raise ValueError(f"{os.fsdecode(path)}: {len(data)} bytes, the level was taken over {length}")
     rows, _ = cpu.checksum_tree_verify(data, [0], [length], nodes, block_log2, nthreads=nthreads)
     return [int(b) for b in rows[:, 1]]
+
+
+def _read_blocks(path, length: int, blocks, block_log2: int):
+    """(buffer, rows [m, 2], offsets [m]): the listed blocks of a file of `length` bytes, each read
+    with one os.pread into a buffer of 64-byte aligned starts -- nothing else of the file is read"""
+    B = 1 << block_log2
+    nb = cpu.tree_nodes(length, block_log2)
+    blocks = [int(j) for j in blocks]
+    if any(j < 0 or j >= nb for j in blocks):
+        raise ValueError(f"a file of {length} bytes has blocks 0 .. {nb - 1}")
+    sizes = [max(0, min(B, length - j * B)) for j in blocks]
+    offs = np.zeros(len(blocks), np.uint64)
+    cur = 0
+    for r, size in enumerate(sizes):
+        offs[r] = cur
+        cur += (size + 63) // 64 * 64 + 64
+    buf = np.zeros(cur + 64, np.uint8)
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        for j, size, o in zip(blocks, sizes, offs):
+            got, o = 0, int(o)
+            while got < size:
+                part = os.pread(fd, size - got, j * B + got)
+                if not part:
+                    raise ValueError(f"{os.fsdecode(path)}: block {j} ends before byte {j * B + size}")
+                buf[o + got:o + got + len(part)] = np.frombuffer(part, np.uint8)
+                got += len(part)
+    finally:
+        os.close(fd)
+    rows = np.array([[0, j] for j in blocks], np.uint64).reshape(-1, 2)
+    return buf, rows, offs
+
+
+def verify_blocks_file(path: Union[str, os.PathLike], length: int, nodes, blocks, block_log2: int = 17,
+                       nthreads: int = cpu.THREADS) -> List[int]:
+    """The listed blocks of `path` (a file of `length` bytes) whose node differs from `nodes` (its
+    level), in list order; [] when they all match.  Reads only those blocks: blocks as they arrive,
+    or the ones a sender resent after verify_file named them."""
+    buf, rows, offs = _read_blocks(path, length, blocks, block_log2)
+    bad, _ = cpu.checksum_tree_blocks_verify(buf, [length], rows, offs, nodes, block_log2, nthreads=nthreads)
+    return [int(b) for b in bad[:, 1]]
+
+
+def update_file(path: Union[str, os.PathLike], length: int, nodes, blocks, block_log2: int = 17,
+                nthreads: int = cpu.THREADS) -> Tuple[str, np.ndarray]:
+    """(hex, nodes) of `path`, now `length` bytes, after a change that touched only `blocks`: the
+    level `nodes` taken before the change with those blocks' nodes replaced, and file_checksum's 64
+    hex digits from it.  Reads only the listed blocks.  After a write in place `blocks` are the
+    blocks written; after an append or a truncation they are blocks_to_rehash(old length, length),
+    and the level is cut or grown to the new block count first (every block it gains has to be
+    listed)."""
+    nb = cpu.tree_nodes(length, block_log2)
+    old = np.ascontiguousarray(nodes, dtype=np.uint8).reshape(-1, 32)
+    listed = {int(j) for j in blocks}
+    if any(j not in listed for j in range(len(old), nb)):
+        raise ValueError("a block past the old level's end is not listed")
+    level = np.zeros((nb, 32), np.uint8)
+    level[:min(nb, len(old))] = old[:nb]
+    if not listed:  # an empty list is a no-op of the library: the root of the level as it stands
+        return cpu.checksum_tree_roots(level, [length], block_log2)[0].tobytes().hex(), level
+    buf, rows, offs = _read_blocks(path, length, blocks, block_log2)
+    level, roots = cpu.checksum_tree_blocks_update(buf, [length], rows, offs, level, block_log2, nthreads)
+    return roots[0].tobytes().hex(), level
+
+
+def blocks_to_rehash(len_old: int, len_new: int, block_log2: int) -> List[int]:
+    """The blocks of a file that went from len_old to len_new bytes whose old nodes cannot be kept
+    even if no byte before min(len_old, len_new) changed: the complement of common_blocks among the
+    new file's blocks.  Every block when either length is a single block (its node is or was a root
+    hash), else the blocks from min(len_old, len_new) // B on."""
+    if block_log2 < 10:
+        raise ValueError("a block is at least one 1024-byte chunk")
+    B = 1 << block_log2
+    nb_new = max(1, -(-len_new // B))
+    if min(len_old, len_new) <= B:
+        return list(range(nb_new))
+    return list(range(min(len_old, len_new) // B, nb_new))
 
 
 def common_blocks(len_a: int, len_b: int, block_log2: int) -> List[int]:
