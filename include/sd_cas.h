@@ -1083,6 +1083,59 @@ int sd_cpu_checksum_tree_blocks_update(const uint8_t* data, const uint64_t* lens
                                        uint32_t block_log2, const uint64_t* rows, const uint64_t* data_offsets,
                                        size_t m, uint8_t* nodes, uint8_t* hash32, int nthreads);
 
+/* Block proofs: a listed block checked against the file's checksum and length ALONE -- what the
+ * library's database keeps per file_path (integrity_checksum, size_in_bytes) -- instead of against
+ * a stored level.  The project's own level-wise definitions; not Bao's byte format.
+ *   levels    of a file of nb nodes: level 0 is N_0 .. N_{nb-1}, n_0 = nb; level L+1 has n_{L+1} =
+ *             ceil(n_L / 2) nodes, node i = parent(level L's node 2i, node 2i+1) if 2i+1 < n_L, else
+ *             a copy of the carried node 2i; ROOT goes on the one parent formed when n_L == 2; the
+ *             height is h = ceil(log2 nb), 0 for nb == 1
+ *   proof     of block j: for L = 0 .. h-1, i = j >> L, s = i ^ 1: if s < n_L one 32-byte entry, level
+ *             L's node s, else nothing (the node was carried).  Entries bottom-up, packed.  Their
+ *             count p(len, k, j) depends only on the length, block_log2 and j: nothing about a
+ *             proof's shape is taken from the sender
+ *   climb     from the block's node cv, at each level that has an entry: cv = parent(entry, cv) if i
+ *             is odd, else parent(cv, entry), ROOT iff n_L == 2.  The result must equal the file's
+ *             checksum; for nb == 1 the proof is empty and the node is the checksum
+ *   trusted   the checksum AND the length: a proof is checked for a block of a file of that length
+ *   layout    proof_base[0 .. m] is the exclusive prefix sum of the rows' entry counts: row r's
+ *             proof is proof_base[r+1] - proof_base[r] entries at byte 32 proof_base[r]
+ * d_proofs / d_proofs_out / d_roots / d_nodes_out are 16-byte aligned. */
+/* p(len, block_log2, block).  GPU-free.  A block the file does not have, or a block_log2 outside
+ * 17..20, is SD_ERR_INVALID. */
+int sd_checksum_tree_proof_entries(uint64_t len, uint32_t block_log2, uint64_t block, uint32_t* entries);
+/* proof_base[0 .. m] (host) of the list's rows.  GPU-free. */
+int sd_checksum_tree_blocks_proof_layout(sd_checksum_tree_blocks* blocks, uint64_t* proof_base);
+/* Every row's proof, in list order (repeats allowed), from d_nodes (the whole level layout,
+ * node_base[n_files] x 32 B, as _update takes it) -> d_proofs_out (proof_base[m] x 32 B).  Reads no
+ * file bytes, data_offsets play no part, and only the levels of files with at least one row are
+ * read: the others may hold anything.  Asynchronous on `stream`; one prove of a list at a time (the
+ * first plans the passes, and the list owns the scratch of the listed files' interior levels:
+ * fewer than nb + h nodes per listed file). */
+int sd_checksum_tree_blocks_prove(sd_cas_ctx* ctx, sd_checksum_tree_blocks* blocks, const uint8_t* d_nodes,
+                                  uint8_t* d_proofs_out, void* stream);
+/* Hashes the listed bytes, climbs each row's node through its proof (d_proofs, laid out by
+ * proof_base) and compares the result with d_roots[32 f] (n_files x 32 B, the layout
+ * sd_checksum_tree_roots writes; only the listed files' entries are read).
+ *   d_nodes_out (m x 32 B, may be NULL): the rows' nodes, list order -- a receiver assembles its own
+ *     level from the blocks that passed
+ *   d_bad, d_rows_out, capacity, *count, SD_ERR_CAPACITY, stats[4]: exactly as
+ *     sd_checksum_tree_blocks_verify (rows in LIST order, a repeated row once per repeat)
+ * Runs on `stream` and syncs it; uses the context's pooled slot as _verify does. */
+int sd_checksum_tree_blocks_verify_proofs(sd_cas_ctx* ctx, sd_checksum_tree_blocks* blocks, const uint8_t* d_data,
+                                          const uint8_t* d_proofs, const uint8_t* d_roots, uint8_t* d_nodes_out,
+                                          uint8_t* d_bad, uint64_t* d_rows_out, uint64_t capacity, uint64_t* count,
+                                          uint64_t stats[4], void* stream);
+/* The same over host memory on host cores, with the device calls' rules.  _prove takes no
+ * data_offsets: it reads no file bytes. */
+int sd_cpu_checksum_tree_blocks_prove(const uint8_t* nodes, const uint64_t* lens, size_t n_files, uint32_t block_log2,
+                                      const uint64_t* rows, size_t m, uint8_t* proofs_out);
+int sd_cpu_checksum_tree_blocks_verify_proofs(const uint8_t* data, const uint64_t* lens, size_t n_files,
+                                              uint32_t block_log2, const uint64_t* rows, const uint64_t* data_offsets,
+                                              size_t m, const uint8_t* proofs, const uint8_t* roots,
+                                              uint8_t* nodes_out, uint8_t* bad, uint64_t* rows_out, uint64_t capacity,
+                                              uint64_t* count, uint64_t stats[4], int nthreads);
+
 /* ---------------------------------------------------------------- synthetic data */
 /* Device generator of SURVEY.md §8(d) (seed 0x5D5DCA51D, splitmix64 counter stream),
  * for benchmarks and parity tests: writes the exact cas message of each synthetic file

@@ -294,6 +294,88 @@ def checksum_tree_blocks_update(data, lens, rows, data_offsets, nodes, block_log
     return nd, roots[:len(ls)]
 
 
+def tree_proof_entries(length: int, block: int, block_log2: int = 17) -> int:
+    """sd_checksum_tree_proof_entries: the 32-byte entries of the proof of `block` of a file of
+    `length` bytes -- the levels at which the block's node has a sibling on its way to the root."""
+    v = ctypes.c_uint32(0)
+    check(lib().sd_checksum_tree_proof_entries(int(length), int(block_log2), int(block), ctypes.byref(v)))
+    return int(v.value)
+
+
+def tree_proof_base(lens, rows, block_log2: int = 17) -> np.ndarray:
+    """proof_base uint64 [m + 1] of a list's rows: the exclusive prefix sum of their entry counts."""
+    ls = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+    rw = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2)
+    base = np.zeros(len(rw) + 1, np.uint64)
+    for r, (f, j) in enumerate(rw):
+        if int(f) >= len(ls):
+            raise ValueError(f"row {r}: no such file")
+        base[r + 1] = base[r] + np.uint64(tree_proof_entries(int(ls[int(f)]), int(j), block_log2))
+    return base
+
+
+def checksum_tree_blocks_prove(nodes, lens, rows, block_log2: int = 17):
+    """sd_cpu_checksum_tree_blocks_prove: (proofs uint8 [proof_base[m], 32], proof_base) of the
+    listed (file, block) rows from `nodes`, the batch's whole level uint8 [node_base[n_files], 32];
+    only the listed files' levels are read.  Row r's proof is proofs[proof_base[r]:proof_base[r + 1]],
+    bottom-up."""
+    ls = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+    rw = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2)
+    nd = np.ascontiguousarray(nodes, dtype=np.uint8).reshape(-1)
+    if nd.size != 32 * int(tree_node_base(ls, block_log2)[len(ls)]):
+        raise ValueError("nodes is not node_base[n_files] x 32 bytes")
+    base = tree_proof_base(ls, rw, block_log2)
+    total = int(base[len(rw)])
+    out = np.zeros((max(total, 1), 32), np.uint8)
+    check(lib().sd_cpu_checksum_tree_blocks_prove(nd.ctypes.data if nd.size else None, ls.ctypes.data, len(ls),
+                                                  int(block_log2), rw.ctypes.data, len(rw), out.ctypes.data))
+    return out[:total], base
+
+
+def checksum_tree_blocks_verify_proofs(data, lens, rows, data_offsets, proofs, roots, block_log2: int = 17,
+                                       capacity: Optional[int] = None, want_rows: bool = True,
+                                       want_flags: bool = False, want_nodes: bool = False, nthreads: int = THREADS):
+    """sd_cpu_checksum_tree_blocks_verify_proofs: the listed blocks whose node, climbed through its
+    proof (`proofs`, laid out by tree_proof_base), does not reach its file's checksum (`roots` uint8
+    [n_files, 32]; only the listed files' are read).  Returns (rows uint64 [count, 2] in list order,
+    stats uint64 [4]) as checksum_tree_blocks_verify, then the 0/1 byte per row with want_flags and
+    the rows' nodes uint8 [m, 32] with want_nodes.  `capacity` and want_rows as there."""
+    from ._native import SdCasError
+    ls, rw, offs, sizes = _block_list(lens, rows, data_offsets, block_log2)
+    keep, addr = _block_data(data, offs, sizes)
+    m = len(rw)
+    pf = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1)
+    rt = np.ascontiguousarray(roots, dtype=np.uint8).reshape(-1)
+    if sizes is not None:
+        if rt.size != 32 * len(ls):
+            raise ValueError("roots is not n_files x 32 bytes")
+        if pf.size != 32 * int(tree_proof_base(ls, rw, block_log2)[m]):
+            raise ValueError("proofs is not proof_base[m] x 32 bytes")
+    cap = m if capacity is None else int(capacity)
+    out_rows = np.zeros((max(cap, 1), 2), np.uint64)
+    bad = np.zeros(max(m, 1), np.uint8)
+    nodes = np.zeros((max(m, 1), 32), np.uint8)
+    count = ctypes.c_uint64(0)
+    stats = np.zeros(4, np.uint64)
+    rc = lib().sd_cpu_checksum_tree_blocks_verify_proofs(
+        addr, ls.ctypes.data, len(ls), int(block_log2), rw.ctypes.data, offs.ctypes.data, m,
+        pf.ctypes.data if pf.size else None, rt.ctypes.data if rt.size else None,
+        nodes.ctypes.data if want_nodes else None, bad.ctypes.data if want_flags else None,
+        out_rows.ctypes.data if want_rows else None, cap, ctypes.byref(count), stats.ctypes.data, nthreads)
+    try:
+        check(rc)
+    except SdCasError as e:
+        e.needed = int(count.value)
+        e.stats = stats
+        raise
+    out = (out_rows[:int(count.value) if want_rows else 0], stats)
+    if want_flags:
+        out += (bad[:m],)
+    if want_nodes:
+        out += (nodes[:m],)
+    return out
+
+
 def blake3(data: bytes) -> bytes:
     """Full 32-byte BLAKE3 of a host buffer (sd_cpu_checksums of one range)."""
     buf = np.frombuffer(bytes(data) + bytes(64), np.uint8)

@@ -6,18 +6,22 @@
 // p2p/src/spaceblock/block.rs:6,10 (a block to resend needs a checksum) and block_size.rs:20-23
 // (128 KiB blocks); file_checksum is validation/hash.rs:10-24.
 //
-// No BLAKE3 of its own: the level is what k_ck_leaf's LDS tree holds on its way to the 1 MiB CV
+// The level is what k_ck_leaf's LDS tree holds on its way to the 1 MiB CV
 // (k_ck_leaf_tree, cas_kernels.hip), and a level's root is k_ck_reduce run with the level as its
 // level 0 (plan_reduce_passes takes any count per file).  Here: the plan, the copy of one-node
 // files' roots, and the verify's compare / compact on sliced.h's two skeletons.  The listed blocks
 // (sd_checksum_tree_blocks_*) are k_ck_blocks over an item table planned on the host
 // (plan_tree_blocks): its nodes in list order (_run, and _verify's scratch, compared and compacted
 // by the same two skeletons) or scattered into a level that the same reduce then roots (_update).
+// The block proofs (_prove, _verify_proofs) are the only BLAKE3 here, blake3_device.h's parent:
+// k_tree_levels stores the interior levels a reduce passes through, k_tree_proof_gather packs the
+// siblings, and proof_climb, a predicate of the flag skeleton, climbs a row's node to its root.
 #include <hip/hip_runtime.h>
 
 #include <memory>
 #include <vector>
 
+#include "blake3_device.h"
 #include "sd_api_impl.h"
 #include "sliced.h"
 
@@ -145,6 +149,145 @@ struct blocks_scratch {
         counts = reinterpret_cast<uint64_t*>(p);
     }
 };
+
+// ------------------------------------------------------------------------------------ proofs
+// Block proofs (include/sd_cas.h): the siblings on a block's way up, and the climb back to the root.
+__device__ __forceinline__ void put_cv(uint32_t* dst, const uint32_t (&cv)[8]) {
+    uint4* d = reinterpret_cast<uint4*>(dst);
+    d[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
+    d[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+}
+__device__ __forceinline__ void get_cv(uint32_t (&cv)[8], const uint32_t* src) {
+    const uint4* s = reinterpret_cast<const uint4*>(src);
+    const uint4 a = s[0], b = s[1];
+    cv[0] = a.x; cv[1] = a.y; cv[2] = a.z; cv[3] = a.w;
+    cv[4] = b.x; cv[5] = b.y; cv[6] = b.z; cv[7] = b.w;
+}
+
+// Interior levels: k_ck_reduce's LDS tree over up to 256 consecutive nodes of one file's level, but
+// every level it passes through is stored, the carried odd node included: node t of the group's
+// level l goes to slot lvl_off[lvl_tab + l - 1] + (first >> l) + t of the scratch.  An aligned group
+// of 256 is a complete subtree under the level-wise rule, and in a file's last, short group the
+// local carry (2t + 1 >= the group's count) is the file's own, so the slots are the file's levels.
+// No ROOT: the levels stored end below the root.  src is the caller's level (pass 0) or the scratch
+// itself (a level an earlier pass stored), so neither pointer is __restrict__.
+__global__ __launch_bounds__(256) void k_tree_levels(const uint32_t* src, uint32_t* scratch,
+                                                     const ck_levels_wg* __restrict__ wgs,
+                                                     const uint64_t* __restrict__ lvl_off) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[256][8];
+    const ck_levels_wg w = wgs[blockIdx.x];
+    const uint32_t t = threadIdx.x;
+    if (t < w.count) {
+        uint32_t cv[8];
+        get_cv(cv, src + (w.src_base + t) * 8);
+        put_cv(lds[t], cv);
+    }
+    __syncthreads();
+    uint32_t n = w.count;
+    for (uint32_t l = 1; l <= w.levels; l++) {
+        const uint32_t P = n >> 1;
+        const bool carry = n & 1u;
+        uint32_t res[8];
+        bool have = false;
+        if (t < P) {
+            uint32_t a[8], b[8];
+            get_cv(a, lds[2 * t]);
+            get_cv(b, lds[2 * t + 1]);
+            sdb3::parent<false>(res, a, b, 0u);
+            have = true;
+        } else if (carry && t == P) {
+            get_cv(res, lds[n - 1]);
+            have = true;
+        }
+        __syncthreads();
+        if (have) {
+            put_cv(lds[t], res);
+            put_cv(scratch + (lvl_off[w.lvl_tab + l - 1] + (w.first >> l) + t) * 8, res);
+        }
+        __syncthreads();
+        n = P + (carry ? 1u : 0u);
+    }
+}
+
+// Proof gather: one lane per row copies the siblings that exist, bottom-up, to the row's place
+// among the packed proofs: level 0's from the caller's level, the others from the scratch.
+__global__ __launch_bounds__(256) void k_tree_proof_gather(const ck_proof_row* __restrict__ prow,
+                                                           const uint64_t* __restrict__ list, uint64_t m,
+                                                           const uint4* __restrict__ nodes,
+                                                           const uint4* __restrict__ scratch,
+                                                           const uint64_t* __restrict__ lvl_off,
+                                                           uint4* __restrict__ out) {
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < m; r += (uint64_t)gridDim.x * blockDim.x) {
+        const ck_proof_row w = prow[r];
+        uint64_t j = list[2 * r + 1];
+        uint4* o = out + 2 * w.pbase;
+        uint32_t L = 0;
+        for (uint64_t n = w.nb; n > 1; n = (n + 1) >> 1, j >>= 1, L++) {
+            const uint64_t s = j ^ 1;
+            if (s >= n) continue;  // the node was carried: this level contributes nothing
+            const uint4* p = L == 0 ? nodes + 2 * (w.node0 + s) : scratch + 2 * (lvl_off[w.lvl_tab + L - 1] + s);
+            o[0] = p[0];
+            o[1] = p[1];
+            o += 2;
+        }
+    }
+}
+
+// Climb: row i's node (list order) climbed through its proof differs from its file's root; the
+// file is marked.  A lane makes as many dependent compressions as its row has entries, so the
+// lanes of one wave leave the loop at different depths (nb = 1: none).
+struct proof_climb {
+    const uint32_t* __restrict__ got;
+    const uint32_t* __restrict__ proofs;
+    const uint32_t* __restrict__ roots;
+    const ck_proof_row* __restrict__ prow;
+    const uint64_t* __restrict__ list;
+    uint8_t* __restrict__ file_bad;
+    __device__ bool operator()(uint64_t i, uint64_t) const {
+        const ck_proof_row w = prow[i];
+        uint64_t j = list[2 * i + 1];
+        uint32_t cv[8];
+        get_cv(cv, got + 8 * i);
+        const uint32_t* e = proofs + 8 * w.pbase;
+        for (uint64_t n = w.nb; n > 1; n = (n + 1) >> 1, j >>= 1) {
+            if ((j ^ 1) >= n) continue;
+            uint32_t s[8], a[8], b[8];
+            get_cv(s, e);
+            e += 8;
+            const bool odd = j & 1;
+#pragma unroll
+            for (int k = 0; k < 8; k++) a[k] = odd ? s[k] : cv[k], b[k] = odd ? cv[k] : s[k];
+            sdb3::parent<false>(cv, a, b, n == 2 ? (uint32_t)sdb3::ROOT : 0u);
+        }
+        uint32_t want[8];
+        get_cv(want, roots + 8 * (uint64_t)w.file);
+        bool d = false;
+#pragma unroll
+        for (int k = 0; k < 8; k++) d |= cv[k] != want[k];
+        if (d) file_bad[w.file] = 1;
+        return d;
+    }
+};
+
+// the first proof call's tables: the rows' and the listed files' level offsets
+void plan_blocks_proof_rows(sd_checksum_tree_blocks* b) {
+    plan_tree_proofs(b->proofs, b->plan.node_base, b->rows.data(), b->m(), false);
+    b->ptab.begin();
+    b->o_prow = b->ptab.add(b->proofs.prow);
+    b->o_lvl = b->ptab.add(b->proofs.lvl_off);
+    b->ptab.upload(nullptr);
+}
+
+// the first _prove's: the passes' tables and the scratch of the interior levels
+void plan_blocks_proof_levels(sd_checksum_tree_blocks* b) {
+    if (b->proofs.levels) return;
+    plan_tree_proofs(b->proofs, b->plan.node_base, b->rows.data(), b->m(), true);
+    b->ltab.begin();
+    b->o_lpass.clear();
+    for (const auto& ps : b->proofs.passes) b->o_lpass.push_back(b->ltab.add(ps));
+    b->ltab.upload(nullptr);
+    b->levels.ensure(32 * b->proofs.scratch_nodes);
+}
 
 // _update's roots: the reduce passes over the whole level layout, as plan_tree's
 void plan_blocks_roots(sd_checksum_tree_blocks* b) {
@@ -448,6 +591,103 @@ int sd_checksum_tree_blocks_update(sd_cas_ctx* ctx, sd_checksum_tree_blocks* b, 
     HIP_CHECK(sdk::launch_ck_blocks(d_data, b->d_items(), (uint32_t)b->m(), b->block_log2, true,
                                     reinterpret_cast<uint32_t*>(d_nodes), s));
     run_level_roots(b, b->n_files, d_nodes, d_hash32, s);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_blocks_proof_layout(sd_checksum_tree_blocks* b, uint64_t* proof_base) {
+    SD_GUARD_BEGIN
+    if (!b || !proof_base) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (b->proofs.proof_base.empty()) plan_tree_proofs(b->proofs, b->plan.node_base, b->rows.data(), b->m(), false);
+    std::copy(b->proofs.proof_base.begin(), b->proofs.proof_base.end(), proof_base);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_blocks_prove(sd_cas_ctx* ctx, sd_checksum_tree_blocks* b, const uint8_t* d_nodes,
+                                  uint8_t* d_proofs_out, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !b || (b->m() && !d_nodes)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_aligned16(d_nodes, "d_nodes");
+    check_aligned16(d_proofs_out, "d_proofs_out");
+    const uint64_t m = b->m();
+    if (m == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    if (!b->ptab.bytes) plan_blocks_proof_rows(b);
+    if (b->proofs.proof_base[m] == 0) return SD_OK;  // one-node files only: every proof is empty
+    if (!d_proofs_out) throw sd_failure(SD_ERR_INVALID, "null argument");
+    plan_blocks_proof_levels(b);
+    uint32_t* scratch = b->levels.as<uint32_t>();
+    for (size_t k = 0; k < b->proofs.passes.size(); k++) {
+        hipLaunchKernelGGL(k_tree_levels, dim3((uint32_t)b->proofs.passes[k].size()), dim3(256), 0, s,
+                           k == 0 ? reinterpret_cast<const uint32_t*>(d_nodes) : scratch, scratch, b->d_lpass(k),
+                           b->d_lvl_off());
+        HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_tree_proof_gather, dim3(flat_grid(m)), dim3(256), 0, s, b->d_prow(), b->d_rows(), m,
+                       reinterpret_cast<const uint4*>(d_nodes), reinterpret_cast<const uint4*>(scratch), b->d_lvl_off(),
+                       reinterpret_cast<uint4*>(d_proofs_out));
+    HIP_CHECK(hipGetLastError());
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_blocks_verify_proofs(sd_cas_ctx* ctx, sd_checksum_tree_blocks* b, const uint8_t* d_data,
+                                          const uint8_t* d_proofs, const uint8_t* d_roots, uint8_t* d_nodes_out,
+                                          uint8_t* d_bad, uint64_t* d_rows_out, uint64_t capacity, uint64_t* count,
+                                          uint64_t stats[4], void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !b || (b->m() && (!d_data || !d_roots))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_aligned16(d_proofs, "d_proofs");
+    check_aligned16(d_roots, "d_roots");
+    check_aligned16(d_nodes_out, "d_nodes_out");
+    if (count) *count = 0;
+    if (stats) memset(stats, 0, 4 * sizeof(uint64_t));
+    const uint64_t n = b->n_files, m = b->m();
+    if (m == 0) return SD_OK;
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    if (!b->ptab.bytes) plan_blocks_proof_rows(b);
+    if (b->proofs.proof_base[m] && !d_proofs) throw sd_failure(SD_ERR_INVALID, "null argument");
+    auto slot = ctx->acquire();
+    struct Rel {
+        sd_cas_ctx* c;
+        std::unique_ptr<Slot>* s;
+        ~Rel() { c->release(std::move(*s)); }
+    } rel{ctx, &slot};
+    slot->staged.ensure(blocks_scratch::bytes(m, n));
+    slot->host_hashes.ensure(2 * BLOCKS * sizeof(uint64_t));
+    const blocks_scratch x(slot->staged.p, m, n);
+    uint8_t* nodes = d_nodes_out ? d_nodes_out : x.nodes;
+    HIP_CHECK(sdk::launch_ck_blocks(d_data, b->d_items(), (uint32_t)m, b->block_log2, false,
+                                    reinterpret_cast<uint32_t*>(nodes), s));
+    HIP_CHECK(hipMemsetAsync(x.file_bad, 0, n, s));
+    uint8_t* flags = d_bad ? d_bad : x.flags;
+    const uint32_t g_rows = sliced_grid(m), g_files = sliced_grid(n);
+    launch_flag(g_rows, s,
+                proof_climb{reinterpret_cast<const uint32_t*>(nodes), reinterpret_cast<const uint32_t*>(d_proofs),
+                            reinterpret_cast<const uint32_t*>(d_roots), b->d_prow(), b->d_rows(), x.file_bad},
+                nullptr, m, flags, x.counts);
+    launch_flag(g_files, s, tree_file_marked{x.file_bad}, nullptr, n, nullptr, x.counts + BLOCKS);
+    HIP_CHECK(hipGetLastError());
+    const uint64_t* h = reinterpret_cast<const uint64_t*>(slot->host_hashes.p);
+    HIP_CHECK(hipMemcpyAsync(slot->host_hashes.p, x.counts, 2 * BLOCKS * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    uint64_t bad_rows = 0, bad_files = 0;
+    for (uint32_t g = 0; g < g_rows; g++) bad_rows += h[g];
+    for (uint32_t g = 0; g < g_files; g++) bad_files += h[BLOCKS + g];
+    if (bad_rows > m || bad_files > n || bad_files > bad_rows)
+        throw sd_failure(SD_ERR_INTERNAL, "verify_proofs: inconsistent totals");
+    if (count) *count = bad_rows;
+    if (stats) stats[0] = n, stats[1] = m, stats[2] = bad_rows, stats[3] = bad_files;
+    if (!d_rows_out) return SD_OK;
+    if (capacity < bad_rows) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of differing rows");
+    if (bad_rows == 0) return SD_OK;
+    blocks_rows rows{{flags}, b->d_rows(), d_rows_out};
+    launch_compact(g_rows, s, rows, nullptr, m, x.counts, nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
     return SD_OK;
     SD_GUARD_END
 }

@@ -55,7 +55,91 @@ void plan_tree_blocks(TreeBlocksPlan& p, const uint64_t* lens, size_t n_files, u
     p.repeats = std::adjacent_find(slots.begin(), slots.end()) != slots.end();
 }
 
+void plan_tree_proofs(TreeProofPlan& p, const std::vector<uint64_t>& node_base, const uint64_t* rows, size_t m,
+                      bool levels) {
+    const size_t n = node_base.size() - 1;
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    if (p.proof_base.empty()) {
+        for (size_t r = 0; r < m; r++) {  // everything refused before anything is allocated
+            const uint64_t f = rows[2 * r], j = rows[2 * r + 1];
+            if (f >= n) throw sd_failure(SD_ERR_INVALID, "block row " + std::to_string(r) + ": no such file");
+            if (j >= node_base[f + 1] - node_base[f])
+                throw sd_failure(SD_ERR_INVALID, "block row " + std::to_string(r) + ": no such block");
+        }
+        // the listed files' interior levels 1 .. h - 1 in the scratch, file by file in list order
+        std::vector<uint32_t> tab(n, NONE);
+        p.lvl_off.clear();
+        p.scratch_nodes = 0;
+        p.prow.resize(m);
+        p.proof_base.assign(m + 1, 0);
+        for (size_t r = 0; r < m; r++) {
+            const uint64_t f = rows[2 * r], j = rows[2 * r + 1], nb = node_base[f + 1] - node_base[f];
+            if (tab[f] == NONE) {
+                if (p.lvl_off.size() >= (1ull << 31)) {
+                    p.proof_base.clear();
+                    throw sd_failure(SD_ERR_INVALID, "list too large");
+                }
+                tab[f] = (uint32_t)p.lvl_off.size();
+                for (uint64_t c = (nb + 1) >> 1; c > 1; c = (c + 1) >> 1) {
+                    p.lvl_off.push_back(p.scratch_nodes);
+                    p.scratch_nodes += c;
+                }
+            }
+            p.prow[r] = ck_proof_row{node_base[f], nb, p.proof_base[r], tab[f], (uint32_t)f};
+            p.proof_base[r + 1] = p.proof_base[r] + tree_proof_entries(nb, j);
+        }
+    }
+    if (!levels || p.levels) return;
+    // the passes: a listed file's level 8p in groups of 256, each stored through min(8, h - 1 - 8p) levels
+    std::vector<uint8_t> seen(n, 0);
+    p.passes.clear();
+    for (size_t r = 0; r < m; r++) {
+        const uint64_t f = rows[2 * r];
+        if (seen[f]) continue;
+        seen[f] = 1;
+        const uint64_t nb = node_base[f + 1] - node_base[f];
+        const uint32_t h = tree_height(nb), tab = p.prow[r].lvl_tab;
+        uint64_t cnt = nb;
+        for (uint32_t q = 0; 8 * q + 1 < h; q++) {
+            if (p.passes.size() <= q) p.passes.emplace_back();
+            const uint64_t src = q == 0 ? node_base[f] : p.lvl_off[tab + 8 * q - 1];
+            const uint32_t lv = std::min<uint32_t>(8, h - 1 - 8 * q);
+            for (uint64_t g = 0; g * 256 < cnt; g++)
+                p.passes[q].push_back(ck_levels_wg{src + 256 * g, 256 * g, (uint32_t)std::min<uint64_t>(256, cnt - 256 * g),
+                                                   lv, tab + 8 * q, 0});
+            cnt = (cnt + 255) >> 8;
+        }
+    }
+    for (const auto& ps : p.passes)
+        if (ps.size() >= (1ull << 31)) throw sd_failure(SD_ERR_INVALID, "list too large");
+    p.levels = true;
+}
+
 namespace {
+
+// block j's proof from the file's level 0 (`level`) and its interior levels (`scratch` by lvl_off[tab ..])
+// -> out, bottom-up
+void cpu_gather_proof(const uint8_t* level, const uint8_t* scratch, const uint64_t* lvl_off, uint64_t nb, uint64_t j,
+                      uint8_t* out) {
+    uint32_t L = 0;
+    for (uint64_t n = nb; n > 1; n = (n + 1) >> 1, j >>= 1, L++) {
+        const uint64_t s = j ^ 1;
+        if (s >= n) continue;
+        memcpy(out, L == 0 ? level + 32 * s : scratch + 32 * (lvl_off[L - 1] + s), 32);
+        out += 32;
+    }
+}
+
+// block j's node climbed through its proof -> out (the root it claims)
+void cpu_climb(const uint8_t* node, const uint8_t* proof, uint64_t nb, uint64_t j, uint8_t out[32]) {
+    memcpy(out, node, 32);
+    for (uint64_t n = nb; n > 1; n = (n + 1) >> 1, j >>= 1) {
+        if ((j ^ 1) >= n) continue;
+        if (j & 1) cpu_parent(proof, out, n == 2, out);
+        else cpu_parent(out, proof, n == 2, out);
+        proof += 32;
+    }
+}
 
 // the items' nodes -> out + 32 * (scatter ? the item's level slot : its row), one task per item
 void cpu_block_nodes(const uint8_t* data, const TreeBlocksPlan& p, bool scatter, uint8_t* out, int nthreads) {
@@ -245,6 +329,96 @@ int sd_cpu_checksum_tree_blocks_update(const uint8_t* data, const uint64_t* lens
     if (m == 0) return SD_OK;
     cpu_block_nodes(data, p, true, nodes, nthreads);
     cpu_tree_roots(nodes, n_files, p.node_base, hash32);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_proof_entries(uint64_t len, uint32_t block_log2, uint64_t block, uint32_t* entries) {
+    SD_GUARD_BEGIN
+    if (!entries) throw sd_failure(SD_ERR_INVALID, "null argument");
+    std::vector<uint64_t> nb;
+    plan_tree_layout(&len, 1, block_log2, nb);
+    if (block >= nb[1]) throw sd_failure(SD_ERR_INVALID, "no such block");
+    *entries = tree_proof_entries(nb[1], block);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_checksum_tree_blocks_prove(const uint8_t* nodes, const uint64_t* lens, size_t n_files, uint32_t block_log2,
+                                      const uint64_t* rows, size_t m, uint8_t* proofs_out) {
+    SD_GUARD_BEGIN
+    if ((n_files && !lens) || (m && (!nodes || !rows))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    std::vector<uint64_t> node_base;
+    plan_tree_layout(lens, n_files, block_log2, node_base);
+    TreeProofPlan p;
+    plan_tree_proofs(p, node_base, rows, m, false);
+    if (m == 0 || p.proof_base[m] == 0) return SD_OK;
+    if (!proofs_out) throw sd_failure(SD_ERR_INVALID, "null argument");
+    // every listed file's interior levels, level by level, the odd node carried
+    std::vector<uint8_t> scratch(32 * p.scratch_nodes);
+    std::vector<uint8_t> seen(n_files, 0);
+    for (size_t r = 0; r < m; r++) {
+        const ck_proof_row& w = p.prow[r];
+        if (seen[w.file]) continue;
+        seen[w.file] = 1;
+        const uint8_t* src = nodes + 32 * w.node0;
+        uint32_t L = 1;
+        for (uint64_t n = w.nb; ((n + 1) >> 1) > 1; n = (n + 1) >> 1, L++) {
+            uint8_t* dst = scratch.data() + 32 * p.lvl_off[w.lvl_tab + L - 1];
+            for (uint64_t i = 0; 2 * i + 1 < n; i++) cpu_parent(src + 64 * i, src + 64 * i + 32, false, dst + 32 * i);
+            if (n & 1) memcpy(dst + 32 * (n >> 1), src + 32 * (n - 1), 32);
+            src = dst;
+        }
+    }
+    for (size_t r = 0; r < m; r++) {
+        const ck_proof_row& w = p.prow[r];
+        cpu_gather_proof(nodes + 32 * w.node0, scratch.data(), p.lvl_off.data() + w.lvl_tab, w.nb, rows[2 * r + 1],
+                         proofs_out + 32 * w.pbase);
+    }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_checksum_tree_blocks_verify_proofs(const uint8_t* data, const uint64_t* lens, size_t n_files,
+                                              uint32_t block_log2, const uint64_t* rows, const uint64_t* data_offsets,
+                                              size_t m, const uint8_t* proofs, const uint8_t* roots,
+                                              uint8_t* nodes_out, uint8_t* bad, uint64_t* rows_out, uint64_t capacity,
+                                              uint64_t* count, uint64_t stats[4], int nthreads) {
+    SD_GUARD_BEGIN
+    if ((n_files && !lens) || (m && (!data || !rows || !data_offsets || !roots)))
+        throw sd_failure(SD_ERR_INVALID, "null argument");
+    TreeBlocksPlan p;
+    plan_tree_blocks(p, lens, n_files, block_log2, rows, data_offsets, m);
+    TreeProofPlan pp;
+    plan_tree_proofs(pp, p.node_base, rows, m, false);
+    if (m && pp.proof_base[m] && !proofs) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (count) *count = 0;
+    if (stats) memset(stats, 0, 4 * sizeof(uint64_t));
+    if (m == 0) return SD_OK;
+    std::vector<uint8_t> own;
+    if (!nodes_out) own.resize(32 * m), nodes_out = own.data();
+    cpu_block_nodes(data, p, false, nodes_out, nthreads);
+    std::vector<uint8_t> differs(m), file_bad(n_files, 0);
+    cpu_parallel_for(m, nthreads, [&](size_t r) {
+        const ck_proof_row& w = pp.prow[r];
+        uint8_t top[32];
+        cpu_climb(nodes_out + 32 * r, proofs + 32 * w.pbase, w.nb, rows[2 * r + 1], top);
+        differs[r] = memcmp(top, roots + 32 * (uint64_t)w.file, 32) != 0;
+    });
+    uint64_t st[4] = {n_files, m, 0, 0};
+    for (size_t r = 0; r < m; r++) {
+        if (bad) bad[r] = differs[r];
+        st[2] += differs[r];
+        if (differs[r] && !file_bad[rows[2 * r]]) file_bad[rows[2 * r]] = 1, st[3]++;
+    }
+    if (count) *count = st[2];
+    if (stats) memcpy(stats, st, sizeof st);
+    if (rows_out) {
+        if (capacity < st[2]) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of differing rows");
+        uint64_t q = 0;
+        for (size_t r = 0; r < m; r++)
+            if (differs[r]) rows_out[2 * q] = rows[2 * r], rows_out[2 * q + 1] = rows[2 * r + 1], q++;
+    }
     return SD_OK;
     SD_GUARD_END
 }

@@ -523,7 +523,222 @@ static void test_blocks_concurrent_calls() {
     CHECK(ok == std::vector<int>(4, 1));
 }
 
+// ---------------------------------------------------------------- block proofs
+// the model's climb: block j's node through `proof` to the root it claims (include/sd_cas.h, block proofs)
+static cv_t m_climb(cv_t cv, const uint8_t* proof, uint64_t nb, uint64_t j, size_t* used) {
+    size_t at = 0;
+    for (uint64_t n = nb; n > 1; n = (n + 1) / 2, j >>= 1) {
+        if ((j ^ 1) >= n) continue;
+        const cv_t e = m_get(proof + 32 * at++);
+        cv = (j & 1) ? m_parent(e, cv, n == 2) : m_parent(cv, e, n == 2);
+    }
+    *used = at;
+    return cv;
+}
+
+static void test_proofs() {
+    for (uint32_t k : {17u, 20u}) {
+        const uint64_t B = 1ull << k;
+        batch_t b;  // nb = 1 (empty, 1 byte), 2, 3, 5, 8, 9
+        b.build(k, {0, 1, B + 1, 2 * B + 4097, 4 * B + 77, 8 * B, 8 * B + 1}, 40 + k);
+        const answer_t want = model(b);
+        list_t l;
+        l.every(b, 5 + k);
+        l.add(b, 5, 3), l.add(b, 4, 4);  // repeats
+        const size_t m = l.m();
+        std::vector<uint64_t> base(m + 1, 0);
+        for (size_t r = 0; r < m; r++) {
+            uint32_t e = 99;
+            CHECK(sd_checksum_tree_proof_entries(b.lens[l.rows[2 * r]], k, l.rows[2 * r + 1], &e) == SD_OK);
+            base[r + 1] = base[r] + e;
+        }
+        bytes proofs(32 * base[m] + 32, 0xA5);  // one guard row
+        CHECK(sd_cpu_checksum_tree_blocks_prove(want.nodes.data(), b.lens.data(), b.n(), k, l.rows.data(), m, proofs.data()) == SD_OK);
+        CHECK(std::all_of(proofs.end() - 32, proofs.end(), [](uint8_t x) { return x == 0xA5; }));
+        for (size_t r = 0; r < m; r++) {  // every proof climbs to the model's root, using exactly its entries
+            const uint64_t f = l.rows[2 * r], j = l.rows[2 * r + 1];
+            size_t used = 0;
+            const cv_t top = m_climb(m_get(want.nodes.data() + 32 * (b.base[f] + j)), proofs.data() + 32 * base[r],
+                                     b.base[f + 1] - b.base[f], j, &used);
+            CHECK(used == base[r + 1] - base[r]);
+            CHECK(top == m_get(want.roots.data() + 32 * f));
+        }
+        // verify_proofs: clean, then one flipped byte, one flipped entry and one flipped root
+        uint64_t count = 99, stats[4];
+        bytes bad(m + 1, 0xA5), nodes(32 * m + 32, 0xA5);
+        std::vector<uint64_t> rows(2 * m + 2, 0xA5A5);
+        CHECK(sd_cpu_checksum_tree_blocks_verify_proofs(l.data.data(), b.lens.data(), b.n(), k, l.rows.data(), l.offs.data(), m,
+                                                        proofs.data(), want.roots.data(), nodes.data(), bad.data(), rows.data(),
+                                                        m, &count, stats, 3) == SD_OK);
+        CHECK(count == 0 && stats[0] == b.n() && stats[1] == m && stats[2] == 0 && stats[3] == 0);
+        CHECK(std::all_of(bad.begin(), bad.end() - 1, [](uint8_t x) { return x == 0; }) && bad[m] == 0xA5);
+        CHECK(nodes.size() == 32 * m + 32 && memcmp(nodes.data(), run_blocks(b, l, 2).data(), 32 * m) == 0);
+        CHECK(std::all_of(nodes.end() - 32, nodes.end(), [](uint8_t x) { return x == 0xA5; }));
+        CHECK(std::all_of(rows.begin(), rows.end(), [](uint64_t x) { return x == 0xA5A5; }));
+        list_t fl = l;
+        bytes fp = proofs, fr = want.roots;
+        size_t r_byte = 0, r_entry = 0;
+        for (size_t r = 0; r < m; r++) {
+            if (l.rows[2 * r] == 6 && l.rows[2 * r + 1] == 8) r_byte = r;   // the 1-byte trailing block
+            if (l.rows[2 * r] == 3 && l.rows[2 * r + 1] == 2) r_entry = r;  // nb = 3, carried once: one entry
+        }
+        CHECK(base[r_entry + 1] - base[r_entry] == 1);
+        fl.data[fl.offs[r_byte]] ^= 0x80;
+        fp[32 * base[r_entry] + 31] ^= 0x01;
+        fr[32 * 2 + 5] ^= 0x10;  // file 2 (nb = 2): both of its rows
+        bytes want_bad(m, 0);
+        std::vector<uint64_t> want_rows;
+        for (size_t r = 0; r < m; r++) {
+            want_bad[r] = r == r_byte || r == r_entry || l.rows[2 * r] == 2;
+            if (want_bad[r]) want_rows.push_back(l.rows[2 * r]), want_rows.push_back(l.rows[2 * r + 1]);
+        }
+        CHECK(want_rows.size() == 8);
+        for (int mask = 0; mask < 4; mask++) {  // bad and rows each NULL in turn, nodes_out NULL
+            std::fill(bad.begin(), bad.end(), 0xA5);
+            std::fill(rows.begin(), rows.end(), 0xA5A5);
+            count = 99;
+            CHECK(sd_cpu_checksum_tree_blocks_verify_proofs(fl.data.data(), b.lens.data(), b.n(), k, l.rows.data(), l.offs.data(), m,
+                                                            fp.data(), fr.data(), nullptr, mask & 1 ? bad.data() : nullptr,
+                                                            mask & 2 ? rows.data() : nullptr, 4, &count,
+                                                            mask == 3 ? stats : nullptr, 1 + mask) == SD_OK);
+            CHECK(count == 4);
+            if (mask & 1) CHECK(memcmp(bad.data(), want_bad.data(), m) == 0 && bad[m] == 0xA5);
+            if (mask & 2) CHECK(std::equal(want_rows.begin(), want_rows.end(), rows.begin()) && rows[8] == 0xA5A5);
+        }
+        CHECK(stats[0] == b.n() && stats[1] == m && stats[2] == 4 && stats[3] == 3);
+        std::fill(rows.begin(), rows.end(), 0xA5A5);
+        count = 0;
+        CHECK(sd_cpu_checksum_tree_blocks_verify_proofs(fl.data.data(), b.lens.data(), b.n(), k, l.rows.data(), l.offs.data(), m,
+                                                        fp.data(), fr.data(), nullptr, nullptr, rows.data(), 3, &count, stats,
+                                                        2) == SD_ERR_CAPACITY);
+        CHECK(count == 4 && stats[2] == 4 && std::all_of(rows.begin(), rows.end(), [](uint64_t x) { return x == 0xA5A5; }));
+    }
+}
+
+static void test_proofs_levels_and_refusals() {
+    // levels alone: random nodes, nb = 255, 256, 257, 513; an unlisted file's level is never read
+    const uint32_t k = 17;
+    const std::vector<uint64_t> nbs = {255, 256, 300, 257, 513};
+    std::vector<uint64_t> lens, base(1, 0);
+    for (uint64_t nb : nbs) lens.push_back(nb << k), base.push_back(base.back() + nb);
+    bytes level(32 * base.back());
+    for (size_t i = 0; i < level.size(); i += 8) {
+        const uint64_t v = mix(77, i);
+        memcpy(level.data() + i, &v, 8);
+    }
+    std::vector<uint64_t> rows;
+    for (size_t f = 0; f < nbs.size(); f++)
+        if (f != 2)
+            for (uint64_t j : {uint64_t(0), uint64_t(1), nbs[f] / 2, uint64_t(254), nbs[f] - 2, nbs[f] - 1}) rows.push_back(f), rows.push_back(j);
+    const size_t m = rows.size() / 2;
+    std::vector<uint64_t> pb(m + 1, 0);
+    for (size_t r = 0; r < m; r++) {
+        uint32_t e = 0;
+        CHECK(sd_checksum_tree_proof_entries(lens[rows[2 * r]], k, rows[2 * r + 1], &e) == SD_OK);
+        pb[r + 1] = pb[r] + e;
+    }
+    uint32_t e = 0;
+    CHECK(sd_checksum_tree_proof_entries(513ull << k, k, 512, &e) == SD_OK && e == 1);
+    CHECK(sd_checksum_tree_proof_entries(513ull << k, k, 0, &e) == SD_OK && e == 10);
+    CHECK(sd_checksum_tree_proof_entries(5ull << k, k, 4, &e) == SD_OK && e == 1);
+    CHECK(sd_checksum_tree_proof_entries(3ull << k, k, 2, &e) == SD_OK && e == 1);
+    bytes proofs(32 * pb[m]), again(32 * pb[m]);
+    CHECK(sd_cpu_checksum_tree_blocks_prove(level.data(), lens.data(), lens.size(), k, rows.data(), m, proofs.data()) == SD_OK);
+    for (size_t r = 0; r < m; r++) {
+        const uint64_t f = rows[2 * r], j = rows[2 * r + 1];
+        std::vector<cv_t> lvl;
+        for (uint64_t i = base[f]; i < base[f + 1]; i++) lvl.push_back(m_get(level.data() + 32 * i));
+        size_t used = 0;
+        CHECK(m_climb(lvl[j], proofs.data() + 32 * pb[r], nbs[f], j, &used) == m_merge(lvl, true));
+        CHECK(used == pb[r + 1] - pb[r]);
+    }
+    bytes garbage = level;
+    std::fill(garbage.begin() + 32 * base[2], garbage.begin() + 32 * base[3], 0x5A);
+    CHECK(sd_cpu_checksum_tree_blocks_prove(garbage.data(), lens.data(), lens.size(), k, rows.data(), m, again.data()) == SD_OK);
+    CHECK(again == proofs);
+    // refusals: nothing written
+    std::fill(again.begin(), again.end(), 0xA5);
+    e = 7;
+    CHECK(sd_checksum_tree_proof_entries(1ull << k, k, 1, &e) == SD_ERR_INVALID);
+    CHECK(sd_checksum_tree_proof_entries(0, k, 1, &e) == SD_ERR_INVALID);
+    for (uint32_t bad_k : {0u, 16u, 21u, ~0u}) CHECK(sd_checksum_tree_proof_entries(1ull << 30, bad_k, 0, &e) == SD_ERR_INVALID);
+    CHECK(sd_checksum_tree_proof_entries(1ull << 30, k, 0, nullptr) == SD_ERR_INVALID && e == 7);
+    const uint64_t no_file[2] = {5, 0}, no_block[2] = {0, 255};
+    CHECK(sd_cpu_checksum_tree_blocks_prove(level.data(), lens.data(), lens.size(), k, no_file, 1, again.data()) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree_blocks_prove(level.data(), lens.data(), lens.size(), k, no_block, 1, again.data()) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree_blocks_prove(level.data(), lens.data(), lens.size(), 16, rows.data(), m, again.data()) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree_blocks_prove(nullptr, lens.data(), lens.size(), k, rows.data(), m, again.data()) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree_blocks_prove(level.data(), nullptr, lens.size(), k, rows.data(), m, again.data()) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree_blocks_prove(level.data(), lens.data(), lens.size(), k, nullptr, m, again.data()) == SD_ERR_INVALID);
+    CHECK(sd_cpu_checksum_tree_blocks_prove(level.data(), lens.data(), lens.size(), k, rows.data(), m, nullptr) == SD_ERR_INVALID);
+    CHECK(std::all_of(again.begin(), again.end(), [](uint8_t x) { return x == 0xA5; }));
+    const uint64_t B = 1ull << k;
+    batch_t b;
+    b.build(k, {100, B + 1}, 3);
+    list_t l;
+    l.add(b, 0, 0), l.add(b, 1, 1);
+    const answer_t want = model(b);
+    uint8_t pf[32];
+    uint64_t count = 0;
+    CHECK(sd_cpu_checksum_tree_blocks_prove(want.nodes.data(), b.lens.data(), 2, k, l.rows.data(), 2, pf) == SD_OK);
+    auto ver = [&](const uint8_t* d, const uint64_t* of, const uint8_t* p, const uint8_t* rt) {
+        return sd_cpu_checksum_tree_blocks_verify_proofs(d, b.lens.data(), 2, k, l.rows.data(), of, 2, p, rt, nullptr, nullptr,
+                                                         nullptr, 0, &count, nullptr, 1);
+    };
+    const uint64_t odd[2] = {0, l.offs[1] + 8};
+    CHECK(ver(l.data.data(), l.offs.data(), pf, want.roots.data()) == SD_OK && count == 0);
+    CHECK(ver(nullptr, l.offs.data(), pf, want.roots.data()) == SD_ERR_INVALID);
+    CHECK(ver(l.data.data(), nullptr, pf, want.roots.data()) == SD_ERR_INVALID);
+    CHECK(ver(l.data.data(), odd, pf, want.roots.data()) == SD_ERR_INVALID);
+    CHECK(ver(l.data.data(), l.offs.data(), nullptr, want.roots.data()) == SD_ERR_INVALID);
+    CHECK(ver(l.data.data(), l.offs.data(), pf, nullptr) == SD_ERR_INVALID);
+    // an empty list: every call does nothing
+    uint64_t stats[4] = {9, 9, 9, 9};
+    count = 9;
+    CHECK(sd_cpu_checksum_tree_blocks_prove(nullptr, b.lens.data(), 2, k, nullptr, 0, nullptr) == SD_OK);
+    CHECK(sd_cpu_checksum_tree_blocks_verify_proofs(nullptr, b.lens.data(), 2, k, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                                                    nullptr, nullptr, 0, &count, stats, 1) == SD_OK);
+    CHECK(count == 0 && stats[0] == 0 && stats[1] == 0 && stats[2] == 0 && stats[3] == 0);
+}
+
+static void test_proofs_concurrent_calls() {
+    const uint32_t k = 17;
+    const uint64_t B = 1ull << k;
+    batch_t b;
+    b.build(k, {B + 1, 4 * B + 77, 8 * B + 1, 5}, 61);
+    const answer_t want = model(b);
+    list_t l;
+    l.every(b, 6);
+    const size_t m = l.m();
+    size_t total = 0;
+    for (size_t r = 0; r < m; r++) {
+        uint32_t e = 0;
+        CHECK(sd_checksum_tree_proof_entries(b.lens[l.rows[2 * r]], k, l.rows[2 * r + 1], &e) == SD_OK);
+        total += e;
+    }
+    bytes proofs(32 * total);
+    CHECK(sd_cpu_checksum_tree_blocks_prove(want.nodes.data(), b.lens.data(), b.n(), k, l.rows.data(), m, proofs.data()) == SD_OK);
+    std::vector<std::thread> ts;
+    std::vector<int> ok(4, 0);
+    for (int t = 0; t < 4; t++)
+        ts.emplace_back([&, t] {
+            bytes mine(32 * total);
+            uint64_t count = 9;
+            int good = sd_cpu_checksum_tree_blocks_prove(want.nodes.data(), b.lens.data(), b.n(), k, l.rows.data(), m, mine.data()) == SD_OK;
+            good &= mine == proofs;
+            good &= sd_cpu_checksum_tree_blocks_verify_proofs(l.data.data(), b.lens.data(), b.n(), k, l.rows.data(), l.offs.data(), m,
+                                                              mine.data(), want.roots.data(), nullptr, nullptr, nullptr, 0, &count,
+                                                              nullptr, 1 + t) == SD_OK;
+            ok[t] = good && count == 0;
+        });
+    for (auto& t : ts) t.join();
+    CHECK(ok == std::vector<int>(4, 1));
+}
+
 int main() {
+    test_proofs();
+    test_proofs_levels_and_refusals();
+    test_proofs_concurrent_calls();
     test_blocks();
     test_blocks_verify_and_update();
     test_blocks_refusals_and_empty();

@@ -256,6 +256,14 @@ void cpu_root_from_cvs(const uint8_t* cvs, uint64_t nb, uint8_t out[32]) {
     memcpy(out, o, 32);
 }
 
+void cpu_parent(const uint8_t l[32], const uint8_t r[32], bool root, uint8_t out[32]) {
+    uint32_t a[8], b[8], o[8];
+    memcpy(a, l, 32);
+    memcpy(b, r, 32);
+    parent_cv(a, b, root ? ROOT : 0, o);
+    memcpy(out, o, 32);
+}
+
 void cpu_blake3(const uint8_t* p, size_t n, uint8_t out[32]) {
     CpuHasher h;
     h.update(p, n);

@@ -180,6 +180,16 @@ struct sd_checksum_tree_blocks {
     size_t o_base = 0;
     std::vector<size_t> o_pass;
     sdi::DevBuf lvl[2];
+    // the proofs, planned by the first proof call: the rows' table and the listed files' level
+    // offsets (ptab); _prove's passes (ltab) and the interior levels they fill (levels)
+    TreeProofPlan proofs;
+    sdi::Tables ptab, ltab;
+    size_t o_prow = 0, o_lvl = 0;
+    std::vector<size_t> o_lpass;
+    sdi::DevBuf levels;
+    const ck_proof_row* d_prow() const { return ptab.at<ck_proof_row>(o_prow); }
+    const uint64_t* d_lvl_off() const { return ptab.at<uint64_t>(o_lvl); }
+    const ck_levels_wg* d_lpass(size_t k) const { return ltab.at<ck_levels_wg>(o_lpass[k]); }
     size_t m() const { return plan.items.size(); }
     uint64_t total() const { return plan.node_base.back(); }
     const ck_block_item* d_items() const { return tab.at<ck_block_item>(o_items); }

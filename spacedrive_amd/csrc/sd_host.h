@@ -257,6 +257,53 @@ struct TreeBlocksPlan {
 void plan_tree_blocks(TreeBlocksPlan& p, const uint64_t* lens, size_t n_files, uint32_t block_log2,
                       const uint64_t* rows, const uint64_t* data_offsets, size_t m);
 
+// Block proofs (include/sd_cas.h, block proofs).  Level L of a file of nb nodes has n_L nodes, n_0 =
+// nb, n_{L+1} = ceil(n_L / 2); the height h = ceil(log2 nb) is the first L with n_L == 1.
+inline uint32_t tree_height(uint64_t nb) {
+    uint32_t h = 0;
+    for (uint64_t n = nb; n > 1; n = (n + 1) >> 1) h++;
+    return h;
+}
+// p(len, k, j): the levels at which block j's node has a sibling (nb from tree_nodes, j < nb)
+inline uint32_t tree_proof_entries(uint64_t nb, uint64_t j) {
+    uint32_t p = 0;
+    for (uint64_t n = nb; n > 1; n = (n + 1) >> 1, j >>= 1) p += (j ^ 1) < n;
+    return p;
+}
+// one row of a list for the proof kernels (k_tree_proof_gather, proof_climb; checksum_tree.hip): 32 bytes
+struct ck_proof_row {
+    uint64_t node0;    // node_base[f]: the file's first slot of the level layout
+    uint64_t nb;       // the file's nodes
+    uint64_t pbase;    // proof_base[r]: the row's first entry among the packed proofs
+    uint32_t lvl_tab;  // index into lvl_off of the file's level 1 (prove; 0 when the file has none)
+    uint32_t file;
+};
+static_assert(sizeof(ck_proof_row) == 32, "two 16-byte loads per row");
+// one workgroup of an interior-levels pass (k_tree_levels): up to 256 consecutive nodes of one
+// file's level 8p, reduced through `levels` levels, each of them stored
+struct ck_levels_wg {
+    uint64_t src_base;  // the group's first node in the source buffer (the caller's level, or the scratch)
+    uint64_t first;     // its index within the file's source level: a multiple of 256
+    uint32_t count;     // nodes in this group (1..256)
+    uint32_t levels;    // levels to store (1..8)
+    uint32_t lvl_tab;   // index into lvl_off of the first level stored
+    uint32_t pad;
+};
+static_assert(sizeof(ck_levels_wg) == 32, "two 16-byte loads per workgroup");
+// A list's proofs planned from node_base[0 .. n_files] and the rows.  Throws SD_ERR_INVALID on a
+// file or block past the end.  With `levels`: the scratch layout of the interior levels 1 .. h - 1
+// of every listed file (lvl_off, in nodes) and the passes that fill it, 8 levels a pass.
+struct TreeProofPlan {
+    std::vector<ck_proof_row> prow;
+    std::vector<uint64_t> proof_base;  // m + 1
+    bool levels = false;
+    std::vector<uint64_t> lvl_off;
+    std::vector<std::vector<ck_levels_wg>> passes;
+    uint64_t scratch_nodes = 0;
+};
+void plan_tree_proofs(TreeProofPlan& p, const std::vector<uint64_t>& node_base, const uint64_t* rows, size_t m,
+                      bool levels);
+
 // ------------------------------------------------------------------ fingerprints
 // k_cas_gather (gather.hip) builds each file's cas message from its resident bytes.  Its
 // output is cut into 16-byte units; the units of all files, in file order, form one flat
@@ -481,6 +528,8 @@ void cpu_blake3(const uint8_t* p, size_t n, uint8_t out[32]);
 void cpu_blake3_batch(const uint8_t* const* msg, const uint64_t* len, size_t n, uint8_t (*out)[32]);
 // BLAKE3 root of a message from its nb >= 2 consecutive 1 MiB block CVs (32 B each)
 void cpu_root_from_cvs(const uint8_t* cvs, uint64_t nb, uint8_t out[32]);
+// one parent node from its two children's 32 bytes each (ROOT on it when `root`); out may be l or r
+void cpu_parent(const uint8_t l[32], const uint8_t r[32], bool root, uint8_t out[32]);
 // the (non-root) chaining values of 1 MiB blocks [b0, b1) of a message of total_len >= 2
 // blocks, on nthreads threads: block b's 32 bytes at cvs + 32 * b
 void cpu_block_cvs(const uint8_t* msg, uint64_t total_len, uint64_t b0, uint64_t b1, uint8_t* cvs, int nthreads);

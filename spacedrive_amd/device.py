@@ -1032,6 +1032,7 @@ class ChecksumTreeBlocks:
         self.n, self.m, self.bytes_hashed, self.compressions = (int(v) for v in st)
         self.node_base = tree_node_base(self.lens, self.block_log2)
         self.total_nodes = int(self.node_base[self.n])
+        self._proof_base = None
 
     def run(self, d_data: torch.Tensor, d_nodes_out: torch.Tensor, stream=None) -> None:
         """row r's node -> d_nodes_out[32 r], list order"""
@@ -1082,6 +1083,62 @@ class ChecksumTreeBlocks:
         assert d_nodes.numel() >= 32 * self.total_nodes and d_hash32.numel() >= 32 * self.n
         check(lib().sd_checksum_tree_blocks_update(self.ctx.handle, self.handle, _ptr(d_data), _ptr(d_nodes),
                                                    _ptr(d_hash32), _stream(stream)))
+
+    @property
+    def proof_base(self) -> np.ndarray:
+        """uint64 [m + 1]: row r's proof is entries proof_base[r] .. proof_base[r + 1] (32 bytes each)
+        of the packed proofs; the counts follow from the lengths, the block size and the rows alone"""
+        if self._proof_base is None:
+            base = np.zeros(self.m + 1, np.uint64)
+            check(lib().sd_checksum_tree_blocks_proof_layout(self.handle, _ptr(base)))
+            self._proof_base = base
+        return self._proof_base
+
+    def prove(self, d_nodes: torch.Tensor, d_proofs_out: torch.Tensor, stream=None) -> None:
+        """every row's proof, in list order, from the whole level buffer d_nodes -> d_proofs_out
+        (proof_base[m] x 32 bytes); no file byte is read"""
+        assert d_nodes.numel() >= 32 * self.total_nodes and d_proofs_out.numel() >= 32 * int(self.proof_base[self.m])
+        check(lib().sd_checksum_tree_blocks_prove(self.ctx.handle, self.handle, _ptr(d_nodes), _ptr(d_proofs_out),
+                                                  _stream(stream)))
+
+    def verify_proofs(self, d_data: torch.Tensor, d_proofs: torch.Tensor, d_roots: torch.Tensor,
+                      d_nodes_out: Optional[torch.Tensor] = None, d_bad: Optional[torch.Tensor] = None,
+                      d_rows_out: Optional[torch.Tensor] = None, capacity: Optional[int] = None,
+                      want_rows: bool = True, stream=None):
+        """sd_checksum_tree_blocks_verify_proofs: hashes the listed blocks, climbs each row's node
+        through its proof (d_proofs, laid out by proof_base) and compares the result with its file's
+        checksum in d_roots ([n, 32]).  d_nodes_out ([m, 32], optional) receives the rows' nodes.
+        Returns what verify returns: (rows, stats), and d_bad as a third value when given."""
+        assert d_roots.numel() >= 32 * self.n and d_proofs.numel() >= 32 * int(self.proof_base[self.m])
+        assert (d_bad is None or d_bad.numel() >= self.m) and (d_nodes_out is None or d_nodes_out.numel() >= 32 * self.m)
+        st = _stream(stream)
+        count = ctypes.c_uint64(0)
+        stats = np.zeros(4, np.uint64)
+
+        def call(rows, cap):
+            rc = lib().sd_checksum_tree_blocks_verify_proofs(self.ctx.handle, self.handle, _ptr(d_data), _ptr(d_proofs),
+                                                             _ptr(d_roots), _ptr(d_nodes_out), _ptr(d_bad), _ptr(rows),
+                                                             cap, ctypes.byref(count), _ptr(stats), st)
+            try:
+                check(rc)
+            except SdCasError as e:
+                e.needed = int(count.value)
+                e.stats = stats
+                raise
+
+        dev = torch.device("cuda", self.ctx.device)
+        if not want_rows:
+            call(None, 0)
+            rows = torch.empty((0, 2), dtype=torch.int64, device=dev)
+        elif d_rows_out is None:
+            rows = torch.empty((max(self.m, 1), 2), dtype=torch.int64, device=dev)
+            call(rows, self.m)
+            rows = rows[:int(count.value)]
+        else:
+            assert d_rows_out.dtype == torch.int64 and d_rows_out.is_cuda and d_rows_out.is_contiguous()
+            call(d_rows_out, d_rows_out.numel() // 2 if capacity is None else int(capacity))
+            rows = d_rows_out.reshape(-1)[:2 * int(count.value)].reshape(-1, 2)
+        return (rows, stats) if d_bad is None else (rows, stats, d_bad)
 
     def close(self) -> None:
         if self.handle:

@@ -10,6 +10,10 @@ one) and hashed by the library's CPU path, the route it prefers for files in the
 verify_blocks_file and update_file take a list of blocks and read only those (os.pread): blocks as
 they arrive, the blocks a sender resent, the blocks a write in place touched; blocks_to_rehash
 lists the ones an append or a truncation costs.  On the device: ``Context.checksum_tree_blocks``.
+
+prove_blocks and verify_proofs_file are the pair for a receiver that keeps no level, only the
+checksum and the length of the library's database: the sender packs each block's siblings on its
+way up the tree, the receiver climbs them back to the checksum (include/sd_cas.h, block proofs).
 """
 from __future__ import annotations
 
@@ -117,6 +121,34 @@ def update_file(path: Union[str, os.PathLike], length: int, nodes, blocks, block
     buf, rows, offs = _read_blocks(path, length, blocks, block_log2)
     level, roots = cpu.checksum_tree_blocks_update(buf, [length], rows, offs, level, block_log2, nthreads)
     return roots[0].tobytes().hex(), level
+
+
+def prove_blocks(nodes, length: int, blocks, block_log2: int = 17) -> bytes:
+    """The packed proofs of the listed blocks of a file of `length` bytes, from its level `nodes`
+    (uint8 [nb, 32]), in list order: what a sender answers a block request with beside the block's
+    bytes.  Block j's proof is cpu.tree_proof_entries(length, j, block_log2) entries of 32 bytes."""
+    nb = cpu.tree_nodes(length, block_log2)
+    blocks = [int(j) for j in blocks]
+    if any(j < 0 or j >= nb for j in blocks):
+        raise ValueError(f"a file of {length} bytes has blocks 0 .. {nb - 1}")
+    rows = np.array([[0, j] for j in blocks], np.uint64).reshape(-1, 2)
+    proofs, _ = cpu.checksum_tree_blocks_prove(nodes, [length], rows, block_log2)
+    return proofs.tobytes()
+
+
+def verify_proofs_file(path: Union[str, os.PathLike], length: int, checksum, blocks, proofs, block_log2: int = 17,
+                       nthreads: int = cpu.THREADS) -> List[int]:
+    """The listed blocks of `path` that their proofs (prove_blocks' bytes, list order) do not carry
+    to `checksum` (64 hex digits or 32 bytes) for a file of `length` bytes, in list order; [] when
+    every block belongs to that checksum.  The checksum and the length are all the receiver trusts;
+    only the listed blocks are read."""
+    root = bytes.fromhex(checksum) if isinstance(checksum, str) else bytes(checksum)
+    if len(root) != 32:
+        raise ValueError("a checksum is 32 bytes")
+    buf, rows, offs = _read_blocks(path, length, blocks, block_log2)
+    bad, _ = cpu.checksum_tree_blocks_verify_proofs(buf, [length], rows, offs, np.frombuffer(bytes(proofs), np.uint8),
+                                                    np.frombuffer(root, np.uint8), block_log2, nthreads=nthreads)
+    return [int(b) for b in bad[:, 1]]
 
 
 def blocks_to_rehash(len_old: int, len_new: int, block_log2: int) -> List[int]:
