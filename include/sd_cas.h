@@ -1136,6 +1136,79 @@ int sd_cpu_checksum_tree_blocks_verify_proofs(const uint8_t* data, const uint64_
                                               uint8_t* nodes_out, uint8_t* bad, uint64_t* rows_out, uint64_t capacity,
                                               uint64_t* count, uint64_t stats[4], int nthreads);
 
+/* Range proofs: a RUN of blocks [a, b) of one file checked against the checksum and the length alone
+ * -- a resumed or partial transfer, spaceblock's Range::Partial(start..end)
+ * (p2p/src/spaceblock/sb_request.rs:10-15).  Every interior sibling of a contiguous run is computable
+ * from the run itself, so only its two flanks travel: at most 2h entries for the whole run, where
+ * per-block proofs carry up to h entries per block.  Levels, parent, ROOT (on the one parent formed
+ * when n_L == 2), h and the carried odd node are exactly those of the block proofs above.
+ *   range     blocks [a, b) of a file of nb nodes, 0 <= a < b <= nb.  At level L = 0 .. h-1 its nodes
+ *             are lo = a >> L .. hi = (b-1) >> L
+ *   proof     for L = 0 .. h-1, bottom-up and packed: if lo is odd one entry, level L's node lo-1 (the
+ *             left flank); then, if hi is even and hi+1 < n_L, one entry, level L's node hi+1 (the
+ *             right flank).  If hi is even and hi+1 == n_L the node is carried and contributes
+ *             nothing.  The entry count p(len, k, a, b-a) <= 2h follows from the length, block_log2,
+ *             a and b alone: nothing about the shape is the sender's to choose
+ *   climb     start from the range's nodes N_a .. N_{b-1}.  At each level prepend the left entry and
+ *             append the right entry where the rule above says they exist, pair from the (now even)
+ *             lo -- a last unpaired node is the file's own carry -- with ROOT iff n_L == 2.  After h
+ *             levels one node remains, and it must equal the checksum
+ *   special   nb == 1 or [0, nb): the proof is empty, and the climb is sd_checksum_tree_roots'
+ *             computation.  b == a+1: the proof is byte for byte the block proof of block a
+ *   trusted   the checksum AND the length
+ *   ranges    are declared over an existing block list: range_base[0 .. q] (host) ascends strictly
+ *             from range_base[0] == 0 to range_base[q] == m, and range i is rows [range_base[i],
+ *             range_base[i+1]) of the list, which must be (f, a), (f, a+1), ... consecutive blocks of
+ *             one file.  Bytes still sit anywhere per row (data_offsets).  Two ranges may overlap or
+ *             repeat.  q == 0 is valid only for m == 0
+ *   layout    proof_base[0 .. q] is the exclusive prefix sum of the ranges' entry counts
+ * A failing range says "a byte of these blocks or an entry of this proof is wrong", NOT which block:
+ * per-block proofs or a level remain the tools for naming the block.  Every range call on a list
+ * with m > 0 before sd_checksum_tree_blocks_set_ranges is SD_ERR_INVALID.  d_proofs / d_proofs_out /
+ * d_roots / d_nodes_out are 16-byte aligned. */
+/* p(len, block_log2, first, count).  GPU-free.  A range the file does not have, count == 0, or a
+ * block_log2 outside 17..20 is SD_ERR_INVALID. */
+int sd_checksum_tree_range_proof_entries(uint64_t len, uint32_t block_log2, uint64_t first, uint64_t count,
+                                         uint32_t* entries);
+/* Declares the list's ranges.  GPU-free.  Anything but the rules above is SD_ERR_INVALID and the
+ * list is unchanged; calling again replaces the ranges (not while a range call of the list runs). */
+int sd_checksum_tree_blocks_set_ranges(sd_checksum_tree_blocks* blocks, const uint64_t* range_base, size_t q);
+/* proof_base[0 .. q] (host) of the list's ranges.  GPU-free. */
+int sd_checksum_tree_blocks_range_proof_layout(sd_checksum_tree_blocks* blocks, uint64_t* proof_base);
+/* Every range's proof, in range order, from d_nodes (the whole level layout, as _prove takes it) ->
+ * d_proofs_out (proof_base[q] x 32 B).  Reads no file bytes, and only the levels of files with a
+ * range.  Asynchronous on `stream`; one prove_ranges of a list at a time (the list owns the scratch
+ * of those files' interior levels). */
+int sd_checksum_tree_blocks_prove_ranges(sd_cas_ctx* ctx, sd_checksum_tree_blocks* blocks, const uint8_t* d_nodes,
+                                         uint8_t* d_proofs_out, void* stream);
+/* Hashes the listed bytes, climbs each range through its proof (d_proofs, laid out by proof_base)
+ * as a tree reduce -- about m + 2h compressions per range, not m h -- and compares the result with
+ * d_roots[32 f] (n_files x 32 B; only the entries of files with a range are read).
+ *   d_nodes_out (m x 32 B, may be NULL): the rows' nodes in list order, as _verify_proofs gives them
+ *   d_bad (q bytes, may be NULL): 1 where range i fails, else 0
+ *   d_ranges_out (3 x u64 per range, may be NULL): (file, first block, blocks) of the failing ranges
+ *     in RANGE order; *count, capacity and SD_ERR_CAPACITY as sd_checksum_tree_blocks_verify
+ *   stats[4] (host, may be NULL): [0] files, [1] ranges compared, [2] ranges that differ, [3] files
+ *     with at least one
+ * Runs on `stream` and syncs it; uses the context's pooled slot, and the list owns the scratch of the
+ * groups' tops between the passes: one verify_range_proofs of a list at a time. */
+int sd_checksum_tree_blocks_verify_range_proofs(sd_cas_ctx* ctx, sd_checksum_tree_blocks* blocks,
+                                                const uint8_t* d_data, const uint8_t* d_proofs,
+                                                const uint8_t* d_roots, uint8_t* d_nodes_out, uint8_t* d_bad,
+                                                uint64_t* d_ranges_out, uint64_t capacity, uint64_t* count,
+                                                uint64_t stats[4], void* stream);
+/* The same over host memory on host cores: the list's arrays plus range_base are passed again, with
+ * the device calls' rules (the ranges are planned, and climbed group by group, as on the device). */
+int sd_cpu_checksum_tree_blocks_prove_ranges(const uint8_t* nodes, const uint64_t* lens, size_t n_files,
+                                             uint32_t block_log2, const uint64_t* rows, size_t m,
+                                             const uint64_t* range_base, size_t q, uint8_t* proofs_out);
+int sd_cpu_checksum_tree_blocks_verify_range_proofs(const uint8_t* data, const uint64_t* lens, size_t n_files,
+                                                    uint32_t block_log2, const uint64_t* rows,
+                                                    const uint64_t* data_offsets, size_t m, const uint64_t* range_base,
+                                                    size_t q, const uint8_t* proofs, const uint8_t* roots,
+                                                    uint8_t* nodes_out, uint8_t* bad, uint64_t* ranges_out,
+                                                    uint64_t capacity, uint64_t* count, uint64_t stats[4], int nthreads);
+
 /* ---------------------------------------------------------------- synthetic data */
 /* Device generator of SURVEY.md §8(d) (seed 0x5D5DCA51D, splitmix64 counter stream),
  * for benchmarks and parity tests: writes the exact cas message of each synthetic file

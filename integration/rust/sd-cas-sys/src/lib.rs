@@ -324,6 +324,31 @@ extern "C" {
                                                      nodes_out: *mut u8, bad: *mut u8, rows_out: *mut u64,
                                                      capacity: u64, count: *mut u64, stats: *mut u64,
                                                      nthreads: c_int) -> c_int;
+    // range proofs: a run of blocks (Range::Partial) against the checksum and length alone, two flanks per level
+    pub fn sd_checksum_tree_range_proof_entries(len: u64, block_log2: u32, first: u64, count: u64,
+                                                entries: *mut u32) -> c_int;
+    pub fn sd_checksum_tree_blocks_set_ranges(blocks: *mut sd_checksum_tree_blocks, range_base: *const u64,
+                                              q: usize) -> c_int;
+    pub fn sd_checksum_tree_blocks_range_proof_layout(blocks: *mut sd_checksum_tree_blocks,
+                                                      proof_base: *mut u64) -> c_int;
+    pub fn sd_checksum_tree_blocks_prove_ranges(ctx: *mut sd_cas_ctx, blocks: *mut sd_checksum_tree_blocks,
+                                                d_nodes: *const u8, d_proofs_out: *mut u8,
+                                                stream: *mut c_void) -> c_int;
+    pub fn sd_checksum_tree_blocks_verify_range_proofs(ctx: *mut sd_cas_ctx, blocks: *mut sd_checksum_tree_blocks,
+                                                       d_data: *const u8, d_proofs: *const u8, d_roots: *const u8,
+                                                       d_nodes_out: *mut u8, d_bad: *mut u8, d_ranges_out: *mut u64,
+                                                       capacity: u64, count: *mut u64, stats: *mut u64,
+                                                       stream: *mut c_void) -> c_int;
+    pub fn sd_cpu_checksum_tree_blocks_prove_ranges(nodes: *const u8, lens: *const u64, n_files: usize,
+                                                    block_log2: u32, rows: *const u64, m: usize,
+                                                    range_base: *const u64, q: usize, proofs_out: *mut u8) -> c_int;
+    pub fn sd_cpu_checksum_tree_blocks_verify_range_proofs(data: *const u8, lens: *const u64, n_files: usize,
+                                                           block_log2: u32, rows: *const u64,
+                                                           data_offsets: *const u64, m: usize,
+                                                           range_base: *const u64, q: usize, proofs: *const u8,
+                                                           roots: *const u8, nodes_out: *mut u8, bad: *mut u8,
+                                                           ranges_out: *mut u64, capacity: u64, count: *mut u64,
+                                                           stats: *mut u64, nthreads: c_int) -> c_int;
     // device buffers for callers that hold their lists on the host (sd_memcpy syncs `stream`)
     pub fn sd_device_malloc(ctx: *mut sd_cas_ctx, bytes: u64, out: *mut *mut c_void) -> c_int;
     pub fn sd_device_free(ctx: *mut sd_cas_ctx, p: *mut c_void);

@@ -215,6 +215,14 @@ SIGNATURES = [
     ("sd_checksum_tree_blocks_verify_proofs", I32, [P, P, P, P, P, P, P, P, U64, PU64, P, P]),
     ("sd_cpu_checksum_tree_blocks_prove", I32, [P, P, SZ, U32, P, SZ, P]),
     ("sd_cpu_checksum_tree_blocks_verify_proofs", I32, [P, P, SZ, U32, P, P, SZ, P, P, P, P, P, U64, PU64, P, I32]),
+    ("sd_checksum_tree_range_proof_entries", I32, [U64, U32, U64, U64, ctypes.POINTER(U32)]),
+    ("sd_checksum_tree_blocks_set_ranges", I32, [P, P, SZ]),
+    ("sd_checksum_tree_blocks_range_proof_layout", I32, [P, P]),
+    ("sd_checksum_tree_blocks_prove_ranges", I32, [P, P, P, P, P]),
+    ("sd_checksum_tree_blocks_verify_range_proofs", I32, [P, P, P, P, P, P, P, P, U64, PU64, P, P]),
+    ("sd_cpu_checksum_tree_blocks_prove_ranges", I32, [P, P, SZ, U32, P, SZ, P, SZ, P]),
+    ("sd_cpu_checksum_tree_blocks_verify_range_proofs", I32,
+     [P, P, SZ, U32, P, P, SZ, P, SZ, P, P, P, P, P, U64, PU64, P, I32]),
 ]
 SD_TREE_BLOCK_LOG2_MIN, SD_TREE_BLOCK_LOG2_MAX = 17, 20
 SD_CONFIRM_INVALID, SD_CONFIRM_SINGLE, SD_CONFIRM_CONFIRMED, SD_CONFIRM_REFUTED = 0, 1, 2, 3

@@ -376,6 +376,116 @@ def checksum_tree_blocks_verify_proofs(data, lens, rows, data_offsets, proofs, r
     return out
 
 
+def tree_range_proof_entries(length: int, first: int, count: int, block_log2: int = 17) -> int:
+    """sd_checksum_tree_range_proof_entries: the 32-byte entries of the proof of blocks [first,
+    first + count) of a file of `length` bytes -- its left and right flanks, at most two per level."""
+    v = ctypes.c_uint32(0)
+    check(lib().sd_checksum_tree_range_proof_entries(int(length), int(block_log2), int(first), int(count),
+                                                     ctypes.byref(v)))
+    return int(v.value)
+
+
+def _range_base(range_base, m: int) -> np.ndarray:
+    rb = np.ascontiguousarray(range_base, dtype=np.uint64).reshape(-1)
+    if len(rb) == 0:
+        if m:
+            raise ValueError("range_base holds q + 1 entries")
+        rb = np.zeros(1, np.uint64)
+    return rb
+
+
+def tree_range_proof_base(lens, rows, range_base, block_log2: int = 17) -> np.ndarray:
+    """proof_base uint64 [q + 1] of a list's ranges (range i = rows range_base[i] .. range_base[i +
+    1]): the exclusive prefix sum of their entry counts."""
+    ls = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+    rw = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2)
+    rb = _range_base(range_base, len(rw))
+    base = np.zeros(len(rb), np.uint64)
+    for i in range(len(rb) - 1):
+        r0, r1 = int(rb[i]), int(rb[i + 1])
+        if not 0 <= r0 < r1 <= len(rw) or int(rw[r0, 0]) >= len(ls):
+            raise ValueError(f"range {i}: no such rows")
+        base[i + 1] = base[i] + np.uint64(tree_range_proof_entries(int(ls[int(rw[r0, 0])]), int(rw[r0, 1]), r1 - r0,
+                                                                   block_log2))
+    return base
+
+
+def checksum_tree_blocks_prove_ranges(nodes, lens, rows, range_base, block_log2: int = 17):
+    """sd_cpu_checksum_tree_blocks_prove_ranges: (proofs uint8 [proof_base[q], 32], proof_base) of
+    the ranges of the listed rows from `nodes`, the batch's whole level; only the levels of files
+    with a range are read.  Range i's proof is proofs[proof_base[i]:proof_base[i + 1]], bottom-up,
+    the left flank of a level before its right one."""
+    ls = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+    rw = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2)
+    rb = _range_base(range_base, len(rw))
+    nd = np.ascontiguousarray(nodes, dtype=np.uint8).reshape(-1)
+    if nd.size != 32 * int(tree_node_base(ls, block_log2)[len(ls)]):
+        raise ValueError("nodes is not node_base[n_files] x 32 bytes")
+    from ._native import SdCasError
+    total = 0
+    try:
+        base = tree_range_proof_base(ls, rw, rb, block_log2)
+        total = int(base[-1])
+    except (SdCasError, ValueError):  # ranges the library refuses below, with its own message
+        base = np.zeros(len(rb), np.uint64)
+    out = np.zeros((max(total, 1), 32), np.uint8)
+    check(lib().sd_cpu_checksum_tree_blocks_prove_ranges(nd.ctypes.data if nd.size else None, ls.ctypes.data, len(ls),
+                                                         int(block_log2), rw.ctypes.data, len(rw), rb.ctypes.data,
+                                                         len(rb) - 1, out.ctypes.data))
+    return out[:total], base
+
+
+def checksum_tree_blocks_verify_range_proofs(data, lens, rows, data_offsets, range_base, proofs, roots,
+                                             block_log2: int = 17, capacity: Optional[int] = None,
+                                             want_rows: bool = True, want_flags: bool = False,
+                                             want_nodes: bool = False, nthreads: int = THREADS):
+    """sd_cpu_checksum_tree_blocks_verify_range_proofs: the ranges of the listed rows whose blocks,
+    climbed through the range's proof (`proofs`, laid out by tree_range_proof_base), do not reach the
+    file's checksum (`roots` uint8 [n_files, 32]).  Returns (ranges uint64 [count, 3] of (file, first
+    block, blocks) in range order, stats uint64 [4]: files, ranges compared, ranges that differ,
+    files with one), then the 0/1 byte per range with want_flags and the rows' nodes uint8 [m, 32]
+    with want_nodes.  A failing range does not say which of its blocks is wrong."""
+    from ._native import SdCasError
+    ls, rw, offs, sizes = _block_list(lens, rows, data_offsets, block_log2)
+    keep, addr = _block_data(data, offs, sizes)
+    m = len(rw)
+    rb = _range_base(range_base, m)
+    q = len(rb) - 1
+    pf = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1)
+    rt = np.ascontiguousarray(roots, dtype=np.uint8).reshape(-1)
+    if sizes is not None and rt.size != 32 * len(ls):
+        raise ValueError("roots is not n_files x 32 bytes")
+    try:
+        need = 32 * int(tree_range_proof_base(ls, rw, rb, block_log2)[-1])
+    except (SdCasError, ValueError):  # ranges the library refuses below, with its own message
+        need = pf.size
+    if pf.size != need:
+        raise ValueError("proofs is not proof_base[q] x 32 bytes")
+    cap = q if capacity is None else int(capacity)
+    out_rows = np.zeros((max(cap, 1), 3), np.uint64)
+    bad = np.zeros(max(q, 1), np.uint8)
+    nodes = np.zeros((max(m, 1), 32), np.uint8)
+    count = ctypes.c_uint64(0)
+    stats = np.zeros(4, np.uint64)
+    rc = lib().sd_cpu_checksum_tree_blocks_verify_range_proofs(
+        addr, ls.ctypes.data, len(ls), int(block_log2), rw.ctypes.data, offs.ctypes.data, m, rb.ctypes.data, q,
+        pf.ctypes.data if pf.size else None, rt.ctypes.data if rt.size else None,
+        nodes.ctypes.data if want_nodes else None, bad.ctypes.data if want_flags else None,
+        out_rows.ctypes.data if want_rows else None, cap, ctypes.byref(count), stats.ctypes.data, nthreads)
+    try:
+        check(rc)
+    except SdCasError as e:
+        e.needed = int(count.value)
+        e.stats = stats
+        raise
+    out = (out_rows[:int(count.value) if want_rows else 0], stats)
+    if want_flags:
+        out += (bad[:q],)
+    if want_nodes:
+        out += (nodes[:m],)
+    return out
+
+
 def blake3(data: bytes) -> bytes:
     """Full 32-byte BLAKE3 of a host buffer (sd_cpu_checksums of one range)."""
     buf = np.frombuffer(bytes(data) + bytes(64), np.uint8)

@@ -16,6 +16,9 @@
 // The block proofs (_prove, _verify_proofs) are the only BLAKE3 here, blake3_device.h's parent:
 // k_tree_levels stores the interior levels a reduce passes through, k_tree_proof_gather packs the
 // siblings, and proof_climb, a predicate of the flag skeleton, climbs a row's node to its root.
+// The range proofs (_prove_ranges, _verify_range_proofs) take a run of rows at once:
+// k_tree_range_gather packs the run's two flanks, and k_tree_range_climb, the reduce's LDS tree
+// with flanks, climbs the run's nodes to the root they claim, which range_differs compares.
 #include <hip/hip_runtime.h>
 
 #include <memory>
@@ -268,6 +271,184 @@ struct proof_climb {
         return d;
     }
 };
+
+// ------------------------------------------------------------------------------------ ranges
+// Range proofs (include/sd_cas.h): a run of blocks climbed as a tree reduce, its two flanks the
+// only siblings that are not its own.
+//
+// Range climb: k_ck_reduce's 256-node LDS tree with flanks.  A workgroup holds the nodes of one
+// range that fall into one 256-aligned group of the file's level 8p, node i at slot i & 255, so a
+// pair of the file is a pair of slots at every level of the pass and a node's sibling is always in
+// its group.  Before level l's parents are formed, the range's first group puts the left entry
+// beside its first node when that node's index is odd, and its last group the right entry beside
+// its last node when that index is even and the file has a node after it (both from the masks the
+// host planned; the two may be one workgroup).  A last node still unpaired is the file's own
+// carry.  ROOT goes on the last level of the pass that reaches level h.  The group's top goes to
+// the scratch the next pass reads, or to top[range].  src is the rows' nodes (pass 0) or the
+// scratch itself, so neither pointer is __restrict__.
+__global__ __launch_bounds__(256) void k_tree_range_climb(const uint32_t* src, uint32_t* scratch,
+                                                          const uint32_t* __restrict__ proofs,
+                                                          const ck_range_wg* __restrict__ wgs,
+                                                          uint32_t* __restrict__ top) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[256][8];
+    const ck_range_wg w = wgs[blockIdx.x];
+    const uint32_t t = threadIdx.x;
+    const bool first = w.flags & CK_RANGE_FIRST, last = w.flags & CK_RANGE_LAST, fin = w.flags & CK_RANGE_FINAL;
+    uint32_t s = w.start, e = w.start + w.count - 1u;  // the present slots of the current level
+    uint64_t at = w.pbase;                             // the current level's first entry
+    if (t >= s && t <= e) {
+        uint32_t cv[8];
+        get_cv(cv, src + (w.src_base + (t - s)) * 8);
+        put_cv(lds[t], cv);
+    }
+    // level l's flanks into the slots beside [s, e]: lanes that hold no node of that level
+    auto flanks = [&](uint32_t l) {
+        const uint32_t lb = (w.lmask >> l) & 1u, rb = (w.rmask >> l) & 1u;
+        uint32_t cv[8];
+        if (first && lb && t + 1 == s) {
+            get_cv(cv, proofs + at * 8);
+            put_cv(lds[t], cv);
+        }
+        if (last && rb && t == e + 1) {
+            get_cv(cv, proofs + (at + lb) * 8);
+            put_cv(lds[t], cv);
+        }
+        at += lb + rb;
+    };
+    if (w.levels) flanks(0);
+    __syncthreads();
+    for (uint32_t l = 0; l < w.levels; l++) {
+        const uint32_t e2 = e + ((last && ((w.rmask >> l) & 1u)) ? 1u : 0u);  // the last slot with the right entry
+        s >>= 1, e >>= 1;  // the parents' slots: pairs start at the even slot at or below the first
+        uint32_t res[8];
+        bool have = false;
+        if (t >= s && t <= e) {
+            if (2 * t + 1 <= e2) {
+                uint32_t a[8], b[8];
+                get_cv(a, lds[2 * t]);
+                get_cv(b, lds[2 * t + 1]);
+                sdb3::parent<false>(res, a, b, fin && l + 1 == w.levels ? (uint32_t)sdb3::ROOT : 0u);
+            } else {
+                get_cv(res, lds[2 * t]);  // the file's carried odd node
+            }
+            have = true;
+        }
+        __syncthreads();
+        if (have) put_cv(lds[t], res);
+        if (l + 1 < w.levels) flanks(l + 1);
+        __syncthreads();
+    }
+    if (t == 0) {
+        uint32_t cv[8];
+        get_cv(cv, lds[0]);
+        put_cv((fin ? top : scratch) + w.dst * 8, cv);
+    }
+}
+
+// Range gather: one lane per range copies the flanks that exist, bottom-up and left before right,
+// to the range's place among the packed proofs: level 0's from the caller's level, the others from
+// the scratch k_tree_levels filled.
+__global__ __launch_bounds__(256) void k_tree_range_gather(const ck_range_row* __restrict__ rrow, uint64_t q,
+                                                           const uint4* __restrict__ nodes,
+                                                           const uint4* __restrict__ scratch,
+                                                           const uint64_t* __restrict__ lvl_off,
+                                                           uint4* __restrict__ out) {
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < q; r += (uint64_t)gridDim.x * blockDim.x) {
+        const ck_range_row w = rrow[r];
+        uint64_t lo = w.first, hi = w.first + w.count - 1;
+        uint4* o = out + 2 * w.pbase;
+        uint32_t L = 0;
+        for (uint64_t n = w.nb; n > 1; n = (n + 1) >> 1, lo >>= 1, hi >>= 1, L++) {
+            const uint4* lvl = L == 0 ? nodes + 2 * w.node0 : scratch + 2 * lvl_off[w.lvl_tab + L - 1];
+            if (lo & 1) {
+                o[0] = lvl[2 * (lo - 1)];
+                o[1] = lvl[2 * (lo - 1) + 1];
+                o += 2;
+            }
+            if (!(hi & 1) && hi + 1 < n) {
+                o[0] = lvl[2 * (hi + 1)];
+                o[1] = lvl[2 * (hi + 1) + 1];
+                o += 2;
+            }
+        }
+    }
+}
+
+// range i's claimed root differs from its file's; the file is marked
+struct range_differs {
+    const uint4* __restrict__ top;
+    const uint4* __restrict__ roots;
+    const ck_range_row* __restrict__ rrow;
+    uint8_t* __restrict__ file_bad;
+    __device__ bool operator()(uint64_t i, uint64_t) const {
+        const uint64_t f = rrow[i].file;
+        const uint4 a0 = top[2 * i], a1 = top[2 * i + 1], b0 = roots[2 * f], b1 = roots[2 * f + 1];
+        const bool d = a0.x != b0.x || a0.y != b0.y || a0.z != b0.z || a0.w != b0.w || a1.x != b1.x || a1.y != b1.y ||
+                       a1.z != b1.z || a1.w != b1.w;
+        if (d) file_bad[f] = 1;
+        return d;
+    }
+};
+
+// (file, first block, blocks) per flagged range, in range order
+struct range_rows : from_flags {
+    const ck_range_row* __restrict__ rrow;
+    uint64_t* __restrict__ rows;
+    __device__ void emit(uint64_t i, bool flag, uint64_t slot, uint64_t) const {
+        if (!flag) return;
+        rows[3 * slot] = rrow[i].file;
+        rows[3 * slot + 1] = rrow[i].first;
+        rows[3 * slot + 2] = rrow[i].count;
+    }
+};
+
+// the range verify's scratch in a pooled slot: the rows' nodes, the ranges' claimed roots, the
+// flags when the caller wants none, the files' marks, two rows of per-workgroup counts
+struct ranges_scratch {
+    uint8_t *nodes, *top, *flags, *file_bad;
+    uint64_t* counts;
+    static size_t bytes(uint64_t m, uint64_t q, uint64_t n) {
+        return 256 + round256(32 * m) + round256(32 * q) + round256(q) + round256(n) +
+               round256(2 * BLOCKS * sizeof(uint64_t));
+    }
+    ranges_scratch(void* base, uint64_t m, uint64_t q, uint64_t n) {
+        uint8_t* p = reinterpret_cast<uint8_t*>(((uintptr_t)base + 255) & ~uintptr_t(255));
+        nodes = p, p += round256(32 * m);
+        top = p, p += round256(32 * q);
+        flags = p, p += round256(q);
+        file_bad = p, p += round256(n);
+        counts = reinterpret_cast<uint64_t*>(p);
+    }
+};
+
+void need_ranges(const sd_checksum_tree_blocks* b) {
+    if (!b->ranges.set) throw sd_failure(SD_ERR_INVALID, "sd_checksum_tree_blocks_set_ranges has not been called");
+}
+
+// the first range call after _set_ranges: the ranges' rows, the climb passes and their scratch
+void upload_blocks_ranges(sd_checksum_tree_blocks* b) {
+    if (b->ranges_up) return;
+    b->gtab.begin();
+    b->o_rrow = b->gtab.add(b->ranges.rrow);
+    b->o_gpass.clear();
+    for (const auto& ps : b->ranges.passes) b->o_gpass.push_back(b->gtab.add(ps));
+    b->gtab.upload(nullptr);
+    b->tops.ensure(32 * b->ranges.scratch_nodes);
+    b->ranges_up = true;
+}
+
+// the first _prove_ranges': the level offsets, k_tree_levels' passes and the interior levels' scratch
+void plan_blocks_range_levels(sd_checksum_tree_blocks* b) {
+    TreeProofPlan& lv = b->ranges.levels;
+    if (lv.levels) return;
+    plan_tree_proofs(lv, b->plan.node_base, b->ranges.firsts.data(), b->ranges.q(), true);
+    b->gltab.begin();
+    b->o_rlvl = b->gltab.add(lv.lvl_off);
+    b->o_rlpass.clear();
+    for (const auto& ps : lv.passes) b->o_rlpass.push_back(b->gltab.add(ps));
+    b->gltab.upload(nullptr);
+    b->rlevels.ensure(32 * lv.scratch_nodes);
+}
 
 // the first proof call's tables: the rows' and the listed files' level offsets
 void plan_blocks_proof_rows(sd_checksum_tree_blocks* b) {
@@ -686,6 +867,128 @@ int sd_checksum_tree_blocks_verify_proofs(sd_cas_ctx* ctx, sd_checksum_tree_bloc
     if (bad_rows == 0) return SD_OK;
     blocks_rows rows{{flags}, b->d_rows(), d_rows_out};
     launch_compact(g_rows, s, rows, nullptr, m, x.counts, nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_blocks_set_ranges(sd_checksum_tree_blocks* b, const uint64_t* range_base, size_t q) {
+    SD_GUARD_BEGIN
+    if (!b || (q && !range_base)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    plan_tree_ranges(b->ranges, b->plan.node_base, b->rows.data(), b->m(), range_base, q);  // throws: nothing changed
+    b->ranges_up = false;
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_blocks_range_proof_layout(sd_checksum_tree_blocks* b, uint64_t* proof_base) {
+    SD_GUARD_BEGIN
+    if (!b || !proof_base) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (b->m() == 0) {
+        proof_base[0] = 0;
+        return SD_OK;
+    }
+    need_ranges(b);
+    std::copy(b->ranges.proof_base.begin(), b->ranges.proof_base.end(), proof_base);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_blocks_prove_ranges(sd_cas_ctx* ctx, sd_checksum_tree_blocks* b, const uint8_t* d_nodes,
+                                         uint8_t* d_proofs_out, void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !b || (b->m() && !d_nodes)) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_aligned16(d_nodes, "d_nodes");
+    check_aligned16(d_proofs_out, "d_proofs_out");
+    if (b->m() == 0) return SD_OK;
+    need_ranges(b);
+    const uint64_t q = b->ranges.q();
+    if (b->ranges.proof_base[q] == 0) return SD_OK;  // whole files and one-node files only: every proof is empty
+    if (!d_proofs_out) throw sd_failure(SD_ERR_INVALID, "null argument");
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    upload_blocks_ranges(b);
+    plan_blocks_range_levels(b);
+    const TreeProofPlan& lv = b->ranges.levels;
+    uint32_t* scratch = b->rlevels.as<uint32_t>();
+    for (size_t k = 0; k < lv.passes.size(); k++) {
+        hipLaunchKernelGGL(k_tree_levels, dim3((uint32_t)lv.passes[k].size()), dim3(256), 0, s,
+                           k == 0 ? reinterpret_cast<const uint32_t*>(d_nodes) : scratch, scratch, b->d_rlpass(k),
+                           b->d_rlvl_off());
+        HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_tree_range_gather, dim3(flat_grid(q)), dim3(256), 0, s, b->d_rrow(), q,
+                       reinterpret_cast<const uint4*>(d_nodes), reinterpret_cast<const uint4*>(scratch), b->d_rlvl_off(),
+                       reinterpret_cast<uint4*>(d_proofs_out));
+    HIP_CHECK(hipGetLastError());
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_blocks_verify_range_proofs(sd_cas_ctx* ctx, sd_checksum_tree_blocks* b, const uint8_t* d_data,
+                                                const uint8_t* d_proofs, const uint8_t* d_roots, uint8_t* d_nodes_out,
+                                                uint8_t* d_bad, uint64_t* d_ranges_out, uint64_t capacity,
+                                                uint64_t* count, uint64_t stats[4], void* stream) {
+    SD_GUARD_BEGIN
+    if (!ctx || !b || (b->m() && (!d_data || !d_roots))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    check_aligned16(d_proofs, "d_proofs");
+    check_aligned16(d_roots, "d_roots");
+    check_aligned16(d_nodes_out, "d_nodes_out");
+    if (count) *count = 0;
+    if (stats) memset(stats, 0, 4 * sizeof(uint64_t));
+    const uint64_t n = b->n_files, m = b->m();
+    if (m == 0) return SD_OK;
+    need_ranges(b);
+    const uint64_t q = b->ranges.q();
+    if (b->ranges.proof_base[q] && !d_proofs) throw sd_failure(SD_ERR_INVALID, "null argument");
+    ctx->bind();
+    hipStream_t s = ctx->pick(stream);
+    upload_blocks_ranges(b);
+    auto slot = ctx->acquire();
+    struct Rel {
+        sd_cas_ctx* c;
+        std::unique_ptr<Slot>* s;
+        ~Rel() { c->release(std::move(*s)); }
+    } rel{ctx, &slot};
+    slot->staged.ensure(ranges_scratch::bytes(m, q, n));
+    slot->host_hashes.ensure(2 * BLOCKS * sizeof(uint64_t));
+    const ranges_scratch x(slot->staged.p, m, q, n);
+    uint8_t* nodes = d_nodes_out ? d_nodes_out : x.nodes;
+    HIP_CHECK(sdk::launch_ck_blocks(d_data, b->d_items(), (uint32_t)m, b->block_log2, false,
+                                    reinterpret_cast<uint32_t*>(nodes), s));
+    HIP_CHECK(hipMemsetAsync(x.file_bad, 0, n, s));
+    uint32_t* tops = b->tops.as<uint32_t>();
+    for (size_t k = 0; k < b->ranges.passes.size(); k++) {
+        hipLaunchKernelGGL(k_tree_range_climb, dim3((uint32_t)b->ranges.passes[k].size()), dim3(256), 0, s,
+                           k == 0 ? reinterpret_cast<const uint32_t*>(nodes) : tops, tops,
+                           reinterpret_cast<const uint32_t*>(d_proofs), b->d_gpass(k), reinterpret_cast<uint32_t*>(x.top));
+        HIP_CHECK(hipGetLastError());
+    }
+    uint8_t* flags = d_bad ? d_bad : x.flags;
+    const uint32_t g_ranges = sliced_grid(q), g_files = sliced_grid(n);
+    launch_flag(g_ranges, s,
+                range_differs{reinterpret_cast<const uint4*>(x.top), reinterpret_cast<const uint4*>(d_roots), b->d_rrow(),
+                              x.file_bad},
+                nullptr, q, flags, x.counts);
+    launch_flag(g_files, s, tree_file_marked{x.file_bad}, nullptr, n, nullptr, x.counts + BLOCKS);
+    HIP_CHECK(hipGetLastError());
+    const uint64_t* h = reinterpret_cast<const uint64_t*>(slot->host_hashes.p);
+    HIP_CHECK(hipMemcpyAsync(slot->host_hashes.p, x.counts, 2 * BLOCKS * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    uint64_t bad_ranges = 0, bad_files = 0;
+    for (uint32_t g = 0; g < g_ranges; g++) bad_ranges += h[g];
+    for (uint32_t g = 0; g < g_files; g++) bad_files += h[BLOCKS + g];
+    if (bad_ranges > q || bad_files > n || bad_files > bad_ranges)
+        throw sd_failure(SD_ERR_INTERNAL, "verify_range_proofs: inconsistent totals");
+    if (count) *count = bad_ranges;
+    if (stats) stats[0] = n, stats[1] = q, stats[2] = bad_ranges, stats[3] = bad_files;
+    if (!d_ranges_out) return SD_OK;
+    if (capacity < bad_ranges)
+        throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of differing ranges");
+    if (bad_ranges == 0) return SD_OK;
+    range_rows rows{{flags}, b->d_rrow(), d_ranges_out};
+    launch_compact(g_ranges, s, rows, nullptr, q, x.counts, nullptr);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(s));
     return SD_OK;

@@ -6,7 +6,8 @@
 // the block's bytes, finalize_cv -- a block's CV depends only on its bytes and its position.  A
 // file of one node is hashed whole (ROOT), and a level's root is cpu_root_from_cvs over it.  The
 // listed blocks (sd_cpu_checksum_tree_blocks / _verify / _update) are the same two hashers over
-// the items plan_tree_blocks makes, which the device list uses too.  No HIP: built with g++ under
+// the items plan_tree_blocks makes, which the device list uses too.  The range proofs' twins run
+// the workgroups plan_tree_ranges plans for the device, one by one.  No HIP: built with g++ under
 // the sanitizers too (checksum_tree_selftest.cpp).
 #include <string.h>
 
@@ -115,7 +116,115 @@ void plan_tree_proofs(TreeProofPlan& p, const std::vector<uint64_t>& node_base, 
     p.levels = true;
 }
 
+void plan_tree_ranges(TreeRangePlan& out, const std::vector<uint64_t>& node_base, const uint64_t* rows, size_t m,
+                      const uint64_t* range_base, size_t q) {
+    const size_t n = node_base.size() - 1;
+    TreeRangePlan p;
+    p.set = true;
+    p.range_base.assign(1, 0);
+    p.proof_base.assign(1, 0);
+    if (q == 0) {
+        if (m) throw sd_failure(SD_ERR_INVALID, "no ranges over a list with rows");
+        out = std::move(p);
+        return;
+    }
+    if (!range_base) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (q >= (1ull << 32)) throw sd_failure(SD_ERR_INVALID, "list too large");
+    if (range_base[0] != 0 || range_base[q] != m) throw sd_failure(SD_ERR_INVALID, "range_base does not run from 0 to m");
+    std::vector<uint64_t>& firsts = p.firsts;
+    firsts.resize(2 * q);
+    for (size_t i = 0; i < q; i++) {  // everything refused before anything is planned (p is a local)
+        const uint64_t r0 = range_base[i], r1 = range_base[i + 1];
+        if (r1 <= r0 || r1 > m) throw sd_failure(SD_ERR_INVALID, "range " + std::to_string(i) + ": empty or out of order");
+        const uint64_t f = rows[2 * r0], a = rows[2 * r0 + 1];
+        if (f >= n || a >= node_base[f + 1] - node_base[f] || r1 - r0 > node_base[f + 1] - node_base[f] - a)
+            throw sd_failure(SD_ERR_INVALID, "range " + std::to_string(i) + ": no such blocks");
+        for (uint64_t r = r0 + 1; r < r1; r++)
+            if (rows[2 * r] != f || rows[2 * r + 1] != a + (r - r0))
+                throw sd_failure(SD_ERR_INVALID, "range " + std::to_string(i) + ": its rows are not consecutive blocks of one file");
+        firsts[2 * i] = f, firsts[2 * i + 1] = a;
+    }
+    plan_tree_proofs(p.levels, node_base, firsts.data(), q, false);
+    p.range_base.assign(range_base, range_base + q + 1);
+    p.proof_base.assign(q + 1, 0);
+    p.rrow.resize(q);
+    for (size_t i = 0; i < q; i++) {
+        const uint64_t f = firsts[2 * i], a = firsts[2 * i + 1], cnt = range_base[i + 1] - range_base[i];
+        const uint64_t nb = node_base[f + 1] - node_base[f], last = a + cnt - 1;
+        p.rrow[i] = ck_range_row{node_base[f], nb, a, cnt, p.proof_base[i], p.levels.prow[i].lvl_tab, (uint32_t)f};
+        p.proof_base[i + 1] = p.proof_base[i] + tree_range_proof_entries(nb, a, cnt);
+        // the passes: the range's nodes at level 8s in the 256-aligned groups they fall into
+        const uint32_t h = tree_height(nb), n_pass = std::max<uint32_t>(1, (h + 7) / 8);
+        uint64_t src0 = range_base[i], pb = p.proof_base[i], n_lvl = nb;
+        for (uint32_t s = 0; s < n_pass; s++) {
+            const uint32_t Lb = 8 * s, levels = std::min<uint32_t>(8, h - Lb);
+            const bool fin = s + 1 == n_pass;
+            uint8_t lmask = 0, rmask = 0;
+            for (uint32_t l = 0; l < levels; l++, n_lvl = (n_lvl + 1) >> 1) {
+                const uint64_t lo = a >> (Lb + l), hi = last >> (Lb + l);
+                if (lo & 1) lmask |= (uint8_t)(1u << l);
+                if (!(hi & 1) && hi + 1 < n_lvl) rmask |= (uint8_t)(1u << l);
+            }
+            const uint64_t lo = a >> Lb, hi = last >> Lb, g0 = lo >> 8, g1 = hi >> 8;
+            const uint64_t dst0 = fin ? i : p.scratch_nodes;
+            if (!fin) p.scratch_nodes += g1 - g0 + 1;
+            if (p.passes.size() <= s) p.passes.emplace_back();
+            for (uint64_t g = g0; g <= g1; g++) {
+                const uint64_t i0 = std::max(lo, 256 * g), i1 = std::min(hi, 256 * g + 255);
+                const uint8_t flags = (g == g0 ? CK_RANGE_FIRST : 0) | (g == g1 ? CK_RANGE_LAST : 0) | (fin ? CK_RANGE_FINAL : 0);
+                p.passes[s].push_back(ck_range_wg{src0 + (i0 - lo), fin ? dst0 : dst0 + (g - g0), pb, (uint16_t)(i1 - i0 + 1),
+                                                  (uint8_t)(i0 & 255), (uint8_t)levels, lmask, rmask, flags, 0});
+            }
+            pb += (uint64_t)__builtin_popcount(lmask) + (uint64_t)__builtin_popcount(rmask);
+            src0 = dst0;
+        }
+    }
+    for (const auto& ps : p.passes)
+        if (ps.size() >= (1ull << 31)) throw sd_failure(SD_ERR_INVALID, "list too large");
+    out = std::move(p);
+}
+
 namespace {
+
+// one workgroup of a climb pass, as k_tree_range_climb runs it: the group's nodes at their slots,
+// each level's flanks beside them, pairs from the even slot, the file's own carry last
+void cpu_range_wg(const ck_range_wg& w, const uint8_t* src, uint8_t* scratch, const uint8_t* proofs, uint8_t* top) {
+    uint8_t lds[256][32];
+    uint32_t s = w.start, e = w.start + w.count - 1u;
+    memcpy(lds[s], src + 32 * w.src_base, 32 * (size_t)w.count);
+    const bool first = w.flags & CK_RANGE_FIRST, last = w.flags & CK_RANGE_LAST, fin = w.flags & CK_RANGE_FINAL;
+    uint64_t at = w.pbase;
+    for (uint32_t l = 0; l < w.levels; l++) {
+        const uint32_t lb = (w.lmask >> l) & 1u, rb = (w.rmask >> l) & 1u;
+        if (first && lb) memcpy(lds[s - 1], proofs + 32 * at, 32);
+        if (last && rb) memcpy(lds[e + 1], proofs + 32 * (at + lb), 32);
+        at += lb + rb;
+        const uint32_t e2 = e + (last && rb ? 1u : 0u);
+        s >>= 1, e >>= 1;
+        for (uint32_t t = s; t <= e; t++) {
+            if (2 * t + 1 <= e2) cpu_parent(lds[2 * t], lds[2 * t + 1], fin && l + 1 == w.levels, lds[t]);
+            else memcpy(lds[t], lds[2 * t], 32);
+        }
+    }
+    memcpy((fin ? top : scratch) + 32 * w.dst, lds[0], 32);
+}
+
+// every listed file's interior levels 1 .. h - 1 -> scratch (by p.lvl_off), level by level, the odd node carried
+void cpu_fill_levels(const TreeProofPlan& p, const uint8_t* nodes, size_t n_files, uint8_t* scratch) {
+    std::vector<uint8_t> seen(n_files, 0);
+    for (const ck_proof_row& w : p.prow) {
+        if (seen[w.file]) continue;
+        seen[w.file] = 1;
+        const uint8_t* src = nodes + 32 * w.node0;
+        uint32_t L = 1;
+        for (uint64_t n = w.nb; ((n + 1) >> 1) > 1; n = (n + 1) >> 1, L++) {
+            uint8_t* dst = scratch + 32 * p.lvl_off[w.lvl_tab + L - 1];
+            for (uint64_t i = 0; 2 * i + 1 < n; i++) cpu_parent(src + 64 * i, src + 64 * i + 32, false, dst + 32 * i);
+            if (n & 1) memcpy(dst + 32 * (n >> 1), src + 32 * (n - 1), 32);
+            src = dst;
+        }
+    }
+}
 
 // block j's proof from the file's level 0 (`level`) and its interior levels (`scratch` by lvl_off[tab ..])
 // -> out, bottom-up
@@ -354,22 +463,8 @@ int sd_cpu_checksum_tree_blocks_prove(const uint8_t* nodes, const uint64_t* lens
     plan_tree_proofs(p, node_base, rows, m, false);
     if (m == 0 || p.proof_base[m] == 0) return SD_OK;
     if (!proofs_out) throw sd_failure(SD_ERR_INVALID, "null argument");
-    // every listed file's interior levels, level by level, the odd node carried
     std::vector<uint8_t> scratch(32 * p.scratch_nodes);
-    std::vector<uint8_t> seen(n_files, 0);
-    for (size_t r = 0; r < m; r++) {
-        const ck_proof_row& w = p.prow[r];
-        if (seen[w.file]) continue;
-        seen[w.file] = 1;
-        const uint8_t* src = nodes + 32 * w.node0;
-        uint32_t L = 1;
-        for (uint64_t n = w.nb; ((n + 1) >> 1) > 1; n = (n + 1) >> 1, L++) {
-            uint8_t* dst = scratch.data() + 32 * p.lvl_off[w.lvl_tab + L - 1];
-            for (uint64_t i = 0; 2 * i + 1 < n; i++) cpu_parent(src + 64 * i, src + 64 * i + 32, false, dst + 32 * i);
-            if (n & 1) memcpy(dst + 32 * (n >> 1), src + 32 * (n - 1), 32);
-            src = dst;
-        }
-    }
+    cpu_fill_levels(p, nodes, n_files, scratch.data());
     for (size_t r = 0; r < m; r++) {
         const ck_proof_row& w = p.prow[r];
         cpu_gather_proof(nodes + 32 * w.node0, scratch.data(), p.lvl_off.data() + w.lvl_tab, w.nb, rows[2 * r + 1],
@@ -418,6 +513,94 @@ int sd_cpu_checksum_tree_blocks_verify_proofs(const uint8_t* data, const uint64_
         uint64_t q = 0;
         for (size_t r = 0; r < m; r++)
             if (differs[r]) rows_out[2 * q] = rows[2 * r], rows_out[2 * q + 1] = rows[2 * r + 1], q++;
+    }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_checksum_tree_range_proof_entries(uint64_t len, uint32_t block_log2, uint64_t first, uint64_t count,
+                                         uint32_t* entries) {
+    SD_GUARD_BEGIN
+    if (!entries) throw sd_failure(SD_ERR_INVALID, "null argument");
+    std::vector<uint64_t> nb;
+    plan_tree_layout(&len, 1, block_log2, nb);
+    if (count == 0 || first >= nb[1] || count > nb[1] - first) throw sd_failure(SD_ERR_INVALID, "no such range");
+    *entries = tree_range_proof_entries(nb[1], first, count);
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_checksum_tree_blocks_prove_ranges(const uint8_t* nodes, const uint64_t* lens, size_t n_files,
+                                             uint32_t block_log2, const uint64_t* rows, size_t m,
+                                             const uint64_t* range_base, size_t q, uint8_t* proofs_out) {
+    SD_GUARD_BEGIN
+    if ((n_files && !lens) || (m && (!nodes || !rows))) throw sd_failure(SD_ERR_INVALID, "null argument");
+    std::vector<uint64_t> node_base;
+    plan_tree_layout(lens, n_files, block_log2, node_base);
+    TreeRangePlan p;
+    plan_tree_ranges(p, node_base, rows, m, range_base, q);
+    if (p.proof_base[q] == 0) return SD_OK;
+    if (!proofs_out) throw sd_failure(SD_ERR_INVALID, "null argument");
+    std::vector<uint8_t> scratch(32 * p.levels.scratch_nodes);
+    cpu_fill_levels(p.levels, nodes, n_files, scratch.data());
+    for (const ck_range_row& w : p.rrow) {  // the flanks that exist, bottom-up, left before right
+        uint8_t* o = proofs_out + 32 * w.pbase;
+        uint64_t lo = w.first, hi = w.first + w.count - 1;
+        uint32_t L = 0;
+        for (uint64_t n = w.nb; n > 1; n = (n + 1) >> 1, lo >>= 1, hi >>= 1, L++) {
+            const uint8_t* lvl = L == 0 ? nodes + 32 * w.node0 : scratch.data() + 32 * p.levels.lvl_off[w.lvl_tab + L - 1];
+            if (lo & 1) memcpy(o, lvl + 32 * (lo - 1), 32), o += 32;
+            if (!(hi & 1) && hi + 1 < n) memcpy(o, lvl + 32 * (hi + 1), 32), o += 32;
+        }
+    }
+    return SD_OK;
+    SD_GUARD_END
+}
+
+int sd_cpu_checksum_tree_blocks_verify_range_proofs(const uint8_t* data, const uint64_t* lens, size_t n_files,
+                                                    uint32_t block_log2, const uint64_t* rows,
+                                                    const uint64_t* data_offsets, size_t m, const uint64_t* range_base,
+                                                    size_t q, const uint8_t* proofs, const uint8_t* roots,
+                                                    uint8_t* nodes_out, uint8_t* bad, uint64_t* ranges_out,
+                                                    uint64_t capacity, uint64_t* count, uint64_t stats[4], int nthreads) {
+    SD_GUARD_BEGIN
+    if ((n_files && !lens) || (m && (!data || !rows || !data_offsets || !roots)))
+        throw sd_failure(SD_ERR_INVALID, "null argument");
+    TreeBlocksPlan p;
+    plan_tree_blocks(p, lens, n_files, block_log2, rows, data_offsets, m);
+    TreeRangePlan rp;
+    plan_tree_ranges(rp, p.node_base, rows, m, range_base, q);
+    if (rp.proof_base[q] && !proofs) throw sd_failure(SD_ERR_INVALID, "null argument");
+    if (count) *count = 0;
+    if (stats) memset(stats, 0, 4 * sizeof(uint64_t));
+    if (m == 0) return SD_OK;
+    std::vector<uint8_t> own;
+    if (!nodes_out) own.resize(32 * m), nodes_out = own.data();
+    cpu_block_nodes(data, p, false, nodes_out, nthreads);
+    // the device's passes, one task per workgroup: pass s reads what pass s - 1 left in the scratch
+    std::vector<uint8_t> scratch(32 * rp.scratch_nodes), top(32 * q);
+    for (size_t s = 0; s < rp.passes.size(); s++) {
+        const uint8_t* src = s == 0 ? nodes_out : scratch.data();
+        cpu_parallel_for(rp.passes[s].size(), nthreads,
+                         [&](size_t g) { cpu_range_wg(rp.passes[s][g], src, scratch.data(), proofs, top.data()); });
+    }
+    std::vector<uint8_t> differs(q), file_bad(n_files, 0);
+    uint64_t st[4] = {n_files, q, 0, 0};
+    for (size_t i = 0; i < q; i++) {
+        const uint32_t f = rp.rrow[i].file;
+        differs[i] = memcmp(top.data() + 32 * i, roots + 32 * (uint64_t)f, 32) != 0;
+        if (bad) bad[i] = differs[i];
+        st[2] += differs[i];
+        if (differs[i] && !file_bad[f]) file_bad[f] = 1, st[3]++;
+    }
+    if (count) *count = st[2];
+    if (stats) memcpy(stats, st, sizeof st);
+    if (ranges_out) {
+        if (capacity < st[2]) throw sd_failure(SD_ERR_CAPACITY, "capacity is smaller than the number of differing ranges");
+        uint64_t o = 0;
+        for (size_t i = 0; i < q; i++)
+            if (differs[i])
+                ranges_out[3 * o] = rp.rrow[i].file, ranges_out[3 * o + 1] = rp.rrow[i].first, ranges_out[3 * o + 2] = rp.rrow[i].count, o++;
     }
     return SD_OK;
     SD_GUARD_END

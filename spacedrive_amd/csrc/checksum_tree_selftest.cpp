@@ -7,7 +7,11 @@
 // capacity rule over pre-filled buffers and every NULL output; the refusals; an empty batch; and
 // concurrent calls.  The listed blocks (sd_cpu_checksum_tree_blocks, _verify, _update) against the
 // same model: every block of those batches in a scrambled order from scattered places over 0xA5, a
-// block at chunk counter 2^32, a repeated and an omitted row, the patched level.  A program of its own: built plain for the CPU suite (`make
+// block at chunk counter 2^32, a repeated and an omitted row, the patched level.  The range proofs
+// (sd_checksum_tree_range_proof_entries, sd_cpu_checksum_tree_blocks_prove_ranges, _verify_range_proofs)
+// against the model's own range climb: every range of small files, one block equal to the block proof,
+// a flipped entry and a flipped byte, ranges across the groups of 256, the refusals.
+// A program of its own: built plain for the CPU suite (`make
 // checksum-tree-selftest`, tests/test_checksum_tree.py) and under ASan + UBSan and TSan (`make
 // sanitize-checksum-tree`, logs in profiles/checksum_tree/).
 #include <stdio.h>
@@ -735,7 +739,247 @@ static void test_proofs_concurrent_calls() {
     CHECK(ok == std::vector<int>(4, 1));
 }
 
+// ---------------------------------------------------------------- range proofs
+// the model's climb: blocks [a, b) through `proof` to the root they claim (include/sd_cas.h, range proofs)
+static cv_t m_range_climb(std::vector<cv_t> cur, const uint8_t* proof, uint64_t nb, uint64_t a, uint64_t b, size_t* used) {
+    size_t at = 0;
+    uint64_t lo = a, hi = b - 1;
+    for (uint64_t n = nb; n > 1; n = (n + 1) / 2, lo >>= 1, hi >>= 1) {
+        if (lo & 1) cur.insert(cur.begin(), m_get(proof + 32 * at++));
+        if (!(hi & 1) && hi + 1 < n) cur.push_back(m_get(proof + 32 * at++));
+        std::vector<cv_t> nxt;
+        for (size_t i = 0; i + 1 < cur.size(); i += 2) nxt.push_back(m_parent(cur[i], cur[i + 1], n == 2));
+        if (cur.size() & 1) nxt.push_back(cur.back());
+        cur.swap(nxt);
+    }
+    *used = at;
+    return cur[0];
+}
+
+static void test_ranges() {
+    const uint32_t k = 17;
+    const uint64_t B = 1ull << k;
+    batch_t b;  // nb = 1 (empty), 2, 3, 5, 9 with a 1-byte trailing block
+    b.build(k, {0, B + 1, 2 * B + 4097, 4 * B + 77, 8 * B + 1}, 71);
+    const answer_t want = model(b);
+    // every range of every file, each row with bytes of its own
+    list_t l;
+    std::vector<uint64_t> rb(1, 0);
+    std::vector<std::array<uint64_t, 3>> rg;
+    for (size_t f = 0; f < b.n(); f++) {
+        const uint64_t nb = b.base[f + 1] - b.base[f];
+        for (uint64_t a = 0; a < nb; a++)
+            for (uint64_t e = a + 1; e <= nb; e++) {
+                for (uint64_t j = a; j < e; j++) l.add(b, f, j);
+                rb.push_back(l.m());
+                rg.push_back({f, a, e});
+            }
+    }
+    const size_t m = l.m(), q = rg.size();
+    std::vector<uint64_t> pb(q + 1, 0);
+    for (size_t i = 0; i < q; i++) {
+        uint32_t e = 99;
+        CHECK(sd_checksum_tree_range_proof_entries(b.lens[rg[i][0]], k, rg[i][1], rg[i][2] - rg[i][1], &e) == SD_OK);
+        uint32_t h = 0;
+        for (uint64_t n = b.base[rg[i][0] + 1] - b.base[rg[i][0]]; n > 1; n = (n + 1) / 2) h++;
+        CHECK(e <= 2 * h);
+        pb[i + 1] = pb[i] + e;
+    }
+    bytes proofs(32 * pb[q] + 32, 0xA5);  // one guard row
+    CHECK(sd_cpu_checksum_tree_blocks_prove_ranges(want.nodes.data(), b.lens.data(), b.n(), k, l.rows.data(), m, rb.data(), q,
+                                                   proofs.data()) == SD_OK);
+    CHECK(std::all_of(proofs.end() - 32, proofs.end(), [](uint8_t x) { return x == 0xA5; }));
+    for (size_t i = 0; i < q; i++) {  // every proof climbs to the model's root, using exactly its entries
+        const uint64_t f = rg[i][0], a = rg[i][1], e = rg[i][2];
+        std::vector<cv_t> cur;
+        for (uint64_t j = a; j < e; j++) cur.push_back(m_get(want.nodes.data() + 32 * (b.base[f] + j)));
+        size_t used = 0;
+        CHECK(m_range_climb(cur, proofs.data() + 32 * pb[i], b.base[f + 1] - b.base[f], a, e, &used) == m_get(want.roots.data() + 32 * f));
+        CHECK(used == pb[i + 1] - pb[i]);
+        if (e == a + 1) {  // one block: byte for byte the block proof
+            const uint64_t row[2] = {f, a};
+            bytes one(32 * used + 32, 0xA5);
+            CHECK(sd_cpu_checksum_tree_blocks_prove(want.nodes.data(), b.lens.data(), b.n(), k, row, 1, one.data()) == SD_OK);
+            CHECK(memcmp(one.data(), proofs.data() + 32 * pb[i], 32 * used) == 0);
+        }
+        if (a == 0 && e == b.base[f + 1] - b.base[f]) CHECK(used == 0);  // the whole file: empty
+    }
+    // verify: clean, then a flipped entry, a flipped byte of the trailing block, the capacity rule
+    bytes nodes(32 * m + 32, 0xA5), bad(q + 1, 0xA5);
+    std::vector<uint64_t> out(3 * q + 3, 0xA5A5);
+    uint64_t count = 9, stats[4];
+    auto ver = [&](const bytes& d, const bytes& p, uint64_t cap, int nt) {
+        return sd_cpu_checksum_tree_blocks_verify_range_proofs(d.data(), b.lens.data(), b.n(), k, l.rows.data(), l.offs.data(), m,
+                                                               rb.data(), q, p.data(), want.roots.data(), nodes.data(), bad.data(),
+                                                               out.data(), cap, &count, stats, nt);
+    };
+    CHECK(ver(l.data, proofs, q, 3) == SD_OK && count == 0);
+    CHECK(stats[0] == b.n() && stats[1] == q && stats[2] == 0 && stats[3] == 0);
+    CHECK(std::all_of(bad.begin(), bad.begin() + q, [](uint8_t x) { return x == 0; }) && bad[q] == 0xA5);
+    CHECK(std::all_of(out.begin(), out.end(), [](uint64_t x) { return x == 0xA5A5; }));
+    for (size_t r = 0; r < m; r++)
+        CHECK(memcmp(nodes.data() + 32 * r, want.nodes.data() + 32 * (b.base[l.rows[2 * r]] + l.rows[2 * r + 1]), 32) == 0);
+    CHECK(std::all_of(nodes.end() - 32, nodes.end(), [](uint8_t x) { return x == 0xA5; }));
+    size_t ie = 0, ib = 0;  // [2, 5) of the nb = 9 file (entries at two levels); a range that ends with its last block
+    for (size_t i = 0; i < q; i++) {
+        if (rg[i][0] == 4 && rg[i][1] == 2 && rg[i][2] == 5) ie = i;
+        if (rg[i][0] == 4 && rg[i][1] == 6 && rg[i][2] == 9) ib = i;
+    }
+    CHECK(pb[ie + 1] - pb[ie] >= 2);
+    bytes fp = proofs;
+    fp[32 * (pb[ie] + 1) + 9] ^= 1;
+    list_t fl = l;
+    fl.data[fl.offs[rb[ib + 1] - 1]] ^= 0x80;  // the 1-byte trailing block
+    CHECK(ver(fl.data, fp, q, 2) == SD_OK && count == 2 && stats[2] == 2 && stats[3] == 1);
+    const size_t i0 = std::min(ie, ib), i1 = std::max(ie, ib);
+    for (size_t i = 0; i < q; i++) CHECK(bad[i] == (i == ie || i == ib));
+    CHECK(out[0] == 4 && out[1] == rg[i0][1] && out[2] == rg[i0][2] - rg[i0][1]);
+    CHECK(out[3] == 4 && out[4] == rg[i1][1] && out[5] == rg[i1][2] - rg[i1][1] && out[6] == 0xA5A5);
+    std::fill(out.begin(), out.end(), 0xA5A5);
+    CHECK(ver(fl.data, fp, 1, 1) == SD_ERR_CAPACITY && count == 2 && stats[2] == 2);
+    CHECK(std::all_of(out.begin(), out.end(), [](uint64_t x) { return x == 0xA5A5; }));
+    // refusals: a gap, an empty range, base[q] != m, two ranges merged (non-consecutive blocks, then two files)
+    auto refused = [&](std::vector<uint64_t> base) {
+        return sd_cpu_checksum_tree_blocks_verify_range_proofs(l.data.data(), b.lens.data(), b.n(), k, l.rows.data(), l.offs.data(),
+                                                               m, base.data(), base.size() - 1, proofs.data(), want.roots.data(),
+                                                               nullptr, nullptr, nullptr, 0, &count, nullptr, 1) == SD_ERR_INVALID &&
+               sd_cpu_checksum_tree_blocks_prove_ranges(want.nodes.data(), b.lens.data(), b.n(), k, l.rows.data(), m, base.data(),
+                                                        base.size() - 1, fp.data()) == SD_ERR_INVALID;
+    };
+    std::vector<uint64_t> w = rb;
+    w[0] = 1;
+    CHECK(refused(w));
+    w = rb, w.insert(w.begin() + 3, w[3]);
+    CHECK(refused(w));
+    w = rb, w.back() -= 1;
+    CHECK(refused(w));
+    w = rb, w.erase(w.begin() + ie + 1);
+    CHECK(refused(w));
+    w = rb, w.erase(w.begin() + 1);  // the empty file's block and block 0 of the next file
+    CHECK(refused(w));
+    CHECK(refused({0}));
+    uint32_t e = 7;
+    CHECK(sd_checksum_tree_range_proof_entries(8 * B, k, 0, 0, &e) == SD_ERR_INVALID);
+    CHECK(sd_checksum_tree_range_proof_entries(8 * B, k, 7, 2, &e) == SD_ERR_INVALID);
+    CHECK(sd_checksum_tree_range_proof_entries(8 * B, 16, 0, 1, &e) == SD_ERR_INVALID);
+    CHECK(sd_checksum_tree_range_proof_entries(8 * B, k, 0, 1, nullptr) == SD_ERR_INVALID && e == 7);
+    // an empty list
+    count = 9;
+    const uint64_t zero = 0;
+    CHECK(sd_cpu_checksum_tree_blocks_prove_ranges(nullptr, b.lens.data(), b.n(), k, nullptr, 0, &zero, 0, nullptr) == SD_OK);
+    CHECK(sd_cpu_checksum_tree_blocks_verify_range_proofs(nullptr, b.lens.data(), b.n(), k, nullptr, nullptr, 0, nullptr, 0, nullptr,
+                                                          nullptr, nullptr, nullptr, nullptr, 0, &count, stats, 1) == SD_OK);
+    CHECK(count == 0 && stats[1] == 0);
+}
+
+// ranges across the groups of 256 (the device's plan, run group by group on the host): a level of
+// random nodes of nb = 513 and 65 537, proofs against the model's climb; and [254, 258) of the first
+// verified from real bytes, its nodes spliced into the level
+static void test_ranges_across_groups() {
+    const uint32_t k = 17;
+    const uint64_t B = 1ull << k;
+    const std::vector<uint64_t> nbs = {513, 65537};
+    std::vector<uint64_t> lens, base(1, 0);
+    for (uint64_t nb : nbs) lens.push_back(nb << k), base.push_back(base.back() + nb);
+    bytes level(32 * base.back());
+    for (size_t i = 0; i < level.size(); i += 8) {
+        const uint64_t v = mix(79, i);
+        memcpy(level.data() + i, &v, 8);
+    }
+    // the bytes of [254, 258) of file 0, and their nodes into the level
+    bytes data(4 * B + 64);
+    for (size_t i = 0; i < data.size(); i += 8) {
+        const uint64_t v = mix(80, i);
+        memcpy(data.data() + i, &v, std::min<size_t>(8, data.size() - i));
+    }
+    const uint64_t brow[8] = {0, 254, 0, 255, 0, 256, 0, 257}, boff[4] = {0, B, 2 * B, 3 * B};
+    CHECK(sd_cpu_checksum_tree_blocks(data.data(), lens.data(), 2, k, brow, boff, 4, level.data() + 32 * 254, 2) == SD_OK);
+    std::vector<std::array<uint64_t, 3>> rg = {{0, 254, 258}, {0, 255, 257}, {0, 0, 513}, {0, 1, 512}, {0, 256, 512}, {0, 512, 513},
+                                               {1, 65535, 65537}, {1, 1, 65536}, {1, 65536, 65537}, {1, 300, 301}};
+    std::vector<uint64_t> rows, rb(1, 0);
+    for (const auto& r : rg) {
+        for (uint64_t j = r[1]; j < r[2]; j++) rows.push_back(r[0]), rows.push_back(j);
+        rb.push_back(rows.size() / 2);
+    }
+    const size_t m = rows.size() / 2, q = rg.size();
+    std::vector<uint64_t> pb(q + 1, 0);
+    for (size_t i = 0; i < q; i++) {
+        uint32_t e = 0;
+        CHECK(sd_checksum_tree_range_proof_entries(lens[rg[i][0]], k, rg[i][1], rg[i][2] - rg[i][1], &e) == SD_OK);
+        pb[i + 1] = pb[i] + e;
+    }
+    bytes proofs(32 * pb[q] + 32, 0xA5);
+    CHECK(sd_cpu_checksum_tree_blocks_prove_ranges(level.data(), lens.data(), 2, k, rows.data(), m, rb.data(), q, proofs.data()) == SD_OK);
+    CHECK(std::all_of(proofs.end() - 32, proofs.end(), [](uint8_t x) { return x == 0xA5; }));
+    cv_t root[2];
+    for (size_t f = 0; f < 2; f++) {
+        std::vector<cv_t> lvl;
+        for (uint64_t i = base[f]; i < base[f + 1]; i++) lvl.push_back(m_get(level.data() + 32 * i));
+        root[f] = m_merge(lvl, true);
+    }
+    for (size_t i = 0; i < q; i++) {
+        const uint64_t f = rg[i][0];
+        std::vector<cv_t> cur;
+        for (uint64_t j = rg[i][1]; j < rg[i][2]; j++) cur.push_back(m_get(level.data() + 32 * (base[f] + j)));
+        size_t used = 0;
+        CHECK(m_range_climb(cur, proofs.data() + 32 * pb[i], nbs[f], rg[i][1], rg[i][2], &used) == root[f]);
+        CHECK(used == pb[i + 1] - pb[i]);
+    }
+    // the first two ranges as a list of their own over the real bytes: two groups of one pass, two passes
+    bytes roots(64);
+    m_put(root[0], roots.data()), m_put(root[1], roots.data() + 32);
+    const uint64_t vrow[12] = {0, 254, 0, 255, 0, 256, 0, 257, 0, 255, 0, 256}, voff[6] = {0, B, 2 * B, 3 * B, B, 2 * B};
+    const uint64_t vrb[3] = {0, 4, 6};
+    uint64_t count = 9, stats[4];
+    uint8_t bad[2];
+    CHECK(sd_cpu_checksum_tree_blocks_verify_range_proofs(data.data(), lens.data(), 2, k, vrow, voff, 6, vrb, 2, proofs.data(),
+                                                          roots.data(), nullptr, bad, nullptr, 0, &count, stats, 2) == SD_OK);
+    CHECK(count == 0 && stats[1] == 2 && !bad[0] && !bad[1]);
+    data[3 * B + 5] ^= 4;  // block 257: only [254, 258)
+    CHECK(sd_cpu_checksum_tree_blocks_verify_range_proofs(data.data(), lens.data(), 2, k, vrow, voff, 6, vrb, 2, proofs.data(),
+                                                          roots.data(), nullptr, bad, nullptr, 0, &count, stats, 2) == SD_OK);
+    CHECK(count == 1 && bad[0] == 1 && bad[1] == 0);
+}
+
+static void test_ranges_concurrent_calls() {
+    const uint32_t k = 17;
+    const uint64_t B = 1ull << k;
+    batch_t b;
+    b.build(k, {4 * B + 77, 8 * B + 1}, 73);
+    const answer_t want = model(b);
+    list_t l;
+    std::vector<uint64_t> rb(1, 0);
+    const std::vector<std::array<uint64_t, 3>> rg = {{0, 1, 4}, {1, 0, 9}, {1, 3, 8}, {0, 4, 5}};
+    for (const auto& r : rg) {
+        for (uint64_t j = r[1]; j < r[2]; j++) l.add(b, r[0], j);
+        rb.push_back(l.m());
+    }
+    const size_t m = l.m(), q = rb.size() - 1;
+    bytes proofs(32 * 2 * 4 * q);
+    CHECK(sd_cpu_checksum_tree_blocks_prove_ranges(want.nodes.data(), b.lens.data(), b.n(), k, l.rows.data(), m, rb.data(), q,
+                                                   proofs.data()) == SD_OK);
+    std::vector<std::thread> ts;
+    std::vector<int> ok(4, 0);
+    for (int t = 0; t < 4; t++)
+        ts.emplace_back([&, t] {
+            bytes mine(proofs.size());
+            uint64_t count = 9;
+            int good = sd_cpu_checksum_tree_blocks_prove_ranges(want.nodes.data(), b.lens.data(), b.n(), k, l.rows.data(), m, rb.data(),
+                                                                q, mine.data()) == SD_OK;
+            good &= mine == proofs;
+            good &= sd_cpu_checksum_tree_blocks_verify_range_proofs(l.data.data(), b.lens.data(), b.n(), k, l.rows.data(), l.offs.data(),
+                                                                    m, rb.data(), q, mine.data(), want.roots.data(), nullptr, nullptr,
+                                                                    nullptr, 0, &count, nullptr, 1 + t) == SD_OK;
+            ok[t] = good && count == 0;
+        });
+    for (auto& t : ts) t.join();
+    CHECK(ok == std::vector<int>(4, 1));
+}
+
 int main() {
+    test_ranges();
+    test_ranges_across_groups();
+    test_ranges_concurrent_calls();
     test_proofs();
     test_proofs_levels_and_refusals();
     test_proofs_concurrent_calls();

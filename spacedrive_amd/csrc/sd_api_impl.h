@@ -190,6 +190,19 @@ struct sd_checksum_tree_blocks {
     const ck_proof_row* d_prow() const { return ptab.at<ck_proof_row>(o_prow); }
     const uint64_t* d_lvl_off() const { return ptab.at<uint64_t>(o_lvl); }
     const ck_levels_wg* d_lpass(size_t k) const { return ltab.at<ck_levels_wg>(o_lpass[k]); }
+    // the ranges (_set_ranges, GPU-free): their rows and climb passes go up with the first range
+    // call after it (gtab), with the scratch of the groups' tops between the passes (tops);
+    // _prove_ranges' level offsets and passes (gltab) and the interior levels they fill (rlevels)
+    TreeRangePlan ranges;
+    bool ranges_up = false;
+    sdi::Tables gtab, gltab;
+    size_t o_rrow = 0, o_rlvl = 0;
+    std::vector<size_t> o_gpass, o_rlpass;
+    sdi::DevBuf tops, rlevels;
+    const ck_range_row* d_rrow() const { return gtab.at<ck_range_row>(o_rrow); }
+    const ck_range_wg* d_gpass(size_t k) const { return gtab.at<ck_range_wg>(o_gpass[k]); }
+    const uint64_t* d_rlvl_off() const { return gltab.at<uint64_t>(o_rlvl); }
+    const ck_levels_wg* d_rlpass(size_t k) const { return gltab.at<ck_levels_wg>(o_rlpass[k]); }
     size_t m() const { return plan.items.size(); }
     uint64_t total() const { return plan.node_base.back(); }
     const ck_block_item* d_items() const { return tab.at<ck_block_item>(o_items); }

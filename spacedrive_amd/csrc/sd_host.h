@@ -304,6 +304,61 @@ struct TreeProofPlan {
 void plan_tree_proofs(TreeProofPlan& p, const std::vector<uint64_t>& node_base, const uint64_t* rows, size_t m,
                       bool levels);
 
+// Range proofs (include/sd_cas.h, range proofs): blocks [a, a + cnt) of a file of nb nodes, cnt >= 1,
+// a + cnt <= nb.  At level L the range's nodes are lo = a >> L .. hi = (a + cnt - 1) >> L; the left
+// flank exists iff lo is odd, the right one iff hi is even and hi + 1 < n_L.
+inline uint32_t tree_range_proof_entries(uint64_t nb, uint64_t a, uint64_t cnt) {
+    uint32_t p = 0;
+    uint64_t lo = a, hi = a + cnt - 1;
+    for (uint64_t n = nb; n > 1; n = (n + 1) >> 1, lo >>= 1, hi >>= 1) p += (uint32_t)(lo & 1) + (!(hi & 1) && hi + 1 < n);
+    return p;
+}
+// one range of a list for k_tree_range_gather and range_differs (checksum_tree.hip): 48 bytes
+struct ck_range_row {
+    uint64_t node0;    // node_base[f]: the file's first slot of the level layout
+    uint64_t nb;       // the file's nodes
+    uint64_t first;    // a: the range's first block
+    uint64_t count;    // its blocks
+    uint64_t pbase;    // proof_base[i]: the range's first entry among the packed proofs
+    uint32_t lvl_tab;  // index into lvl_off of the file's level 1 (prove; 0 when the file has none)
+    uint32_t file;
+};
+static_assert(sizeof(ck_range_row) == 48, "three 16-byte loads per range");
+// one workgroup of a climb pass (k_tree_range_climb): the nodes of one range that fall into one
+// 256-aligned group of the file's level 8p, climbed through `levels` levels with the range's flanks
+constexpr uint8_t CK_RANGE_FIRST = 1, CK_RANGE_LAST = 2, CK_RANGE_FINAL = 4;
+struct ck_range_wg {
+    uint64_t src_base;  // the group's first present node in the source (pass 0: the rows' nodes; else the scratch)
+    uint64_t dst;       // where its top goes: a scratch slot, or the range (FINAL: top[dst])
+    uint64_t pbase;     // the range's first entry of this pass among the packed proofs
+    uint16_t count;     // present nodes (1..256), at slots start .. start + count - 1
+    uint8_t start;      // (index of the first present node at level 8p) & 255
+    uint8_t levels;     // levels to climb (0..8; 0: a file of one node, the node is the top)
+    uint8_t lmask;      // bit l: the range has a left entry at level 8p + l
+    uint8_t rmask;      // bit l: the range has a right entry at level 8p + l
+    uint8_t flags;      // CK_RANGE_FIRST / _LAST: the range's first / last group; _FINAL: the pass reaches level h
+    uint8_t pad;
+};
+static_assert(sizeof(ck_range_wg) == 32, "two 16-byte loads per workgroup");
+// A list's ranges checked and planned from node_base, the rows and range_base[0 .. q].  Throws
+// SD_ERR_INVALID (p untouched) unless range_base ascends strictly from 0 to m and every range's
+// rows are consecutive blocks of one file.  `levels` is plan_tree_proofs over the ranges' first
+// rows: the scratch layout (and, once asked for, the passes) of the interior levels of the files
+// with a range, which k_tree_levels fills for the gather.
+struct TreeRangePlan {
+    bool set = false;
+    std::vector<uint64_t> range_base;  // q + 1
+    std::vector<uint64_t> proof_base;  // q + 1
+    std::vector<ck_range_row> rrow;
+    std::vector<uint64_t> firsts;                  // q x (file, first block): the rows `levels` is planned over
+    std::vector<std::vector<ck_range_wg>> passes;  // ceil(h_max / 8), at least one when q > 0
+    uint64_t scratch_nodes = 0;                    // the groups' tops between the passes
+    TreeProofPlan levels;
+    size_t q() const { return rrow.size(); }
+};
+void plan_tree_ranges(TreeRangePlan& p, const std::vector<uint64_t>& node_base, const uint64_t* rows, size_t m,
+                      const uint64_t* range_base, size_t q);
+
 // ------------------------------------------------------------------ fingerprints
 // k_cas_gather (gather.hip) builds each file's cas message from its resident bytes.  Its
 // output is cut into 16-byte units; the units of all files, in file order, form one flat

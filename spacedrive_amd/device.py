@@ -1033,6 +1033,7 @@ class ChecksumTreeBlocks:
         self.node_base = tree_node_base(self.lens, self.block_log2)
         self.total_nodes = int(self.node_base[self.n])
         self._proof_base = None
+        self.q, self.range_base, self.range_proof_base = 0, np.zeros(1, np.uint64), np.zeros(1, np.uint64)
 
     def run(self, d_data: torch.Tensor, d_nodes_out: torch.Tensor, stream=None) -> None:
         """row r's node -> d_nodes_out[32 r], list order"""
@@ -1138,6 +1139,68 @@ class ChecksumTreeBlocks:
             assert d_rows_out.dtype == torch.int64 and d_rows_out.is_cuda and d_rows_out.is_contiguous()
             call(d_rows_out, d_rows_out.numel() // 2 if capacity is None else int(capacity))
             rows = d_rows_out.reshape(-1)[:2 * int(count.value)].reshape(-1, 2)
+        return (rows, stats) if d_bad is None else (rows, stats, d_bad)
+
+    def set_ranges(self, range_base) -> None:
+        """sd_checksum_tree_blocks_set_ranges: range i is rows range_base[i] .. range_base[i + 1] of
+        the list, consecutive blocks of one file; range_base uint64 [q + 1] ascends strictly from 0
+        to m.  A refused call leaves the ranges as they were; calling again replaces them."""
+        rb = np.ascontiguousarray(range_base, dtype=np.uint64).reshape(-1)
+        q = max(len(rb) - 1, 0)
+        check(lib().sd_checksum_tree_blocks_set_ranges(self.handle, _ptr(rb) if len(rb) else None, q))
+        self.range_base, self.q = rb, q
+        base = np.zeros(q + 1, np.uint64)
+        check(lib().sd_checksum_tree_blocks_range_proof_layout(self.handle, _ptr(base)))
+        self.range_proof_base = base
+
+    def prove_ranges(self, d_nodes: torch.Tensor, d_proofs_out: torch.Tensor, stream=None) -> None:
+        """every range's proof (its left and right flanks, bottom-up), in range order, from the
+        whole level buffer d_nodes -> d_proofs_out (range_proof_base[q] x 32 bytes)"""
+        assert d_nodes.numel() >= 32 * self.total_nodes
+        assert d_proofs_out.numel() >= 32 * int(self.range_proof_base[self.q])
+        check(lib().sd_checksum_tree_blocks_prove_ranges(self.ctx.handle, self.handle, _ptr(d_nodes),
+                                                         _ptr(d_proofs_out), _stream(stream)))
+
+    def verify_range_proofs(self, d_data: torch.Tensor, d_proofs: torch.Tensor, d_roots: torch.Tensor,
+                            d_nodes_out: Optional[torch.Tensor] = None, d_bad: Optional[torch.Tensor] = None,
+                            d_ranges_out: Optional[torch.Tensor] = None, capacity: Optional[int] = None,
+                            want_rows: bool = True, stream=None):
+        """sd_checksum_tree_blocks_verify_range_proofs: hashes the listed blocks, climbs each range
+        through its proof (d_proofs, laid out by range_proof_base) and compares the result with its
+        file's checksum in d_roots ([n, 32]).  d_nodes_out ([m, 32], optional) receives the rows'
+        nodes.  Returns (ranges int64 [count, 3] of (file, first block, blocks) in range order, stats
+        uint64 [4]: files, ranges compared, ranges that differ, files with one), and d_bad (uint8
+        [q]) as a third value when given.  A failing range does not say which of its blocks is wrong."""
+        assert d_roots.numel() >= 32 * self.n and d_proofs.numel() >= 32 * int(self.range_proof_base[self.q])
+        assert (d_bad is None or d_bad.numel() >= self.q) and (d_nodes_out is None or d_nodes_out.numel() >= 32 * self.m)
+        st = _stream(stream)
+        count = ctypes.c_uint64(0)
+        stats = np.zeros(4, np.uint64)
+
+        def call(rows, cap):
+            rc = lib().sd_checksum_tree_blocks_verify_range_proofs(self.ctx.handle, self.handle, _ptr(d_data),
+                                                                   _ptr(d_proofs), _ptr(d_roots), _ptr(d_nodes_out),
+                                                                   _ptr(d_bad), _ptr(rows), cap, ctypes.byref(count),
+                                                                   _ptr(stats), st)
+            try:
+                check(rc)
+            except SdCasError as e:
+                e.needed = int(count.value)
+                e.stats = stats
+                raise
+
+        dev = torch.device("cuda", self.ctx.device)
+        if not want_rows:
+            call(None, 0)
+            rows = torch.empty((0, 3), dtype=torch.int64, device=dev)
+        elif d_ranges_out is None:
+            rows = torch.empty((max(self.q, 1), 3), dtype=torch.int64, device=dev)
+            call(rows, self.q)
+            rows = rows[:int(count.value)]
+        else:
+            assert d_ranges_out.dtype == torch.int64 and d_ranges_out.is_cuda and d_ranges_out.is_contiguous()
+            call(d_ranges_out, d_ranges_out.numel() // 3 if capacity is None else int(capacity))
+            rows = d_ranges_out.reshape(-1)[:3 * int(count.value)].reshape(-1, 3)
         return (rows, stats) if d_bad is None else (rows, stats, d_bad)
 
     def close(self) -> None:

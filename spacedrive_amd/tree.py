@@ -14,6 +14,8 @@ lists the ones an append or a truncation costs.  On the device: ``Context.checks
 prove_blocks and verify_proofs_file are the pair for a receiver that keeps no level, only the
 checksum and the length of the library's database: the sender packs each block's siblings on its
 way up the tree, the receiver climbs them back to the checksum (include/sd_cas.h, block proofs).
+prove_range and verify_range_file do the same for a contiguous run of blocks, a resumed or partial
+transfer: only the run's two flanks travel (include/sd_cas.h, range proofs).
 """
 from __future__ import annotations
 
@@ -149,6 +151,42 @@ def verify_proofs_file(path: Union[str, os.PathLike], length: int, checksum, blo
     bad, _ = cpu.checksum_tree_blocks_verify_proofs(buf, [length], rows, offs, np.frombuffer(bytes(proofs), np.uint8),
                                                     np.frombuffer(root, np.uint8), block_log2, nthreads=nthreads)
     return [int(b) for b in bad[:, 1]]
+
+
+def _range_rows(length: int, first: int, count: int, block_log2: int) -> List[int]:
+    nb = cpu.tree_nodes(length, block_log2)
+    first, count = int(first), int(count)
+    if first < 0 or count < 1 or first + count > nb:
+        raise ValueError(f"a file of {length} bytes has blocks 0 .. {nb - 1}")
+    return list(range(first, first + count))
+
+
+def prove_range(nodes, length: int, first: int, count: int, block_log2: int = 17) -> bytes:
+    """The proof of blocks [first, first + count) of a file of `length` bytes, from its level `nodes`
+    (uint8 [nb, 32]): what a sender answers a partial request (spaceblock's Range::Partial) with
+    beside the bytes.  Only the run's two flanks travel, cpu.tree_range_proof_entries(length, first,
+    count, block_log2) entries of 32 bytes -- at most two per level, however long the run."""
+    blocks = _range_rows(length, first, count, block_log2)
+    rows = np.array([[0, j] for j in blocks], np.uint64).reshape(-1, 2)
+    proofs, _ = cpu.checksum_tree_blocks_prove_ranges(nodes, [length], rows, [0, len(blocks)], block_log2)
+    return proofs.tobytes()
+
+
+def verify_range_file(path: Union[str, os.PathLike], length: int, checksum, first: int, count: int, proof,
+                      block_log2: int = 17, nthreads: int = cpu.THREADS) -> bool:
+    """Whether blocks [first, first + count) of `path`, climbed through `proof` (prove_range's
+    bytes), reach `checksum` (64 hex digits or 32 bytes) for a file of `length` bytes.  The checksum
+    and the length are all the receiver trusts; only the range is read.  False says a byte of these
+    blocks or an entry of the proof is wrong, not which block: verify_proofs_file names blocks."""
+    root = bytes.fromhex(checksum) if isinstance(checksum, str) else bytes(checksum)
+    if len(root) != 32:
+        raise ValueError("a checksum is 32 bytes")
+    blocks = _range_rows(length, first, count, block_log2)
+    buf, rows, offs = _read_blocks(path, length, blocks, block_log2)
+    bad, _ = cpu.checksum_tree_blocks_verify_range_proofs(buf, [length], rows, offs, [0, len(blocks)],
+                                                          np.frombuffer(bytes(proof), np.uint8),
+                                                          np.frombuffer(root, np.uint8), block_log2, nthreads=nthreads)
+    return len(bad) == 0
 
 
 def blocks_to_rehash(len_old: int, len_new: int, block_log2: int) -> List[int]:
