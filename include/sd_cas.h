@@ -1209,6 +1209,59 @@ int sd_cpu_checksum_tree_blocks_verify_range_proofs(const uint8_t* data, const u
                                                     uint8_t* nodes_out, uint8_t* bad, uint64_t* ranges_out,
                                                     uint64_t capacity, uint64_t* count, uint64_t stats[4], int nthreads);
 
+/* Shared blocks: WHICH blocks of a batch of levels are there more than once -- what sd_dedup_confirm
+ * leaves open about a file it marks SD_CONFIRM_REFUTED (one block rewritten, or all of them?), and
+ * about content that partly repeats: an interrupted copy, a log and its shorter version, an image
+ * written in place.  By the position rule above a full block's node depends on its bytes and its
+ * index only, so two files hold the same bytes in block j exactly when their level nodes at j are
+ * equal.  No file byte is read and nothing is hashed: the nodes are opaque 32-byte values.
+ *   input     the level layout of sd_checksum_tree_run, _roots and _blocks_update: lens[n] (host),
+ *             nb_f = sd_checksum_tree_nodes(lens[f], block_log2), node_base = the exclusive prefix
+ *             sum of nb, m = node_base[n]; d_nodes holds m x 32 B, 16-byte aligned; slot s =
+ *             node_base[f] + j is block j of file f
+ *   class(s)  the slots t = (g, j') with j' == j and all 32 bytes equal.  Equal nodes at different
+ *             block indices are different classes (a node carries its chunk counter, so equal bytes
+ *             at different positions do not give equal nodes anyway).  A one-node file's N_0 is a
+ *             root hash and a trailing partial block's node covers fewer chunks: the byte comparison
+ *             keeps those apart, they need no rule of their own.  Content that is SHIFTED, by an
+ *             insertion or at another offset, is therefore not found: that takes content-defined
+ *             chunking, which this is not.  Aligned blocks only
+ *   d_rep[s]         the smallest slot of class(s); it lies in the lowest-numbered file that holds
+ *                    the block (a file has one slot per j)
+ *   d_class_size[s]  |class(s)|
+ *   shared    d_class_size[s] >= 2;  redundant  d_rep[s] != s: an earlier file has the block
+ *   bytes(s)  min(B, lens[f] - j B); an empty file's one slot has 0 bytes
+ *   d_files_out  4 x u64 per file: [0] nb_f, [1] shared blocks, [2] redundant blocks, [3] redundant bytes
+ *   d_pairs_out  4 x u64 per row (f, g, blocks, bytes): one row per pair g < f such that at least
+ *             max(1, min_blocks) redundant slots of f have their representative in g, blocks and
+ *             bytes summed over those slots; rows ascend by (f, g).  This is the star towards the
+ *             FIRST holder of each block, not all pairs: at most m - 1 rows, however many files
+ *             share the all-zero block.  *n_pairs (host, may be NULL) = the rows.  If d_pairs_out is
+ *             given and capacity < *n_pairs: SD_ERR_CAPACITY with *n_pairs = the requirement and no
+ *             row written; every other output is complete then too.  With d_pairs_out NULL the call
+ *             only counts.  Nothing past the first *n_pairs rows is ever written
+ *   stats[8]  (host, may be NULL) [0] files, [1] blocks (m), [2] classes, [3] classes of size >= 2,
+ *             [4] redundant blocks, [5] redundant bytes, [6] files with a redundant block, [7] files
+ *             EVERY block of which is redundant.  They do not depend on min_blocks or capacity.
+ *             [4] == [1] - [2] == the sum of files[.][2]; [5] == the sum of files[.][3]; with
+ *             min_blocks <= 1 the rows' blocks add up to [4] and their bytes to [5]; file 0 is
+ *             never in [6]
+ * Any output pointer may be NULL.  n == 0 is valid: counts are 0, nothing is written.  A block_log2
+ * outside 17..20, a NULL lens or d_nodes with m > 0, or n >= 2^32 is SD_ERR_INVALID.  Runs on
+ * `stream` and syncs it; scratch comes from the context's pooled slot (grow-only: 77 bytes per slot,
+ * 32 per file and 16 per file of tables, plus the radix sort's; no allocation in a call that fits
+ * what the slot holds).  The grouping is sd_dedup_confirm's with key = j and hash = node, both of
+ * its paths included ("confirm_full_sort" applies; sd_dedup_confirm_stats does not count these
+ * calls).  One device, not collective: sharding a library's levels over ranks is not provided. */
+int sd_checksum_tree_shared(sd_cas_ctx* ctx, const uint64_t* lens, size_t n, uint32_t block_log2,
+                            const uint8_t* d_nodes, uint64_t min_blocks, uint64_t* d_rep, uint64_t* d_class_size,
+                            uint64_t* d_files_out, uint64_t* d_pairs_out, uint64_t capacity, uint64_t* n_pairs,
+                            uint64_t stats[8], void* stream);
+/* The same over host arrays, without a context or a device. */
+int sd_cpu_checksum_tree_shared(const uint64_t* lens, size_t n, uint32_t block_log2, const uint8_t* nodes,
+                                uint64_t min_blocks, uint64_t* rep, uint64_t* class_size, uint64_t* files_out,
+                                uint64_t* pairs_out, uint64_t capacity, uint64_t* n_pairs, uint64_t stats[8]);
+
 /* ---------------------------------------------------------------- synthetic data */
 /* Device generator of SURVEY.md §8(d) (seed 0x5D5DCA51D, splitmix64 counter stream),
  * for benchmarks and parity tests: writes the exact cas message of each synthetic file

@@ -349,6 +349,15 @@ extern "C" {
                                                            roots: *const u8, nodes_out: *mut u8, bad: *mut u8,
                                                            ranges_out: *mut u64, capacity: u64, count: *mut u64,
                                                            stats: *mut u64, nthreads: c_int) -> c_int;
+    // shared blocks: which blocks of a batch of levels are there more than once (aligned blocks only)
+    pub fn sd_checksum_tree_shared(ctx: *mut sd_cas_ctx, lens: *const u64, n: usize, block_log2: u32,
+                                   d_nodes: *const u8, min_blocks: u64, d_rep: *mut u64, d_class_size: *mut u64,
+                                   d_files_out: *mut u64, d_pairs_out: *mut u64, capacity: u64, n_pairs: *mut u64,
+                                   stats: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_cpu_checksum_tree_shared(lens: *const u64, n: usize, block_log2: u32, nodes: *const u8,
+                                       min_blocks: u64, rep: *mut u64, class_size: *mut u64, files_out: *mut u64,
+                                       pairs_out: *mut u64, capacity: u64, n_pairs: *mut u64,
+                                       stats: *mut u64) -> c_int;
     // device buffers for callers that hold their lists on the host (sd_memcpy syncs `stream`)
     pub fn sd_device_malloc(ctx: *mut sd_cas_ctx, bytes: u64, out: *mut *mut c_void) -> c_int;
     pub fn sd_device_free(ctx: *mut sd_cas_ctx, p: *mut c_void);

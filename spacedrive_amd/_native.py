@@ -223,6 +223,8 @@ SIGNATURES = [
     ("sd_cpu_checksum_tree_blocks_prove_ranges", I32, [P, P, SZ, U32, P, SZ, P, SZ, P]),
     ("sd_cpu_checksum_tree_blocks_verify_range_proofs", I32,
      [P, P, SZ, U32, P, P, SZ, P, SZ, P, P, P, P, P, U64, PU64, P, I32]),
+    ("sd_checksum_tree_shared", I32, [P, P, SZ, U32, P, U64, P, P, P, P, U64, PU64, P, P]),
+    ("sd_cpu_checksum_tree_shared", I32, [P, SZ, U32, P, U64, P, P, P, P, U64, PU64, P]),
 ]
 SD_TREE_BLOCK_LOG2_MIN, SD_TREE_BLOCK_LOG2_MAX = 17, 20
 SD_CONFIRM_INVALID, SD_CONFIRM_SINGLE, SD_CONFIRM_CONFIRMED, SD_CONFIRM_REFUTED = 0, 1, 2, 3

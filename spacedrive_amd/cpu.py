@@ -486,6 +486,41 @@ def checksum_tree_blocks_verify_range_proofs(data, lens, rows, data_offsets, ran
     return out
 
 
+def checksum_tree_shared(lens, nodes, block_log2: int = 17, min_blocks: int = 0, capacity: Optional[int] = None,
+                         want_pairs: bool = True):
+    """sd_cpu_checksum_tree_shared: which blocks of a batch of levels (lens uint64 [n], nodes uint8
+    [node_base[n], 32] in the level layout) are there more than once.  Returns (rep uint64 [m],
+    class_size uint64 [m], files uint64 [n, 4], pairs uint64 [n_pairs, 4], stats uint64 [8]): a
+    file's row is (blocks, shared, redundant, redundant bytes), a pair's (f, g, blocks, bytes) with
+    g < f the first holder of those blocks.  `capacity` (default m, always enough) short of the
+    pairs raises SdCasError (SD_ERR_CAPACITY) with ``.needed``; want_pairs=False only counts."""
+    from ._native import SdCasError
+    ls = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+    n = len(ls)
+    m = int(tree_node_base(ls, block_log2)[n])
+    nd = np.ascontiguousarray(nodes, dtype=np.uint8).reshape(-1)
+    if nd.size != 32 * m:
+        raise ValueError("nodes is not node_base[n] x 32 bytes")
+    rep, size = np.zeros(max(m, 1), np.uint64), np.zeros(max(m, 1), np.uint64)
+    files = np.zeros((max(n, 1), 4), np.uint64)
+    cap = m if capacity is None else int(capacity)
+    pairs = np.zeros((max(cap, 1), 4), np.uint64)
+    n_pairs = ctypes.c_uint64(0)
+    stats = np.zeros(8, np.uint64)
+    rc = lib().sd_cpu_checksum_tree_shared(ls.ctypes.data if n else None, n, int(block_log2),
+                                           nd.ctypes.data if m else None, int(min_blocks), rep.ctypes.data,
+                                           size.ctypes.data, files.ctypes.data,
+                                           pairs.ctypes.data if want_pairs else None, cap, ctypes.byref(n_pairs),
+                                           stats.ctypes.data)
+    try:
+        check(rc)
+    except SdCasError as e:
+        e.needed = int(n_pairs.value)
+        e.stats = stats
+        raise
+    return rep[:m], size[:m], files[:n], pairs[:int(n_pairs.value) if want_pairs else 0], stats
+
+
 def blake3(data: bytes) -> bytes:
     """Full 32-byte BLAKE3 of a host buffer (sd_cpu_checksums of one range)."""
     buf = np.frombuffer(bytes(data) + bytes(64), np.uint8)

@@ -167,6 +167,30 @@ class Context:
         check(lib().sd_dedup_confirm_stats(self.handle, _ptr(v)))
         return {"prefix": int(v[0]), "full": int(v[1])}
 
+    def checksum_tree_shared(self, lens, d_nodes, block_log2: int = 17, min_blocks: int = 0, d_rep=None,
+                             d_class_size=None, d_files_out=None, d_pairs_out=None, capacity: int = 0, stream=None):
+        """sd_checksum_tree_shared: which blocks of a batch of levels (lens: host uint64 [n]; d_nodes
+        uint8 [node_base[n], 32] on the device, the layout ChecksumTree.run leaves) are there more
+        than once.  Writes the outputs given (rep, class_size int64 [m]; files int64 [n, 4]; pairs
+        int64 [capacity, 4]) and returns (n_pairs, stats uint64 [8]); a short `capacity` raises
+        SdCasError (SD_ERR_CAPACITY, ``.needed`` rows, ``.stats``) with every other output complete
+        and no pair row written."""
+        ls = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+        n = len(ls)
+        n_pairs = ctypes.c_uint64(0)
+        stats = np.zeros(8, np.uint64)
+        rc = lib().sd_checksum_tree_shared(self.handle, _ptr(ls) if n else None, n, int(block_log2),
+                                           _ptr(d_nodes) if n else None, int(min_blocks), _ptr(d_rep),
+                                           _ptr(d_class_size), _ptr(d_files_out), _ptr(d_pairs_out), capacity,
+                                           ctypes.byref(n_pairs), _ptr(stats), _stream(stream))
+        try:
+            check(rc)
+        except SdCasError as e:
+            e.needed = int(n_pairs.value)
+            e.stats = stats
+            raise
+        return int(n_pairs.value), stats
+
     def dedup_mgpu(self, comm: "Comm", d_hash32, d_valid, n: int, base: int, d_records, d_rep, d_owner,
                    capacity: int, chunk_size: int = 100, stream=None):
         """sd_cas_dedup_mgpu: partition -> RCCL all-to-all -> group -> owners on this rank.

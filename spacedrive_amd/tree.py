@@ -16,6 +16,11 @@ checksum and the length of the library's database: the sender packs each block's
 way up the tree, the receiver climbs them back to the checksum (include/sd_cas.h, block proofs).
 prove_range and verify_range_file do the same for a contiguous run of blocks, a resumed or partial
 transfer: only the run's two flanks travel (include/sd_cas.h, range proofs).
+
+shared_blocks compares the levels of several files with each other, and compare_files does so for
+files on disk: which blocks a file repeats of an earlier one, block for block where they lie --
+what to ask about files the confirm step refuted (include/sd_cas.h, shared blocks).  On the device:
+``Context.checksum_tree_shared``.
 """
 from __future__ import annotations
 
@@ -187,6 +192,32 @@ def verify_range_file(path: Union[str, os.PathLike], length: int, checksum, firs
                                                           np.frombuffer(bytes(proof), np.uint8),
                                                           np.frombuffer(root, np.uint8), block_log2, nthreads=nthreads)
     return len(bad) == 0
+
+
+def shared_blocks(levels, block_log2: int = 17, min_blocks: int = 0):
+    """Which blocks of these files are there more than once (include/sd_cas.h, shared blocks).
+    `levels` is a list of (length, nodes) as file_checksum_tree returns them.  Returns (files, pairs,
+    stats): files uint64 [n, 4] = (blocks, shared, redundant, redundant bytes) per file; pairs uint64
+    [p, 4] = (f, g, blocks, bytes), one row per pair g < f of which g is the FIRST holder of at least
+    max(1, min_blocks) blocks of f, ascending by (f, g); stats uint64 [8].  Blocks are compared where
+    they lie: aligned blocks only, shifted content is not found.  No file is read."""
+    lens = [int(length) for length, _ in levels]
+    parts = [np.ascontiguousarray(nodes, dtype=np.uint8).reshape(-1, 32) for _, nodes in levels]
+    for length, part in zip(lens, parts):
+        if len(part) != cpu.tree_nodes(length, block_log2):
+            raise ValueError(f"a file of {length} bytes has {cpu.tree_nodes(length, block_log2)} nodes")
+    nodes = np.concatenate(parts) if parts else np.zeros((0, 32), np.uint8)
+    _, _, files, pairs, stats = cpu.checksum_tree_shared(lens, nodes, block_log2, min_blocks)
+    return files, pairs, stats
+
+
+def compare_files(paths, block_log2: int = 17, nthreads: int = cpu.THREADS):
+    """shared_blocks of the files at `paths`, each read and hashed once (file_checksum_tree): what to
+    ask about files the confirm step refuted -- do they differ in one block or in all of them?
+    Returns (checksums, files, pairs, stats), the checksums as 64 hex digits per path."""
+    trees = [file_checksum_tree(p, block_log2, nthreads) for p in paths]
+    files, pairs, stats = shared_blocks([(length, nodes) for _, length, nodes in trees], block_log2)
+    return [hexsum for hexsum, _, _ in trees], files, pairs, stats
 
 
 def blocks_to_rehash(len_old: int, len_new: int, block_log2: int) -> List[int]:
