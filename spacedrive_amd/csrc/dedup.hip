@@ -89,36 +89,59 @@ __global__ __launch_bounds__(256) void k_part_count(const uint8_t* __restrict__ 
     if (threadIdx.x < (unsigned)nparts) hist[threadIdx.x * PART_BLOCKS + blockIdx.x] = local[threadIdx.x];
 }
 
-// exclusive scan of hist[nparts * PART_BLOCKS] (destination-major) -> offs; counts[d]
-__global__ __launch_bounds__(1024) void k_part_scan(const uint32_t* __restrict__ hist, int nparts,
-                                                    uint64_t* __restrict__ offs,
-                                                    unsigned long long* __restrict__ counts,
-                                                    unsigned long long* __restrict__ total) {
-    __shared__ uint64_t wsum[16];
-    __shared__ uint64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+// exclusive scan of hist[nparts * PART_BLOCKS] (destination-major) -> offs; counts[d].
+// One workgroup of PART_SCAN_LANES, each lane owning PART_BLOCKS / PART_SCAN_LANES adjacent
+// blocks of a destination: one wave per SIMD, so the workgroup starts wherever a CU has one
+// free wave slot per SIMD (a 1024-lane workgroup needs four, which beside the hash kernels
+// only a kernel's drain tail offers).  With `row` it also completes the exchange row behind
+// the counts -- index base, file count, capacity, valid records (~0: row.bad_index) -- so no
+// copy has to follow it on the stream.
+constexpr uint32_t PART_SCAN_LANES = 256;
+constexpr uint32_t PART_SCAN_PER = PART_BLOCKS / PART_SCAN_LANES;
+static_assert(PART_SCAN_PER == 4, "k_part_scan loads a lane's blocks as one uint4");
+
+__global__ __launch_bounds__(PART_SCAN_LANES) void k_part_scan(const uint32_t* __restrict__ hist, int nparts,
+                                                               uint64_t* __restrict__ offs,
+                                                               unsigned long long* __restrict__ counts,
+                                                               unsigned long long* __restrict__ total,
+                                                               bool with_row, sdk::part_row row) {
+    constexpr uint32_t NW = PART_SCAN_LANES / 64;
+    __shared__ uint64_t wsum[2][NW];  // alternating per destination: one barrier each
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+    uint64_t carry = 0;  // records of the destinations before d (the same in every lane)
     for (int d = 0; d < nparts; d++) {
-        const uint64_t v = hist[d * PART_BLOCKS + threadIdx.x];
-        uint64_t x = v;  // inclusive wave scan
+        const uint4 v = reinterpret_cast<const uint4*>(hist + (size_t)d * PART_BLOCKS)[t];
+        const uint64_t mine = (uint64_t)v.x + v.y + v.z + v.w;
+        uint64_t x = mine;  // inclusive wave scan
         for (int o = 1; o < 64; o <<= 1) {
             const uint64_t y = __shfl_up(x, o);
             if (lane >= (uint32_t)o) x += y;
         }
-        if (lane == 63) wsum[w] = x;
+        if (lane == 63) wsum[d & 1][w] = x;
         __syncthreads();
-        uint64_t before = carry;
-        for (uint32_t k = 0; k < w; k++) before += wsum[k];
-        offs[d * PART_BLOCKS + threadIdx.x] = before + x - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) {
-            counts[d] = before + x - carry;
-            carry = before + x;
+        uint64_t before = carry, all = 0;
+        for (uint32_t k = 0; k < NW; k++) {
+            if (k < w) before += wsum[d & 1][k];
+            all += wsum[d & 1][k];
         }
-        __syncthreads();
+        uint64_t* o4 = offs + (size_t)d * PART_BLOCKS + PART_SCAN_PER * t;
+        uint64_t at = before + x - mine;
+        o4[0] = at;
+        o4[1] = at += v.x;
+        o4[2] = at += v.y;
+        o4[3] = at += v.z;
+        if (t == 0) counts[d] = all;
+        carry += all;
     }
-    if (threadIdx.x == 0) *total = carry;
+    if (t == 0) {
+        *total = carry;
+        if (with_row) {
+            counts[nparts] = row.base;
+            counts[nparts + 1] = row.n;
+            counts[nparts + 2] = row.capacity;
+            counts[nparts + 3] = row.bad_index ? ~0ull : carry;
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void k_part_scatter(const uint8_t* __restrict__ hash32,
@@ -572,14 +595,16 @@ __global__ __launch_bounds__(256) void k_owners(const uint64_t* __restrict__ rec
 namespace sdk {
 
 hipError_t dedup_partition(const uint8_t* hash32, const uint8_t* valid, uint64_t n, uint64_t base, int nparts,
-                           uint64_t* counts, uint64_t* records, uint64_t* scratch, hipStream_t s) {
+                           uint64_t* counts, uint64_t* records, uint64_t* scratch, hipStream_t s,
+                           const part_row* row) {
     // scratch: hist (u32 nparts x PART_BLOCKS), offs (u64 nparts x PART_BLOCKS), total (u64)
     uint32_t* hist = reinterpret_cast<uint32_t*>(scratch);
     uint64_t* offs = scratch + (size_t)nparts * PART_BLOCKS / 2 + 1;
     auto* total = reinterpret_cast<unsigned long long*>(offs + (size_t)nparts * PART_BLOCKS);
     hipLaunchKernelGGL(k_part_count, dim3(PART_BLOCKS), dim3(256), 0, s, hash32, valid, n, nparts, hist);
-    hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(1024), 0, s, hist, nparts, offs,
-                       reinterpret_cast<unsigned long long*>(counts), total);
+    hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(PART_SCAN_LANES), 0, s, hist, nparts, offs,
+                       reinterpret_cast<unsigned long long*>(counts), total, row != nullptr,
+                       row ? *row : part_row{});
     hipLaunchKernelGGL(k_part_scatter, dim3(PART_BLOCKS), dim3(256), 0, s, hash32, valid, n, base, nparts, offs,
                        records);
     return hipGetLastError();

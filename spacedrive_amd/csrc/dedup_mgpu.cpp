@@ -28,6 +28,11 @@
 // host barrier.  It serves one process driving several GPUs, and it rehearses N ranks on
 // one GPU, which RCCL refuses ("Duplicate GPU detected") -- the partition, the gathered
 // plan, the per-peer offsets and the grouping are the same code either way.
+//
+// One rank (one GPU in a workstation) exchanges with nobody, over either transport: step 2
+// is one copy of its row to the host and step 3 is empty -- the partition wrote the records
+// where step 4 reads them (or, with capacity < n, one device copy moves them there after the
+// checks).  The row, the plan, the checks and their order are those of any rank count.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -54,7 +59,7 @@ struct sd_comm {
     size_t send_bytes = 0;
     void* d_rows = nullptr;
     void* d_part_scratch = nullptr;  // sdk::dedup_partition's scratch; its last u64 = valid records
-    uint64_t* h_rows = nullptr;      // pinned: this rank's row extras, then all rows
+    uint64_t* h_rows = nullptr;      // pinned: one spare row, then all rows (the host table)
     // sd_comm_set_timing: events around the phases of the last sd_cas_dedup_mgpu call
     bool timing = false;
     bool timed = false;  // the last call recorded all of ev[]
@@ -288,37 +293,38 @@ int sd_cas_dedup_mgpu_indexed(sd_cas_ctx* ctx, sd_comm* comm, const uint8_t* d_h
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int R = comm->nranks, me = comm->rank;
     const size_t row = (size_t)R + ROW_EXTRA;
+    constexpr uint64_t BAD_INDEX = ~0ull;  // in place of the valid-record count (never that large)
+    const bool bad_index = index && (index->ctx != ctx || index->nparts != R || index->part != me);
+    // One rank exchanges with nobody: its partitioned records are its received records, in
+    // the same order (recv_off[0] == 0).  With room for all n files the partition writes them
+    // straight into d_records_out (at most n records exist, so none can overflow); a smaller
+    // capacity, or an index that will refuse the call, keeps them in d_send until the checks
+    // below have passed, so that a refused call moves no record into the caller's buffers.
+    const bool direct = R == 1 && capacity >= n && !bad_index;
     // 1. partition this rank's records by destination rank
-    if (comm->send_bytes < 16 * n || !comm->d_send) {
+    if (!direct && (comm->send_bytes < 16 * n || !comm->d_send)) {
         if (comm->d_send) HIP_OK(hipFree(comm->d_send));
         comm->d_send = nullptr;
         comm->send_bytes = 16 * (n ? n : 1);
         HIP_OK(hipMalloc(&comm->d_send, comm->send_bytes));
     }
-    // (the partition counts go straight into this rank's all-gather row; no host sync here)
+    // (the partition's scan completes this rank's row -- counts, index base, file count,
+    // capacity, valid records -- on the device; no copy and no host sync here)
     uint64_t* d_row = (uint64_t*)comm->d_rows;
     uint64_t* d_all = d_row + row;
-    const size_t psb = sdk::dedup_partition_scratch(R);
     uint64_t* pscratch = (uint64_t*)comm->d_part_scratch;
+    const sdk::part_row extra{global_index_base, n, capacity, bad_index ? 1u : 0u};
     comm->timed = false;
     mark(comm, 0, s);
-    HIP_OK(sdk::dedup_partition(d_hash32, d_valid, n, global_index_base, R, d_row, (uint64_t*)comm->d_send, pscratch,
-                                s));
+    HIP_OK(sdk::dedup_partition(d_hash32, d_valid, n, global_index_base, R, d_row,
+                                direct ? d_records_out : (uint64_t*)comm->d_send, pscratch, s, &extra));
     mark(comm, 1, s);
-    // 2. all-gather of (counts, index base, file count, capacity, valid records)
-    uint64_t* h_row = comm->h_rows;
-    h_row[R] = global_index_base;
-    h_row[R + 1] = n;
-    h_row[R + 2] = capacity;
-    constexpr uint64_t BAD_INDEX = ~0ull;  // in place of the valid-record count (never that large)
-    const bool bad_index = index && (index->ctx != ctx || index->nparts != R || index->part != me);
-    h_row[R + 3] = BAD_INDEX;
-    HIP_OK(hipMemcpyAsync(d_row + R, h_row + R, sizeof(uint64_t) * (bad_index ? 4 : 3), hipMemcpyHostToDevice, s));
-    if (!bad_index)
-        HIP_OK(hipMemcpyAsync(d_row + R + 3, pscratch + psb / sizeof(uint64_t) - 1, sizeof(uint64_t),
-                              hipMemcpyDeviceToDevice, s));
+    // 2. all-gather of the rows
     uint64_t* all = comm->h_rows + row;
-    if (comm->group) {  // in-process: every rank's row straight into this rank's host table
+    if (R == 1) {  // the one row to the host table; no collective, over either transport
+        HIP_OK(hipMemcpyAsync(all, d_row, sizeof(uint64_t) * row, hipMemcpyDeviceToHost, s));
+        mark(comm, 2, s);
+    } else if (comm->group) {  // in-process: every rank's row straight into this rank's host table
         comm->group->slot_b[me] = comm->d_send;  // read by the peers after the barriers below
         local_allgather(comm, d_row, all, sizeof(uint64_t) * row, s);
         mark(comm, 2, s);
@@ -345,7 +351,10 @@ int sd_cas_dedup_mgpu_indexed(sd_cas_ctx* ctx, sd_comm* comm, const uint8_t* d_h
     // 3. the all-to-all of the 16-byte records: one send and one receive per peer
     mark(comm, 3, s);
     const uint64_t* send = (const uint64_t*)comm->d_send;
-    if (comm->group) {
+    if (R == 1) {  // nothing to exchange: the records are in place, or one copy away
+        if (!direct && *m_out)
+            HIP_OK(hipMemcpyAsync(d_records_out, send, 16 * *m_out, hipMemcpyDeviceToDevice, s));
+    } else if (comm->group) {
         // in-process: pull what each peer sends here from its partitioned records, which
         // start at the sum of its counts to the ranks before this one
         sd_comm_group* g = comm->group;
@@ -370,8 +379,9 @@ int sd_cas_dedup_mgpu_indexed(sd_cas_ctx* ctx, sd_comm* comm, const uint8_t* d_h
         NCCL_OK(ncclGroupEnd());
     }
     mark(comm, 4, s);
-    // bounded, before the grouping's own (unbounded) sync for the group count
-    if (!comm->group) wait_peers(comm, s, "send/receive of the records");
+    // bounded, before the grouping's own (unbounded) sync for the group count; one rank has
+    // no peer to wait for, and the grouping's sync is its second and last wait
+    if (!comm->group && R > 1) wait_peers(comm, s, "send/receive of the records");
     // 4. group by cas_id and assign Objects (chunk-of-100 rule) on the received records
     uint64_t ng = 0;
     dedup_group_owners(ctx, d_records_out, *m_out, plan.ascending ? SD_DEDUP_INDEX_SORTED : 0, d_rep_out,

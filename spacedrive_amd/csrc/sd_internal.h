@@ -56,8 +56,16 @@ hipError_t launch_read_probe(const uint8_t* buf, uint64_t bytes, int pattern, hi
 constexpr uint32_t VALU_PEAK_OPS_PER_ITER = 384;  // k_valu_peak: VALU instructions per wave per iteration
 hipError_t launch_valu_peak(uint32_t* sink, uint32_t iters, uint32_t grid, hipStream_t s);
 // dedup
+// the rest of an exchange row (sd_host.h, SD_EXCHANGE_ROW_EXTRA) behind its nparts counts: with
+// `row`, the partition's scan writes counts[nparts .. nparts + 3] = base, n, capacity and the
+// valid-record total, or ~0 in its place when bad_index is set
+struct part_row {
+    uint64_t base, n, capacity;
+    uint32_t bad_index;
+};
 hipError_t dedup_partition(const uint8_t* hash32, const uint8_t* valid, uint64_t n, uint64_t base, int nparts,
-                           uint64_t* counts, uint64_t* records, uint64_t* scratch, hipStream_t s);
+                           uint64_t* counts, uint64_t* records, uint64_t* scratch, hipStream_t s,
+                           const part_row* row = nullptr);
 // device scratch bytes dedup_partition needs; the valid-record total is its last u64
 size_t dedup_partition_scratch(int nparts);
 hipError_t dedup_group(uint64_t* records, uint64_t m, int flags, uint64_t* rep, uint64_t* n_groups_dev,
