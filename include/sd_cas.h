@@ -1225,7 +1225,8 @@ int sd_cpu_checksum_tree_blocks_verify_range_proofs(const uint8_t* data, const u
  *             root hash and a trailing partial block's node covers fewer chunks: the byte comparison
  *             keeps those apart, they need no rule of their own.  Content that is SHIFTED, by an
  *             insertion or at another offset, is therefore not found: that takes content-defined
- *             chunking, which this is not.  Aligned blocks only
+ *             chunking, which this is not.  Aligned blocks only (shifted content: sd_cdc_cut,
+ *             sd_cdc_hash and sd_cdc_shared below, "content-defined chunks")
  *   d_rep[s]         the smallest slot of class(s); it lies in the lowest-numbered file that holds
  *                    the block (a file has one slot per j)
  *   d_class_size[s]  |class(s)|
@@ -1261,6 +1262,100 @@ int sd_checksum_tree_shared(sd_cas_ctx* ctx, const uint64_t* lens, size_t n, uin
 int sd_cpu_checksum_tree_shared(const uint64_t* lens, size_t n, uint32_t block_log2, const uint8_t* nodes,
                                 uint64_t min_blocks, uint64_t* rep, uint64_t* class_size, uint64_t* files_out,
                                 uint64_t* pairs_out, uint64_t capacity, uint64_t* n_pairs, uint64_t stats[8]);
+
+/* ---------------------------------------------------------------- content-defined chunks */
+/* Content-defined chunks: content that is there more than once at ANY offset -- what the shared
+ * blocks above cannot see (a header rewritten, a log and its rotated copy, an edited document, a
+ * container with one member changed).  A file is cut where its content says so, every chunk gets
+ * the plain BLAKE3 of its bytes as its id, and sd_cdc_shared groups the chunks of a batch of files
+ * by (length, id).  One byte inserted at the front moves the cuts with the content: all chunks but
+ * the first few are found again.
+ *   gear      G[b] = splitmix64(0x5DCDC0DE ^ b), b = 0..255 (add 0x9E3779B97F4A7C15, two
+ *             multiply-xorshift rounds, xorshift 31); G[0] = 0x2df3228afbc5cb53, G[255] =
+ *             0xdd9fba0f5362ab8e
+ *   rolling   per file h(-1) = 0, h(i) = (h(i-1) << 1) + G[byte i] mod 2^64: the last 64 bytes of
+ *             the file only, never a byte before the file's start
+ *   candidate position i is a candidate end e = i + 1 when h(i) & MASK == 0, MASK = the top
+ *             mask_bits bits
+ *   select    per file from s = 0: e = the smallest candidate end with s + min_size <= e <= s +
+ *             max_size, else s + max_size; e = min(e, len); repeat from s = e until e == len.  An
+ *             empty file has the one chunk (0, 0)
+ *   id        BLAKE3 of the chunk's bytes (32 bytes, ROOT, chunk counters from 0): file_checksum
+ *             of the chunk as a file, wherever it lies
+ *   params    valid iff 1 <= mask_bits <= 32, 64 <= min_size <= max_size <= 2^20, reserved == 0;
+ *             anything else is SD_ERR_INVALID before any allocation.  min_size >= 64 makes the
+ *             rolling value equal the one that restarts at each chunk; max_size <= 1 MiB keeps a
+ *             chunk inside one BLAKE3 subtree of 1024 chunk CVs.  The mean chunk is about
+ *             min_size + 2^mask_bits bytes */
+typedef struct sd_cdc_params {
+    uint32_t mask_bits, min_size, max_size, reserved;
+} sd_cdc_params;
+#define SD_CDC_DEFAULT_MASK_BITS 16
+#define SD_CDC_DEFAULT_MIN_SIZE 16384
+#define SD_CDC_DEFAULT_MAX_SIZE 262144
+typedef struct sd_cdc sd_cdc;
+/* The gear table.  Needs no GPU. */
+int sd_cdc_gear(uint64_t out[256]);
+/* A batch of files that are byte ranges of one device buffer: sd_checksum_batch_create's rule
+ * (host arrays, 16-byte aligned starts, the buffer readable to the next 64-byte boundary after
+ * each range; the buffer itself 16-byte aligned).  The sum of ceil(lens[f] / min_size) plus n must
+ * stay below 2^32, else SD_ERR_INVALID.  The batch owns its tables, its candidate bitmap (one bit
+ * per byte) and its chunk table; one cut or hash of it runs at a time. */
+int sd_cdc_create(sd_cas_ctx* ctx, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                  const sd_cdc_params* params, sd_cdc** out);
+void sd_cdc_destroy(sd_cdc* cdc);
+/* Scans the files for candidates and selects the cuts.  Runs on `stream` and syncs it: *n_chunks
+ * (host) sizes the caller's buffers.  One wave walks each file's bitmap, so a single huge file is a
+ * serial walk (DESIGN.md §3.6 has the measured time). */
+int sd_cdc_cut(sd_cas_ctx* ctx, sd_cdc* cdc, const uint8_t* d_data, void* stream, uint64_t* n_chunks);
+/* chunk_base[0 .. n] (host): the exclusive prefix sum of the chunks per file.  After a cut. */
+int sd_cdc_layout(const sd_cdc* cdc, uint64_t* chunk_base);
+/* After a cut: [0] files, [1] bytes, [2] candidates (set bits), [3] chunks, [4] chunks ended at a
+ * candidate, [5] chunks ended at s + max_size with no candidate (forced), [6] chunks that end at
+ * the file's end, counted here whatever else holds (an empty file's one chunk included), [7] BLAKE3
+ * compressions of the hash.  [3] == [4] + [5] + [6]. */
+int sd_cdc_stats(const sd_cdc* cdc, uint64_t out[8]);
+/* The chunks in layout order: d_chunks_out takes 2 x u64 per chunk (offset in its file, length),
+ * d_ids_out 32 bytes per chunk (16-byte aligned).  Either may be NULL.  The data is read once, in
+ * place: a chunk starts at any byte and is realigned in registers.  Asynchronous on `stream` and
+ * without an allocation: the piece CVs of chunks longer than 4 KiB pass through scratch the cut
+ * sized (grow-only, 32 bytes per 4 KiB piece), which is why one cut or hash of a batch runs at a
+ * time.  Before any cut: SD_ERR_INVALID (so are _layout and _stats). */
+int sd_cdc_hash(sd_cas_ctx* ctx, sd_cdc* cdc, const uint8_t* d_data, uint64_t* d_chunks_out,
+                uint8_t* d_ids_out, void* stream);
+/* Which chunks of a batch are there more than once: sd_checksum_tree_shared's contract with the
+ * chunk table in the place of the level -- chunk_base[0 .. n] (host, sd_cdc_layout), d_chunks and
+ * d_ids as sd_cdc_hash leaves them, slot s = chunk_base[f] + k.  Representatives, d_rep,
+ * d_class_size, d_files_out (4 x u64 per file: chunks, shared, redundant, redundant bytes),
+ * d_pairs_out rows (f, g, chunks, bytes) for g < f ascending by (f, g) with at least
+ * max(1, min_chunks) slots, the star towards the first holder, capacity / *n_pairs /
+ * SD_ERR_CAPACITY, count-only calls, any NULL output and n == 0 are as there.  What differs:
+ *   class(s)  the slots of equal length and equal 32 id bytes, at ANY position in any file
+ *   bytes(s)  the chunk's length
+ *   a file may repeat a chunk inside itself: such a slot is redundant, counts in d_files_out and in
+ *             stats[4] and [5], and gets no pair row (rows are for g < f only)
+ *   stats[8]  [0] files, [1] chunks, [2] classes, [3] classes of size >= 2, [4] redundant chunks,
+ *             [5] redundant bytes, [6] files with a redundant chunk, [7] redundant chunks whose
+ *             representative lies in the same file.  With min_chunks <= 1 the rows' chunks add up
+ *             to [4] - [7]
+ * The grouping is sd_dedup_confirm's with key = length and hash = id, both of its paths.  Runs on
+ * `stream` and syncs it; scratch comes from the context's pooled slot. */
+int sd_cdc_shared(sd_cas_ctx* ctx, const uint64_t* chunk_base, size_t n, const uint64_t* d_chunks,
+                  const uint8_t* d_ids, uint64_t min_chunks, uint64_t* d_rep, uint64_t* d_class_size,
+                  uint64_t* d_files_out, uint64_t* d_pairs_out, uint64_t capacity, uint64_t* n_pairs,
+                  uint64_t stats[8], void* stream);
+/* The same over host memory on host cores, without a context or a device.  _cut: chunk_base
+ * [0 .. n] and the stats are always complete; chunks_out (2 x u64 per chunk, may be NULL) takes at
+ * most `capacity` chunks, and a smaller capacity is SD_ERR_CAPACITY with *n_chunks = the
+ * requirement and no chunk written.  _hash takes _cut's arrays back. */
+int sd_cpu_cdc_cut(const uint8_t* data, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                   const sd_cdc_params* params, uint64_t* chunk_base, uint64_t* chunks_out, uint64_t capacity,
+                   uint64_t* n_chunks, uint64_t stats[8], int nthreads);
+int sd_cpu_cdc_hash(const uint8_t* data, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                    const uint64_t* chunk_base, const uint64_t* chunks, uint8_t* ids_out, int nthreads);
+int sd_cpu_cdc_shared(const uint64_t* chunk_base, size_t n, const uint64_t* chunks, const uint8_t* ids,
+                      uint64_t min_chunks, uint64_t* rep, uint64_t* class_size, uint64_t* files_out,
+                      uint64_t* pairs_out, uint64_t capacity, uint64_t* n_pairs, uint64_t stats[8]);
 
 /* ---------------------------------------------------------------- synthetic data */
 /* Device generator of SURVEY.md §8(d) (seed 0x5D5DCA51D, splitmix64 counter stream),

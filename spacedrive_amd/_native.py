@@ -225,7 +225,19 @@ SIGNATURES = [
      [P, P, SZ, U32, P, P, SZ, P, SZ, P, P, P, P, P, U64, PU64, P, I32]),
     ("sd_checksum_tree_shared", I32, [P, P, SZ, U32, P, U64, P, P, P, P, U64, PU64, P, P]),
     ("sd_cpu_checksum_tree_shared", I32, [P, SZ, U32, P, U64, P, P, P, P, U64, PU64, P]),
+    ("sd_cdc_gear", I32, [P]),
+    ("sd_cdc_create", I32, [P, P, P, SZ, P, ctypes.POINTER(P)]),
+    ("sd_cdc_destroy", None, [P]),
+    ("sd_cdc_cut", I32, [P, P, P, P, PU64]),
+    ("sd_cdc_layout", I32, [P, P]),
+    ("sd_cdc_stats", I32, [P, P]),
+    ("sd_cdc_hash", I32, [P, P, P, P, P, P]),
+    ("sd_cdc_shared", I32, [P, P, SZ, P, P, U64, P, P, P, P, U64, PU64, P, P]),
+    ("sd_cpu_cdc_cut", I32, [P, P, P, SZ, P, P, P, U64, PU64, P, I32]),
+    ("sd_cpu_cdc_hash", I32, [P, P, P, SZ, P, P, P, I32]),
+    ("sd_cpu_cdc_shared", I32, [P, SZ, P, P, U64, P, P, P, P, U64, PU64, P]),
 ]
+SD_CDC_DEFAULT = (16, 16384, 262144)  # mask_bits, min_size, max_size
 SD_TREE_BLOCK_LOG2_MIN, SD_TREE_BLOCK_LOG2_MAX = 17, 20
 SD_CONFIRM_INVALID, SD_CONFIRM_SINGLE, SD_CONFIRM_CONFIRMED, SD_CONFIRM_REFUTED = 0, 1, 2, 3
 SD_OBJECT_INDEX_OWNERS = 1

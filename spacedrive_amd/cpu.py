@@ -521,6 +521,123 @@ def checksum_tree_shared(lens, nodes, block_log2: int = 17, min_blocks: int = 0,
     return rep[:m], size[:m], files[:n], pairs[:int(n_pairs.value) if want_pairs else 0], stats
 
 
+class CdcParams(ctypes.Structure):
+    """sd_cdc_params: mask_bits, min_size, max_size, reserved (include/sd_cas.h, content-defined chunks)."""
+    _fields_ = [("mask_bits", ctypes.c_uint32), ("min_size", ctypes.c_uint32), ("max_size", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+def cdc_params(params=None) -> CdcParams:
+    """A CdcParams from None (the default 16 / 16 KiB / 256 KiB), a (mask_bits, min_size, max_size)
+    tuple or a CdcParams."""
+    from ._native import SD_CDC_DEFAULT
+    if isinstance(params, CdcParams):
+        return params
+    mask_bits, min_size, max_size = SD_CDC_DEFAULT if params is None else params
+    return CdcParams(int(mask_bits), int(min_size), int(max_size), 0)
+
+
+def cdc_gear() -> np.ndarray:
+    """sd_cdc_gear: the 256 gear values, uint64."""
+    out = np.zeros(256, np.uint64)
+    check(lib().sd_cdc_gear(out.ctypes.data))
+    return out
+
+
+def cdc_cut(data, offsets, lens, params=None, capacity: Optional[int] = None, want_chunks: bool = True,
+            nthreads: int = THREADS):
+    """sd_cpu_cdc_cut: the content-defined chunks of files that are byte ranges of a host buffer
+    (16-byte aligned starts).  Returns (chunk_base uint64 [n + 1], chunks uint64 [m, 2] = (offset in
+    the file, length) in layout order, stats uint64 [8]).  `capacity` (default: enough) short of the
+    chunks raises SdCasError (SD_ERR_CAPACITY) with ``.needed``; want_chunks=False only counts."""
+    from ._native import SdCasError
+    buf = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    ls = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+    n = len(ls)
+    if len(offs) != n:
+        raise ValueError("offsets and lens differ in length")
+    if n and int((offs + ls).max()) > buf.size:
+        raise ValueError("a range ends past the buffer")
+    pr = cdc_params(params)
+    base = np.zeros(n + 1, np.uint64)
+    stats = np.zeros(8, np.uint64)
+    count = ctypes.c_uint64(0)
+
+    def call(chunks, cap):
+        return lib().sd_cpu_cdc_cut(buf.ctypes.data if buf.size else None, offs.ctypes.data if n else None,
+                                    ls.ctypes.data if n else None, n, ctypes.byref(pr), base.ctypes.data,
+                                    None if chunks is None else chunks.ctypes.data, cap, ctypes.byref(count),
+                                    stats.ctypes.data, nthreads)
+    if capacity is None:  # count first, then exactly enough
+        check(call(None, 0))
+        capacity = int(count.value)
+    chunks = np.zeros((max(int(capacity), 1), 2), np.uint64)
+    if want_chunks:
+        try:
+            check(call(chunks, int(capacity)))
+        except SdCasError as e:
+            e.needed = int(count.value)
+            e.stats = stats
+            raise
+    else:
+        check(call(None, 0))
+    return base, chunks[:int(count.value) if want_chunks else 0], stats
+
+
+def cdc_hash(data, offsets, lens, chunk_base, chunks, nthreads: int = THREADS) -> np.ndarray:
+    """sd_cpu_cdc_hash: the ids uint8 [m, 32] of the chunks cdc_cut returned -- the BLAKE3 of each
+    chunk's bytes, file_checksum of the chunk as a file."""
+    buf = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    ls = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+    base = np.ascontiguousarray(chunk_base, dtype=np.uint64).reshape(-1)
+    ch = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1, 2)
+    n = len(ls)
+    if len(offs) != n or len(base) != n + 1 or len(ch) != (int(base[n]) if n else 0):
+        raise ValueError("chunk_base is not [n + 1] or chunks is not chunk_base[n] rows")
+    if n and int((offs + ls).max()) > buf.size:
+        raise ValueError("a range ends past the buffer")
+    ids = np.zeros((max(len(ch), 1), 32), np.uint8)
+    check(lib().sd_cpu_cdc_hash(buf.ctypes.data if buf.size else None, offs.ctypes.data if n else None,
+                                ls.ctypes.data if n else None, n, base.ctypes.data, ch.ctypes.data if len(ch) else None,
+                                ids.ctypes.data, nthreads))
+    return ids[:len(ch)]
+
+
+def cdc_shared(chunk_base, chunks, ids, min_chunks: int = 0, capacity: Optional[int] = None, want_pairs: bool = True):
+    """sd_cpu_cdc_shared: which chunks of a batch (cdc_cut's chunk_base and chunks, cdc_hash's ids)
+    are there more than once, at any offset.  Returns (rep uint64 [m], class_size uint64 [m], files
+    uint64 [n, 4], pairs uint64 [n_pairs, 4], stats uint64 [8]) as checksum_tree_shared does, with
+    chunks for blocks; stats[7] counts the redundant chunks a file repeats of itself, which get no
+    pair row."""
+    from ._native import SdCasError
+    base = np.ascontiguousarray(chunk_base, dtype=np.uint64).reshape(-1)
+    n = max(len(base) - 1, 0)
+    m = int(base[n]) if n else 0
+    ch = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1, 2)
+    hs = np.ascontiguousarray(ids, dtype=np.uint8).reshape(-1)
+    if len(ch) != m or hs.size != 32 * m:
+        raise ValueError("chunks or ids is not chunk_base[n] rows")
+    rep, size = np.zeros(max(m, 1), np.uint64), np.zeros(max(m, 1), np.uint64)
+    files = np.zeros((max(n, 1), 4), np.uint64)
+    cap = m if capacity is None else int(capacity)
+    pairs = np.zeros((max(cap, 1), 4), np.uint64)
+    n_pairs = ctypes.c_uint64(0)
+    stats = np.zeros(8, np.uint64)
+    rc = lib().sd_cpu_cdc_shared(base.ctypes.data if n else None, n, ch.ctypes.data if m else None,
+                                 hs.ctypes.data if m else None, int(min_chunks), rep.ctypes.data, size.ctypes.data,
+                                 files.ctypes.data, pairs.ctypes.data if want_pairs else None, cap,
+                                 ctypes.byref(n_pairs), stats.ctypes.data)
+    try:
+        check(rc)
+    except SdCasError as e:
+        e.needed = int(n_pairs.value)
+        e.stats = stats
+        raise
+    return rep[:m], size[:m], files[:n], pairs[:int(n_pairs.value) if want_pairs else 0], stats
+
+
 def blake3(data: bytes) -> bytes:
     """Full 32-byte BLAKE3 of a host buffer (sd_cpu_checksums of one range)."""
     buf = np.frombuffer(bytes(data) + bytes(64), np.uint8)

@@ -228,6 +228,24 @@ void plan_checksum(CkPlan& p, const uint64_t* offsets, const uint64_t* lens, siz
 // leaf blocks for plan_checksum, the blocks of a checksum tree's level for its roots).
 void plan_reduce_passes(CkPlan& p, std::vector<uint64_t> level_n, std::vector<uint64_t> base);
 
+// ------------------------------------------------------------------ content-defined chunks (cdc_host.cpp)
+// the gear table of include/sd_cas.h's content-defined chunks (256 entries)
+const uint64_t* cdc_gear();
+// throws SD_ERR_INVALID unless the parameters are valid
+void cdc_check_params(const sd_cdc_params* p);
+// the ranges' rule (16-byte aligned starts, the sum of ceil(len / min_size) plus n below 2^32);
+// params already checked.  Returns the bytes of all files
+uint64_t cdc_check_ranges(const uint64_t* offsets, const uint64_t* lens, size_t n, const sd_cdc_params& p);
+// BLAKE3 compressions of a message of len bytes: its 64-byte blocks and its parents
+inline uint64_t cdc_compressions(uint64_t len) {
+    if (len == 0) return 1;
+    const uint64_t chunks = (len + 1023) / 1024;
+    return (len / 1024) * 16 + (len % 1024 + 63) / 64 + chunks - 1;
+}
+// the host half of sd_cdc_shared and the whole of sd_cpu_cdc_shared's checks: chunk_base ascends
+// from 0, every file has a chunk, n < 2^32.  Returns m = chunk_base[n] (0 for n == 0)
+uint64_t cdc_check_layout(const uint64_t* chunk_base, size_t n);
+
 // ------------------------------------------------------------------ checksum trees
 // nb of include/sd_cas.h's checksum trees; block_log2 already checked
 inline uint64_t tree_nodes(uint64_t len, uint32_t block_log2) {
