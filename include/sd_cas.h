@@ -1357,6 +1357,80 @@ int sd_cpu_cdc_shared(const uint64_t* chunk_base, size_t n, const uint64_t* chun
                       uint64_t min_chunks, uint64_t* rep, uint64_t* class_size, uint64_t* files_out,
                       uint64_t* pairs_out, uint64_t capacity, uint64_t* n_pairs, uint64_t stats[8]);
 
+/* Deltas: acting on shared chunks.  Files 0 .. n_base-1 of a chunk table are the BASE (what a
+ * receiver holds), files n_base .. n-1 the TARGETS, 0 <= n_base <= n.  The plan turns the table and
+ * sd_cdc_shared's d_rep over it into a recipe: runs that copy from a base file or from a literal
+ * buffer, and the few literal bytes.  It reads tables only, never data and never ids, so a sender
+ * that has the receiver's chunk table (lengths and ids) in front of its own can plan.
+ *   kind(s)   of target slot s with r = d_rep[s]:
+ *             zero     its length is 0 (an empty file's one chunk): a literal chunk of 0 bytes
+ *                      whatever its class; emits no run
+ *             copy     r lies in a base file g: source 1 + g, source offset chunks[r].offset
+ *             literal  r == s: its bytes are appended to the literal buffer; lit_off[s] = the sum of
+ *                      the lengths of the literal slots before s in slot order
+ *             repeat   r is an earlier target slot (a literal, by the representatives' rule): source
+ *                      0, source offset lit_off[r] -- sent once, referred to again
+ *   runs      per target file, consecutive non-zero chunks k, k + 1 merge iff they have the same
+ *             source and src_off(k) + len(k) == src_off(k + 1); never across a file boundary.  A row
+ *             is 4 x u64 (t, source, src_off, bytes), t = the target's file index - n_base; rows
+ *             ascend by t, then by position in the file.  A run's destination offset in its file is
+ *             the sum of the bytes of that file's earlier runs.  A target identical to base file g
+ *             is the one row (t, 1 + g, 0, len)
+ *   d_lit_off one u64 per target slot (slot s at s - chunk_base[n_base]): the offset in the literal
+ *             buffer for a literal or a repeat, ~0 for a copy or a zero
+ *   d_files_out  6 x u64 per target: chunks, copied chunks, copied bytes, new literal bytes,
+ *             repeated bytes, runs
+ *   stats[8]  [0] target files, [1] target chunks, [2] copied chunks, [3] copied bytes, [4] literal
+ *             chunks (zeros included), [5] literal bytes = the literal buffer's size, [6] repeated
+ *             chunks, [7] runs.  [1] == [2] + [4] + [6]; the targets' bytes == [3] + [5] + the
+ *             repeated bytes (the sum of the files' fifth column)
+ * d_runs_out / capacity / *n_runs / SD_ERR_CAPACITY are sd_cdc_shared's pair rows' rule: NULL only
+ * counts, a short capacity writes no row and leaves the requirement in *n_runs with everything else
+ * complete, nothing is written past *n_runs.  Any output may be NULL; n_base == n or n == 0 gives
+ * zeros.  n_base > n, a NULL table with slots, or a d_rep that is not a representative table
+ * (r > s, lengths that differ, a representative that has one itself) is SD_ERR_INVALID, the first
+ * two before any allocation.  Runs on `stream` and syncs it; scratch comes from the context's pooled
+ * slot.  The plan also sizes the context's delta scratch for sd_cdc_delta_pack over this table. */
+int sd_cdc_delta_plan(sd_cas_ctx* ctx, const uint64_t* chunk_base, size_t n, size_t n_base, const uint64_t* d_chunks,
+                      const uint64_t* d_rep, uint64_t* d_lit_off, uint64_t* d_runs_out, uint64_t capacity,
+                      uint64_t* n_runs, uint64_t* d_files_out, uint64_t stats[8], void* stream);
+/* Gathers the literal slots' bytes into d_lit_out at their lit_off (stats[5] bytes): the tables as
+ * the plan took and left them, offsets[0 .. n) (host) the files' ranges in d_data as sd_cdc_create
+ * took them.  Only target ranges of d_data are read, under sd_cdc_create's promise (16-byte aligned
+ * buffer and starts, readable to the next 64-byte boundary after a range); d_lit_out has no
+ * alignment rule.  Asynchronous on `stream` and without an allocation after a plan over the same
+ * table: its segment list lives in the context's delta scratch, so one pack or apply of a context
+ * runs at a time.  The tables are trusted: they are the plan's own. */
+int sd_cdc_delta_pack(sd_cas_ctx* ctx, const uint64_t* chunk_base, size_t n, size_t n_base, const uint64_t* offsets,
+                      const uint64_t* d_chunks, const uint64_t* d_lit_off, const uint64_t* d_rep, const uint8_t* d_data,
+                      uint8_t* d_lit_out, void* stream);
+/* Rebuilds the targets: run (t, source, src_off, bytes) copies `bytes` bytes from source 0 = d_lit
+ * [0, lit_bytes) or source 1 + g = d_base + base_offsets[g] [0, base_lens[g]) to d_out +
+ * out_offsets[t] at the run's destination offset.  The recipe is UNTRUSTED (it arrives off a wire)
+ * and is validated first, on the device, with one host wait for the verdict:
+ *   t < n_targets and the rows ascend by t; source <= n_base; src_off + bytes is at most the
+ *   source's length, computed without 64-bit wrap; every file's runs sum to out_lens[t] (a file
+ *   without a run is empty)
+ * Anything else is SD_ERR_INVALID with NO byte of d_out written.  Only then are the bytes copied,
+ * asynchronously on `stream`.  Output ranges have no alignment rule (and must not overlap); d_base,
+ * base_offsets and d_lit follow sd_cdc_create's (d_lit as one range from 0).  base_offsets,
+ * base_lens, out_offsets, out_lens are host arrays; n_runs, n_base and n_targets stay below 2^32. */
+int sd_cdc_delta_apply(sd_cas_ctx* ctx, const uint64_t* d_runs, uint64_t n_runs, const uint64_t* base_offsets,
+                       const uint64_t* base_lens, size_t n_base, const uint8_t* d_base, const uint8_t* d_lit,
+                       uint64_t lit_bytes, const uint64_t* out_offsets, const uint64_t* out_lens, size_t n_targets,
+                       uint8_t* d_out, void* stream);
+/* The same over host arrays on host cores, with the same rules and refusals (no alignment rule). */
+int sd_cpu_cdc_delta_plan(const uint64_t* chunk_base, size_t n, size_t n_base, const uint64_t* chunks,
+                          const uint64_t* rep, uint64_t* lit_off, uint64_t* runs_out, uint64_t capacity,
+                          uint64_t* n_runs, uint64_t* files_out, uint64_t stats[8]);
+int sd_cpu_cdc_delta_pack(const uint64_t* chunk_base, size_t n, size_t n_base, const uint64_t* offsets,
+                          const uint64_t* chunks, const uint64_t* lit_off, const uint64_t* rep, const uint8_t* data,
+                          uint8_t* lit_out);
+int sd_cpu_cdc_delta_apply(const uint64_t* runs, uint64_t n_runs, const uint64_t* base_offsets,
+                           const uint64_t* base_lens, size_t n_base, const uint8_t* base, const uint8_t* lit,
+                           uint64_t lit_bytes, const uint64_t* out_offsets, const uint64_t* out_lens, size_t n_targets,
+                           uint8_t* out, int nthreads);
+
 /* ---------------------------------------------------------------- synthetic data */
 /* Device generator of SURVEY.md §8(d) (seed 0x5D5DCA51D, splitmix64 counter stream),
  * for benchmarks and parity tests: writes the exact cas message of each synthetic file

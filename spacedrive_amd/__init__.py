@@ -12,7 +12,7 @@ from . import cpu  # noqa: F401  (the library's explicit CPU path, sd_cpu_*)
 from . import split  # noqa: F401  (one file's checksum over many ranks)
 from . import tree  # noqa: F401  (a file's checksum with its block level; verify names the blocks)
 from . import cdc  # noqa: F401  (content-defined chunks: shared content at any offset)
-from .cdc import Cdc  # noqa: F401
+from .cdc import Cdc, delta_files, patch_files  # noqa: F401
 from .cas import (FileMetadata, UnexpectedEofError, cas_ids_files_stats, cas_ids_host_stats, checksums_host_stats,  # noqa: F401
                   checksums_learned,
                   coalescer_stats, file_checksum,
@@ -25,4 +25,4 @@ __all__ = ["generate_cas_id", "generate_cas_ids", "file_checksum", "file_checksu
            "UnexpectedEofError", "Context", "CasBatch", "ChecksumBatch", "default_context", "stage_plan",
            "SdCasError", "cas_ids_files_stats", "cas_ids_host_stats", "checksums_host_stats", "file_checksums_stats", "file_checksums_learned", "checksums_learned", "coalescer_stats",
            "set_tuning", "get_tuning", "host_cpu_budget", "rccl_info", "fingerprints", "fingerprints_stats", "FingerprintBatch",
-           "ObjectIndex", "HostObjectIndex", "cpu", "ChecksumTree", "ChecksumTreeBlocks", "tree", "cdc", "Cdc"]
+           "ObjectIndex", "HostObjectIndex", "cpu", "ChecksumTree", "ChecksumTreeBlocks", "tree", "cdc", "Cdc", "delta_files", "patch_files"]

@@ -236,6 +236,12 @@ SIGNATURES = [
     ("sd_cpu_cdc_cut", I32, [P, P, P, SZ, P, P, P, U64, PU64, P, I32]),
     ("sd_cpu_cdc_hash", I32, [P, P, P, SZ, P, P, P, I32]),
     ("sd_cpu_cdc_shared", I32, [P, SZ, P, P, U64, P, P, P, P, U64, PU64, P]),
+    ("sd_cdc_delta_plan", I32, [P, P, SZ, SZ, P, P, P, P, U64, PU64, P, P, P]),
+    ("sd_cdc_delta_pack", I32, [P, P, SZ, SZ, P, P, P, P, P, P, P]),
+    ("sd_cdc_delta_apply", I32, [P, P, U64, P, P, SZ, P, P, U64, P, P, SZ, P, P]),
+    ("sd_cpu_cdc_delta_plan", I32, [P, SZ, SZ, P, P, P, P, U64, PU64, P, P]),
+    ("sd_cpu_cdc_delta_pack", I32, [P, SZ, SZ, P, P, P, P, P, P]),
+    ("sd_cpu_cdc_delta_apply", I32, [P, U64, P, P, SZ, P, P, U64, P, P, SZ, P, I32]),
 ]
 SD_CDC_DEFAULT = (16, 16384, 262144)  # mask_bits, min_size, max_size
 SD_TREE_BLOCK_LOG2_MIN, SD_TREE_BLOCK_LOG2_MAX = 17, 20

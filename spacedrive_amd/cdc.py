@@ -6,6 +6,10 @@ A file is cut where its content says so (a gear rolling hash over the last 64 by
 its top mask_bits bits are zero, between min_size and max_size bytes after the last one), every
 chunk's id is the BLAKE3 of its bytes, and chunks are grouped by (length, id).
 
+``delta_files`` / ``patch_files`` act on the answer: a file stored or sent as another file's chunks
+plus its own few (sd_cdc_delta_plan, _pack, _apply; csrc/cdc_delta.hip), rebuilt and checked against
+its checksum.
+
 ``Cdc`` runs the three steps on the device over a torch buffer that holds the files as byte ranges
 (csrc/cdc.hip, csrc/tree_shared.hip); ``chunk_files`` and ``compare_files`` read files from disk,
 upload them once and use it, or the library's CPU twins (cpu.cdc_cut, cpu.cdc_hash, cpu.cdc_shared)
@@ -14,6 +18,7 @@ where there is no device.
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
@@ -182,3 +187,177 @@ def compare_files(paths: list, params=None, min_chunks: int = 0, device=None, nt
     out = _run(list(paths), params, min_chunks, True, device, nthreads)
     return out[4], out[5], out[6]
 
+
+
+# ---------------------------------------------------------------- deltas
+def delta_plan(ctx, chunk_base, n_base: int, d_chunks, d_rep, d_lit_off=None, d_runs_out=None, capacity: int = 0,
+               d_files_out=None, stream=None):
+    """sd_cdc_delta_plan: files n_base .. n-1 of the table as runs out of files 0 .. n_base-1 and a
+    literal buffer.  Returns (n_runs, stats uint64 [8]); the outputs given are written (lit_off int64
+    [target slots]; runs int64 [capacity, 4] = (t, source, src_off, bytes); files int64 [targets, 6]).
+    A short `capacity` raises SdCasError (SD_ERR_CAPACITY, ``.needed`` rows, ``.stats``)."""
+    from .device import _ptr, _stream
+    base = np.ascontiguousarray(chunk_base, dtype=np.uint64).reshape(-1)
+    n = max(len(base) - 1, 0)
+    n_runs = ctypes.c_uint64(0)
+    stats = np.zeros(8, np.uint64)
+    rc = lib().sd_cdc_delta_plan(ctx.handle, base.ctypes.data if n else None, n, int(n_base), _ptr(d_chunks) if n else None,
+                                 _ptr(d_rep) if n else None, _ptr(d_lit_off), _ptr(d_runs_out), capacity,
+                                 ctypes.byref(n_runs), _ptr(d_files_out), stats.ctypes.data, _stream(stream))
+    try:
+        check(rc)
+    except SdCasError as e:
+        e.needed = int(n_runs.value)
+        e.stats = stats
+        raise
+    return int(n_runs.value), stats
+
+
+def delta_pack(ctx, chunk_base, n_base: int, offsets, d_chunks, d_lit_off, d_rep, d_data, d_lit_out, stream=None) -> None:
+    """sd_cdc_delta_pack: the literal slots' bytes from d_data (the files at host `offsets`) into
+    d_lit_out at their lit_off.  Asynchronous on the stream."""
+    from .device import _ptr, _stream
+    base = np.ascontiguousarray(chunk_base, dtype=np.uint64).reshape(-1)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    n = max(len(base) - 1, 0)
+    if len(offs) != n:
+        raise ValueError("offsets is not one per file")
+    check(lib().sd_cdc_delta_pack(ctx.handle, base.ctypes.data if n else None, n, int(n_base), offs.ctypes.data if n else None,
+                                  _ptr(d_chunks) if n else None, _ptr(d_lit_off), _ptr(d_rep) if n else None, _ptr(d_data),
+                                  _ptr(d_lit_out), _stream(stream)))
+
+
+def delta_apply(ctx, d_runs, n_runs: int, base_offsets, base_lens, d_base, d_lit, lit_bytes: int, out_offsets, out_lens,
+                d_out, stream=None) -> None:
+    """sd_cdc_delta_apply: validates the recipe on the device (a refused one raises SdCasError,
+    SD_ERR_INVALID, with no byte of d_out written), then copies the runs into d_out at the host
+    `out_offsets`.  The copy is asynchronous on the stream."""
+    from .device import _ptr, _stream
+    bo = np.ascontiguousarray(base_offsets, dtype=np.uint64).reshape(-1)
+    bl = np.ascontiguousarray(base_lens, dtype=np.uint64).reshape(-1)
+    oo = np.ascontiguousarray(out_offsets, dtype=np.uint64).reshape(-1)
+    ol = np.ascontiguousarray(out_lens, dtype=np.uint64).reshape(-1)
+    if len(bo) != len(bl) or len(oo) != len(ol):
+        raise ValueError("offsets and lens differ in length")
+    check(lib().sd_cdc_delta_apply(ctx.handle, _ptr(d_runs) if n_runs else None, int(n_runs),
+                                   bo.ctypes.data if len(bl) else None, bl.ctypes.data if len(bl) else None, len(bl),
+                                   _ptr(d_base), _ptr(d_lit) if lit_bytes else None, int(lit_bytes),
+                                   oo.ctypes.data if len(ol) else None, ol.ctypes.data if len(ol) else None, len(ol),
+                                   _ptr(d_out), _stream(stream)))
+
+
+@dataclass
+class Delta:
+    """What delta_files leaves and patch_files takes: the recipe, the literal bytes, and what the
+    rebuilt files must be.  No wire or file format is defined for it."""
+    runs: np.ndarray         # uint64 [r, 4] = (t, source, src_off, bytes); source 0 = literals, 1 + g = base file g
+    literals: np.ndarray     # uint8
+    target_lens: np.ndarray  # uint64 [targets]
+    checksums: np.ndarray    # uint8 [targets, 32]: file_checksum of each target
+    files: np.ndarray        # uint64 [targets, 6]: chunks, copied chunks, copied bytes, new literal bytes, repeated bytes, runs
+    stats: np.ndarray        # uint64 [8] of sd_cdc_delta_plan
+    params: tuple            # (mask_bits, min_size, max_size)
+
+
+def _cpu_checksums(buf, offs, lens, nthreads) -> np.ndarray:
+    n = len(lens)
+    out = np.zeros((max(n, 1), 32), np.uint8)
+    if n:
+        check(lib().sd_cpu_checksums(buf.ctypes.data, offs.ctypes.data, lens.ctypes.data, n, out.ctypes.data, nthreads))
+    return out[:n]
+
+
+def _device_checksums(ctx, d_data, offs, lens) -> np.ndarray:
+    import torch
+    n = len(lens)
+    if n == 0:
+        return np.zeros((0, 32), np.uint8)
+    hs = torch.zeros(n * 32, dtype=torch.uint8, device="cuda")
+    ctx.checksum_batch(offs, lens).run(d_data, hs)
+    return hs.cpu().numpy().reshape(n, 32)
+
+
+def delta_files(base_paths, target_paths, params=None, device=None, nthreads: int = cpu.THREADS) -> Delta:
+    """What does a holder of the files at `base_paths` need to rebuild those at `target_paths`?  Base
+    and targets are read once and uploaded once; cut, hash, shared, plan and pack run on the device
+    (or on the CPU twins where there is none), and the targets' checksums come from the checksum
+    batch over the same upload.  Returns a Delta."""
+    base_paths, target_paths = list(base_paths), list(target_paths)
+    buf, offs, lens = _pack(base_paths + target_paths)
+    nb, n = len(base_paths), len(lens)
+    pr = cdc_params(params)
+    ptuple = (int(pr.mask_bits), int(pr.min_size), int(pr.max_size))
+    if not _use_device(device):
+        base, chunks, _ = cpu.cdc_cut(buf, offs, lens, pr, nthreads=nthreads)
+        ids = cpu.cdc_hash(buf, offs, lens, base, chunks, nthreads)
+        rep = cpu.cdc_shared(base, chunks, ids, want_pairs=False)[0]
+        lit_off, runs, files, stats = cpu.cdc_delta_plan(base, nb, chunks, rep)
+        lit = cpu.cdc_delta_pack(buf, offs, base, nb, chunks, rep, lit_off, int(stats[5]))
+        sums = _cpu_checksums(buf, offs[nb:], lens[nb:], nthreads)
+        return Delta(runs.copy(), lit.copy(), lens[nb:].copy(), sums, files.copy(), stats, ptuple)
+    import torch
+    from .device import default_context
+    ctx = default_context()
+    d_data = torch.from_numpy(buf).cuda()
+    c = Cdc(ctx, offs, lens, pr)
+    try:
+        m = c.cut(d_data)
+        base = c.layout()
+        mt = m - (int(base[nb]) if n else 0)
+        d_chunks = torch.zeros((max(m, 1), 2), dtype=torch.int64, device="cuda")
+        d_ids = torch.zeros((max(m, 1), 32), dtype=torch.uint8, device="cuda")
+        c.hash(d_data, d_chunks, d_ids)
+        d_rep = torch.zeros(max(m, 1), dtype=torch.int64, device="cuda")
+        c.shared(d_chunks, d_ids, d_rep=d_rep)
+        d_lit_off = torch.zeros(max(mt, 1), dtype=torch.int64, device="cuda")
+        d_runs = torch.zeros((max(mt, 1), 4), dtype=torch.int64, device="cuda")
+        d_files = torch.zeros((max(n - nb, 1), 6), dtype=torch.int64, device="cuda")
+        n_runs, stats = delta_plan(ctx, base, nb, d_chunks, d_rep, d_lit_off, d_runs, mt, d_files)
+        d_lit = torch.zeros(max(int(stats[5]), 1), dtype=torch.uint8, device="cuda")
+        delta_pack(ctx, base, nb, offs, d_chunks, d_lit_off, d_rep, d_data, d_lit)
+        sums = _device_checksums(ctx, d_data, offs[nb:], lens[nb:])
+        return Delta(d_runs[:n_runs].cpu().numpy().view(np.uint64), d_lit[:int(stats[5])].cpu().numpy(), lens[nb:].copy(), sums,
+                     d_files[:n - nb].cpu().numpy().view(np.uint64), stats, ptuple)
+    finally:
+        c.close()
+
+
+def patch_files(base_paths, delta: Delta, device=None, nthreads: int = cpu.THREADS) -> list:
+    """Rebuilds the targets of `delta` from the files at `base_paths` and checks every one against
+    delta.checksums.  Returns the rebuilt files as uint8 arrays.  A recipe that is not valid for these
+    base files raises SdCasError (nothing is rebuilt); a rebuilt file whose checksum differs raises
+    ValueError naming it."""
+    buf, offs, lens = _pack(list(base_paths))
+    out_lens = np.ascontiguousarray(delta.target_lens, dtype=np.uint64).reshape(-1)
+    nt = len(out_lens)
+    sums = np.ascontiguousarray(delta.checksums, dtype=np.uint8).reshape(-1, 32)
+    if len(sums) != nt:
+        raise ValueError("delta.checksums is not one per target")
+    out_offs, cur = np.zeros(nt, np.uint64), 0
+    for t in range(nt):  # as _pack lays files out: what the checksum batch reads
+        out_offs[t] = cur
+        cur += (int(out_lens[t]) + 63) // 64 * 64 + 64
+    runs = np.ascontiguousarray(delta.runs, dtype=np.uint64).reshape(-1, 4)
+    lit = np.ascontiguousarray(delta.literals, dtype=np.uint8).reshape(-1)
+    if not _use_device(device):
+        out = np.zeros(cur + 64, np.uint8)
+        cpu.cdc_delta_apply(runs, buf, offs, lens, lit, out_lens, out, out_offs, nthreads)
+        got = _cpu_checksums(out, out_offs, out_lens, nthreads)
+    else:
+        import torch
+        from .device import default_context
+        ctx = default_context()
+        d_base = torch.from_numpy(buf).cuda()
+        lit_pad = np.zeros((len(lit) + 63) // 64 * 64 + 64, np.uint8)
+        lit_pad[:len(lit)] = lit
+        d_lit = torch.from_numpy(lit_pad).cuda()
+        d_runs = torch.from_numpy(runs.view(np.int64).reshape(-1).copy() if len(runs) else np.zeros(4, np.int64)).cuda()
+        d_out = torch.zeros(cur + 64, dtype=torch.uint8, device="cuda")
+        delta_apply(ctx, d_runs, len(runs), offs, lens, d_base, d_lit, len(lit), out_offs, out_lens, d_out)
+        got = _device_checksums(ctx, d_out, out_offs, out_lens)
+        out = d_out.cpu().numpy()
+    for t in range(nt):
+        if not np.array_equal(got[t], sums[t]):
+            raise ValueError(f"target {t}: the rebuilt file's checksum {got[t].tobytes().hex()} is not the delta's "
+                             f"{sums[t].tobytes().hex()}")
+    return [out[int(o):int(o) + int(ln)].copy() for o, ln in zip(out_offs, out_lens)]

@@ -638,6 +638,95 @@ def cdc_shared(chunk_base, chunks, ids, min_chunks: int = 0, capacity: Optional[
     return rep[:m], size[:m], files[:n], pairs[:int(n_pairs.value) if want_pairs else 0], stats
 
 
+def _table(chunk_base, chunks, rep):
+    base = np.ascontiguousarray(chunk_base, dtype=np.uint64).reshape(-1)
+    n = max(len(base) - 1, 0)
+    m = int(base[n]) if n else 0
+    ch = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1, 2)
+    rp = np.ascontiguousarray(rep, dtype=np.uint64).reshape(-1)
+    if len(ch) != m or len(rp) != m:
+        raise ValueError("chunks or rep is not chunk_base[n] rows")
+    return base, n, m, ch, rp
+
+
+def cdc_delta_plan(chunk_base, n_base: int, chunks, rep, capacity: Optional[int] = None, want_runs: bool = True):
+    """sd_cpu_cdc_delta_plan: the recipe that rebuilds files n_base .. n-1 of a chunk table (cdc_cut's
+    chunk_base and chunks, cdc_shared's rep) from files 0 .. n_base-1 and a literal buffer.  Returns
+    (lit_off uint64 [target slots], runs uint64 [r, 4] = (t, source, src_off, bytes), files uint64
+    [targets, 6], stats uint64 [8]); source 0 is the literal buffer, 1 + g base file g.  `capacity`
+    (default: enough) short of the runs raises SdCasError (SD_ERR_CAPACITY, ``.needed``, ``.stats``)."""
+    from ._native import SdCasError
+    base, n, m, ch, rp = _table(chunk_base, chunks, rep)
+    if not 0 <= int(n_base) <= n:
+        raise ValueError("n_base outside 0..n")
+    mt = m - (int(base[n_base]) if n else 0)
+    nt = n - int(n_base)
+    lit_off = np.zeros(max(mt, 1), np.uint64)
+    files = np.zeros((max(nt, 1), 6), np.uint64)
+    cap = mt if capacity is None else int(capacity)
+    runs = np.zeros((max(cap, 1), 4), np.uint64)
+    n_runs = ctypes.c_uint64(0)
+    stats = np.zeros(8, np.uint64)
+    rc = lib().sd_cpu_cdc_delta_plan(base.ctypes.data if n else None, n, int(n_base), ch.ctypes.data if m else None,
+                                     rp.ctypes.data if m else None, lit_off.ctypes.data, runs.ctypes.data if want_runs else None,
+                                     cap, ctypes.byref(n_runs), files.ctypes.data, stats.ctypes.data)
+    try:
+        check(rc)
+    except SdCasError as e:
+        e.needed = int(n_runs.value)
+        e.stats = stats
+        raise
+    return lit_off[:mt], runs[:int(n_runs.value) if want_runs else 0], files[:nt], stats
+
+
+def cdc_delta_pack(data, offsets, chunk_base, n_base: int, chunks, rep, lit_off, lit_bytes: int) -> np.ndarray:
+    """sd_cpu_cdc_delta_pack: the literal buffer uint8 [lit_bytes] (stats[5] of the plan) -- the target
+    files' literal chunks, each once, at their lit_off."""
+    buf = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    base, n, m, ch, rp = _table(chunk_base, chunks, rep)
+    lo = np.ascontiguousarray(lit_off, dtype=np.uint64).reshape(-1)
+    if len(offs) != n or not 0 <= int(n_base) <= n or len(lo) != m - (int(base[n_base]) if n else 0):
+        raise ValueError("offsets is not [n] or lit_off is not one per target slot")
+    lit = np.zeros(max(int(lit_bytes), 1), np.uint8)
+    check(lib().sd_cpu_cdc_delta_pack(base.ctypes.data if n else None, n, int(n_base), offs.ctypes.data if n else None,
+                                      ch.ctypes.data if m else None, lo.ctypes.data if len(lo) else None,
+                                      rp.ctypes.data if m else None, buf.ctypes.data if buf.size else None, lit.ctypes.data))
+    return lit[:int(lit_bytes)]
+
+
+def cdc_delta_apply(runs, base_data, base_offsets, base_lens, literals, out_lens, out=None, out_offsets=None,
+                    nthreads: int = THREADS):
+    """sd_cpu_cdc_delta_apply: rebuilds the targets from the base files (byte ranges of base_data) and
+    the literal buffer.  The recipe is validated first; a refused one raises SdCasError
+    (SD_ERR_INVALID) with nothing written.  Returns (out uint8, out_offsets uint64 [targets]): the
+    targets packed back to back unless `out` and `out_offsets` are given."""
+    rn = np.ascontiguousarray(runs, dtype=np.uint64).reshape(-1, 4)
+    bd = np.ascontiguousarray(base_data, dtype=np.uint8).reshape(-1)
+    bo = np.ascontiguousarray(base_offsets, dtype=np.uint64).reshape(-1)
+    bl = np.ascontiguousarray(base_lens, dtype=np.uint64).reshape(-1)
+    lit = np.ascontiguousarray(literals, dtype=np.uint8).reshape(-1)
+    ol = np.ascontiguousarray(out_lens, dtype=np.uint64).reshape(-1)
+    if len(bo) != len(bl):
+        raise ValueError("base_offsets and base_lens differ in length")
+    if len(bl) and int((bo + bl).max()) > bd.size:
+        raise ValueError("a base range ends past the buffer")
+    if out is None:
+        oo = np.concatenate([[0], np.cumsum(ol)[:-1]]).astype(np.uint64) if len(ol) else np.zeros(0, np.uint64)
+        out = np.zeros(max(int(ol.sum()) if len(ol) else 0, 1), np.uint8)
+    else:
+        oo = np.ascontiguousarray(out_offsets, dtype=np.uint64).reshape(-1)
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or len(oo) != len(ol):
+            raise ValueError("out is not a contiguous uint8 array or out_offsets is not one per target")
+        if len(ol) and int((oo + ol).max()) > out.size:
+            raise ValueError("an output range ends past the buffer")
+    check(lib().sd_cpu_cdc_delta_apply(rn.ctypes.data if len(rn) else None, len(rn), bo.ctypes.data if len(bl) else None,
+                                       bl.ctypes.data if len(bl) else None, len(bl), bd.ctypes.data if bd.size else None,
+                                       lit.ctypes.data if lit.size else None, lit.size, oo.ctypes.data if len(ol) else None,
+                                       ol.ctypes.data if len(ol) else None, len(ol), out.ctypes.data, nthreads))
+    return out, oo
+
+
 def blake3(data: bytes) -> bytes:
     """Full 32-byte BLAKE3 of a host buffer (sd_cpu_checksums of one range)."""
     buf = np.frombuffer(bytes(data) + bytes(64), np.uint8)

@@ -317,6 +317,22 @@ struct Slot {
     }
 };
 
+// The CDC deltas' working set (cdc_delta.hip), one per context: the segment lists and prefix sums
+// of a pack or an apply (grown by sd_cdc_delta_plan and sd_cdc_delta_apply, so a pack allocates
+// nothing), and the host tables, which go up through pinned memory: `up` marks the end of the last
+// upload, after which the next call may overwrite them.
+struct DeltaWork {
+    DevBuf scratch;
+    Tables tab;
+    hipEvent_t up = nullptr;
+    DeltaWork() = default;
+    DeltaWork(const DeltaWork&) = delete;
+    DeltaWork& operator=(const DeltaWork&) = delete;
+    ~DeltaWork() {
+        if (up) (void)hipEventDestroy(up);
+    }
+};
+
 }  // namespace sdi
 
 struct sd_cas_ctx {
@@ -365,6 +381,7 @@ struct sd_cas_ctx {
         return coal;
     }
     std::vector<std::unique_ptr<sdi::Slot>> free_slots;
+    sdi::DeltaWork delta;  // sd_cdc_delta_pack / _apply: one of them runs at a time
 
     std::unique_ptr<sdi::Slot> acquire() {
         {

@@ -245,6 +245,14 @@ inline uint64_t cdc_compressions(uint64_t len) {
 // the host half of sd_cdc_shared and the whole of sd_cpu_cdc_shared's checks: chunk_base ascends
 // from 0, every file has a chunk, n < 2^32.  Returns m = chunk_base[n] (0 for n == 0)
 uint64_t cdc_check_layout(const uint64_t* chunk_base, size_t n);
+// the deltas' argument rules, both halves (cdc_delta_host.cpp).  _plan: cdc_check_layout, n_base <= n,
+// no NULL table with slots; returns the target slots and leaves the first one at *t0
+uint64_t cdc_delta_check_plan(const uint64_t* chunk_base, size_t n, size_t n_base, const void* chunks, const void* rep,
+                              uint64_t* t0);
+// _apply: counts below 2^32, no NULL array with entries, no NULL buffer that a length says is read
+void cdc_delta_check_apply(const void* runs, uint64_t n_runs, const uint64_t* base_offsets, const uint64_t* base_lens,
+                           size_t n_base, const void* base, const void* lit, uint64_t lit_bytes,
+                           const uint64_t* out_offsets, const uint64_t* out_lens, size_t n_targets, const void* out);
 
 // ------------------------------------------------------------------ checksum trees
 // nb of include/sd_cas.h's checksum trees; block_log2 already checked
